@@ -27,6 +27,9 @@ exchange_frame are tested on one GPU through its in-process loopback transport (
 Timed region: inputs (scene, BVH, textures, env maps) resident in HBM; K steps bracketed by barrier + torch.cuda.synchronize on
 both sides; time = max over ranks; value = rays traced by all ranks in the K steps / that time.  Rays are counted by the kernels
 (every traversal started).  The accumulation is reset before it could reach max_accumulated_frames, so no timed step is a no-op.
+`--dump-outputs DIR` writes, right after the timed steps, the accumulation image the last timed step left in the caller's output
+(DIR/image.npy, float32 (H, W, 4); above 64 MB a fixed, seeded pixel sample): the scenes are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Extra objects on the JSON line (rank 0, N = 1):
   roofline     - for the single DOMINANT KERNEL (largest share of a launch's GPU time; k_wf_traverse): achieved = its algorithmic
@@ -84,6 +87,9 @@ def main():
     ap.add_argument("--no-pmc-live", action="store_true", help="do not collect the dominant kernel's FETCH_SIZE / WRITE_SIZE in this run (two rocprofv3 --pmc child runs of a short "
                                                                "version of the same command); roofline.traffic then comes from the committed profile")
     ap.add_argument("--save-image", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (rank 0): "
+                         "image.npy = the (H, W, 4) float32 accumulation target pt_trace wrote into, as the caller holds it")
     ap.add_argument("--mode", default="wavefront", choices=["wavefront", "megakernel"])
     ap.add_argument("--stage-blocks", type=int, default=0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo + --single-device rehearses N ranks on a 1-GPU box through the test double")
@@ -96,6 +102,10 @@ def main():
     ap.add_argument("--animate", action="store_true", help="dynamic path (--config figure / sponza_figure): skin -> BVH refit -> trace every step, accumulation reset each frame")
     ap.add_argument("--rebuild", action="store_true", help="with --animate: full LBVH rebuild every frame instead of the refit (the round-1 behaviour, for comparison)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.warmup < 0:
+        raise SystemExit("bench.py: --warmup must be >= 0")
 
     # ---- `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves, as a child process, BEFORE any GPU call
     if args.gpus < 1:
@@ -286,6 +296,8 @@ def main():
     headline_weak = world > 1 and args.headline == "weak" and not args.animate
     spp = weak_spp if headline_weak else base_spp
     elapsed, rays_total, kernel_ms = timed_run(spp, 0)
+    if rank == 0 and args.dump_outputs:               # before anything below renders into `out` again
+        dump_outputs(args.dump_outputs, {"image": r.readback(out)})
 
     result = None
     if rank == 0:
@@ -588,6 +600,27 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Writes every array as directory/<name>.npy in float32 (float64 stays float64).  An image whose float32 size would exceed
+    DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its pixels instead (rows in ascending pixel order), and <name>_pixels.npy holds
+    their flat indices y * W + x as float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > DUMP_LIMIT_BYTES:
+            flat = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = DUMP_LIMIT_BYTES // 2 // flat[0].nbytes
+            pix = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=keep, replace=False))
+            np.save(os.path.join(directory, name + "_pixels.npy"), pix.astype(np.float64))
+            a = flat[pix]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def pmc_live(kernels, spp, config, timeout_s=240):

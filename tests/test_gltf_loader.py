@@ -603,11 +603,9 @@ def test_exr_rejects_what_the_reference_rejects():
 
 
 def test_sheen_lut_exr_of_the_reference_matches_the_committed_table():
-    """The one data fixture the reference ships (Resources/Sheen_E.exr) was decoded to tests/golden/sheen_e_16x16.npy by
-    tools/decode_sheen_lut.py; the C++ EXR reader must produce the same table (channel R) when the file is present."""
-    p = "/root/reference/Resources/Sheen_E.exr"
-    if not os.path.exists(p):
-        pytest.skip("reference tree not present (GPU box)")
+    """The one data fixture the reference ships (Resources/Sheen_E.exr, stored unchanged as tests/golden/sheen_e.exr) was decoded to
+    tests/golden/sheen_e_16x16.npy by tools/decode_sheen_lut.py; the C++ EXR reader must produce the same table (channel R)."""
+    p = os.path.join(os.path.dirname(__file__), "golden", "sheen_e.exr")
     with pytest.raises(MiptError, match="missing R, G or B"):          # the environment-map loader's rules reject a Y-only file
         G.load_rgb32f(p)
     got, half = G.decode_rgb32f(open(p, "rb").read(), 2)               # LoadLookupTables rules: one HALF channel (PIZ file whose only block is stored raw)
