@@ -909,6 +909,42 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the shade stage's texture sampler on caller-supplied queries, one per lane (pt_shading.h
+// debug_sample_query).  mat_slot: 2 per query (material, slot 0..14 or 16..19); tc: 4 per query (tc0.xy, tc1.xy); out_rgba: 4 per query;
+// out_taps (may be null): 5 per query (i0, i1, j0, j1, and ia: the first column of the texel pair loaded for each row).  unit 0: the wavefront stages' build (tables in LDS), 1: the megakernel's.
+extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* mat_slot, const float* tc, uint32_t n, float* out_rgba, int32_t* out_taps) {
+    if (!ctx || unit < 0 || unit > 1 || (n && (!mat_slot || !tc || !out_rgba))) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t mat = mat_slot[2 * i], slot = mat_slot[2 * i + 1];
+        if (mat >= (uint32_t)ctx->n_materials || !(slot < (uint32_t)SLOT_COUNT || (slot >= 16u && slot <= 19u)))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_sample_texture: query " + std::to_string(i) + " names material " + std::to_string(mat) +
+                                                      " slot " + std::to_string(slot) + " (" + std::to_string(ctx->n_materials) + " materials)");
+    }
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    SceneRec sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.rmats = ctx->d_rmats; sc.n_materials = (uint32_t)ctx->n_materials;
+    sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
+    uint32_t* d_ms = nullptr; float *d_tc = nullptr, *d_out = nullptr; int32_t* d_taps = nullptr;
+    auto done = [&](int code, const std::string& why) { hipFree(d_ms); hipFree(d_tc); hipFree(d_out); hipFree(d_taps); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
+    if (hipMalloc((void**)&d_ms, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_tc, (size_t)n * 16) != hipSuccess ||
+        hipMalloc((void**)&d_out, (size_t)n * 16) != hipSuccess || hipMalloc((void**)&d_taps, (size_t)n * 20) != hipSuccess) {
+        (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_sample_texture: query buffers");
+    }
+    hipError_t e = hipMemcpyAsync(d_ms, mat_slot, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tc, tc, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_sample_texture_wf(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
+        else launch_debug_sample_texture_mk(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && out_taps) e = hipMemcpyAsync(out_taps, d_taps, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_sample_texture: ") + hipGetErrorString(e));
+}
+
 int pt_scene_set_lights(pt_ctx* ctx, const pt_light* l, int count) {
     if (!ctx || (count > 0 && !l) || count < 0) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);

@@ -104,6 +104,8 @@ struct StageTimers {
     std::vector<uint8_t> kind;           // STAGE_* of the k-th launch
     size_t used = 0;                     // launches recorded by the last pt_trace
 };
+void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
+void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream);
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks);

@@ -137,6 +137,21 @@ void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n,
     hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_rays, n, rf, mode, d_out);
 }
 
+// Test hook (pt_debug_sample_texture, mipt_api.hip): the sampler as the megakernel runs it -- sRGB table and material records in global memory.
+__global__ __launch_bounds__(kBlock) void k_debug_sample_texture_mk(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
+                                                                 uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const vec2 uv[2] = {{tc[4 * i], tc[4 * i + 1]}, {tc[4 * i + 2], tc[4 * i + 3]}};
+    int32_t t5[5];
+    const vec4 r = debug_sample_query(sc, mat_slot[2 * i], (int)mat_slot[2 * i + 1], uv, t5);
+    out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
+    for (int c = 0; c < 5; c++) taps[5 * i + c] = t5[c];
+}
+void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_sample_texture_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
+}
 // Test hook (pt_debug_math): the kernels' own math routines on caller-supplied arguments, for the bit-for-bit comparison with the oracle's.
 // op: 0 atan2(a, b)  1 pow(a, b)  2 exp(a)  3 log2(a)  4 exp2(a)  5 sin(a)  6 cos(a)  7 a / b by fdiv  8 pow5(a)
 __global__ __launch_bounds__(256) void k_debug_math(int op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {

@@ -492,19 +492,26 @@ PT_DEV vec3 normal_adaptation(vec3 ng, vec3 ns, vec3 v) {          // PathTracer
     if (rdng < 0) return normalize(v + normalize(r - rdng * ng));
     return ns;
 }
-PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, const MatHeader& h, const HitGeom& a, vec3 view, unsigned& taps) {
-    Surface s;
-    s.emissive_texel = v3(0);
-    // The three usual PBR textures are fetched as ONE batch: their slot records are loaded together, their twelve texel
-    // gathers are issued together (unbound slots read a 1x1 white texel, so there is no branch to split the batch).
-    const uint32_t mid = (uint32_t)(m - sc.rmats);
+// The texels get_surface filters: the albedo / normal / metal-rough taps and the four texels of each footprint, and for RM_TRIO_EMISSIVE
+// materials the filtered emissive texel that came with the interleaved copy (zero otherwise).
+struct PbrTexels {
+    TexTaps k_alb, k_nrm, k_mr;
+    uint32_t a00, a10, a01, a11, n00, n10, n01, n11, m00, m10, m01, m11;
+    vec4 emissive;
+};
+// The three usual PBR textures are fetched as ONE batch: their slot records are loaded together, their twelve texel
+// gathers are issued together (unbound slots read a 1x1 white texel, so there is no branch to split the batch).
+// get_surface and the sampler's test hook (pt_debug_sample_texture) both fetch through this function.
+PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHeader& h, const vec2 tc[2]) {
+    PbrTexels f;
+    f.emissive = vec4{0, 0, 0, 0};
 #if PT_TEX_PAIRS && PT_TEX_TRIO
     // Materials whose three textures share one footprint (RM_TRIO, the usual glTF PBR set) read it from the interleaved copy: one set
     // of addresses and weights, two dwordx4 per texel row.  Both paths are wave-uniform branches; a wave of trio materials only (every
     // wave of the bench scene) never enters the general one.
     const bool trio = (h.bound_mask & RM_TRIO) != 0;
     const RTex t_alb = material_slot012(sc, mid, SLOT_ALBEDO);
-    const TexTaps k_alb = texture_taps(t_alb, a.tc);
+    const TexTaps k_alb = texture_taps(t_alb, tc);
     TexTaps k_nrm = k_alb, k_mr = k_alb;
     k_nrm.srgb = (h.bound_mask & RM_TRIO_SRGB_N) ? (uint32_t)RT_SRGB : 0u; k_mr.srgb = (h.bound_mask & RM_TRIO_SRGB_M) ? (uint32_t)RT_SRGB : 0u;
     uint32_t a00 = 0, a10 = 0, a01 = 0, a11 = 0, n00 = 0, n10 = 0, n01 = 0, n11 = 0, m00 = 0, m10 = 0, m01 = 0, m11 = 0;
@@ -524,14 +531,14 @@ PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, co
             if (h.bound_mask & RM_TRIO_EMISSIVE) {
                 TexTaps k_em = k_alb;
                 k_em.srgb = (h.bound_mask & RM_TRIO_SRGB_E) ? (uint32_t)RT_SRGB : 0u;
-                s.emissive_texel = xyz(resolve_taps(k_em, t00.w, t10.w, t01.w, t11.w, sc.srgb_lut));
+                f.emissive = resolve_taps(k_em, t00.w, t10.w, t01.w, t11.w, sc.srgb_lut);
             }
         }
     }
     if (__any(!trio)) {
         if (!trio) {
             const RTex t_nrm = material_slot012(sc, mid, SLOT_NORMAL), t_mr = material_slot012(sc, mid, SLOT_METALLIC_ROUGHNESS);
-            k_nrm = texture_taps(t_nrm, a.tc); k_mr = texture_taps(t_mr, a.tc);
+            k_nrm = texture_taps(t_nrm, tc); k_mr = texture_taps(t_mr, tc);
             const uint2 ar0 = tap_row(k_alb, 0), ar1 = tap_row(k_alb, 1), nr0 = tap_row(k_nrm, 0), nr1 = tap_row(k_nrm, 1), mr0 = tap_row(k_mr, 0), mr1 = tap_row(k_mr, 1);
             const TexQuad qa = tap_quad(k_alb, ar0, ar1), qn = tap_quad(k_nrm, nr0, nr1), qm = tap_quad(k_mr, mr0, mr1);
             a00 = qa.t00; a10 = qa.t10; a01 = qa.t01; a11 = qa.t11;
@@ -541,7 +548,7 @@ PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, co
     }
 #else
     const RTex t_alb = material_slot012(sc, mid, SLOT_ALBEDO), t_nrm = material_slot012(sc, mid, SLOT_NORMAL), t_mr = material_slot012(sc, mid, SLOT_METALLIC_ROUGHNESS);
-    const TexTaps k_alb = texture_taps(t_alb, a.tc), k_nrm = texture_taps(t_nrm, a.tc), k_mr = texture_taps(t_mr, a.tc);
+    const TexTaps k_alb = texture_taps(t_alb, tc), k_nrm = texture_taps(t_nrm, tc), k_mr = texture_taps(t_mr, tc);
 #if PT_TEX_PAIRS
     const uint2 ar0 = tap_row(k_alb, 0), ar1 = tap_row(k_alb, 1), nr0 = tap_row(k_nrm, 0), nr1 = tap_row(k_nrm, 1), mr0 = tap_row(k_mr, 0), mr1 = tap_row(k_mr, 1);
     const TexQuad qa = tap_quad(k_alb, ar0, ar1), qn = tap_quad(k_nrm, nr0, nr1), qm = tap_quad(k_mr, mr0, mr1);
@@ -554,6 +561,18 @@ PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, co
     const uint32_t m00 = gload(k_mr.p00), m10 = gload(k_mr.p10), m01 = gload(k_mr.p01), m11 = gload(k_mr.p11);
 #endif
 #endif
+    f.k_alb = k_alb; f.k_nrm = k_nrm; f.k_mr = k_mr;
+    f.a00 = a00; f.a10 = a10; f.a01 = a01; f.a11 = a11;
+    f.n00 = n00; f.n10 = n10; f.n01 = n01; f.n11 = n11;
+    f.m00 = m00; f.m10 = m10; f.m01 = m01; f.m11 = m11;
+    return f;
+}
+PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, const MatHeader& h, const HitGeom& a, vec3 view, unsigned& taps) {
+    Surface s;
+    const PbrTexels f = fetch_pbr_texels(sc, (uint32_t)(m - sc.rmats), h, a.tc);
+    s.emissive_texel = xyz(f.emissive);
+    const TexTaps &k_alb = f.k_alb, &k_nrm = f.k_nrm, &k_mr = f.k_mr;
+    const uint32_t a00 = f.a00, a10 = f.a10, a01 = f.a01, a11 = f.a11, n00 = f.n00, n10 = f.n10, n01 = f.n01, n11 = f.n11, m00 = f.m00, m10 = f.m10, m01 = f.m01, m11 = f.m11;
     const bool b_alb = slot_bound(h.bound_mask, SLOT_ALBEDO), b_nrm = slot_bound(h.bound_mask, SLOT_NORMAL), b_mr = slot_bound(h.bound_mask, SLOT_METALLIC_ROUGHNESS);
     taps += (b_alb ? 1u : 0u) + (b_nrm ? 1u : 0u) + (b_mr ? 1u : 0u);
     vec4 bc = h.base_color_factor * a.color;                                                      // GetBaseColor, Material.hlsli:98-106
@@ -616,6 +635,47 @@ PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, co
     s.cc_rough = hmax(s.cc_rough, kMinRoughness);
     if (flags & PT_FLAG_MATERIAL_USE_GEOMETRIC_NORMALS) { s.n = a.ng; s.cc_n = a.ng; }
     return s;
+}
+
+// Test hook (pt_debug_sample_texture): one texture query per lane, through the shade stage's own sampler.  slot 0..14: sample_slot;
+// 16..19: albedo, normal, metal-rough and emissive as get_surface fetches them (the interleaved copy for RM_TRIO materials, the batched
+// general path otherwise).  taps5: the columns i0, i1 and rows j0, j1 the footprint used, and the first column ia of the texel pair loaded
+// for each row.  Call with every lane of the wave that has a query.
+PT_DEV vec4 debug_sample_query(const SceneRec& sc, uint32_t mid, int slot, const vec2 tc[2], int32_t taps5[5]) {
+    const RMat* m = sc.rmats + mid;
+    unsigned taps = 0;
+    const uint32_t* base;
+    TexTaps k;
+    vec4 r;
+    if (slot < SLOT_COUNT) {
+        const RTex t = load_rtex(&m->tex[slot]);
+        k = texture_taps(t, tc); base = t.texels;
+        r = sample_slot(sc, m, slot, tc, taps);
+    } else {
+        const MatHeader h = material_header(sc, mid);
+        const PbrTexels f = fetch_pbr_texels(sc, mid, h, tc);
+        const int s = slot == 16 ? SLOT_ALBEDO : slot == 17 ? SLOT_NORMAL : slot == 18 ? SLOT_METALLIC_ROUGHNESS : SLOT_EMISSIVE;
+#if PT_TEX_PAIRS && PT_TEX_TRIO
+        const bool trio = (h.bound_mask & RM_TRIO) != 0;
+#else
+        const bool trio = false;
+#endif
+        const RTex t = load_rtex(&m->tex[trio ? SLOT_ALBEDO : s]);  // the texture whose rows the footprint's pointers index
+        base = t.texels;
+        if (slot == 16) { k = f.k_alb; r = resolve_taps(k, f.a00, f.a10, f.a01, f.a11, sc.srgb_lut); }
+        else if (slot == 17) { k = f.k_nrm; r = resolve_taps(k, f.n00, f.n10, f.n01, f.n11, sc.srgb_lut); }
+        else if (slot == 18) { k = f.k_mr; r = resolve_taps(k, f.m00, f.m10, f.m01, f.m11, sc.srgb_lut); }
+        else if (trio && (h.bound_mask & RM_TRIO_EMISSIVE)) { k = f.k_alb; r = f.emissive; }
+        else { const RTex te = load_rtex(&m->tex[SLOT_EMISSIVE]); k = texture_taps(te, tc); base = te.texels; r = sample_slot(sc, m, SLOT_EMISSIVE, tc, taps); }
+    }
+#if PT_TEX_PAIRS
+    taps5[0] = k.i0; taps5[1] = k.i1;
+    taps5[2] = (int32_t)((k.p0 - base) / k.width); taps5[3] = (int32_t)((k.p1 - base) / k.width);
+    taps5[4] = k.ia;
+#else
+    (void)k; (void)base; taps5[0] = taps5[1] = taps5[2] = taps5[3] = taps5[4] = -1;     // (the four-gather build keeps no columns)
+#endif
+    return r;
 }
 
 // ---------------------------------------------------------------- BSDF terms (Bsdf.hlsli)

@@ -788,6 +788,23 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_shadow(SceneRec s
     else if (st.overflow | st.deep) flush_rare(counters, st);
 }
 
+// Test hook (pt_debug_sample_texture, mipt_api.hip): the sampler as this file's stages run it -- sRGB table and material records in LDS.
+__global__ __launch_bounds__(kBlock) void k_debug_sample_texture_wf(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
+                                                                 uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
+    stage_luts(sc);
+    stage_materials(sc);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const vec2 uv[2] = {{tc[4 * i], tc[4 * i + 1]}, {tc[4 * i + 2], tc[4 * i + 3]}};
+    int32_t t5[5];
+    const vec4 r = debug_sample_query(sc, mat_slot[2 * i], (int)mat_slot[2 * i + 1], uv, t5);
+    out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
+    for (int c = 0; c < 5; c++) taps[5 * i + c] = t5[c];
+}
+void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_sample_texture_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
+}
 __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output) {
     const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;       // pixel slot; its samples sit pixel_slots apart
     uint32_t px, py;

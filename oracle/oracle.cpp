@@ -1406,6 +1406,17 @@ void orc_sample_bsdf(void* h, uint32_t flags, const float* sp36, const float* u3
 void orc_sample_texture(void* h, int tex, int sampler, const float* uv, float* out4) {
     Oracle* o = (Oracle*)h; float4 r = SampleLevel0(o->textures[tex], o->samplers[sampler], {uv[0], uv[1]}); out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
 }
+// SampleTexture of one material slot (0 normal, 1 albedo, 2 metal-rough, 3 occlusion, 4 emissive, 5 specular, ..., 14 thickness: the order
+// of the Material record's texture addresses); tc4 = tc0.xy, tc1.xy.  An unbound slot gives white, as the product's unbound slots do.
+void orc_sample_material_slot(void* h, int material, int slot, const float* tc4, float* out4) {
+    Oracle* o = (Oracle*)h; const Material& m = o->materials[material];
+    const TextureAddress* s[15] = {&m.normal, &m.albedo, &m.metallic_roughness, &m.occlusion, &m.emissive, &m.specular, &m.specular_color, &m.clearcoat,
+                                   &m.clearcoat_roughness, &m.clearcoat_normal, &m.anisotropy, &m.sheen_color, &m.sheen_roughness, &m.transmission, &m.thickness};
+    const float2 tc[2] = {{tc4[0], tc4[1]}, {tc4[2], tc4[3]}};
+    float4 r = {1, 1, 1, 1};
+    if (s[slot]->descriptor != -1) r = SampleTexture(*o, *s[slot], tc);
+    out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
+}
 void orc_sample_cube(void* h, int env, const float* d, float level, float* out3) {
     float3 r = SampleCubeLevel(((Oracle*)h)->envs[env], {d[0], d[1], d[2]}, level); out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
 }

@@ -78,6 +78,8 @@ def lib():
         L.orc_evaluate_bsdf.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_sample_bsdf.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_sample_texture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_sample_material_slot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_sample_material_slot.restype = None
         L.orc_sample_importance_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_decode_tangent_space.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_random.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
@@ -218,6 +220,21 @@ class Oracle:
         else:
             arr = (abi.PtBone * len(bones))(*bones)
             self.L.orc_skin_run(self.h, C.byref(params), C.byref(arr), len(bones))
+
+    def sample_material_slot(self, material, slot, tc):
+        """SampleTexture of material slot `slot` (0..14, the Material record's order) at tc = (tc0.x, tc0.y, tc1.x, tc1.y), as RGBA.
+        tc may also be (n, 4) with material and slot arrays of length n: the n queries one after another."""
+        tc = _f(tc)
+        if tc.ndim == 1:
+            out = np.zeros(4, np.float32)
+            self.L.orc_sample_material_slot(self.h, int(material), int(slot), _p(tc), _p(out))
+            return out
+        out = np.zeros((len(tc), 4), np.float32)
+        f, h = self.L.orc_sample_material_slot, self.h
+        base_tc, base_out = tc.ctypes.data, out.ctypes.data
+        for i, (m, k) in enumerate(zip(np.asarray(material).tolist(), np.asarray(slot).tolist())):
+            f(h, m, k, base_tc + 16 * i, base_out + 16 * i)
+        return out
 
     def trace(self, settings, params, output, nthreads=None):
         """output: float32 array (H, W, 4), modified in place (the accumulation target)."""
