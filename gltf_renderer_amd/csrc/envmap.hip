@@ -85,9 +85,8 @@ __global__ __launch_bounds__(256) void k_importance_block(const float* __restric
     out[((size_t)(y >> 2) * (n >> 2) + (x >> 2)) * 16 + (y & 3) * 4 + (x & 3)] = in[(size_t)y * n + x];
 }
 
-hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStream_t stream) {
-    int N = (w / 4) / 2;
-    N = (N > 1 ? N : 1) + 1;                                     // EnvironmentMap.cpp:92 (quirk q11)
+// The cube's mip layout for mip-0 size N and the device memory of the cube chain and the sum pyramid.
+static hipError_t env_alloc(EnvDevice& e, int N) {
     e.mips = 0;
     size_t off = 0;
     for (int n = N;; n >>= 1) {
@@ -99,13 +98,43 @@ hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStr
     e.levels = 0;
     uint32_t lo = 0;
     for (int r = e.imp_res; r >= 1; r >>= 1) { e.level_offset[e.levels++] = lo; lo += (uint32_t)r * r; }
-    if ((err = hipMalloc(&e.importance, (size_t)lo * 4))) return err;
-    hipLaunchKernelGGL(k_equirect_to_cube, dim3((N + 255) / 256, N, 6), dim3(256), 0, stream, d_equirect, w, h, e.cube, N);
+    return hipMalloc(&e.importance, (size_t)lo * 4);
+}
+
+static void env_cube_mips(EnvDevice& e, hipStream_t stream) {
     for (int l = 1; l < e.mips; l++) {
         int n = e.mip_n[l];
         hipLaunchKernelGGL(k_cube_mip, dim3((n + 255) / 256, n, 6), dim3(256), 0, stream, e.cube + e.mip_offset[l - 1], e.mip_n[l - 1],
                            e.cube + e.mip_offset[l], n);
     }
+}
+
+// What the sampler needs beyond the pyramid: its blocked copies and its apex.  Shared by env_build and env_build_raw.
+static hipError_t env_finish(EnvDevice& e, hipStream_t stream) {
+    // blocked copies for the two-levels-per-fetch sampling descent (pt_shading.h sample_importance_map)
+    static_assert(sizeof(e.blocked_offset) / sizeof(e.blocked_offset[0]) == 5, "five level pairs");
+    if (e.imp_res != 1024 || e.levels != 11) return hipErrorInvalidValue;       // IMPORTANCE_MAP_SIZE is a constant of the reference
+    hipError_t err;
+    uint32_t bo = 0;
+    for (int k = 0; k < 5; k++) { int n = 4 << (2 * k); e.blocked_offset[k] = bo; bo += (uint32_t)n * n; }
+    if ((err = hipMalloc(&e.blocked, (size_t)bo * 4))) return err;
+    for (int k = 0; k < 5; k++) {
+        int n = 4 << (2 * k), l = 8 - 2 * k;                     // level l has resolution 1024 >> l
+        hipLaunchKernelGGL(k_importance_block, dim3((n + 255) / 256, n), dim3(256), 0, stream, e.importance + e.level_offset[l],
+                           e.blocked + e.blocked_offset[k], n);
+    }
+    if ((err = hipMemcpyAsync(&e.total, e.importance + e.level_offset[e.levels - 1], 4, hipMemcpyDeviceToHost, stream))) return err;
+    if ((err = hipStreamSynchronize(stream))) return err;
+    return hipGetLastError();
+}
+
+hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStream_t stream) {
+    int N = (w / 4) / 2;
+    N = (N > 1 ? N : 1) + 1;                                     // EnvironmentMap.cpp:92 (quirk q11)
+    hipError_t err;
+    if ((err = env_alloc(e, N))) return err;
+    hipLaunchKernelGGL(k_equirect_to_cube, dim3((N + 255) / 256, N, 6), dim3(256), 0, stream, d_equirect, w, h, e.cube, N);
+    env_cube_mips(e, stream);
     // mip_level = clamp(log2((6*N)/1024), 0, mips) with INTEGER division (quirk q10)
     float level = log2f((float)((6u * (uint32_t)N) / (uint32_t)e.imp_res));
     level = level < 0 || !(level == level) ? 0.f : level;       // log2(0) = -inf clamps to 0
@@ -119,20 +148,16 @@ hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStr
         hipLaunchKernelGGL(k_importance_level, dim3((n + 255) / 256, n), dim3(256), 0, stream, e.importance + e.level_offset[l - 1],
                            e.importance + e.level_offset[l], n);
     }
-    // blocked copies for the two-levels-per-fetch sampling descent (pt_shading.h sample_importance_map)
-    static_assert(sizeof(e.blocked_offset) / sizeof(e.blocked_offset[0]) == 5, "five level pairs");
-    if (e.imp_res != 1024 || e.levels != 11) return hipErrorInvalidValue;       // IMPORTANCE_MAP_SIZE is a constant of the reference
-    uint32_t bo = 0;
-    for (int k = 0; k < 5; k++) { int n = 4 << (2 * k); e.blocked_offset[k] = bo; bo += (uint32_t)n * n; }
-    if ((err = hipMalloc(&e.blocked, (size_t)bo * 4))) return err;
-    for (int k = 0; k < 5; k++) {
-        int n = 4 << (2 * k), l = 8 - 2 * k;                     // level l has resolution 1024 >> l
-        hipLaunchKernelGGL(k_importance_block, dim3((n + 255) / 256, n), dim3(256), 0, stream, e.importance + e.level_offset[l],
-                           e.blocked + e.blocked_offset[k], n);
-    }
-    if ((err = hipMemcpyAsync(&e.total, e.importance + e.level_offset[e.levels - 1], 4, hipMemcpyDeviceToHost, stream))) return err;
-    if ((err = hipStreamSynchronize(stream))) return err;
-    return hipGetLastError();
+    return env_finish(e, stream);
+}
+
+hipError_t env_build_raw(EnvDevice& e, int n, const uint16_t* cube_rgba16f, const float* pyramid, hipStream_t stream) {
+    hipError_t err;
+    if ((err = env_alloc(e, n))) return err;
+    if ((err = hipMemcpyAsync(e.cube, cube_rgba16f, (size_t)6 * n * n * 4 * 2, hipMemcpyHostToDevice, stream))) return err;
+    if ((err = hipMemcpyAsync(e.importance, pyramid, (size_t)(e.level_offset[e.levels - 1] + 1) * 4, hipMemcpyHostToDevice, stream))) return err;
+    env_cube_mips(e, stream);
+    return env_finish(e, stream);
 }
 
 void env_free(EnvDevice& e) {

@@ -945,6 +945,66 @@ extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* ma
     return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_sample_texture: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the environment light on caller-supplied queries, one per lane (pt_vertex.h debug_env_query:
+// op 0 SAMPLE, 1 PDF, 2 CUBE, 3 MISS; 8 input and 16 output floats per query).  unit 0: the wavefront stages' build (the coarse pyramid
+// levels staged into LDS as env_prepass stages them), 1: the megakernel's (global memory).
+extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const float* in, uint32_t n, float* out) {
+    if (!ctx || unit < 0 || unit > 1 || op < 0 || op > 3 || (n && (!in || !out))) return PT_ERR_INVALID_ARGUMENT;
+    if (env < 0 || env >= (int)ctx->envs.size() || !ctx->envs[env]) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_query: environment " + std::to_string(env));
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    const EnvDevice& ed = *ctx->envs[env];
+    SceneRec sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.env.cube = ed.cube; sc.env.cube_n = ed.mip_n[0]; sc.env.importance = ed.importance;
+    for (int i = 0; i < 12; i++) sc.env.level_offset[i] = ed.level_offset[i];
+    sc.env.imp_res = ed.imp_res; sc.env.imp_levels = ed.levels; sc.env.imp_total = ed.total;
+    sc.env.blocked = ed.blocked;
+    for (int i = 0; i < 5; i++) sc.env.blocked_offset[i] = ed.blocked_offset[i];
+    sc.has_env = 1;
+    const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 16 * 4;
+    float *d_in = nullptr, *d_out = nullptr;
+    auto done = [&](int code, const std::string& why) { hipFree(d_in); hipFree(d_out); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
+    if (hipMalloc((void**)&d_in, in_bytes) != hipSuccess || hipMalloc((void**)&d_out, out_bytes) != hipSuccess) {
+        (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_env_query: query buffers");
+    }
+    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, ctx->stream);      // unused outputs keep the caller's values
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in, n, d_out, ctx->stream);
+        else launch_debug_env_query_mk(sc, op, d_in, n, d_out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_env_query: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid
+// (level 0 first), as the oracle's orc_env_create_raw takes them -- so both sides can sample a crafted pyramid.
+extern "C" int pt_debug_env_create_raw(pt_ctx* ctx, int cube_n, const uint16_t* cube_rgba16f, const float* pyramid, int* env_out) {
+    if (!ctx || cube_n < 1 || cube_n > 16384 || !cube_rgba16f || !pyramid || !env_out) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    EnvDevice* env = new EnvDevice();
+    hipError_t e = env_build_raw(*env, cube_n, cube_rgba16f, pyramid, ctx->stream);
+    if (e) { env_free(*env); delete env; return ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_create_raw: ") + hipGetErrorString(e)); }
+    if (!ctx->free_envs.empty()) { *env_out = ctx->free_envs.back(); ctx->free_envs.pop_back(); ctx->envs[*env_out] = env; }
+    else { ctx->envs.push_back(env); *env_out = (int)ctx->envs.size() - 1; }
+    return PT_OK;
+}
+
+// test hook (not part of include/mipt.h): the five 4x4-blocked copies of pyramid levels 8, 6, 4, 2, 0 (EnvRec::blocked: 4^2 + 16^2 + 64^2 +
+// 256^2 + 1024^2 = 1118480 floats, coarsest first), as the sampler reads them.
+extern "C" int pt_debug_env_read_blocked(pt_ctx* ctx, int env, float* out) {
+    if (!ctx || !out) return PT_ERR_INVALID_ARGUMENT;
+    if (env < 0 || env >= (int)ctx->envs.size() || !ctx->envs[env]) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_read_blocked: environment " + std::to_string(env));
+    ENTER(ctx);
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const EnvDevice& ed = *ctx->envs[env];
+    HIPOK(hipMemcpy(out, ed.blocked, (size_t)(ed.blocked_offset[4] + 1024u * 1024u) * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 int pt_scene_set_lights(pt_ctx* ctx, const pt_light* l, int count) {
     if (!ctx || (count > 0 && !l) || count < 0) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);

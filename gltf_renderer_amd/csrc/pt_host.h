@@ -73,6 +73,8 @@ struct EnvDevice {
     float total = 0.f;                 // the pyramid's apex (sum of the whole map), read back once: a kernel argument instead of a load per sample
 };
 hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStream_t stream);
+// A map from a cube mip 0 (n x n RGBA16F faces) and a whole sum pyramid given on the host (test hook pt_debug_env_create_raw)
+hipError_t env_build_raw(EnvDevice& e, int n, const uint16_t* cube_rgba16f, const float* pyramid, hipStream_t stream);
 void env_free(EnvDevice& e);
 
 // ---- skin_tonemap.hip -------------------------------------------------------------------------
@@ -106,6 +108,8 @@ struct StageTimers {
 };
 void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
 void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
+void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream);
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks);

@@ -152,6 +152,16 @@ void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_sl
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_sample_texture_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
 }
+// Test hook (pt_debug_env_query, mipt_api.hip): the environment light as the megakernel runs it -- the whole pyramid in global memory.
+__global__ __launch_bounds__(kBlock) void k_debug_env_query_mk(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_env_query(sc, op, in + (size_t)kEnvQueryIn * i, out + (size_t)kEnvQueryOut * i, importance_lds_top());
+}
+void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_env_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
+}
 // Test hook (pt_debug_math): the kernels' own math routines on caller-supplied arguments, for the bit-for-bit comparison with the oracle's.
 // op: 0 atan2(a, b)  1 pow(a, b)  2 exp(a)  3 log2(a)  4 exp2(a)  5 sin(a)  6 cos(a)  7 a / b by fdiv  8 pow5(a)
 __global__ __launch_bounds__(256) void k_debug_math(int op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {

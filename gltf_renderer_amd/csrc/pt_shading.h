@@ -1122,18 +1122,27 @@ PT_DEV size_t cube_tap_index(int n, int face, int i, int j) {
 PT_DEV vec3 cube_unpack(uint2 q) {                                       // 8-B RGBA16F texel
     return {half_bits_to_float((uint16_t)(q.x & 0xffff)), half_bits_to_float((uint16_t)(q.x >> 16)), half_bits_to_float((uint16_t)(q.y & 0xffff))};
 }
-// TextureCube.SampleLevel(linear, dir, 0) (PathTracer.lib.hlsl:700,1042)
-PT_DEV vec3 sample_cube(const uint16_t* cube, int n, vec3 d) {
+// The bilinear footprint of TextureCube.SampleLevel(linear, dir, 0): the texel index of each of the four taps (after re-projection)
+// and its weight, in the order 00, 10, 01, 11.  False for a direction without a face (NaN components, the zero vector).
+PT_DEV bool cube_footprint(int n, vec3 d, size_t a[4], float w[4]) {
     int face; float u, v;
     dir_to_face(d, face, u, v);
-    if (!(u == u) || !(v == v)) return v3(0);
+    if (!(u == u) || !(v == v)) return false;
     float x = u * (float)n - 0.5f, y = v * (float)n - 0.5f;
     float fx0 = floorf(x), fy0 = floorf(y);
     float fx = x - fx0, fy = y - fy0;
     int i0 = (int)fx0, j0 = (int)fy0;
-    float w00 = (1 - fx) * (1 - fy), w10 = fx * (1 - fy), w01 = (1 - fx) * fy, w11 = fx * fy;
-    const size_t a00 = cube_tap_index(n, face, i0, j0), a10 = cube_tap_index(n, face, i0 + 1, j0);
-    const size_t a01 = cube_tap_index(n, face, i0, j0 + 1), a11 = cube_tap_index(n, face, i0 + 1, j0 + 1);
+    w[0] = (1 - fx) * (1 - fy); w[1] = fx * (1 - fy); w[2] = (1 - fx) * fy; w[3] = fx * fy;
+    a[0] = cube_tap_index(n, face, i0, j0); a[1] = cube_tap_index(n, face, i0 + 1, j0);
+    a[2] = cube_tap_index(n, face, i0, j0 + 1); a[3] = cube_tap_index(n, face, i0 + 1, j0 + 1);
+    return true;
+}
+// TextureCube.SampleLevel(linear, dir, 0) (PathTracer.lib.hlsl:700,1042)
+PT_DEV vec3 sample_cube(const uint16_t* cube, int n, vec3 d) {
+    size_t a[4]; float w[4];
+    if (!cube_footprint(n, d, a, w)) return v3(0);
+    const size_t a00 = a[0], a10 = a[1], a01 = a[2], a11 = a[3];
+    const float w00 = w[0], w10 = w[1], w01 = w[2], w11 = w[3];
     const uint2* texels = (const uint2*)cube;
     const uint2 q00 = gload_u2(texels + a00), q10 = gload_u2(texels + a10), q01 = gload_u2(texels + a01), q11 = gload_u2(texels + a11);
     return cube_unpack(q00) * w00 + cube_unpack(q10) * w10 + cube_unpack(q01) * w01 + cube_unpack(q11) * w11;
@@ -1178,12 +1187,13 @@ PT_DEV void stage_importance_top(const SceneRec&) {}
 PT_DEV const float4* importance_lds_top() { return nullptr; }
 #endif
 // `lds_top`: the three coarsest level pairs in LDS (importance_lds_top() or a caller's staging), unused when kImpLdsLevels == 0
-PT_DEV vec2 sample_importance_map(const EnvRec& e, float ux, float uy, float& pdf, const float4* lds_top) {    // Sampling.hlsli:123-163
+// px_out / py_out: the level-0 texel the descent chose (the test hook reads them; production discards them)
+PT_DEV vec2 sample_importance_map_texel(const EnvRec& e, float ux, float uy, float& pdf, const float4* lds_top, uint32_t& px_out, uint32_t& py_out) {   // Sampling.hlsli:123-163
     // The reference descends ten levels with four dependent point loads each.  Here one 64-B fetch of a 4x4 block of the
     // finer level of a pair serves two levels: the coarser level's 2x2 values are re-summed from the block in the order the
     // pyramid build uses (k_importance_level: ((ul + ll) + ur) + lr), which reproduces the stored sums bit for bit.
 #ifdef PT_PROBE_NO_DESCENT      // PROBE ONLY: what the five-level descent costs the shade stage (wrong sampling, timing only)
-    pdf = 1.0f;
+    pdf = 1.0f; px_out = py_out = 0;
     return {ux, uy};
 #endif
     uint32_t px = 0, py = 0;
@@ -1207,8 +1217,13 @@ PT_DEV vec2 sample_importance_map(const EnvRec& e, float ux, float uy, float& pd
         py = (py << 2) | (sy << 1) | ty;
     }
     float w = (float)e.imp_res;
+    px_out = px; py_out = py;
     pdf = fdiv(w * w * value, e.imp_total);                          // value = level-0 texel (px, py); imp_total = mips[10][0]
     return {fdiv((float)px + ux, w), fdiv((float)py + uy, w)};      // both axes / width (quirk q10)
+}
+PT_DEV vec2 sample_importance_map(const EnvRec& e, float ux, float uy, float& pdf, const float4* lds_top) {
+    uint32_t px, py;
+    return sample_importance_map_texel(e, ux, uy, pdf, lds_top, px, py);
 }
 // SampleEnvironmentMap's hit-independent half (PathTracer.lib.hlsl:688-703): direction, solid-angle pdf and radiance of the sample
 // the random numbers (u0, u1) pick.  It depends on the pixel's random sequence only, never on the hit, which is what lets the

@@ -30,17 +30,66 @@ struct Followups {
     uint32_t hint_env, hint_light;   // occluder-cache words of the two shadow rays (fetched here, early, so that the push does not wait for them)
 };
 
+// The environment-map branch of Miss, in three parts (shade_miss and the test hook pt_debug_env_query call them): the radiance along
+// `dir`, the solid-angle pdf with which environment_light_sample would have drawn it, and the balance-heuristic weight.
+PT_DEV vec3 miss_environment_color(const SceneRec& sc, float environment_intensity, vec3 dir) {
+    return sc.has_env ? environment_intensity * sample_cube(sc.env.cube, sc.env.cube_n, dir) : v3(0);
+}
+PT_DEV float miss_environment_pdf(const SceneRec& sc, vec3 dir) {
+    return sc.has_env ? fdiv(importance_map_pdf(sc.env, square_to_uv(sphere_to_square(normalize(dir)))), 4 * kPi) : 0.f;
+}
+// IEEE division, not fdiv: the previous bounce's pdf can be subnormal, and so can the quotient -- outside fdiv's contract, where its
+// result parted from the oracle's (tests/test_gpu_envmap.py).  One division per escaping path.
+PT_DEV float miss_mis_weight(float prev_pdf, float env_pdf) { return prev_pdf / (prev_pdf + env_pdf); }   // BalanceHeuristic :383-386
+
 PT_DEV vec3 shade_miss(const SceneRec& sc, const FrameConstants& fc, vec3 dir, const PathState& ps) {
     const uint32_t flags = fc.flags;
     vec3 c;
     if (flags & PT_FLAG_ENVIRONMENT_MAP) {
-        c = sc.has_env ? fc.environment_intensity * sample_cube(sc.env.cube, sc.env.cube_n, dir) : v3(0);
-        if ((flags & PT_FLAG_ENVIRONMENT_MIS) && ps.prev_mis) {
-            float env_pdf = sc.has_env ? fdiv(importance_map_pdf(sc.env, square_to_uv(sphere_to_square(normalize(dir)))), 4 * kPi) : 0.f;
-            c *= fdiv(ps.prev_pdf, ps.prev_pdf + env_pdf);                                              // BalanceHeuristic :383-386
-        }
+        c = miss_environment_color(sc, fc.environment_intensity, dir);
+        if ((flags & PT_FLAG_ENVIRONMENT_MIS) && ps.prev_mis) c *= miss_mis_weight(ps.prev_pdf, miss_environment_pdf(sc, dir));
     } else c = fc.environment_intensity * v3p(fc.environment_color);
     return ps.beta * c;
+}
+
+// Test hook (pt_debug_env_query): one environment-light query per lane, through the production functions.  `in` holds 8 floats and `out`
+// 16 floats per query (unused outputs are left alone); `lds_top` as for sample_importance_map.
+//   op 0 SAMPLE  in u0, u1, environment_intensity   out sample_importance_map's uv.x, uv.y, pdf, px, py; environment_light_sample's
+//                                                    dir.xyz, pdf, color.rgb
+//   op 1 PDF     in uv.x, uv.y                       out importance_map_pdf(uv)
+//   op 2 CUBE    in dir.xyz                          out sample_cube(dir).rgb, then (face, i, j) of the taps 00, 10, 01, 11 after
+//                                                    re-projection (-1 for a direction without a face)
+//   op 3 MISS    in dir.xyz, prev_pdf, intensity     out miss colour.rgb, env_pdf, MIS-weighted colour.rgb
+constexpr int kEnvQueryIn = 8, kEnvQueryOut = 16;
+PT_DEV void debug_env_query(const SceneRec& sc, int op, const float* __restrict__ in, float* __restrict__ out, const float4* lds_top) {
+    if (op == 0) {
+        float pdf;
+        uint32_t px, py;
+        const vec2 uv = sample_importance_map_texel(sc.env, in[0], in[1], pdf, lds_top, px, py);
+        const EnvSample e = environment_light_sample(sc, in[2], in[0], in[1], lds_top);
+        out[0] = uv.x; out[1] = uv.y; out[2] = pdf; out[3] = (float)px; out[4] = (float)py;
+        out[5] = e.dir.x; out[6] = e.dir.y; out[7] = e.dir.z; out[8] = e.pdf; out[9] = e.color.x; out[10] = e.color.y; out[11] = e.color.z;
+    } else if (op == 1) {
+        out[0] = importance_map_pdf(sc.env, {in[0], in[1]});
+    } else if (op == 2) {
+        const vec3 d = {in[0], in[1], in[2]};
+        const vec3 c = sample_cube(sc.env.cube, sc.env.cube_n, d);
+        out[0] = c.x; out[1] = c.y; out[2] = c.z;
+        size_t a[4]; float w[4];
+        const bool ok = cube_footprint(sc.env.cube_n, d, a, w);
+        const size_t n = (size_t)sc.env.cube_n;
+        for (int t = 0; t < 4; t++) {
+            out[3 + 3 * t] = ok ? (float)(a[t] / (n * n)) : -1.0f;
+            out[4 + 3 * t] = ok ? (float)(a[t] % n) : -1.0f;
+            out[5 + 3 * t] = ok ? (float)(a[t] / n % n) : -1.0f;
+        }
+    } else {
+        const vec3 d = {in[0], in[1], in[2]};
+        const vec3 c = miss_environment_color(sc, in[4], d);
+        const float env_pdf = miss_environment_pdf(sc, d);
+        const vec3 m = c * miss_mis_weight(in[3], env_pdf);
+        out[0] = c.x; out[1] = c.y; out[2] = c.z; out[3] = env_pdf; out[4] = m.x; out[5] = m.y; out[6] = m.z;
+    }
 }
 
 // Returns true when the path ends at this vertex for a debug output (fu.add holds beta * debug colour).

@@ -805,6 +805,22 @@ void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_sl
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_sample_texture_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
 }
+// Test hook (pt_debug_env_query, mipt_api.hip): the environment light as this file's stages run it -- the three coarsest level pairs of the
+// importance pyramid staged, as env_prepass stages them, into LDS of the traversal stack's type and size.  Every lane stages before any
+// lane without a query leaves.
+__global__ __launch_bounds__(kBlock) void k_debug_env_query_wf(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    __shared__ int s_stack[kStackLds * kBlock];
+    static_assert((size_t)kStackLds * kBlock * sizeof(int) >= (size_t)kImpLdsFloat4 * sizeof(float4), "the traversal stack's LDS must hold the importance pyramid's coarse levels");
+    float4* top = (float4*)s_stack;
+    stage_importance_top_into(sc, top);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_env_query(sc, op, in + (size_t)kEnvQueryIn * i, out + (size_t)kEnvQueryOut * i, top);
+}
+void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_env_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
+}
 __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output) {
     const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;       // pixel slot; its samples sit pixel_slots apart
     uint32_t px, py;

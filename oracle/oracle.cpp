@@ -142,34 +142,39 @@ static inline float3 cube_texel(const std::vector<uint16_t>& mip, int n, int fac
 }
 // One bilinear tap with seamless edges: a tap outside the face is re-projected through its
 // direction onto the neighbouring face and fetched point-wise there.
-static float3 cube_tap(const std::vector<uint16_t>& mip, int n, int face, int i, int j) {
-    if (i >= 0 && i < n && j >= 0 && j < n) return cube_texel(mip, n, face, i, j);
-    float2 uv = {((float)i + 0.5f) / (float)n, ((float)j + 0.5f) / (float)n};
-    float3 d = CubemapToDirection(face, uv);
-    int f2; float u, v;
-    dir_to_face(d, f2, u, v);
-    int ii = (int)floorf(u * (float)n), jj = (int)floorf(v * (float)n);
-    ii = ii < 0 ? 0 : (ii >= n ? n - 1 : ii); jj = jj < 0 ? 0 : (jj >= n ? n - 1 : jj);
-    return cube_texel(mip, n, f2, ii, jj);
+// `tap` (may be null): the (face, i, j) fetched, for the query export orc_env_query_many
+static float3 cube_tap(const std::vector<uint16_t>& mip, int n, int face, int i, int j, int* tap = nullptr) {
+    if (!(i >= 0 && i < n && j >= 0 && j < n)) {
+        float2 uv = {((float)i + 0.5f) / (float)n, ((float)j + 0.5f) / (float)n};
+        float3 d = CubemapToDirection(face, uv);
+        float u, v;
+        dir_to_face(d, face, u, v);
+        i = (int)floorf(u * (float)n), j = (int)floorf(v * (float)n);
+        i = i < 0 ? 0 : (i >= n ? n - 1 : i); j = j < 0 ? 0 : (j >= n ? n - 1 : j);
+    }
+    if (tap) { tap[0] = face; tap[1] = i; tap[2] = j; }
+    return cube_texel(mip, n, face, i, j);
 }
-static float3 SampleCubeMip(const std::vector<uint16_t>& mip, int n, float3 d) {
+// taps12 (may be null): (face, i, j) of the taps 00, 10, 01, 11; -1 for a direction without a face
+static float3 SampleCubeMip(const std::vector<uint16_t>& mip, int n, float3 d, int* taps12 = nullptr) {
     int face; float u, v;
     dir_to_face(d, face, u, v);
-    if (!(u == u) || !(v == v)) return {0, 0, 0};
+    if (!(u == u) || !(v == v)) { if (taps12) for (int k = 0; k < 12; k++) taps12[k] = -1; return {0, 0, 0}; }
     float x = u * (float)n - 0.5f, y = v * (float)n - 0.5f;
     float fx0 = floorf(x), fy0 = floorf(y);
     float fx = x - fx0, fy = y - fy0;
     int i0 = (int)fx0, j0 = (int)fy0;
     float w00 = (1 - fx) * (1 - fy), w10 = fx * (1 - fy), w01 = (1 - fx) * fy, w11 = fx * fy;
-    return cube_tap(mip, n, face, i0, j0) * w00 + cube_tap(mip, n, face, i0 + 1, j0) * w10 +
-           cube_tap(mip, n, face, i0, j0 + 1) * w01 + cube_tap(mip, n, face, i0 + 1, j0 + 1) * w11;
+    return cube_tap(mip, n, face, i0, j0, taps12) * w00 + cube_tap(mip, n, face, i0 + 1, j0, taps12 ? taps12 + 3 : nullptr) * w10 +
+           cube_tap(mip, n, face, i0, j0 + 1, taps12 ? taps12 + 6 : nullptr) * w01 + cube_tap(mip, n, face, i0 + 1, j0 + 1, taps12 ? taps12 + 9 : nullptr) * w11;
 }
-static float3 SampleCubeLevel(const EnvMap& e, float3 d, float level) {
+// taps12: those of mip floor(level)
+static float3 SampleCubeLevel(const EnvMap& e, float3 d, float level, int* taps12 = nullptr) {
     int nm = (int)e.cube.size();
     level = clamp(level, 0.f, (float)(nm - 1));
     int l0 = (int)floorf(level), l1 = l0 + 1 < nm ? l0 + 1 : l0;
     float f = level - (float)l0;
-    float3 a = SampleCubeMip(e.cube[l0], e.cube_n[l0], d);
+    float3 a = SampleCubeMip(e.cube[l0], e.cube_n[l0], d, taps12);
     if (f == 0 || l1 == l0) return a;
     float3 b = SampleCubeMip(e.cube[l1], e.cube_n[l1], d);
     return a * (1 - f) + b * f;
@@ -559,7 +564,8 @@ static inline float imp_load(const EnvMap& e, int level, uint32_t x, uint32_t y)
     if (x >= n || y >= n) return 0.f;             // out-of-range Load returns 0
     return e.imp[level][(size_t)y * n + x];
 }
-static float2 SampleImportanceMap(const EnvMap& e, float2 u, float& pdf) {     // :123-163
+// texel (may be null): the level-0 texel (px, py) the descent chose
+static float2 SampleImportanceMap(const EnvMap& e, float2 u, float& pdf, uint32_t* texel = nullptr) {     // :123-163
     uint32_t width = e.imp_res, height = e.imp_res; int mips = (int)e.imp.size();
     pdf = 1;
     uint32_t px = 0, py = 0;
@@ -581,6 +587,7 @@ static float2 SampleImportanceMap(const EnvMap& e, float2 u, float& pdf) {     /
             else { py++; u.y = (u.y - prob_upper) / (1 - prob_upper); }
         }
     }
+    if (texel) { texel[0] = px; texel[1] = py; }
     pdf = (float)width * (float)height * imp_load(e, 0, px, py) / imp_load(e, mips - 1, 0, 0);
     return {((float)px + u.x) / (float)width, ((float)py + u.y) / (float)width};   // both / width (quirk q10)
 }
@@ -590,6 +597,24 @@ static float ImportanceMapPdf(const EnvMap& e, float2 uv) {                    /
     int2 p = UVToPixel(uv, {e.imp_res, e.imp_res});
     float value = (p.x < 0 || p.y < 0) ? 0.f : imp_load(e, 0, (uint32_t)p.x, (uint32_t)p.y);
     return (float)e.imp_res * (float)e.imp_res * value / total;
+}
+// SampleEnvironmentMap (PathTracer.lib.hlsl:688-703) without the shadow ray: direction, solid-angle pdf and radiance of the sample u picks.
+// The NEE block of ClosestHit and orc_env_query_many call it.
+struct EnvLightSample { float3 direction; float pdf; float3 color; };
+static EnvLightSample SampleEnvironmentLight(const EnvMap& e, float intensity, float2 u, uint32_t* texel = nullptr) {
+    EnvLightSample s;
+    float2 uv = SampleImportanceMap(e, u, s.pdf, texel);
+    s.direction = SquareToSphere(UvToUnitSquare(uv));
+    s.pdf /= 4 * PI;
+    s.color = intensity * SampleCubeLevel(e, s.direction, 0);
+    return s;
+}
+// Miss's environment branch (:1037-1051, :705-710) in parts: radiance along the ray and the pdf of the environment sampler for it.
+// Miss and orc_env_query_many call them.
+static float3 MissEnvironmentColor(const EnvMap* e, float intensity, float3 direction) { return e ? intensity * SampleCubeLevel(*e, direction, 0) : F3(0); }
+static float MissEnvironmentPdf(const EnvMap* e, float3 direction) {
+    float3 l = normalize(direction);
+    return e ? ImportanceMapPdf(*e, UnitSquareToUv(SphereToSquare(l))) / (4 * PI) : 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -762,12 +787,9 @@ struct Tracer {
     // Miss, :1037-1051
     void Miss(Payload& payload, const RayDesc& ray) {
         if (sc.flags & F_ENVIRONMENT_MAP) {
-            payload.color = env ? sc.environment_intensity * SampleCubeLevel(*env, ray.direction, 0) : F3(0);
-            if ((sc.flags & F_ENVIRONMENT_MIS) && (payload.flags & PAYLOAD_FLAG_MIS)) {
-                float3 l = normalize(ray.direction);
-                float env_pdf = env ? ImportanceMapPdf(*env, UnitSquareToUv(SphereToSquare(l))) / (4 * PI) : 0.f;   // :705-710
-                payload.color *= BalanceHeuristic(payload.bsdf_pdf, env_pdf);
-            }
+            payload.color = MissEnvironmentColor(env, sc.environment_intensity, ray.direction);
+            if ((sc.flags & F_ENVIRONMENT_MIS) && (payload.flags & PAYLOAD_FLAG_MIS))
+                payload.color *= BalanceHeuristic(payload.bsdf_pdf, MissEnvironmentPdf(env, ray.direction));
         } else payload.color = sc.environment_intensity * sc.environment_color;
     }
     void TraceRay(uint32_t ray_flags, uint32_t mask, const RayDesc& ray, Payload& payload) {
@@ -845,10 +867,8 @@ struct Tracer {
                 float4 r = rand4(payload.random_count);
                 LightRay lr;
                 if (env) {                                                       // SampleEnvironmentMap :688-703
-                    float2 uv = SampleImportanceMap(*env, {r.x, r.y}, light_pdf);
-                    lr.direction = SquareToSphere(UvToUnitSquare(uv));
-                    light_pdf /= 4 * PI;
-                    lr.color = sc.environment_intensity * SampleCubeLevel(*env, lr.direction, 0);
+                    const EnvLightSample es = SampleEnvironmentLight(*env, sc.environment_intensity, {r.x, r.y});
+                    lr.direction = es.direction; light_pdf = es.pdf; lr.color = es.color;
                 } else { lr.direction = {0, 0, 1}; lr.color = F3(0); light_pdf = 1; }
                 lr.color *= TraceShadowRay(ray_origin, lr.direction, false);
                 if (any_gt0(lr.color)) {
@@ -1422,6 +1442,35 @@ void orc_sample_cube(void* h, int env, const float* d, float level, float* out3)
 }
 void orc_sample_importance_map(void* h, int env, const float* u2, float* uv_pdf3) {
     float pdf; float2 uv = SampleImportanceMap(((Oracle*)h)->envs[env], {u2[0], u2[1]}, pdf); uv_pdf3[0] = uv.x; uv_pdf3[1] = uv.y; uv_pdf3[2] = pdf;
+}
+// The environment light on n queries, with the layout of the product's test hook pt_debug_env_query (8 input and 16 output floats per query;
+// unused outputs are left alone).  op 0 SAMPLE: in u0, u1, intensity -> uv, pdf, px, py of SampleImportanceMap, then SampleEnvironmentLight's
+// direction, pdf, color.  1 PDF: in uv -> ImportanceMapPdf.  2 CUBE: in dir -> SampleCubeLevel(dir, 0) and (face, i, j) of its four taps.
+// 3 MISS: in dir, prev_pdf, intensity -> Miss's colour, env_pdf and BalanceHeuristic(prev_pdf, env_pdf) * colour.
+void orc_env_query_many(void* h, int env, int op, const float* in, uint32_t n, float* out) {
+    const EnvMap& e = ((Oracle*)h)->envs[env];
+    for (uint32_t q = 0; q < n; q++, in += 8, out += 16) {
+        if (op == 0) {
+            uint32_t t[2]; float pdf;
+            float2 uv = SampleImportanceMap(e, {in[0], in[1]}, pdf, t);
+            const EnvLightSample s = SampleEnvironmentLight(e, in[2], {in[0], in[1]});
+            out[0] = uv.x; out[1] = uv.y; out[2] = pdf; out[3] = (float)t[0]; out[4] = (float)t[1];
+            out[5] = s.direction.x; out[6] = s.direction.y; out[7] = s.direction.z; out[8] = s.pdf; out[9] = s.color.x; out[10] = s.color.y; out[11] = s.color.z;
+        } else if (op == 1) {
+            out[0] = ImportanceMapPdf(e, {in[0], in[1]});
+        } else if (op == 2) {
+            int taps[12];
+            float3 c = SampleCubeLevel(e, {in[0], in[1], in[2]}, 0, taps);
+            out[0] = c.x; out[1] = c.y; out[2] = c.z;
+            for (int k = 0; k < 12; k++) out[3 + k] = (float)taps[k];
+        } else {
+            const float3 d = {in[0], in[1], in[2]};
+            const float3 c = MissEnvironmentColor(&e, in[4], d);
+            const float env_pdf = MissEnvironmentPdf(&e, d);
+            const float3 m = c * BalanceHeuristic(in[3], env_pdf);
+            out[0] = c.x; out[1] = c.y; out[2] = c.z; out[3] = env_pdf; out[4] = m.x; out[5] = m.y; out[6] = m.z;
+        }
+    }
 }
 float orc_importance_map_pdf(void* h, int env, const float* uv) { return ImportanceMapPdf(((Oracle*)h)->envs[env], {uv[0], uv[1]}); }
 void orc_tonemap_pixel(const void* cfg, const float* rgb, float* out) { float3 r = tonemap_pixel(*(const TonemapConfig*)cfg, {rgb[0], rgb[1], rgb[2]}, 0, 0); out[0] = r.x; out[1] = r.y; out[2] = r.z; }

@@ -81,6 +81,8 @@ def lib():
         L.orc_sample_material_slot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_sample_material_slot.restype = None
         L.orc_sample_importance_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_env_query_many.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_env_query_many.restype = None
         L.orc_decode_tangent_space.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_random.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.orc_cubemap_to_direction.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
@@ -234,6 +236,18 @@ class Oracle:
         base_tc, base_out = tc.ctypes.data, out.ctypes.data
         for i, (m, k) in enumerate(zip(np.asarray(material).tolist(), np.asarray(slot).tolist())):
             f(h, m, k, base_tc + 16 * i, base_out + 16 * i)
+        return out
+
+    ENV_SAMPLE, ENV_PDF, ENV_CUBE, ENV_MISS = 0, 1, 2, 3
+
+    def env_query_many(self, env, op, inp):
+        """The environment light on n queries (orc_env_query_many): inp (n, <= 8) float32, zero-padded to 8 per query; returns (n, 16)
+        float32, zeros where an op has no output."""
+        inp = _f(inp)
+        q = np.zeros((len(inp), 8), np.float32)
+        q[:, :inp.shape[1]] = inp
+        out = np.zeros((len(inp), 16), np.float32)
+        self.L.orc_env_query_many(self.h, int(env), int(op), _p(q), len(q), _p(out))
         return out
 
     def trace(self, settings, params, output, nthreads=None):

@@ -1,0 +1,598 @@
+"""The environment light (pt_shading.h: dir_to_face, cube_tap_index, cube_footprint, sample_cube, importance_step,
+sample_importance_map_texel, environment_light_sample, importance_map_pdf; pt_vertex.h: the environment branch of shade_miss), query by
+query, through the test hook pt_debug_env_query on both kernel builds:
+  unit 0  the wavefront build: the three coarsest level pairs of the blocked pyramid staged into LDS borrowed from the traversal stack,
+          as env_prepass stages them;
+  unit 1  the megakernel build: every level pair read from global memory.
+
+Every query is checked against
+  * the CPU oracle's SampleImportanceMap / SampleEnvironmentLight / ImportanceMapPdf / SampleCubeLevel / Miss parts (orc_env_query_many):
+    every output bit-identical, NaN positions included;
+  * the other build: bit-identical;
+  * a float64 statement of the same operations, written here from the HLSL rules and sharing no code with the oracle: the same texel
+    (except within float32 rounding of a split, counted), uv, pdf, direction and cube taps, within derived bounds.
+
+The maps come from equirectangular images through env_create on both sides, and from crafted level-0 maps (single texels, ties,
+zero-mass regions, huge ranges, +inf, negative and NaN texels) through pt_debug_env_create_raw / orc_env_create_raw.  The random numbers
+sit on dyadic ties, on the float32 ulps either side of each split along the chosen path, at 0, 1 - 2^-24 and 1, and on the renderer's own
+random sequence; directions on cube axes with signed zeros, face diagonals and corners, texel centres and borders +-1 ulp, near the poles,
+non-unit, zero, infinite and NaN."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from gltf_renderer_amd import scenes
+
+f32 = np.float32
+u32 = np.uint32
+SAMPLE, PDF, CUBE, MISS = 0, 1, 2, 3
+IMP = 1024
+LEVEL_OFF = np.cumsum([0] + [(IMP >> i) ** 2 for i in range(11)])
+FOUR_PI = f32(4) * f32(3.14159265359)            # 4 * kPi, as the kernels and the oracle form it
+INTENSITY = f32(1.5)
+PREV_PDFS = [0.0, 1.0e-40, 1.0, 1.0e30, math.inf]
+
+
+# ---------------------------------------------------------------- hooks
+@pytest.fixture(scope="module")
+def R():
+    from gltf_renderer_amd.renderer import Renderer
+    return Renderer
+
+
+def _fn(L, name, argtypes):
+    f = getattr(L, name)
+    f.restype = C.c_int
+    f.argtypes = argtypes
+    return f
+
+
+def gpu_query(r, env, unit, op, inp):
+    inp = np.asarray(inp, f32)
+    q = np.zeros((len(inp), 8), f32)
+    q[:, :inp.shape[1]] = inp
+    out = np.zeros((len(q), 16), f32)
+    f = _fn(r.L, "pt_debug_env_query", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p])
+    rc = f(r.h, env, unit, op, q.ctypes.data, len(q), out.ctypes.data)
+    assert rc == 0, rc
+    return out
+
+
+def gpu_create_raw(r, n, cube, pyramid):
+    cube = np.ascontiguousarray(cube, np.uint16); pyramid = np.ascontiguousarray(pyramid, f32)
+    out = C.c_int()
+    f = _fn(r.L, "pt_debug_env_create_raw", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    rc = f(r.h, n, cube.ctypes.data, pyramid.ctypes.data, C.addressof(out))
+    assert rc == 0, rc
+    return out.value
+
+
+def gpu_read_blocked(r, env):
+    out = np.zeros(16 + 256 + 4096 + 65536 + IMP * IMP, f32)
+    f = _fn(r.L, "pt_debug_env_read_blocked", [C.c_void_p, C.c_int, C.c_void_p])
+    rc = f(r.h, env, out.ctypes.data)
+    assert rc == 0, rc
+    return out
+
+
+def same_bits(a, b):
+    """Bit-identical, except that any NaN equals any NaN."""
+    a = np.asarray(a, f32); b = np.asarray(b, f32)
+    return (a.view(u32) == b.view(u32)) | (np.isnan(a) & np.isnan(b))
+
+
+# ---------------------------------------------------------------- maps
+def build_pyramid(level0):
+    """The 2x2 sum pyramid in float32, in the build's order ((ul + ll) + ur) + lr (k_importance_level), flattened level 0 first."""
+    levels = [np.asarray(level0, f32)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        while levels[-1].shape[0] > 1:
+            l = levels[-1]
+            levels.append(((l[0::2, 0::2] + l[1::2, 0::2]) + l[0::2, 1::2]) + l[1::2, 1::2])
+    return np.concatenate([l.ravel() for l in levels])
+
+
+def pyramid_levels(pyr):
+    return [pyr[LEVEL_OFF[i]:LEVEL_OFF[i + 1]].reshape(IMP >> i, IMP >> i) for i in range(11)]
+
+
+def random_cube(rng, n):
+    c = np.zeros((6, n, n, 4), np.float16)
+    c[..., :3] = rng.uniform(0, 4, (6, n, n, 3))
+    c[..., 3] = 1
+    return c.view(np.uint16)
+
+
+def crafted_level0(rng):
+    """(name, level-0 map) pairs: what the descent's divisions meet outside fdiv's normal-number contract."""
+    maps = []
+    for (y, x) in [(0, 0), (1023, 1023), (301, 517)]:
+        m = np.zeros((IMP, IMP), f32); m[y, x] = 3.0
+        maps.append(("one texel at (%d,%d)" % (x, y), m))
+    maps.append(("power-of-two constant", np.full((IMP, IMP), 2.0, f32)))
+    yy, xx = np.mgrid[:IMP, :IMP]
+    maps.append(("zero checkerboard", (((xx + yy) & 1) * rng.uniform(0.5, 2.0, (IMP, IMP))).astype(f32)))
+    m = rng.uniform(0.1, 1.0, (IMP, IMP)).astype(f32); m[:512, 512:] = 0
+    maps.append(("zero quadrant", m))
+    m = rng.uniform(0.1, 1.0, (IMP, IMP)).astype(f32); m[:, :512] = 0
+    maps.append(("zero half", m))
+    maps.append(("1e-9 .. 6.5e4", (10.0 ** rng.uniform(-9, math.log10(6.5e4), (IMP, IMP))).astype(f32)))
+    m = rng.uniform(0.1, 1.0, (IMP, IMP)).astype(f32); m[700, 200] = np.inf
+    maps.append(("+inf texel", m))
+    maps.append(("negative texels", rng.uniform(-0.5, 1.0, (IMP, IMP)).astype(f32)))
+    m = rng.uniform(0.1, 1.0, (IMP, IMP)).astype(f32); m[100, 900] = np.nan
+    maps.append(("NaN texel", m))
+    maps.append(("all zeros", np.zeros((IMP, IMP), f32)))
+    return maps
+
+
+def equirect_images(rng):
+    imgs = [("sky 256x128", scenes.sky_image(256, 128, 300.0)), ("sky 2048x1024", scenes.sky_image(2048, 1024, 1.0e4))]
+    for k, (w, h) in enumerate([(64, 32), (257, 129), (640, 200)]):      # the random families of the preprocessing test
+        img = (rng.random((h, w, 3)) ** 4 * 10.0 ** rng.uniform(-3, 5)).astype(f32)
+        if k == 0: img[: h // 2] = 0
+        if k == 2: img[:] = 0; img[h // 3, w // 5] = 3.0e5
+        imgs.append(("random %dx%d" % (w, h), img))
+    for (w, h) in [(1, 1), (4, 2), (8, 4)]:
+        imgs.append(("%dx%d" % (w, h), rng.uniform(0.1, 3.0, (h, w, 3)).astype(f32)))
+    imgs.append(("4096x64 (two mips blended)", rng.uniform(0.0, 2.0, (64, 4096, 3)).astype(f32)))
+    img = rng.uniform(0.1, 1.0, (64, 128, 3)).astype(f32); img[20:24, 40:44] = 1.0e5
+    imgs.append(("texel above 65504", img))
+    return imgs
+
+
+# ---------------------------------------------------------------- float64 statement of SampleImportanceMap (Sampling.hlsli:123-163)
+def descent64(lv, ux, uy):
+    """Ten levels, float64, from the float32 pyramid values.  Returns px, py, the renormalised coordinates, the distance of the
+    input u from the nearest split point (or cell edge) of the path in input coordinates, and the split points per level."""
+    lv = [l.astype(np.float64) for l in lv]
+    n = len(ux)
+    u0x = np.asarray(ux, np.float64); u0y = np.asarray(uy, np.float64)
+    ux = u0x.copy(); uy = u0y.copy()
+    px = np.zeros(n, np.int64); py = np.zeros(n, np.int64)
+    ax, bx, ay, by = np.zeros(n), np.ones(n), np.zeros(n), np.ones(n)
+    dx = np.full(n, np.inf); dy = np.full(n, np.inf)
+    splits_x, splits_y = [], []
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for i in range(9, -1, -1):
+            px *= 2; py *= 2
+            l = lv[i]
+            ul, ur, ll, lr = l[py, px], l[py, px + 1], l[py + 1, px], l[py + 1, px + 1]
+            left, right = ul + ll, ur + lr
+            pl = left / (left + right)
+            sx = ax + bx * pl
+            splits_x.append(sx)
+            dx = np.fmin(dx, np.fmin(np.abs(u0x - sx), np.fmin(np.abs(u0x - ax), np.abs(u0x - (ax + bx)))))
+            go_left = ux < pl
+            ux = np.where(go_left, ux / pl, (ux - pl) / (1 - pl))
+            ax, bx = np.where(go_left, ax, sx), np.where(go_left, bx * pl, bx * (1 - pl))
+            px += (~go_left).astype(np.int64)
+            pu = np.where(go_left, ul / left, ur / right)
+            sy = ay + by * pu
+            splits_y.append(sy)
+            dy = np.fmin(dy, np.fmin(np.abs(u0y - sy), np.fmin(np.abs(u0y - ay), np.abs(u0y - (ay + by)))))
+            up = uy < pu
+            uy = np.where(up, uy / pu, (uy - pu) / (1 - pu))
+            ay, by = np.where(up, ay, sy), np.where(up, by * pu, by * (1 - pu))
+            py += (~up).astype(np.int64)
+    return px, py, ux, uy, np.fmin(dx, dy), splits_x, splits_y, bx, by
+
+
+def square_to_sphere64(uv):
+    s = np.stack([uv[:, 0] * 2 - 1, uv[:, 1] * -2 + 1], 1).astype(np.float64)
+    d = 1 - (np.abs(s[:, 0]) + np.abs(s[:, 1]))
+    r = 1 - np.abs(d)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        phi = np.where(r == 0, 0.0, (np.pi / 4) * ((np.abs(s[:, 1]) - np.abs(s[:, 0])) / r + 1))
+    f = r * np.sqrt(np.maximum(2 - r * r, 0))
+    return np.stack([f * np.sign(s[:, 0]) * np.cos(phi), f * np.sign(s[:, 1]) * np.sin(phi), np.sign(d) * (1 - r * r)], 1)
+
+
+# ---------------------------------------------------------------- float64 statement of TextureCube.SampleLevel(linear, d, 0)
+FACE_AXES = {0: ((1, 0, 0), (0, 0, -1), (0, -1, 0)), 1: ((-1, 0, 0), (0, 0, 1), (0, -1, 0)), 2: ((0, 1, 0), (1, 0, 0), (0, 0, 1)),
+             3: ((0, -1, 0), (1, 0, 0), (0, 0, -1)), 4: ((0, 0, 1), (1, 0, 0), (0, -1, 0)), 5: ((0, 0, -1), (-1, 0, 0), (0, -1, 0))}
+
+
+def face_uv64(d):
+    """D3D major-axis selection (ties to x, then y) and the face coordinates, float64; also the distance to a face tie."""
+    d = np.asarray(d, np.float64)
+    a = np.abs(d)
+    fx = (a[:, 0] >= a[:, 1]) & (a[:, 0] >= a[:, 2])
+    fy = ~fx & (a[:, 1] >= a[:, 2])
+    face = np.where(fx, np.where(d[:, 0] >= 0, 0, 1), np.where(fy, np.where(d[:, 1] >= 0, 2, 3), np.where(d[:, 2] >= 0, 4, 5)))
+    # (axis, sign) of sc and tc per face: the face's u and v directions (components picked, not dot products: inf * 0 is NaN)
+    su = np.array([(2, -1), (2, 1), (0, 1), (0, 1), (0, 1), (0, -1)]); sv = np.array([(1, -1), (1, -1), (2, 1), (2, -1), (1, -1), (1, -1)])
+    k = np.arange(len(d))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ma = a[k, face // 2]
+        u = 0.5 * (su[face, 1] * d[k, su[face, 0]] / ma + 1)
+        v = 0.5 * (sv[face, 1] * d[k, sv[face, 0]] / ma + 1)
+        m = a.max(1)
+        tie = np.fmin(np.abs(a[:, 0] - a[:, 1]), np.fmin(np.abs(a[:, 0] - a[:, 2]), np.abs(a[:, 1] - a[:, 2]))) / m
+    return face, u, v, tie
+
+
+def cube_ref64(cube_f, n, d):
+    """Taps (n, 4, 3) as (face, i, j), weights (n, 4), a validity mask, the distance to the nearest tie of the footprint (a floor
+    boundary of the texel coordinate, a face tie of the direction or of a re-projected tap, in face-coordinate units), and counts of
+    re-projected and corner taps."""
+    face, u, v, tie = face_uv64(d)
+    ok = ~(np.isnan(u) | np.isnan(v))
+    u = np.where(ok, u, 0.5); v = np.where(ok, v, 0.5)
+    x, y = u * n - 0.5, v * n - 0.5
+    i0, j0 = np.floor(x), np.floor(y)
+    fx, fy = x - i0, y - j0
+    near = np.fmin(tie, np.fmin(np.abs(x - np.round(x)), np.abs(y - np.round(y))) / n)
+    taps = np.zeros((len(d), 4, 3), np.int64)
+    w = np.stack([(1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy], 1)
+    reproj = np.zeros(len(d), bool); corner = np.zeros(len(d), bool)
+    fd = np.array([FACE_AXES[f][0] for f in range(6)], np.float64)
+    ud = np.array([FACE_AXES[f][1] for f in range(6)], np.float64)
+    vd = np.array([FACE_AXES[f][2] for f in range(6)], np.float64)
+    for t, (di, dj) in enumerate([(0, 0), (1, 0), (0, 1), (1, 1)]):
+        i = (i0 + di).astype(np.int64); j = (j0 + dj).astype(np.int64)
+        out = ~((i >= 0) & (i < n) & (j >= 0) & (j < n))
+        reproj |= out & ok
+        corner |= ~((i >= 0) & (i < n)) & ~((j >= 0) & (j < n)) & ok
+        s = 2 * (i + 0.5) / n - 1; tt = 2 * (j + 0.5) / n - 1
+        dd = fd[face] + s[:, None] * ud[face] + tt[:, None] * vd[face]
+        f2, u2, v2, tie2 = face_uv64(dd)
+        i2 = np.clip(np.floor(u2 * n), 0, n - 1).astype(np.int64); j2 = np.clip(np.floor(v2 * n), 0, n - 1).astype(np.int64)
+        near2 = np.fmin(tie2, np.fmin(np.abs(u2 * n - np.round(u2 * n)), np.abs(v2 * n - np.round(v2 * n))) / n)
+        near = np.where(out, np.fmin(near, near2), near)
+        taps[:, t] = np.stack([np.where(out, f2, face), np.where(out, i2, i), np.where(out, j2, j)], 1)
+    rgb = np.zeros((len(d), 3)); tmax = np.zeros((len(d), 3))
+    for t in range(4):
+        c = cube_f[taps[:, t, 0], taps[:, t, 2], taps[:, t, 1], :3].astype(np.float64)
+        rgb += w[:, t:t + 1] * c
+        tmax = np.maximum(tmax, np.abs(c))
+    return taps, w, ok, near, rgb, tmax, reproj, corner
+
+
+# ---------------------------------------------------------------- queries
+def ulps(x, k):
+    """x and its k float32 neighbours on each side."""
+    x = np.asarray(x, f32)
+    out = [x]
+    lo = hi = x
+    for _ in range(k):
+        lo = np.nextafter(lo, f32(-np.inf)); hi = np.nextafter(hi, f32(np.inf))
+        out += [lo, hi]
+    return np.concatenate(out)
+
+
+def rng_block(oracle_lib, n):
+    L = oracle_lib.lib()
+    out = np.zeros((n, 4), f32)
+    for k in range(n):
+        L.orc_random(k % 37, k // 37, 11, k % 7, out[k].ctypes.data_as(C.c_void_p))
+    return out[:, :2]
+
+
+def sample_queries(rng, lv, rngu):
+    top = f32(1) - f32(2.0 ** -24)
+    ends = np.array([[a, b] for a in (0, top, 1) for b in (0, top, 1)], f32)
+    m = rng.integers(1, 13, 400)
+    dy = (rng.integers(0, 2 ** 12, (400, 2)) % (2 ** m[:, None])) / (2.0 ** m[:, None])
+    rnd = rng.random((1500, 2)).astype(f32)
+    # the float32 ulps either side of each level's split along the path of 24 random queries, so that renormalised coordinates reach
+    # exactly 0 and 1.0: the split's preimage in input coordinates, +-2 ulps, in x with y random and in y with x random
+    base = rng.random((24, 2))
+    _, _, _, _, _, sxs, sys_, _, _ = descent64(lv, base[:, 0], base[:, 1])
+    ties = []
+    for k in range(10):
+        for axis, s in ((0, sxs[k]), (1, sys_[k])):
+            good = np.isfinite(s) & (s >= 0) & (s <= 1)
+            v = ulps(np.clip(s[good], 0, 1), 2)
+            q = np.tile(base[good], (5, 1)).astype(f32)
+            q[:, axis] = v
+            ties.append(q)
+    ties = np.concatenate(ties) if ties else np.zeros((0, 2), f32)
+    q = np.concatenate([ends, dy.astype(f32), rnd, ties, rngu]).astype(f32)
+    return np.clip(q, 0, 1)
+
+
+def cube_dirs(rng, n):
+    d = [rng.normal(size=(600, 3))]
+    d[0] /= np.linalg.norm(d[0], axis=1, keepdims=True)
+    ax = []
+    for a in range(3):
+        for s in (1.0, -1.0):
+            for z1 in (0.0, -0.0):
+                for z2 in (0.0, -0.0):
+                    v = [z1, z2]; v.insert(a, s); ax.append(v)
+    d.append(np.array(ax))
+    diag = [[sx, sy, sz] for sx in (1, -1) for sy in (1, -1) for sz in (1, -1)]              # corners
+    diag += [[sx, sy, 0] for sx in (1, -1) for sy in (1, -1)] + [[sx, 0, sz] for sx in (1, -1) for sz in (1, -1)]
+    diag += [[0, sy, sz] for sy in (1, -1) for sz in (1, -1)]                                 # face diagonals
+    diag = np.array(diag, np.float64)
+    d += [diag, diag / np.linalg.norm(diag, axis=1, keepdims=True)]
+    # texel centres and borders (+-1 ulp) on every face, in face coordinates on the unit cube (ma = 1 exactly) and normalised; the
+    # footprints of coordinates within half a texel of an edge leave the face, and of both edges at once a corner
+    fc = []
+    coords = np.concatenate([(np.arange(n) + 0.5) / n, np.arange(n + 1) / n]) * 2 - 1
+    coords = np.concatenate([coords, 2 * (np.array([0.25, 0.75, n - 0.25, n - 0.75]) / n) - 1])
+    cs = ulps(coords.astype(f32), 1).astype(np.float64)
+    cs = cs[(cs >= -1) & (cs <= 1)]
+    for f in range(6):
+        F, U, V = (np.array(a, np.float64) for a in FACE_AXES[f])
+        s = rng.choice(cs, 80); t = rng.choice(cs, 80)
+        edge = rng.choice(cs[np.abs(cs) > 1 - 1.0 / n], 40)
+        s = np.concatenate([s, edge, rng.choice(cs, 40)]); t = np.concatenate([t, rng.choice(cs, 40), edge])
+        p = F + s[:, None] * U + t[:, None] * V
+        fc += [p, p / np.linalg.norm(p, axis=1, keepdims=True)]
+    d += fc
+    pole = np.array([[1e-4, 2e-4, 1], [-3e-5, 1e-5, -1], [1e-7, 0, 1], [0, -1e-7, -1], [2e-4, -2e-4, 1]], np.float64)
+    d += [pole / np.linalg.norm(pole, axis=1, keepdims=True)]
+    d += [d[0][:60] * s for s in (2.0, 0.5, 1024.0, 3.0, 1e-3, 1e5, 0.7)]                       # non-unit
+    d += [np.array([[0, 0, 0], [np.inf, 0.5, 0.1], [-np.inf, np.inf, 0], [0.2, np.nan, 0.5], [np.nan, np.nan, np.nan], [0.3, 0.1, -np.inf]])]
+    return np.concatenate(d).astype(f32)
+
+
+def pdf_uvs(rng, sample_uv):
+    b = ulps((np.arange(0, IMP + 1, 37) / IMP).astype(f32), 1)
+    g = np.stack([rng.choice(b, 400), rng.choice(b, 400)], 1)
+    extra = np.array([[0, 0], [1, 1], [-0.25, 0.5], [0.5, 1.5], [np.nan, 0.5], [0.5, np.inf]], f32)
+    return np.concatenate([sample_uv, rng.random((300, 2)), g, extra]).astype(f32)
+
+
+# ---------------------------------------------------------------- checks
+class Coverage:
+    def __init__(self):
+        self.c = {}
+        self.fails = []
+
+    def add(self, k, v):
+        self.c[k] = self.c.get(k, 0) + int(v)
+
+
+def check_sample(name, lv, q, out, cov):
+    """(c), with the side's SAMPLE outputs."""
+    l0 = lv[0]; total = lv[10][0, 0]
+    px = out[:, 3].astype(np.int64); py = out[:, 4].astype(np.int64)
+    assert ((px >= 0) & (px < IMP) & (py >= 0) & (py < IMP)).all(), name
+    rpx, rpy, rux, ruy, dist, _, _, bx, by = descent64(lv, q[:, 0], q[:, 1])
+    diff = (rpx != px) | (rpy != py)
+    cov.add("descent exceptions", diff.sum())
+    assert (dist[diff] <= 2.0 ** -20).all(), (name, q[diff][dist[diff] > 2.0 ** -20][:4], dist[diff].max())
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        # pdf = w * w * level0[py, px] / total, float32
+        want = (f32(IMP * IMP) * l0[py, px]) / total
+        assert same_bits(out[:, 2], want).all(), (name, np.flatnonzero(~same_bits(out[:, 2], want))[:4])
+        fin = np.isfinite(want) & (want > 0) & np.isfinite(total) & (total > 0)
+        w64 = IMP * IMP * l0[py, px].astype(np.float64) / float(total) if np.isfinite(total) and total != 0 else np.zeros(len(q))
+        assert (np.abs(out[fin, 2] - w64[fin]) <= 1e-6 * np.abs(w64[fin])).all(), name
+        uv = out[:, :2].astype(np.float64)
+        uv64 = np.stack([(rpx + rux) / IMP, (rpy + ruy) / IMP], 1)
+        # uv within 1e-6, widened for small cells: each of the ten renormalisations per axis rounds the coordinate and the split (<= 2^-24
+        # each), and the descent below scales those errors by b_k / b, b_k = the level-k cell's width in input coordinates and b = the
+        # texel's.  So the final coordinate is off by <= 20 * 2^-24 / b, uv by that / 1024: 1.2e-6 for an even map, more beside a sun.
+        # (With negative texels the split probabilities leave [0, 1] and a renormalisation can amplify without bound: those maps are held
+        # to the oracle bit for bit and to the float64 texel choice, not to this bound.)
+        tol = 1e-6 + 20 * 2.0 ** -24 / (IMP * np.abs(np.stack([bx, by], 1)))
+        ok = ~diff & np.isfinite(uv).all(1) & np.isfinite(uv64).all(1) & bool((l0 >= 0).all())
+        assert (np.abs(uv[ok] - uv64[ok]) <= tol[ok]).all(), (name, (np.abs(uv[ok] - uv64[ok]) / tol[ok]).max())
+        cov.add("non-finite uv (escapes and NaN maps)", (~np.isfinite(uv).all(1)).sum())
+        # a tie hit: a renormalised coordinate reached exactly 0 (it stays 0 down to level 0, so uv * 1024 lands on the texel corner)
+        tie = ((uv[:, 0] * IMP == px) & (q[:, 0] > 0)) | ((uv[:, 1] * IMP == py) & (q[:, 1] > 0))
+        cov.add("ties hit", tie.sum())
+        cov.add("escapes into zero-mass texels", ((l0[py, px] == 0) & (total != 0)).sum())
+        # environment_light_sample: dir = square_to_sphere(uv), pdf / (4 pi), colour (checked against CUBE by the caller)
+        fu = np.isfinite(uv).all(1)
+        d64 = square_to_sphere64(uv[fu])
+        dr = out[fu, 5:8].astype(np.float64)
+        assert (np.abs(dr - d64) <= 2e-6).all(), (name, np.abs(dr - d64).max())
+        assert (np.abs(np.linalg.norm(dr, axis=1) - 1) <= 2e-6).all(), name
+        assert same_bits(out[:, 8], out[:, 2] / FOUR_PI).all(), name
+    return diff
+
+
+def check_cube(name, cube_f, n, d, out, cov):
+    """(d), with the side's CUBE outputs."""
+    taps, w, ok, near, rgb, tmax, reproj, corner = cube_ref64(cube_f, n, d)
+    got = out[:, 3:15].reshape(-1, 4, 3).astype(np.int64)
+    assert (got[~ok] == -1).all() and (out[~ok, :3] == 0).all(), name
+    assert ((got[ok] >= 0).all() and (got[ok][..., 0] < 6).all() and (got[ok][..., 1:] < n).all()), name
+    bad = ok & (got != taps).any((1, 2))
+    cov.add("cube tie exceptions", bad.sum())
+    assert (near[bad] <= 1e-6).all(), (name, d[bad & (near > 1e-6)][:4])
+    cov.add("taps re-projected across an edge", (reproj & ~bad).sum())
+    cov.add("corner taps", (corner & ~bad).sum())
+    # RGB: the texels are exact halves; each weight comes from fx = u * n - 0.5 - floor, where u carries <= 2^-24 (one division of
+    # |q| <= 1 within an ulp, + 1, * 0.5), u * n and - 0.5 add <= n * 2^-24 each: |dfx| <= e = 1.5 * n * 2^-23.  A weight (1 - fx)(1 - fy)
+    # is off by <= 2e + 3 * 2^-24, the four of them by 8e + 12 * 2^-24, and the four products and three sums round 7 more times.
+    e = 1.5 * n * 2.0 ** -23
+    tol = (8 * e + 19 * 2.0 ** -24) * tmax
+    good = ok & ~bad & np.isfinite(tmax).all(1)          # a footprint on an RGBA16F infinity is held to the oracle's bits only
+    err = np.abs(out[good, :3] - rgb[good])
+    assert (err <= tol[good] + 1e-30).all(), (name, err.max(), d[good][np.argmax((err - tol[good]).max(1))])
+
+
+def check_q9(name, lv, uv, pdf):
+    """(e) ImportanceMapPdf at a uv reads texel max(floor(uv * 1024) - 1, 0) per axis (UVToPixel's off-by-one, quirk q9)."""
+    fin = np.isfinite(uv).all(1) & (uv >= 0).all(1) & (uv < 1).all(1)
+    t = np.maximum(np.floor(uv[fin].astype(np.float64) * IMP) - 1, 0).astype(np.int64)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        want = (f32(IMP * IMP) * lv[0][t[:, 1], t[:, 0]]) / lv[10][0, 0]
+    assert same_bits(pdf[fin], want).all(), name
+
+
+def run_map(name, lv, cube_u16, n, query, rng, oracle_q, rngu, cov, units=(0, 1)):
+    """Every op on one map.  query(unit, op, inp) -> outputs of one side; oracle_q(op, inp) -> the oracle's."""
+    cube_f = cube_u16.view(np.float16).astype(np.float32)
+    qs = sample_queries(rng, lv, rngu)
+    sq = np.concatenate([qs, np.full((len(qs), 1), INTENSITY, f32)], 1)
+    dirs = cube_dirs(rng, n)
+    mq = np.concatenate([np.repeat(dirs, len(PREV_PDFS), 0), np.tile(np.array(PREV_PDFS, f32), len(dirs))[:, None],
+                         np.full((len(dirs) * len(PREV_PDFS), 1), INTENSITY, f32)], 1)
+    res = {}
+    pq = None
+    for unit in units:
+        s = query(unit, SAMPLE, sq)
+        res[(unit, SAMPLE)] = s
+        if pq is None: pq = pdf_uvs(rng, s[:, :2])               # the first len(qs) of them are the samples' uv (q9)
+        res[(unit, PDF)] = query(unit, PDF, pq)
+        res[(unit, CUBE)] = query(unit, CUBE, dirs)
+        res[(unit, MISS)] = query(unit, MISS, mq)
+        res[(unit, "col")] = query(unit, CUBE, s[:, 5:8])
+    inputs = {SAMPLE: sq, PDF: pq, CUBE: dirs, MISS: mq}
+    for unit in units:
+        s = res[(unit, SAMPLE)]
+        check_sample(name, lv, qs, s, cov)
+        # the sample's colour is intensity * the CUBE op at the same direction, bit for bit
+        assert same_bits(s[:, 9:12], INTENSITY * res[(unit, "col")][:, :3]).all(), name
+        check_cube(name, cube_f, n, dirs, res[(unit, CUBE)], cov)
+        check_q9(name, lv, s[:, :2], res[(unit, PDF)][:len(s), 0])
+        for op in (SAMPLE, PDF, CUBE, MISS):
+            o = res[(unit, op)]
+            cov.add("NaN outputs unit %d" % unit, np.isnan(o).sum()); cov.add("inf outputs unit %d" % unit, np.isinf(o).sum())
+    # bit identity is gathered over every map and op and asserted by the caller, so that one run shows every difference
+    if len(units) == 2:
+        for op in (SAMPLE, PDF, CUBE, MISS, "col"):
+            a, b = res[(0, op)], res[(1, op)]
+            bad = (a.view(u32) != b.view(u32)).any(1)
+            if bad.any(): cov.fails.append((name, "unit 0 vs 1", op, int(bad.sum()), a[bad][:2].tolist(), b[bad][:2].tolist()))
+    if oracle_q is not None:
+        for op in (SAMPLE, PDF, CUBE, MISS):
+            o = oracle_q(op, inputs[op])
+            ok = same_bits(res[(units[0], op)], o)
+            bad = ~ok.all(1)
+            if bad.any():
+                cov.fails.append((name, "oracle", op, int(bad.sum()), "fields", sorted(set(np.nonzero(~ok)[1].tolist())),
+                                  inputs[op][bad][:3].tolist(), res[(units[0], op)][bad][:3].tolist(), o[bad][:3].tolist()))
+            cov.add("NaN outputs oracle", np.isnan(o).sum()); cov.add("inf outputs oracle", np.isinf(o).sum())
+    return res
+
+
+def blocked_permutation(lv):
+    out = []
+    for k in range(5):
+        l = lv[8 - 2 * k]; nn = l.shape[0]
+        out.append(l.reshape(nn // 4, 4, nn // 4, 4).transpose(0, 2, 1, 3).ravel())
+    return np.concatenate(out)
+
+
+# ---------------------------------------------------------------- tests
+@pytest.mark.gpu
+def test_environment_light_matches_oracle_and_float64_query_by_query(R, oracle_lib):
+    rng = np.random.default_rng(2026)
+    r = R(); o = oracle_lib.Oracle()
+    cov = Coverage()
+    rngu = rng_block(oracle_lib, 512)
+    maps = []
+    for name, img in equirect_images(rng):
+        eg, eo = r.env_create(img), o.env_create(img)
+        n, cube, pyr = r.env_read(eg)
+        n2, cube2, pyr2 = o.env_read(eo)
+        assert n == n2 and np.array_equal(cube, cube2) and np.array_equal(pyr.view(u32), pyr2.view(u32)), name
+        maps.append((name, eg, eo, n, cube, pyr))
+    for name, l0 in crafted_level0(rng):
+        n = 5
+        cube = random_cube(rng, n); pyr = build_pyramid(l0)
+        maps.append((name, gpu_create_raw(r, n, cube, pyr), o.env_create_raw(n, cube, pyr), n, cube, pyr))
+    for name, eg, eo, n, cube, pyr in maps:
+        lv = pyramid_levels(pyr)
+        # (g) the blocked copies are the 4x4-block permutation of levels 8, 6, 4, 2, 0
+        assert np.array_equal(gpu_read_blocked(r, eg).view(u32), blocked_permutation(lv).view(u32)), name
+        run_map(name, lv, cube, n, lambda unit, op, q: gpu_query(r, eg, unit, op, q), rng,
+                lambda op, q: o.env_query_many(eo, op, q), rngu, cov)
+    print("coverage:", cov.c)
+    for f in cov.fails: print("DIFF", f)
+    assert not cov.fails, cov.fails[:3]
+    assert cov.c["ties hit"] >= 100
+    assert cov.c["escapes into zero-mass texels"] >= 1
+    assert cov.c["taps re-projected across an edge"] >= 1000 and cov.c["corner taps"] >= 50
+    assert cov.c["NaN outputs unit 0"] > 0 and cov.c["NaN outputs unit 1"] > 0 and cov.c["NaN outputs oracle"] > 0
+    r.close(); o.close()
+
+
+def chi2_sf(x, k):
+    """Survival function of chi-square with k degrees of freedom (Wilson-Hilferty)."""
+    z = ((x / k) ** (1 / 3) - (1 - 2 / (9 * k))) / math.sqrt(2 / (9 * k))
+    return 0.5 * math.erfc(z / math.sqrt(2))
+
+
+@pytest.mark.gpu
+def test_importance_sampling_distribution_and_escapes(R, oracle_lib):
+    """(f) 2^24 random u through the wavefront build's sampler land in a 16x16 grid of coarse cells in proportion to their mass
+    (chi-square, p > 1e-4); the zero-mass cells receive only escapes (a renormalised coordinate of exactly 1.0 followed by a 0/0 split),
+    each of which the oracle reproduces bit for bit.  (Uniform float32 u rarely escape; the main test places u on the splits.)"""
+    rng = np.random.default_rng(5)
+    r = R(); o = oracle_lib.Oracle()
+    l0 = rng.uniform(0.1, 1.0, (IMP, IMP)).astype(f32)
+    l0[:512, 512:] = 0; l0[::64, :] = 0; l0[700:764, 64:128] = 0          # a zero quadrant, zero rows, one zero coarse cell
+    n = 5; cube = random_cube(rng, n); pyr = build_pyramid(l0)
+    eg = gpu_create_raw(r, n, cube, pyr); eo = o.env_create_raw(n, cube, pyr)
+    mass = l0.astype(np.float64).reshape(16, 64, 16, 64).sum((1, 3))
+    counts = np.zeros((16, 16), np.int64)
+    esc_q, esc_out = [], []
+    N, chunk = 1 << 24, 1 << 21
+    for c in range(N // chunk):
+        q = np.zeros((chunk, 3), f32); q[:, :2] = rng.random((chunk, 2), dtype=np.float32); q[:, 2] = 1
+        s = gpu_query(r, eg, 0, SAMPLE, q)
+        px = s[:, 3].astype(np.int64); py = s[:, 4].astype(np.int64)
+        np.add.at(counts, (py // 64, px // 64), 1)
+        e = l0[py, px] == 0
+        esc_q.append(q[e]); esc_out.append(s[e])
+    esc_q = np.concatenate(esc_q); esc_out = np.concatenate(esc_out)
+    zero = mass == 0
+    assert counts[zero].sum() <= len(esc_q)
+    expect = N * mass[~zero] / mass.sum()
+    chi2 = float((((counts[~zero] - expect) ** 2) / expect).sum())
+    p = chi2_sf(chi2, int((~zero).sum()) - 1)
+    print("distribution: chi2 %.1f over %d cells, p = %.3g; %d escapes" % (chi2, int((~zero).sum()), p, len(esc_q)))
+    assert p > 1e-4, (chi2, p)
+    # every escape ends on a zero-mass texel with pdf 0 and matches the oracle
+    assert (esc_out[:, 2] == 0).all()
+    oo = o.env_query_many(eo, SAMPLE, esc_q)
+    assert same_bits(esc_out, oo).all()
+    r.close(); o.close()
+
+
+@pytest.mark.gpu
+def test_env_query_hooks_reject_bad_arguments(R):
+    r = R()
+    eg = r.env_create(np.ones((4, 8, 3), f32))
+    q = np.zeros((300, 8), f32)
+    out = np.zeros((300, 16), f32)
+    f = _fn(r.L, "pt_debug_env_query", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p])
+    for env, unit, op in [(eg + 1, 0, 0), (-1, 1, 1), (eg, 2, 0), (eg, -1, 0), (eg, 0, 4), (eg, 1, -1)]:
+        assert f(r.h, env, unit, op, q.ctypes.data, 300, out.ctypes.data) != 0, (env, unit, op)
+    assert f(r.h, eg, 0, 0, None, 300, out.ctypes.data) != 0
+    assert f(r.h, eg, 0, 0, q.ctypes.data, 0, out.ctypes.data) == 0
+    fb = _fn(r.L, "pt_debug_env_read_blocked", [C.c_void_p, C.c_int, C.c_void_p])
+    assert fb(r.h, eg + 7, out.ctypes.data) != 0
+    fr = _fn(r.L, "pt_debug_env_create_raw", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    h = C.c_int()
+    assert fr(r.h, 0, q.ctypes.data, q.ctypes.data, C.addressof(h)) != 0
+    r.close()
+
+
+def test_oracle_env_query_export_follows_the_float64_statement(oracle_lib):
+    """orc_env_query_many against the single-query exports and the float64 statement above, on crafted maps and an equirect image:
+    the same checks the GPU test applies to the kernels (this one runs without a GPU)."""
+    rng = np.random.default_rng(9)
+    o = oracle_lib.Oracle()
+    cov = Coverage()
+    rngu = rng_block(oracle_lib, 128)
+    L = oracle_lib.lib()
+    maps = []
+    for name, l0 in crafted_level0(rng)[:9:2] + crafted_level0(rng)[-3:]:
+        n = 5; cube = random_cube(rng, n); pyr = build_pyramid(l0)
+        maps.append((name, o.env_create_raw(n, cube, pyr), n, cube, pyr))
+    eo = o.env_create(scenes.sky_image(256, 128, 300.0))
+    maps.append(("sky 256x128",) + (eo,) + o.env_read(eo))
+    for name, eo, n, cube, pyr in maps:
+        lv = pyramid_levels(pyr)
+        res = run_map(name, lv, cube, n, lambda unit, op, q: o.env_query_many(eo, op, q), rng, None, rngu, cov, units=(0,))
+        single = np.zeros(3, f32)
+        q = sample_queries(np.random.default_rng(3), lv, rngu)[:50]
+        s = o.env_query_many(eo, SAMPLE, np.concatenate([q, np.ones((len(q), 1), f32)], 1))
+        for k in range(len(q)):
+            L.orc_sample_importance_map(o.h, eo, np.ascontiguousarray(q[k]).ctypes.data_as(C.c_void_p), single.ctypes.data_as(C.c_void_p))
+            assert same_bits(single, s[k, :3]).all(), (name, k)
+    print("coverage:", cov.c)
+    assert cov.c["ties hit"] > 0 and cov.c["taps re-projected across an edge"] > 0 and cov.c["corner taps"] > 0
+    o.close()
