@@ -242,6 +242,11 @@ class PtStats(C.Structure):
                 ("bvh_stack_capacity", C.c_uint32), ("accel_builder_fallbacks", C.c_uint32), ("deep_stack_pushes", C.c_uint64)]
 
 
+class PtAdaptiveConfig(C.Structure):
+    """pt_adaptive_config: tile-level adaptive sampling (pt_set_adaptive; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("threshold", C.c_float)]
+
+
 STAGE_NAMES = ("generate", "trace", "shade", "shadow", "resolve")
 EXCHANGE_GATHER, EXCHANGE_REDUCE = 0, 1
 BUILDER_LBVH, BUILDER_PLOC, BUILDER_PLOC_REINSERT = 0, 1, 2
@@ -257,3 +262,4 @@ assert C.sizeof(PtInstanceDesc) == 176
 assert C.sizeof(PtExecuteParams) == 168
 assert C.sizeof(PtBone) == 128
 assert C.sizeof(PtStats) == 152
+assert C.sizeof(PtAdaptiveConfig) == 16

@@ -10,6 +10,7 @@
 // There is no CPU fallback anywhere in this file: every compute entry point launches HIP kernels.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -102,6 +103,14 @@ struct pt_ctx {
     int samples_per_trace = 1;
     bool cull_null_shadow = false;
     bool counters_enabled = false;
+    // ---- adaptive sampling (pt_set_adaptive): per rank-local tile state and the half buffer, for one size and tile shard
+    pt_adaptive_config adaptive = {0, 2, 2, 0.0f};
+    bool adaptive_restart = false;                // pt_set_adaptive: the next pt_trace starts a new accumulation
+    AdaptiveTile* d_ad_tiles = nullptr; size_t ad_tiles_cap = 0;
+    float4* d_ad_half = nullptr; size_t ad_half_cap = 0;
+    uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
+    bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
+    int ad_frames = -1;                           // accumulated_frames the tile state stands for (-1: none)
 
     // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
     float previous_world_to_clip[16] = {0};
@@ -335,8 +344,18 @@ public:
         if (!mat4_inverse(ep->world_to_view, view_to_world) || !mat4_inverse(world_to_clip, clip_to_world))
             return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
         bool reset = memcmp(world_to_clip, ctx->previous_world_to_clip, 64) != 0 || settings->reset;   // :267-271
+        // Adaptive sampling (pt_set_adaptive) applies to accumulating calls without a debug output.  Its tile state describes the output
+        // only if the last accumulation step was adaptive and of the same size and tile shard: otherwise the call starts a new one.
+        const bool adaptive = ctx->adaptive.enable != 0 && (settings->flags & PT_FLAG_ACCUMULATE) && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
+        if (adaptive && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive sampling runs in the wavefront mode only");
+        if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
+                         (ep->tile_rank_count ? ep->tile_rank_count : 1u) != ctx->ad_rank_count || ctx->accumulated_frames != ctx->ad_frames))
+            reset = true;
         if (reset) ctx->accumulated_frames = 0;
-        if (ctx->accumulated_frames < settings->max_accumulated_frames) {               // :273
+        // an adaptive accumulation ends where its tiles must stop: min(max_samples, max_accumulated_frames)
+        const int frame_cap = adaptive ? std::min(ctx->adaptive.max_samples, settings->max_accumulated_frames) : settings->max_accumulated_frames;
+        if (ctx->accumulated_frames < frame_cap) {                                       // :273
             if (ep->light_count > ctx->n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "light_count exceeds uploaded lights");
             if (ep->environment_map >= 0 && (ep->environment_map >= (int)ctx->envs.size() || !ctx->envs[ep->environment_map]))
                 return ctx->fail(PT_ERR_BAD_HANDLE, "bad environment map handle");
@@ -393,7 +412,7 @@ public:
             int batch = 1;
             if ((settings->flags & PT_FLAG_ACCUMULATE) && settings->debug_output == PT_DEBUG_OUTPUT_NONE) {
                 batch = ctx->samples_per_trace;
-                const long long room = (long long)settings->max_accumulated_frames - ctx->accumulated_frames;
+                const long long room = (long long)frame_cap - ctx->accumulated_frames;
                 if ((long long)batch > room) batch = (int)room;
             }
             fc.cull_null_shadow = ctx->cull_null_shadow ? 1u : 0u;
@@ -457,14 +476,40 @@ public:
                     if (ctx->d_occ && ctx->occ_stale) { HIPOK(hipMemsetAsync(ctx->d_occ, 0xff, ctx->occ_pixels * 8 * 4, ctx->stream)); ctx->occ_stale = false; }
                     occ = ctx->d_occ;
                 }
+                AdaptiveArgs ad = {};
+                if (adaptive) {
+                    // tile state (rank-local tiles) and half buffer; a new accumulation makes every tile active with 0 samples
+                    const size_t px = (size_t)ep->width * ep->height, tiles = fc.my_tiles ? fc.my_tiles : 1;
+                    if (tiles > ctx->ad_tiles_cap || px > ctx->ad_half_cap) {
+                        HIPOK(hipStreamSynchronize(ctx->stream));
+                        hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
+                        ctx->d_ad_tiles = nullptr; ctx->d_ad_half = nullptr; ctx->ad_tiles_cap = ctx->ad_half_cap = 0; ctx->ad_ready = false;
+                        if (hipMalloc((void**)&ctx->d_ad_tiles, tiles * sizeof(AdaptiveTile)) != hipSuccess || hipMalloc((void**)&ctx->d_ad_half, px * 16) != hipSuccess) {
+                            (void)hipGetLastError();
+                            return ctx->fail(PT_ERR_OUT_OF_MEMORY, "adaptive tile state");
+                        }
+                        ctx->ad_tiles_cap = tiles; ctx->ad_half_cap = px;
+                    }
+                    if (ctx->accumulated_frames == 0) {
+                        const AdaptiveTile fresh = {1u, 0u, 0.0f, 0u};
+                        const std::vector<AdaptiveTile> init(tiles, fresh);
+                        HIPOK(staged_upload(ctx, ctx->d_ad_tiles, init.data(), tiles * sizeof(AdaptiveTile)));
+                        HIPOK(hipMemsetAsync(ctx->d_ad_half, 0, px * 16, ctx->stream));
+                    }
+                    ad.tiles = ctx->d_ad_tiles; ad.half = ctx->d_ad_half;
+                    ad.min_samples = ctx->adaptive.min_samples; ad.cap = frame_cap; ad.threshold = ctx->adaptive.threshold;
+                    ctx->ad_w = ep->width; ctx->ad_h = ep->height; ctx->ad_rank = fc.tile_rank; ctx->ad_rank_count = fc.tile_rank_count;
+                    ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
+                }
                 HIPOK(launch_wavefront(sc, fc, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->d_workspace, stage_blocks,
-                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, occ));
+                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, occ, adaptive ? &ad : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
             ctx->have_trace = true;
             if (settings->flags & PT_FLAG_ACCUMULATE) ctx->accumulated_frames += batch;   // :355-359
             else ctx->accumulated_frames = 0;
+            ctx->ad_frames = adaptive ? ctx->accumulated_frames : -1;
         }
         memcpy(ctx->previous_world_to_clip, world_to_clip, 64);                          // :366
         return PT_OK;
@@ -630,6 +675,7 @@ void pt_destroy(pt_ctx* ctx) {
     exchange_free(ctx->exchange);
     hipFree(ctx->d_deep);
     hipFree(ctx->d_occ);
+    hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
     for (int k = 0; k < StagingRing::kSlots; k++) {
         if (ctx->staging.host[k]) hipHostFree(ctx->staging.host[k]);
         if (ctx->staging.done[k]) hipEventDestroy(ctx->staging.done[k]);
@@ -1184,6 +1230,42 @@ int pt_set_bounce_limit(pt_ctx* ctx, int limit) {
 int pt_set_samples_per_trace(pt_ctx* ctx, int samples) {
     if (!ctx || samples < 1 || samples > PT_MAX_SAMPLES_PER_TRACE) return PT_ERR_INVALID_ARGUMENT;
     ctx->samples_per_trace = samples;
+    return PT_OK;
+}
+
+int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_config* config) {
+    if (!ctx || !config) return PT_ERR_INVALID_ARGUMENT;
+    if (config->enable) {
+        if (config->min_samples < 2) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive: min_samples < 2");
+        if (config->max_samples < config->min_samples) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive: max_samples < min_samples");
+        if (!std::isfinite(config->threshold) || config->threshold < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive: threshold must be finite and >= 0");
+    }
+    ctx->adaptive = *config;
+    ctx->adaptive_restart = true;
+    return PT_OK;
+}
+
+int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* active_tiles, uint32_t* tile_samples, float* tile_error, float* half_rgba32f) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->ad_ready) return ctx->fail(PT_ERR_NOT_READY, "no adaptive trace yet");
+    if (width != ctx->ad_w || height != ctx->ad_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive_read: size differs from the traced one");
+    ENTER(ctx);
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    std::vector<AdaptiveTile> t(ctx->ad_my_tiles);
+    if (!t.empty()) HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
+    const size_t ntiles = (size_t)((width + PT_TILE - 1) / PT_TILE) * ((height + PT_TILE - 1) / PT_TILE);
+    if (tile_samples) memset(tile_samples, 0, ntiles * sizeof(uint32_t));
+    if (tile_error) memset(tile_error, 0, ntiles * sizeof(float));
+    int32_t active = 0;
+    for (size_t l = 0; l < t.size(); l++) {                     // rank-local tile l is global tile rank + l * rank_count
+        const size_t g = ctx->ad_rank + l * ctx->ad_rank_count;
+        if (g >= ntiles) break;
+        if (tile_samples) tile_samples[g] = t[l].samples;
+        if (tile_error) tile_error[g] = t[l].error;
+        active += t[l].active ? 1 : 0;
+    }
+    if (active_tiles) *active_tiles = active;
+    if (half_rgba32f) HIPOK(hipMemcpy(half_rgba32f, ctx->d_ad_half, (size_t)width * height * 16, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -113,9 +113,26 @@ void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, ui
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream);
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks);
+// Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
+// An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
+struct AdaptiveTile {
+    uint32_t active;          // 1: gets the call's samples; 0: retired, no rays, its pixels are not written
+    uint32_t samples;         // samples in the tile after the last call that reached it
+    float error;              // its last error estimate E (max over its pixels)
+    uint32_t pad;
+};
+// What the adaptive instantiations of k_wf_generate / k_wf_resolve take as their own argument (FrameConstants stays as it is).
+struct AdaptiveArgs {
+    AdaptiveTile* tiles;      // my_tiles entries
+    float4* half;             // res_x * res_y: running mean of the samples with an even per-tile index
+    int32_t min_samples;
+    int32_t cap;              // min(max_samples, max_accumulated_frames)
+    float threshold;
+};
 // occ_cache: the context's occluder cache (res_x * res_y * 8 words, persistent across calls; nullptr = none), see WfBuffers::occ_cache
+// adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache);
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive = nullptr);
 
 // ---- sort_scan.hip: the build's two data-parallel primitives, hand-written (stable LSD radix sort of (u64, u32) pairs over 63 key bits; u32 exclusive scan)
 size_t radix_sort_temp_bytes(size_t n);

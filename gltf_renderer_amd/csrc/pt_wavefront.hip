@@ -189,7 +189,16 @@ constexpr uint32_t kXcds = 8;
 #define PT_GEN_XCD_BANDS 0      // measured on MI355X (Sponza-class 1080p, 8 spp / launch): 0 (tiles dealt round-robin) 4473 Mrays/s,
                                 // 1 (row bands) 4339, 2 (column bands) 4274 -- see the comment above and DESIGN.md section 4
 #endif
-__global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters) {
+// Adaptive sampling (pt_set_adaptive): is the tile of a workgroup-round's (tile, sample) pair still active?  `slot0` = the round's first
+// slot (workgroup-uniform), so the state is read once per round; a retired tile pushes no ray and every later stage is unchanged.
+PT_DEV bool adaptive_tile_active(const FrameConstants& fc, const AdaptiveArgs& ad, uint32_t slot0) {
+    const uint32_t pair = slot0 >> 8;                                 // sample * my_tiles + rank-local tile
+    if (pair >= fc.my_tiles * fc.spp) return false;
+    const uint32_t local_tile = pair - slot_sample(fc, slot0) * fc.my_tiles;
+    return ad.tiles[local_tile].active != 0;
+}
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad) {
     const ShardView sv = shard_view(wf);
     const uint32_t per_xcd = gridDim.x / kXcds;                       // the grid is a multiple of kShards, kShards of kXcds
     const uint32_t xcd = blockIdx.x % kXcds, member = blockIdx.x / kXcds;
@@ -214,12 +223,14 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
 #endif
         const uint32_t slot = sample * fc.pixel_slots + tile * kBlock + threadIdx.x;
         uint32_t px = 0, py = 0;
-        const bool valid = tile_in_region < n_tiles && slot_pixel(fc, slot, px, py);
+        bool valid = tile_in_region < n_tiles && slot_pixel(fc, slot, px, py);
+        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, sample * fc.pixel_slots + tile * kBlock); valid = valid && tile_on; }
 #else       // A/B: tiles dealt round-robin over all workgroups (every XCD sees the whole screen); rounds are sized for either
         const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
         const uint32_t sample = slot_sample(fc, slot);
         uint32_t px = 0, py = 0;
-        const bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
+        bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
+        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
 #endif
         int rc = 0;
         Ray ray;
@@ -821,7 +832,63 @@ void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, ui
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_env_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
 }
-__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output) {
+// Adaptive sampling: the per-pixel error of the accumulated image I against the half buffer A (the mean of the samples with an even
+// per-tile index), in float32 in this order with IEEE division and a correctly rounded square root; a NaN counts as +inf.
+PT_DEV float adaptive_pixel_error(const float4 I, const float4 A) {
+    const float d = (fabsf(I.x - A.x) + fabsf(I.y - A.y)) + fabsf(I.z - A.z);
+    const float s = (I.x + I.y) + I.z;
+    const float e = d / (1e-4f + sqrtf(fmaxf(s, 0.0f)));
+    return e != e ? INFINITY : e;
+}
+// The adaptive resolve of one tile (one block): blend the batch into I and, on even per-tile indices, into A; the tile's error E is the
+// max of its pixels' errors (wave64 max by cross-lane swaps, then the four waves through LDS), and one lane writes the tile's count, E and
+// whether it retires.  A retired tile's block leaves at once: its output and half-buffer pixels are not written.  Active tiles all hold
+// fc.accumulated_frames samples, so a tile's image is, bit for bit, the uniform accumulation after its own count.
+PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, float4* __restrict__ output, const AdaptiveArgs& ad) {
+    const uint32_t tile = blockIdx.x;                                 // rank-local tile: the resolve grid is one block per tile
+    if (ad.tiles[tile].active == 0) return;                           // (block-uniform)
+    const uint32_t pslot = tile * kBlock + threadIdx.x;
+    uint32_t px = 0, py = 0;
+    const bool in_image = pslot < fc.pixel_slots && slot_pixel(fc, pslot, px, py);
+    float e = -INFINITY;
+    if (in_image) {
+        const size_t at = (size_t)py * fc.res_x + px;
+        float4 pixel = make_float4(0, 0, 0, 0), half = pixel;
+        if (fc.accumulated_frames != 0) { pixel = output[at]; half = ad.half[at]; }
+        for (uint32_t k = 0; k < fc.spp; k++) {
+            const uint32_t slot = k * fc.pixel_slots + pslot;
+            float4 Lq = SLD(wf.L[SIDX(slot)]);
+            vec3 L = v3(Lq.x, Lq.y, Lq.z);
+            apply_pending(wf, slot, __float_as_uint(Lq.w), L);
+            L = sanitize_sample(fc, L);
+            const int n = fc.accumulated_frames + (int)k;             // the sample's per-tile index
+            pixel = n != 0 ? blend_sample(pixel, n, L) : make_float4(L.x, L.y, L.z, 1.0f);
+            if ((n & 1) == 0) half = n != 0 ? blend_sample(half, n >> 1, L) : make_float4(L.x, L.y, L.z, 1.0f);
+        }
+        output[at] = pixel;
+        ad.half[at] = half;
+        e = adaptive_pixel_error(pixel, half);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e = fmaxf(e, __shfl_xor(e, off, 64));
+    __shared__ float s_err[kBlock / 64];
+    if ((threadIdx.x & 63u) == 0) s_err[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float E = s_err[0];
+#pragma unroll
+        for (uint32_t w = 1; w < kBlock / 64; w++) E = fmaxf(E, s_err[w]);
+        const int n = fc.accumulated_frames + (int)fc.spp;
+        const bool retire = n >= ad.cap || (n >= ad.min_samples && E <= ad.threshold);
+        AdaptiveTile t;
+        t.active = retire ? 0u : 1u; t.samples = (uint32_t)n; t.error = E; t.pad = 0;
+        ad.tiles[tile] = t;
+    }
+}
+
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output, AdaptiveArgs ad) {
+    if (ADAPTIVE) { resolve_adaptive(fc, wf, output, ad); return; }
     const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;       // pixel slot; its samples sit pixel_slots apart
     uint32_t px, py;
     if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
@@ -910,7 +977,7 @@ int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -936,7 +1003,9 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
     if (e) return e;
     const dim3 block(kBlock), full(fc.my_tiles), stage(kShards * wf.blocks_per_shard);
     if (timers) { hipEvent_t ev = event_at(0); if (ev) hipEventRecord(ev, stream); else timers = nullptr; }
-    hipLaunchKernelGGL(k_wf_generate, stage, block, 0, stream, fc, wf, counters);
+    AdaptiveArgs ad = {};
+    if (adaptive) { ad = *adaptive; hipLaunchKernelGGL(k_wf_generate<true>, stage, block, 0, stream, fc, wf, counters, ad); }
+    else hipLaunchKernelGGL(k_wf_generate<false>, stage, block, 0, stream, fc, wf, counters, ad);
     mark(STAGE_GENERATE);
     const uint32_t flags = fc.flags;
     const int iterations = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 1 : fc.max_bounces + 1;
@@ -1047,7 +1116,8 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
         mark(STAGE_SHADOW);
     }
 #endif
-    hipLaunchKernelGGL(k_wf_resolve, full, block, 0, stream, fc, wf, output);
+    if (adaptive) hipLaunchKernelGGL(k_wf_resolve<true>, full, block, 0, stream, fc, wf, output, ad);
+    else hipLaunchKernelGGL(k_wf_resolve<false>, full, block, 0, stream, fc, wf, output, ad);
     mark(STAGE_RESOLVE);
     return hipGetLastError();
 }

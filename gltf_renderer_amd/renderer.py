@@ -23,7 +23,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # ABI 2
            "pt_buffer_destroy", "pt_texture_destroy", "pt_env_destroy", "pt_accel_request_rebuild", "pt_set_accel_builder", "pt_enable_stage_timing",
            "pt_exchange_unique_id", "pt_exchange_probe", "pt_exchange_create", "pt_exchange_create_loopback", "pt_exchange_frame", "pt_exchange_destroy",
-           "pt_tiles_packed_bytes", "pt_tiles_pack", "pt_tiles_unpack"]
+           "pt_tiles_packed_bytes", "pt_tiles_pack", "pt_tiles_unpack",
+           # adaptive sampling (additive: the ABI version stays 2)
+           "pt_set_adaptive", "pt_adaptive_read"]
 
 
 class MiptError(RuntimeError):
@@ -95,6 +97,8 @@ def load_library():
     L.pt_tiles_packed_bytes.restype = C.c_size_t
     L.pt_tiles_pack.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.pt_tiles_unpack.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.pt_set_adaptive.argtypes = [vp, vp]
+    L.pt_adaptive_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -220,6 +224,24 @@ class Renderer:
     def set_samples_per_trace(self, samples):
         """Sample batch: one trace() then stands for `samples` consecutive frames (bit-identical to issuing them one by one)."""
         self._check(self.L.pt_set_samples_per_trace(self.h, int(samples)))
+
+    def set_adaptive(self, min_samples, max_samples, threshold, enable=True):
+        """Tile-level adaptive sampling (include/mipt.h pt_set_adaptive): on accumulating calls, a 16x16 tile stops getting samples
+        once it holds max_samples (or settings.max_accumulated_frames), or at least min_samples with its error <= threshold.
+        The next trace() starts a new accumulation."""
+        cfg = abi.PtAdaptiveConfig(int(bool(enable)), int(min_samples), int(max_samples), float(threshold))
+        self._check(self.L.pt_set_adaptive(self.h, C.byref(cfg)))
+
+    def adaptive_read(self, width, height):
+        """State after the last adaptive trace: (active tile count, samples (tiles_y, tiles_x) uint32, error (tiles_y, tiles_x)
+        float32, half image (height, width, 4) float32).  Tiles another rank renders read 0."""
+        ty, tx = (height + abi.TILE - 1) // abi.TILE, (width + abi.TILE - 1) // abi.TILE
+        active = C.c_int32()
+        samples = np.zeros((ty, tx), np.uint32)
+        error = np.zeros((ty, tx), np.float32)
+        half = np.zeros((height, width, 4), np.float32)
+        self._check(self.L.pt_adaptive_read(self.h, width, height, C.byref(active), _p(samples), _p(error), _p(half)))
+        return active.value, samples, error, half
 
     def set_null_shadow_culling(self, on):
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""

@@ -411,6 +411,32 @@ int pt_set_bounce_limit(pt_ctx* ctx, int limit);      /* default PT_REFERENCE_MA
  * or with a debug output, the batch is ignored: the call renders the one sample of `frame`, as always.  Default 1. */
 #define PT_MAX_SAMPLES_PER_TRACE 64
 int pt_set_samples_per_trace(pt_ctx* ctx, int samples);
+/* Tile-level adaptive sampling (absent upstream: the reference renders every pixel every frame).  Off by default; with it off, or on a
+ * call without FLAG_ACCUMULATE or with a debug output, pt_trace is exactly as described above.  On an adaptive call every 16x16 tile
+ * of the rank that is still ACTIVE gets the call's samples, with the seeds and blend weights of the uniform accumulation (active tiles
+ * all hold the context's accumulated_frames samples); a RETIRED tile gets no rays and its output pixels are not written.  Besides the
+ * output the context keeps a W x H RGBA32F half buffer A: the running mean of the samples with an even per-tile index (0, 2, 4 ...).
+ * After the call's samples each active tile gets an error E, the max over its in-image pixels of
+ *     e = ((|I.r-A.r| + |I.g-A.g|) + |I.b-A.b|) / (1e-4 + sqrt(max((I.r + I.g) + I.b, 0)))   (float32, a NaN counts as +inf)
+ * with I the accumulated output, and retires once its count n >= min(max_samples, max_accumulated_frames), or n >= min_samples and
+ * E <= threshold.  Tile t of the output is then bit-identical to tile t of the uniform accumulation after tile_samples[t] frames.
+ * A new accumulation (accumulated_frames 0 after the reset check, a new size or tile shard, or the first trace after pt_set_adaptive)
+ * makes every tile active again.  The batch is clamped to min(max_samples, max_accumulated_frames) - accumulated_frames.
+ * Wavefront mode only: an adaptive call in PT_MODE_MEGAKERNEL fails with PT_ERR_INVALID_ARGUMENT and leaves the output untouched. */
+typedef struct pt_adaptive_config {
+    int32_t enable;        /* 0 = off (default) */
+    int32_t min_samples;   /* >= 2: samples every tile takes before it may stop */
+    int32_t max_samples;   /* >= min_samples: a tile stops here (and at settings->max_accumulated_frames) */
+    float   threshold;     /* finite, >= 0: a tile stops once its error <= threshold */
+} pt_adaptive_config;
+/* PT_ERR_INVALID_ARGUMENT for a bad config (checked when enable != 0).  Forces a new accumulation on the next pt_trace. */
+int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_config* config);
+/* The state after the last adaptive trace.  Synchronises the stream.  Tiles are row-major, ceil(W/16) x ceil(H/16), GLOBAL tile ids:
+ * active_tiles = this rank's tiles still active; tile_samples = each tile's count (at retirement, or the current one); tile_error = its
+ * last E; half_rgba32f = the half buffer (W * H * 4 floats).  Tiles another rank owns read 0.  Every pointer may be NULL.
+ * PT_ERR_NOT_READY before the first adaptive trace, PT_ERR_INVALID_ARGUMENT for a size other than the one traced. */
+int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* active_tiles,
+                     uint32_t* tile_samples, float* tile_error, float* half_rgba32f);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -2,6 +2,11 @@
 """Render a .gltf / .glb file on an MI355X through the C-ABI only: loader (include/mipt_scene.h) -> path tracer (include/mipt.h).
 
   python tools/render_gltf.py scene.glb --env sky.hdr --spp 64 --size 1280 720 --out frame.png [--animation 0 --time 0.5]
+  python tools/render_gltf.py scene.glb --spp 256 --adaptive 0.05 --min-spp 16 --sample-map samples.png
+
+--adaptive THRESHOLD: tile-level adaptive sampling (pt_set_adaptive): a 16x16 tile stops at --spp samples, or earlier once it has
+--min-spp and its error estimate is <= THRESHOLD; the samples used are printed against tiles x spp.  --sample-map writes the
+per-tile counts as a grey PNG (white = --spp).
 
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
@@ -27,6 +32,10 @@ def main():
     ap.add_argument("--azimuth", type=float, default=0.6)
     ap.add_argument("--inclination", type=float, default=-0.35)
     ap.add_argument("--out", default="frame.png")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD")
+    ap.add_argument("--min-spp", type=int, default=16)
+    ap.add_argument("--batch", type=int, default=8, help="samples per pt_trace with --adaptive")
+    ap.add_argument("--sample-map", default="")
     a = ap.parse_args()
 
     import torch
@@ -79,9 +88,30 @@ def main():
     p.environment_map = -1 if env is None else env
     p.tile_rank, p.tile_rank_count = 0, 1
     out = r.create_output(w, h)
-    for frame in range(a.spp):
-        p.frame = frame
-        r.trace(st, p, out)
+    if a.adaptive is None:
+        for frame in range(a.spp):
+            p.frame = frame
+            r.trace(st, p, out)
+    else:
+        # trace batches until no tile is active or every tile holds --spp samples
+        r.set_samples_per_trace(min(a.batch, 64))
+        r.set_adaptive(min(a.min_spp, a.spp), a.spp, a.adaptive)
+        frame, active = 0, 1
+        while active and frame < a.spp:
+            p.frame = frame
+            r.trace(st, p, out)
+            frame += min(a.batch, 64)
+            active = r.adaptive_read(w, h)[0]
+        _, samples, _, _ = r.adaptive_read(w, h)
+        pix = np.zeros((samples.shape[0] * abi.TILE, samples.shape[1] * abi.TILE), np.int64)
+        pix[:h, :w] = 1
+        pix = pix.reshape(samples.shape[0], abi.TILE, samples.shape[1], abi.TILE).sum(axis=(1, 3))
+        used, full = int((samples.astype(np.int64) * pix).sum()), w * h * a.spp
+        print("adaptive %.4g: %d of %d tile-samples (%d tiles x %d spp), %d pixel-samples = %.1f %% of uniform; tile counts %d..%d"
+              % (a.adaptive, int(samples.sum()), samples.size * a.spp, samples.size, a.spp, used, 100.0 * used / full, samples.min(), samples.max()))
+        if a.sample_map:
+            grey = np.repeat(np.repeat((255.0 * samples / a.spp).astype(np.uint8), abi.TILE, 0), abi.TILE, 1)[:h, :w]
+            gltf.write_png(a.sample_map, np.dstack([grey, grey, grey, np.full_like(grey, 255)]), 3)
     torch.cuda.synchronize()
     _, rgba8 = r.tonemap(out, want_rgba8=True)
     if a.out.lower().endswith(".exr"):
