@@ -247,6 +247,11 @@ class PtAdaptiveConfig(C.Structure):
     _fields_ = [("enable", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("threshold", C.c_float)]
 
 
+class PtAovConfig(C.Structure):
+    """pt_aov_config: first-hit albedo and normal/depth targets (pt_set_aov; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("albedo", C.c_void_p), ("normal_depth", C.c_void_p)]
+
+
 STAGE_NAMES = ("generate", "trace", "shade", "shadow", "resolve")
 EXCHANGE_GATHER, EXCHANGE_REDUCE = 0, 1
 BUILDER_LBVH, BUILDER_PLOC, BUILDER_PLOC_REINSERT = 0, 1, 2
@@ -263,3 +268,4 @@ assert C.sizeof(PtExecuteParams) == 168
 assert C.sizeof(PtBone) == 128
 assert C.sizeof(PtStats) == 152
 assert C.sizeof(PtAdaptiveConfig) == 16
+assert C.sizeof(PtAovConfig) == 24

@@ -111,6 +111,9 @@ struct pt_ctx {
     uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
     bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
     int ad_frames = -1;                           // accumulated_frames the tile state stands for (-1: none)
+    // ---- first-hit AOVs (pt_set_aov): the caller's targets
+    pt_aov_config aov = {0, nullptr, nullptr};
+    bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
 
     // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
     float previous_world_to_clip[16] = {0};
@@ -348,7 +351,11 @@ public:
         // only if the last accumulation step was adaptive and of the same size and tile shard: otherwise the call starts a new one.
         const bool adaptive = ctx->adaptive.enable != 0 && (settings->flags & PT_FLAG_ACCUMULATE) && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
         if (adaptive && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive sampling runs in the wavefront mode only");
+        // First-hit AOVs (pt_set_aov) are written by every call without a debug output, under the output's counts and resets.
+        const bool aov = ctx->aov.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
+        if (aov && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "AOVs are written in the wavefront mode only");
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
         if (adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
                          (ep->tile_rank_count ? ep->tile_rank_count : 1u) != ctx->ad_rank_count || ctx->accumulated_frames != ctx->ad_frames))
             reset = true;
@@ -455,7 +462,7 @@ public:
                 fc.spp = (uint32_t)batch;
                 if ((unsigned long long)fc.pixel_slots * fc.spp > 0x7fffffffull) return ctx->fail(PT_ERR_CAPACITY, "sample batch too large for this resolution");
                 const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * fc.spp);
-                size_t need = wavefront_workspace_bytes(fc, stage_blocks);
+                size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov);
                 if (need > ctx->workspace_cap) {
                     HIPOK(hipStreamSynchronize(ctx->stream));
                     hipFree(ctx->d_workspace); ctx->d_workspace = nullptr; ctx->workspace_cap = 0;
@@ -501,8 +508,9 @@ public:
                     ctx->ad_w = ep->width; ctx->ad_h = ep->height; ctx->ad_rank = fc.tile_rank; ctx->ad_rank_count = fc.tile_rank_count;
                     ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
                 }
+                const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
                 HIPOK(launch_wavefront(sc, fc, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->d_workspace, stage_blocks,
-                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, occ, adaptive ? &ad : nullptr));
+                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, occ, adaptive ? &ad : nullptr, aov ? &av : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
@@ -1242,6 +1250,14 @@ int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_config* config) {
     }
     ctx->adaptive = *config;
     ctx->adaptive_restart = true;
+    return PT_OK;
+}
+
+int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config) {
+    if (!ctx || !config) return PT_ERR_INVALID_ARGUMENT;
+    if (config->enable && !config->albedo && !config->normal_depth) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "aov: enabled without a target");
+    ctx->aov = *config;
+    ctx->aov_restart = true;
     return PT_OK;
 }
 

@@ -112,7 +112,7 @@ void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, ui
 void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream);
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks);
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false);   // aov: with the two AOV record arrays behind the rest
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
 struct AdaptiveTile {
@@ -129,10 +129,21 @@ struct AdaptiveArgs {
     int32_t cap;              // min(max_samples, max_accumulated_frames)
     float threshold;
 };
+// First-hit AOVs (pt_set_aov): what k_wf_aov and the AOV instantiations of k_wf_resolve take as their own argument.  One record per
+// slot and target, written by k_wf_aov between the primary traversal and the first shade stage, blended by the resolve.
+struct AovArgs {
+    float4* rec_albedo;       // per slot: (sp.albedo, 1); zeros for a miss or a non-finite sample (workspace, set by launch_wavefront)
+    float4* rec_normal;       // per slot: (sp.n, hit.t); zeros likewise
+    float4* albedo;           // the caller's targets, res_x * res_y each; either may be nullptr
+    float4* normal_depth;
+};
 // occ_cache: the context's occluder cache (res_x * res_y * 8 words, persistent across calls; nullptr = none), see WfBuffers::occ_cache
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
+// aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
+//      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive = nullptr);
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive = nullptr,
+                            const AovArgs* aov = nullptr);
 
 // ---- sort_scan.hip: the build's two data-parallel primitives, hand-written (stable LSD radix sort of (u64, u32) pairs over 63 key bits; u32 exclusive scan)
 size_t radix_sort_temp_bytes(size_t n);

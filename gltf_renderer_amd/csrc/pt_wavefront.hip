@@ -832,6 +832,72 @@ void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, ui
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_env_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
 }
+// First-hit AOVs (pt_set_aov): albedo, shading normal and depth of the vertex the camera ray reaches, one 32-B record per slot.  A stage
+// of its own between the primary traversal and the first shade stage -- queue 0's rays and wf.hit are intact in that window -- so that
+// the shade stage, priced by the register allocation of its one function, stays what it is.  It walks the shard's segment like every
+// stage, stages the tables the vertex fetch and get_surface read, and runs exactly the code the shade stage runs up to the debug
+// outputs COLOR / SHADING_NORMAL (shade_closest_hit): the records are those values bit for bit.  A miss writes zeros; so does a
+// target whose sample has a non-finite component (no luminance clamp, SHOW_NAN / SHOW_INF do not apply).  Texture taps are not counted.
+// The records are written once and read once by the resolve: non-temporal, like the queues.
+PT_DEV bool aov_finite(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w); }
+__global__ __launch_bounds__(kBlock) void k_wf_aov(SceneRec sc_in, FrameConstants fc, WfBuffers wf, AovArgs av) {
+    SceneRec sc = sc_in; sc.small_tables = 0u;
+    const ShardView sv = shard_view(wf);
+    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
+    if (sv.member * kBlock >= n) return;                              // (workgroup-uniform) nothing of the segment is this workgroup's
+    stage_luts(sc);
+    stage_tangent_lut(sc);
+    stage_instances(sc);
+    stage_materials(sc);
+    const size_t base = (size_t)sv.shard * wf.seg_cap;
+    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
+        const float4 o = QLD(wf.ray_o[0][base + i]), d = QLD(wf.ray_d[0][base + i]), h = QLD(wf.hit[base + i]);
+        const uint32_t slot = __float_as_uint(d.w), hb = __float_as_uint(h.w);
+        float4 ra = make_float4(0, 0, 0, 0), rn = ra;
+        if (hb != kMissTri) {
+            const ShadePacket* packet_at = sc.shade + (hb & 0x7fffffffu);
+            RawPacket packet = load_shade_packet_raw(packet_at);
+            const ShadeInst inst = load_shade_inst(sc, raw_packet_inst(packet));
+            if (inst.streams & (SI_TEXCOORD1 | SI_COLOR)) load_shade_packet_extra(packet, packet_at);
+            const PacketVerts pv = unpack_shade_packet(packet);
+            const RMat* mat = sc.rmats + inst.material_id;
+            const MatHeader mh = material_header(sc, inst.material_id);
+            HitGeom va = get_vertex_attributes(sc, inst, pv, v3(1 - h.y - h.z, h.y, h.z));
+            if (!(hb >> 31)) { va.ng = -va.ng; va.n = -va.n; va.t = -va.t; va.tw = -va.tw; }
+            const vec3 view = -normalize(v3(d.x, d.y, d.z));
+            unsigned taps = 0;
+            const Surface sp = get_surface(sc, fc.flags, mat, mh, va, view, taps);
+            ra = make_float4(sp.albedo.x, sp.albedo.y, sp.albedo.z, 1.0f);
+            rn = make_float4(sp.n.x, sp.n.y, sp.n.z, h.x);
+            if (!aov_finite(ra)) ra = make_float4(0, 0, 0, 0);
+            if (!aov_finite(rn)) rn = make_float4(0, 0, 0, 0);
+        }
+        if (av.albedo) QST(av.rec_albedo[SIDX(slot)], ra);
+        if (av.normal_depth) QST(av.rec_normal[SIDX(slot)], rn);
+    }
+}
+// the running mean of a four-component AOV record: blend_sample's weight on every component
+PT_DEV float4 blend_aov(float4 h, int accumulated, float4 v) {
+    const float blend = fdiv(1.0f, (float)accumulated + 1.0f);
+    return make_float4(h.x + blend * (v.x - h.x), h.y + blend * (v.y - h.y), h.z + blend * (v.z - h.z), h.w + blend * (v.w - h.w));
+}
+// The AOV part of a resolve thread: the batch's records of pixel slot `pslot` blended in sample order into one target, with the
+// beauty's counts (`first` = samples already in the target; < 0: the call does not accumulate and the target takes the one sample).
+PT_DEV void resolve_aov_target(const FrameConstants& fc, const WfBuffers& wf, const float4* __restrict__ rec, float4* __restrict__ target, uint32_t pslot, size_t at, int first) {
+    float4 pixel = make_float4(0, 0, 0, 0);
+    if (first > 0) pixel = target[at];
+    for (uint32_t k = 0; k < fc.spp; k++) {
+        const float4 v = QLD(rec[SIDX(k * fc.pixel_slots + pslot)]);
+        const int n = first + (int)k;
+        pixel = n > 0 ? blend_aov(pixel, n, v) : v;
+    }
+    target[at] = pixel;
+}
+PT_DEV void resolve_aov(const FrameConstants& fc, const WfBuffers& wf, const AovArgs& av, uint32_t pslot, size_t at, int first) {
+    if (av.albedo) resolve_aov_target(fc, wf, av.rec_albedo, av.albedo, pslot, at, first);
+    if (av.normal_depth) resolve_aov_target(fc, wf, av.rec_normal, av.normal_depth, pslot, at, first);
+}
+
 // Adaptive sampling: the per-pixel error of the accumulated image I against the half buffer A (the mean of the samples with an even
 // per-tile index), in float32 in this order with IEEE division and a correctly rounded square root; a NaN counts as +inf.
 PT_DEV float adaptive_pixel_error(const float4 I, const float4 A) {
@@ -844,7 +910,8 @@ PT_DEV float adaptive_pixel_error(const float4 I, const float4 A) {
 // max of its pixels' errors (wave64 max by cross-lane swaps, then the four waves through LDS), and one lane writes the tile's count, E and
 // whether it retires.  A retired tile's block leaves at once: its output and half-buffer pixels are not written.  Active tiles all hold
 // fc.accumulated_frames samples, so a tile's image is, bit for bit, the uniform accumulation after its own count.
-PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, float4* __restrict__ output, const AdaptiveArgs& ad) {
+template <bool AOV>
+PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, float4* __restrict__ output, const AdaptiveArgs& ad, const AovArgs& av) {
     const uint32_t tile = blockIdx.x;                                 // rank-local tile: the resolve grid is one block per tile
     if (ad.tiles[tile].active == 0) return;                           // (block-uniform)
     const uint32_t pslot = tile * kBlock + threadIdx.x;
@@ -868,6 +935,7 @@ PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, floa
         output[at] = pixel;
         ad.half[at] = half;
         e = adaptive_pixel_error(pixel, half);
+        if (AOV) resolve_aov(fc, wf, av, pslot, at, fc.accumulated_frames);       // (an adaptive call accumulates)
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e = fmaxf(e, __shfl_xor(e, off, 64));
@@ -886,9 +954,11 @@ PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, floa
     }
 }
 
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output, AdaptiveArgs ad) {
-    if (ADAPTIVE) { resolve_adaptive(fc, wf, output, ad); return; }
+// AOV: the instantiations of calls with AOV targets (pt_set_aov) also blend the records k_wf_aov wrote, next to the beauty pixel; the
+// others take `av` and never look at it.
+template <bool ADAPTIVE, bool AOV>
+__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output, AdaptiveArgs ad, AovArgs av) {
+    if (ADAPTIVE) { resolve_adaptive<AOV>(fc, wf, output, ad, av); return; }
     const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;       // pixel slot; its samples sit pixel_slots apart
     uint32_t px, py;
     if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
@@ -908,6 +978,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuff
         pixel = (accumulate && accumulated != 0) ? blend_sample(pixel, accumulated, L) : make_float4(L.x, L.y, L.z, 1.0f);
     }
     *outp = pixel;
+    if (AOV) resolve_aov(fc, wf, av, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -936,9 +1007,12 @@ static uint32_t seg_cap_for(const FrameConstants& fc, uint32_t blocks_per_shard)
 static uint32_t chunks_per_shard_for(size_t slots) { return (uint32_t)(((slots + kBlock - 1) / kBlock + kShards - 1) / kShards); }
 static size_t state_slots_for(size_t slots) { return (size_t)chunks_per_shard_for(slots) * kShards * kBlock; }
 
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks) {
+// the AOV records (AovArgs::rec_albedo, rec_normal) lie behind everything carve() hands out: a workspace without them is laid out as ever
+static size_t aov_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, false) + 255) & ~(size_t)255; }
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov) {
     const uint32_t bps = blocks_per_shard_for(stage_blocks);
     const size_t slots = state_slots_for((size_t)fc.my_tiles * kBlock * fc.spp);
+    if (aov) return aov_records_offset(fc, stage_blocks) + slots * (2 * 16);
     const size_t q = (size_t)kShards * seg_cap_for(fc, bps);
     return slots * (5 * 16) + q * (4 * 16 + 4 * 16 + 16 + 2 * 16 + 2 * 2 * 16 + (PT_OCC_CACHE ? 2 * 4 : 0)) + kCounterArrays * kShards * kCounterStride * 4 + 52 * 256;
 }
@@ -977,7 +1051,7 @@ int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive, const AovArgs* aov) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -1003,6 +1077,12 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
     if (e) return e;
     const dim3 block(kBlock), full(fc.my_tiles), stage(kShards * wf.blocks_per_shard);
     if (timers) { hipEvent_t ev = event_at(0); if (ev) hipEventRecord(ev, stream); else timers = nullptr; }
+    AovArgs av = {};
+    if (aov) {
+        av = *aov;
+        av.rec_albedo = (float4*)((char*)workspace + aov_records_offset(fc, stage_blocks));
+        av.rec_normal = av.rec_albedo + state_slots_for(slots);
+    }
     AdaptiveArgs ad = {};
     if (adaptive) { ad = *adaptive; hipLaunchKernelGGL(k_wf_generate<true>, stage, block, 0, stream, fc, wf, counters, ad); }
     else hipLaunchKernelGGL(k_wf_generate<false>, stage, block, 0, stream, fc, wf, counters, ad);
@@ -1081,6 +1161,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
 #endif
         mark(STAGE_TRACE);
     }
+    if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
     for (int b = 0; b < iterations; b++) {
         const int cur = b & 1;
 #if PT_LATE_GRID
@@ -1109,6 +1190,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
         ray_flags(b, rf, rmask);
         launch_trace(stage, wf, cur, b, rf, rmask);
         mark(STAGE_TRACE);
+        if (aov && b == 0) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }
         launch_shade(stage, wf, cur, b);
         mark(STAGE_SHADE);
         if (count) hipLaunchKernelGGL(k_wf_shadow<true>, stage, block, 0, stream, sc, wf, b, flags, fc.max_ray_length, counters);
@@ -1116,8 +1198,10 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
         mark(STAGE_SHADOW);
     }
 #endif
-    if (adaptive) hipLaunchKernelGGL(k_wf_resolve<true>, full, block, 0, stream, fc, wf, output, ad);
-    else hipLaunchKernelGGL(k_wf_resolve<false>, full, block, 0, stream, fc, wf, output, ad);
+    if (aov) { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, true>), full, block, 0, stream, fc, wf, output, ad, av);
+               else hipLaunchKernelGGL((k_wf_resolve<false, true>), full, block, 0, stream, fc, wf, output, ad, av); }
+    else { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, false>), full, block, 0, stream, fc, wf, output, ad, av);
+           else hipLaunchKernelGGL((k_wf_resolve<false, false>), full, block, 0, stream, fc, wf, output, ad, av); }
     mark(STAGE_RESOLVE);
     return hipGetLastError();
 }

@@ -25,7 +25,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            "pt_exchange_unique_id", "pt_exchange_probe", "pt_exchange_create", "pt_exchange_create_loopback", "pt_exchange_frame", "pt_exchange_destroy",
            "pt_tiles_packed_bytes", "pt_tiles_pack", "pt_tiles_unpack",
            # adaptive sampling (additive: the ABI version stays 2)
-           "pt_set_adaptive", "pt_adaptive_read"]
+           "pt_set_adaptive", "pt_adaptive_read",
+           # first-hit AOVs (additive likewise)
+           "pt_set_aov"]
 
 
 class MiptError(RuntimeError):
@@ -99,6 +101,7 @@ def load_library():
     L.pt_tiles_unpack.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.pt_set_adaptive.argtypes = [vp, vp]
     L.pt_adaptive_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.pt_set_aov.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -242,6 +245,17 @@ class Renderer:
         half = np.zeros((height, width, 4), np.float32)
         self._check(self.L.pt_adaptive_read(self.h, width, height, C.byref(active), _p(samples), _p(error), _p(half)))
         return active.value, samples, error, half
+
+    def set_aov(self, albedo=None, normal_depth=None):
+        """First-hit AOVs (include/mipt.h pt_set_aov): albedo (rgb, coverage) and normal_depth (signed world-space shading normal,
+        hit distance) are float32 CUDA tensors (H, W, 4) like the output, caller-owned; either may be None, both None turns AOVs off.
+        They accumulate with the output, sample for sample.  The next trace() starts a new accumulation."""
+        for t in (albedo, normal_depth):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4)
+        cfg = abi.PtAovConfig(int(albedo is not None or normal_depth is not None), albedo.data_ptr() if albedo is not None else None,
+                              normal_depth.data_ptr() if normal_depth is not None else None)
+        self._check(self.L.pt_set_aov(self.h, C.byref(cfg)))
+        self._aov = (albedo, normal_depth)           # the library keeps the pointers: keep the tensors alive with the renderer
 
     def set_null_shadow_culling(self, on):
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""

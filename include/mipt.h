@@ -437,6 +437,29 @@ int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_config* config);
  * PT_ERR_NOT_READY before the first adaptive trace, PT_ERR_INVALID_ARGUMENT for a size other than the one traced. */
 int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* active_tiles,
                      uint32_t* tile_samples, float* tile_error, float* half_rgba32f);
+/* First-hit AOVs (absent upstream): albedo, shading normal and depth of the vertex each pixel-sample's camera ray reaches, accumulated
+ * beside the output for denoisers and compositing.  Off by default; with it off pt_trace is exactly as described above, and with it on
+ * the output, the ray counts and accumulated_frames are what they are without it.  The targets are device pointers to W * H float4,
+ * caller-owned like pt_execute_params.output (so pt_readback, pt_tonemap, pt_tiles_pack and pt_exchange_frame take them as they are);
+ * either may be NULL.  Per sample, under the call's flags:
+ *     albedo        rgb = the surface's base colour (what PT_DEBUG_OUTPUT_COLOR shows), w = 1 (coverage)
+ *     normal_depth  xyz = the signed world-space shading normal after the back-face flip (PT_DEBUG_OUTPUT_SHADING_NORMAL shows
+ *                   (xyz + 1) / 2), w = the camera ray's hit distance t
+ * A miss contributes zeros to both; so does, to its target, a sample with a non-finite component (the luminance clamp, FLAG_SHOW_NAN
+ * and FLAG_SHOW_INF do not apply).  Each target is the running mean of its samples with the output's weights 1 / (n + 1), in sample
+ * order, under the output's counts and resets: a sample batch equals the calls one by one, a call without FLAG_ACCUMULATE leaves the
+ * one sample, a tile shard writes only the rank's tiles, and a tile retired by adaptive sampling is not written (it equals the uniform
+ * AOV after its own count).  albedo.rgb / albedo.w is the mean over the samples that hit; the mean of normals is not unit length.
+ * A call with a debug output leaves the targets untouched.  Wavefront mode only: a call with AOVs enabled in PT_MODE_MEGAKERNEL fails
+ * with PT_ERR_INVALID_ARGUMENT and writes nothing. */
+typedef struct pt_aov_config {
+    int32_t enable;          /* 0 = off (default) */
+    void*   albedo;          /* device, W*H float4, caller-owned, may be NULL */
+    void*   normal_depth;    /* device, W*H float4, caller-owned, may be NULL */
+} pt_aov_config;
+/* PT_ERR_INVALID_ARGUMENT if enable != 0 and both targets are NULL.  Forces a new accumulation on the next pt_trace, so that the
+ * targets and the output always hold the same samples. */
+int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -8,6 +8,10 @@
 --min-spp and its error estimate is <= THRESHOLD; the samples used are printed against tiles x spp.  --sample-map writes the
 per-tile counts as a grey PNG (white = --spp).
 
+--aov PREFIX: first-hit AOVs (pt_set_aov), accumulated with the frame: PREFIX_albedo.png (the mean albedo of the samples that hit,
+rgb / coverage, linear, 8 bit), PREFIX_normal.png ((n / |n| + 1) / 2 of the mean world-space shading normal where coverage > 0,
+black elsewhere) and PREFIX_depth.npy (float32 H x W: the mean of the camera rays' hit distances, a miss counting 0).
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -18,6 +22,21 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def aov_images(albedo, normal_depth):
+    """(albedo rgb8, normal rgb8, depth float32) from the two accumulated AOV targets (H, W, 4)."""
+    cover = albedo[..., 3]
+    hit = cover > 0
+    alb = np.zeros(albedo.shape[:2] + (3,), np.float32)
+    alb[hit] = albedo[..., :3][hit] / cover[hit][:, None]
+    n = normal_depth[..., :3].astype(np.float64)
+    ln = np.linalg.norm(n, axis=-1)
+    ok = hit & (ln > 0)
+    enc = np.zeros(n.shape, np.float64)
+    enc[ok] = (n[ok] / ln[ok][:, None] + 1.0) / 2.0
+    to8 = lambda x: (np.clip(x, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    return to8(alb), to8(enc), np.ascontiguousarray(normal_depth[..., 3], np.float32)
 
 
 def main():
@@ -36,6 +55,7 @@ def main():
     ap.add_argument("--min-spp", type=int, default=16)
     ap.add_argument("--batch", type=int, default=8, help="samples per pt_trace with --adaptive")
     ap.add_argument("--sample-map", default="")
+    ap.add_argument("--aov", default="", metavar="PREFIX")
     a = ap.parse_args()
 
     import torch
@@ -88,6 +108,9 @@ def main():
     p.environment_map = -1 if env is None else env
     p.tile_rank, p.tile_rank_count = 0, 1
     out = r.create_output(w, h)
+    if a.aov:
+        aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
+        r.set_aov(aov_albedo, aov_nd)
     if a.adaptive is None:
         for frame in range(a.spp):
             p.frame = frame
@@ -120,6 +143,12 @@ def main():
         gltf.write_pfm(a.out, r.readback(out)[..., :3])
     else:
         gltf.write_png(a.out, rgba8, 3)                                  # tone-mapped (AgX + sRGB), ToneMapper.ps.hlsl
+    if a.aov:
+        opaque = np.full((h, w, 1), 255, np.uint8)
+        alb8, nrm8, depth = aov_images(r.readback(aov_albedo), r.readback(aov_nd))
+        gltf.write_png(a.aov + "_albedo.png", np.dstack([alb8, opaque]), 3)
+        gltf.write_png(a.aov + "_normal.png", np.dstack([nrm8, opaque]), 3)
+        np.save(a.aov + "_depth.npy", depth)
     s = r.stats()
     print("%s: %d triangles, %d lights, %d spp, %.2f ms/frame, %.0f Mrays/s -> %s" % (a.path, s.bvh_triangles, lights, a.spp, s.trace_ms, s.rays / max(s.trace_ms, 1e-9) / 1e3 / max(a.spp, 1) * 1.0, a.out))
 
