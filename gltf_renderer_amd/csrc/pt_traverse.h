@@ -1,7 +1,8 @@
 // pt_traverse.h -- software BVH traversal for gfx950 (replaces DXR TraceRay).
 //
 // One lane = one ray.  Traversal of 64-B 4-wide nodes with 8-bit quantised child boxes (3 x dwordx4 + 1 x dwordx2
-// loads per node; each word holds one bound of all four children, dequantised with v_cvt_f32_ubyte + v_fma, then
+// loads per node; each word holds one bound of all four children, the near and the far word of each axis are picked by the sign of the
+// ray's inverse direction (PT_SLAB_SELECT), dequantised with v_cvt_f32_ubyte + v_fma, then
 // the slab test of the four boxes is straight VALU on registers.  Measured: an extra dwordx4 load per node step
 // costs 6 % of the frame, 110 extra VALU instructions per node step cost 1 %), children visited near-to-far (4-key sorting network on (entry distance | slot) packed in one uint), 48-B world-space
 // triangle packets (3 x dwordx4), a per-lane stack held in LDS ([depth][lane] layout: conflict-free
@@ -48,6 +49,14 @@ namespace pt {
 #endif
 #ifndef PT_SLAB_SUBTRACT_FIRST
 #define PT_SLAB_SUBTRACT_FIRST 1
+#endif
+// 1 (default): a 4-wide node step picks, per axis, the NEAR and the FAR plane word of all four children by the sign of the ray's inv BEFORE it
+// dequantises them (two selects per axis), and the slab test uses them directly instead of fminf / fmaxf of every pair of plane distances: 15
+// vector instructions fewer in every copy of the step (tools/kernel_sizes.sh).  The values are the same: lo <= hi per child (the builder's quantisation keeps the order) and inv is
+// finite and not NaN for every finite direction (trav_init clamps it to +-1e30), so (near - o) * inv <= (far - o) * inv and no 0 * inf occurs;
+// only the sign of a zero distance can differ, which can change a visiting order but never a hit (candidate_stands).  Measured: EXPERIMENTS.md.
+#ifndef PT_SLAB_SELECT
+#define PT_SLAB_SELECT 1
 #endif
 #if PT_SLAB_SUBTRACT_FIRST
 #define PT_SLAB_T(P, A) (((P) - t.o.A) * t.inv.A)
@@ -206,7 +215,11 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
 #pragma clang fp contract(fast)       // box tests only decide the visiting order: fused multiply-adds here cannot change a hit (csrc/Makefile)
     const float4* np = (const float4*)sc.nodes + (size_t)t.cur * 4;
     const float4 hd = np[0], chf = np[1], qxy = np[2];
+#ifdef PT_PROBE_NODE3         // diagnostic build only: no fourth load, the z planes are the x planes' bytes (wrong images: for timing a three-load step)
+    const float2 qz = make_float2(qxy.x, qxy.y);
+#else
     const float2 qz = *(const float2*)(np + 3);
+#endif
     if (COUNT) st.nodes++;
 #ifdef PT_PROBE_VALU          // diagnostic build only: PT_PROBE_VALU extra dependent VALU instructions per node step
     { float x = t.tmin; _Pragma("unroll") for (int i = 0; i < PT_PROBE_VALU; i++) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(x)); if (x == 123.456f) st.overflow++; }
@@ -219,16 +232,27 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     const uint32_t wlx = __float_as_uint(qxy.x), whx = __float_as_uint(qxy.y), wly = __float_as_uint(qxy.z), why = __float_as_uint(qxy.w);
     const uint32_t wlz = __float_as_uint(qz.x), whz = __float_as_uint(qz.y);
 #define PT_DQ4(W, S, O) make_float4(bvh_dequant((W) & 0xffu, S, O), bvh_dequant(((W) >> 8) & 0xffu, S, O), bvh_dequant(((W) >> 16) & 0xffu, S, O), bvh_dequant((W) >> 24, S, O))
+#if PT_SLAB_SELECT
+    // lo? / hi? hold the planes the ray meets first / last on each axis (hi / lo swapped where it runs towards minus)
+    const bool nx = t.inv.x < 0.0f, ny = t.inv.y < 0.0f, nz = t.inv.z < 0.0f;
+    const float4 lox = PT_DQ4(nx ? whx : wlx, sx, hd.x), hix = PT_DQ4(nx ? wlx : whx, sx, hd.x), loy = PT_DQ4(ny ? why : wly, sy, hd.y), hiy = PT_DQ4(ny ? wly : why, sy, hd.y);
+    const float4 loz = PT_DQ4(nz ? whz : wlz, sz, hd.z), hiz = PT_DQ4(nz ? wlz : whz, sz, hd.z);
+#define PT_SLAB_NEAR(A, B) (A)
+#define PT_SLAB_FAR(A, B) (B)
+#else
     const float4 lox = PT_DQ4(wlx, sx, hd.x), hix = PT_DQ4(whx, sx, hd.x), loy = PT_DQ4(wly, sy, hd.y), hiy = PT_DQ4(why, sy, hd.y);
     const float4 loz = PT_DQ4(wlz, sz, hd.z), hiz = PT_DQ4(whz, sz, hd.z);
+#define PT_SLAB_NEAR(A, B) fminf(A, B)
+#define PT_SLAB_FAR(A, B) fmaxf(A, B)
+#endif
 #undef PT_DQ4
     uint32_t key[4];
 #define PT_SLAB(K, CH, LX, LY, LZ, HX, HY, HZ)                                                                            \
     {                                                                                                                     \
         float a0 = PT_SLAB_T(LX, x), b0 = PT_SLAB_T(HX, x), a1 = PT_SLAB_T(LY, y), b1 = PT_SLAB_T(HY, y);                   \
         float a2 = PT_SLAB_T(LZ, z), b2 = PT_SLAB_T(HZ, z);                                                                \
-        float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));                              \
-        float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), limit)) * 1.0000004f;                  \
+        float tn = fmaxf(fmaxf(PT_SLAB_NEAR(a0, b0), PT_SLAB_NEAR(a1, b1)), fmaxf(PT_SLAB_NEAR(a2, b2), t.tmin));          \
+        float tx = fminf(fminf(PT_SLAB_FAR(a0, b0), PT_SLAB_FAR(a1, b1)), fminf(PT_SLAB_FAR(a2, b2), limit)) * 1.0000004f; \
         key[K] = (tn <= tx && CH != kEmptyChild) ? ((__float_as_uint(tn) & ~3u) | (uint32_t)K) : 0xffffffffu;              \
     }
     PT_SLAB(0, c0, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x)
@@ -236,6 +260,8 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     PT_SLAB(2, c2, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z)
     PT_SLAB(3, c3, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w)
 #undef PT_SLAB
+#undef PT_SLAB_NEAR
+#undef PT_SLAB_FAR
     // a step pushes at most three entries: if no active lane is within three of the LDS part's end, every push is a plain ds_write
     const bool shallow = __ballot(t.sp + 3 > kStackLds) == 0;
     if (!ORDERED) {

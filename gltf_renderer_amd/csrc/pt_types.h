@@ -95,6 +95,10 @@ static_assert(sizeof(BvhNode) == 64, "BvhNode");
 // Quantisation is conservative (lo rounded down, hi rounded up, checked with the very fma the traversal uses), so a ray enters a
 // superset of the children it would enter with exact boxes and finds the same hits.
 // child >= 0: wide node index; child < 0: leaf reference (below); kEmptyChild: unused slot (never entered).
+// The node uses 56 of its 64 bytes and the fourth load brings 8 of them.  A 48-B payload in the same 64-B line and stride (origin as
+// 16-bit cell indices on a per-tree grid, 5-bit step exponents below the root's: three dwordx4 loads, explicit child references kept) was
+// built and measured: bit-identical images, 0.6 % more node visits, traversal stage 14.05 against 13.84 ms -- the fourth load of a line
+// the step has already asked for is not what a step waits for.  Not kept (profiles/EXPERIMENTS.md).
 #ifndef PT_BVH_WIDTH
 #define PT_BVH_WIDTH 4          // children per wide node: 4 (64-B node, 4 loads per step) or 8 (96-B node, 6 loads per step).  Measured:
                                 // 8-wide takes 10.4 node steps per ray instead of 15.4 with the same loads per ray and is 7 % SLOWER
