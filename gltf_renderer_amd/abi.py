@@ -252,6 +252,16 @@ class PtAovConfig(C.Structure):
     _fields_ = [("enable", C.c_int32), ("albedo", C.c_void_p), ("normal_depth", C.c_void_p)]
 
 
+class PtDenoiseConfig(C.Structure):
+    """pt_denoise_config: the a-trous filter over the first-hit AOVs (pt_denoise; an extension, absent upstream)."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_depth", C.c_float), ("sigma_color", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        return cls(5, 1, 7, 0.02, 1.0)
+
+
 STAGE_NAMES = ("generate", "trace", "shade", "shadow", "resolve")
 EXCHANGE_GATHER, EXCHANGE_REDUCE = 0, 1
 BUILDER_LBVH, BUILDER_PLOC, BUILDER_PLOC_REINSERT = 0, 1, 2
@@ -269,3 +279,4 @@ assert C.sizeof(PtBone) == 128
 assert C.sizeof(PtStats) == 152
 assert C.sizeof(PtAdaptiveConfig) == 16
 assert C.sizeof(PtAovConfig) == 24
+assert C.sizeof(PtDenoiseConfig) == 20

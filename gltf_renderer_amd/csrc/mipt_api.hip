@@ -114,6 +114,8 @@ struct pt_ctx {
     // ---- first-hit AOVs (pt_set_aov): the caller's targets
     pt_aov_config aov = {0, nullptr, nullptr};
     bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
+    // ---- pt_denoise: two ping-pong signal images and the guide image, dn_pixels float4 each, for one image size
+    float4* d_denoise = nullptr; size_t dn_pixels = 0;
 
     // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
     float previous_world_to_clip[16] = {0};
@@ -684,6 +686,7 @@ void pt_destroy(pt_ctx* ctx) {
     hipFree(ctx->d_deep);
     hipFree(ctx->d_occ);
     hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
+    hipFree(ctx->d_denoise);
     for (int k = 0; k < StagingRing::kSlots; k++) {
         if (ctx->staging.host[k]) hipHostFree(ctx->staging.host[k]);
         if (ctx->staging.done[k]) hipEventDestroy(ctx->staging.done[k]);
@@ -1374,6 +1377,42 @@ int pt_tonemap(pt_ctx* ctx, const pt_tonemap_config* cfg, const void* device_rgb
     HIPOK(hipStreamSynchronize(ctx->stream));
     if (host_rgb) HIPOK(hipMemcpy(host_rgb, d_rgb, n * 12, hipMemcpyDeviceToHost));
     if (host_rgba8) HIPOK(hipMemcpy(host_rgba8, d_q, n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- the a-trous denoiser over the first-hit AOVs (denoise.hip) ----------------------------------------------------------------
+static bool images_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config, const void* color, const void* albedo, const void* normal_depth,
+               uint32_t width, uint32_t height, void* out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!color || !albedo || !normal_depth || !out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: null image");
+    if (width == 0 || height == 0 || width > (1u << 30) || height > (1u << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: bad size");
+    pt_denoise_config cfg = {5, 1, 7, 0.02f, 1.0f};
+    if (config) cfg = *config;
+    if (cfg.iterations < 0 || cfg.iterations > 6) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: iterations outside 0..6");
+    if (cfg.normal_power_log2 < 0 || cfg.normal_power_log2 > 10) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: normal_power_log2 outside 0..10");
+    if (!std::isfinite(cfg.sigma_depth) || !(cfg.sigma_depth > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_depth must be finite and > 0");
+    if (!std::isfinite(cfg.sigma_color) || cfg.sigma_color < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_color must be finite and >= 0");
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    if (images_overlap(out, albedo, bytes) || images_overlap(out, normal_depth, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out aliases a guide image");
+    if (out != color && images_overlap(out, color, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out overlaps color without being color");
+    ENTER(ctx);
+    if (cfg.iterations == 0) {                  // the identity: a copy, or nothing in place
+        if (out != color) HIPOK(hipMemcpyAsync(out, color, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return PT_OK;
+    }
+    if (n != ctx->dn_pixels) {
+        HIPOK(hipStreamSynchronize(ctx->stream));
+        hipFree(ctx->d_denoise); ctx->d_denoise = nullptr; ctx->dn_pixels = 0;
+        HIPOK(hipMalloc(&ctx->d_denoise, 3 * bytes));
+        ctx->dn_pixels = n;
+    }
+    float4* s = ctx->d_denoise;
+    HIPOK(launch_denoise(cfg, (const float4*)color, (const float4*)albedo, (const float4*)normal_depth, width, height, (float4*)out, s, s + n, s + 2 * n, ctx->stream));
     return PT_OK;
 }
 

@@ -27,7 +27,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # adaptive sampling (additive: the ABI version stays 2)
            "pt_set_adaptive", "pt_adaptive_read",
            # first-hit AOVs (additive likewise)
-           "pt_set_aov"]
+           "pt_set_aov",
+           # the denoiser over them (additive likewise)
+           "pt_denoise"]
 
 
 class MiptError(RuntimeError):
@@ -102,6 +104,7 @@ def load_library():
     L.pt_set_adaptive.argtypes = [vp, vp]
     L.pt_adaptive_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.pt_set_aov.argtypes = [vp, vp]
+    L.pt_denoise.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     _LIB = L
     return L
 
@@ -256,6 +259,21 @@ class Renderer:
                               normal_depth.data_ptr() if normal_depth is not None else None)
         self._check(self.L.pt_set_aov(self.h, C.byref(cfg)))
         self._aov = (albedo, normal_depth)           # the library keeps the pointers: keep the tensors alive with the renderer
+
+    def denoise(self, color, albedo, normal_depth, out=None, config=None):
+        """The a-trous filter over the first-hit AOVs (include/mipt.h pt_denoise): color, albedo and normal_depth are float32 CUDA tensors
+        (H, W, 4) -- the output of trace() and the targets of set_aov(), or any images of that layout.  out: where the result goes (None = a
+        new tensor; `color` itself filters in place); config: abi.PtDenoiseConfig (None = the defaults).  Asynchronous on the context's
+        stream.  Returns the output tensor."""
+        t = self.torch
+        if out is None:
+            out = t.empty_like(color)
+        for x in (color, albedo, normal_depth, out):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+        h, w = color.shape[:2]
+        self._check(self.L.pt_denoise(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
+                                      C.c_void_p(albedo.data_ptr()), C.c_void_p(normal_depth.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
+        return out
 
     def set_null_shadow_culling(self, on):
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""

@@ -460,6 +460,42 @@ typedef struct pt_aov_config {
 /* PT_ERR_INVALID_ARGUMENT if enable != 0 and both targets are NULL.  Forces a new accumulation on the next pt_trace, so that the
  * targets and the output always hold the same samples. */
 int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config);
+/* Denoiser (absent upstream): an edge-avoiding a-trous filter over an image and its first-hit AOVs.  One pure function of three images,
+ * C = color, A = albedo, N = normal_depth in the layout pt_set_aov writes: it reads no pt_trace state, so it takes the images after an
+ * exchange, after adaptive sampling, or a rank's partial image alike.  All four images are device pointers to W * H float4, caller-owned
+ * like pt_execute_params.output; out == color filters in place.  Enqueued on the context's stream, asynchronous like pt_trace.  The
+ * scratch (two signal images and one guide image of W * H float4) belongs to the context: reallocated when the size changes, freed by
+ * pt_destroy.  All arithmetic is float32, in the order written; cov = A.w.
+ *   Prepare, per pixel:
+ *     a' = max(A.rgb + (1 - cov), 1e-3) channel-wise if demodulate, else 1 (a miss counts as albedo 1, so a silhouette pixel demodulates
+ *          consistently);  signal S = C.rgb / a';  guide n = N.xyz / |N.xyz| with |N.xyz| = sqrt((x x + y y) + z z), and z = N.w / cov.
+ *     The pixel is VALID iff cov > 0, |N.xyz| > 0, z is finite and > 0, and every component of S and n is finite.  An invalid pixel is
+ *     never a neighbour -- its weight is 0 by a select, not by a product, so a NaN cannot leak -- and leaves the call with out = C, all
+ *     four channels bit for bit: background, tiles another rank renders, non-finite samples.
+ *   Pass i = 0 .. iterations - 1, step s = 2^i: for a valid centre p the taps are q = p + s (dx, dy), dx, dy in -2 .. 2, dy outer, dx
+ *     inner; taps outside the image or invalid are skipped.  With h = (1/16, 1/4, 3/8, 1/4, 1/16) and L = (S.r + S.g) + S.b,
+ *         w  = ((h[dy] h[dx]) wn) exp(-(ez + ec))
+ *         wn = clamp((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0, 1), squared normal_power_log2 times
+ *         ez = |z_p - z_q| / ((sigma_depth s) z_p + 1e-6)
+ *         ec = ((dr dr + dg dg) + db db) / (sigma_i^2 ((L_p + L_q)(L_p + L_q)) + 1e-8), d = S_p - S_q, sigma_i = sigma_color 2^-i;
+ *              0 when sigma_color == 0
+ *     and S'_p = (sum of w S_q) / (sum of w), the sums sequential in tap order.  The centre tap keeps the sum of w near 9/64 or above.
+ *     The colour term is relative and symmetric: an absolute sigma removes almost no noise at low sample counts, and a centre-only
+ *     relative term leaves black drop-out pixels black.
+ *   After the passes a valid pixel gets out.rgb = S a' and out.w = C.w.  iterations = 0 gives out = C bit for bit everywhere.
+ * PT_ERR_INVALID_ARGUMENT, with nothing written: a NULL ctx (answered before any device call), a NULL image, a zero width or height, a
+ * width or height above 2^30, a config value outside the ranges below, out overlapping albedo or normal_depth (or color without being
+ * color). */
+typedef struct pt_denoise_config {
+    int32_t iterations;         /* 0..6 passes; pass i taps at spacing 2^i.  default 5 */
+    int32_t demodulate;         /* non-zero: filter colour / albedo', multiply back.  default 1 */
+    int32_t normal_power_log2;  /* 0..10: normal weight = max(0, n_p . n_q)^(2^k) by k squarings.  default 7 */
+    float   sigma_depth;        /* finite, > 0.  default 0.02 */
+    float   sigma_color;        /* finite, >= 0; 0 = colour term off.  default 1 */
+} pt_denoise_config;            /* 20 bytes */
+int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config /* NULL = defaults */,
+               const void* color, const void* albedo, const void* normal_depth,
+               uint32_t width, uint32_t height, void* out);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Run ON THE GPU BOX: what pt_denoise costs at 1920 x 1080 on the 8-spp images of config 3 (the Sponza-class scene), timed from outside
+with stream events -- pt_stats does not grow for it.  For iterations 1, 3 and 5: the median of CALLS calls after WARMUP warm-ups, and
+the share of the L2 gather rate that figure stands for (a pass reads 25 taps x 32 B per pixel through L2; MI355X_MICROARCH: 16.8 TB/s).
+Beside it the single-sample pt_trace launch of the same build, the cost a user weighs the filter against.
+usage: python tools/denoise_probe.py [--calls 30] [--size 1920 1080] [--json FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+L2_GATHER_BYTES_PER_S = 16.8e12
+TAP_BYTES = 25 * 32
+
+
+def pass_bytes(width, height, iterations):
+    """Bytes the passes of one call read through L2: 25 taps of one signal and one guide float4 per pixel and pass."""
+    return width * height * TAP_BYTES * iterations
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--size", type=int, nargs=2, default=[1920, 1080])
+    ap.add_argument("--json", default="")
+    ap.add_argument("--no-trace", action="store_true", help="skip the pt_trace launches")
+    a = ap.parse_args()
+    if a.calls < 20:
+        raise SystemExit("denoise_probe.py: --calls must be >= 20")
+
+    import torch
+    from gltf_renderer_amd import abi, scenes
+    from gltf_renderer_amd.renderer import Renderer
+    if not torch.cuda.is_available():
+        raise SystemExit("denoise_probe.py: no GPU, nothing measured")
+
+    s = scenes.sponza_class()
+    s.width, s.height = a.size
+    w, h = a.size
+    r = Renderer(0)
+    hd = s.upload(r)
+    r.build_accel()
+    out, alb, nd, den = (r.create_output(w, h) for _ in range(4))
+    r.set_aov(alb, nd)
+    st = abi.PtSettings.from_buffer_copy(bytes(s.settings))
+    st.reset = 1
+    r.set_samples_per_trace(8)
+    r.trace(st, s.execute_params(0, env_handle=hd["env"]), out)            # the 8-spp images
+    torch.cuda.synchronize()
+    cov = r.readback(alb)[..., 3]
+    res = {"width": w, "height": h, "calls": a.calls, "warmup": a.warmup, "covered_pixels": float((cov > 0).mean()), "denoise": {}}
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), min(ms), max(ms)
+
+    for it in (1, 3, 5):
+        cfg = abi.PtDenoiseConfig.default()
+        cfg.iterations = it
+        med, lo, hi = timed(lambda: r.denoise(out, alb, nd, out=den, config=cfg))
+        share = pass_bytes(w, h, it) / (med * 1e-3) / L2_GATHER_BYTES_PER_S
+        res["denoise"][str(it)] = {"ms_median": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4), "l2_gather_share": round(share, 4)}
+        print("pt_denoise %dx%d, %d iteration(s): median %.4f ms (min %.4f, max %.4f) of %d calls, %.1f %% of the L2 gather rate"
+              % (w, h, it, med, lo, hi, a.calls, 100.0 * share), flush=True)
+
+    def finish():
+        print(json.dumps(res))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        r.close()
+
+    if a.no_trace:
+        finish()
+        return
+    # the single-sample pt_trace launch of the same build (AOVs off, as bench.py times it)
+    r.set_aov(None, None)
+    r.set_samples_per_trace(1)
+    frame = [8]
+
+    def trace_one():
+        r.trace(st, s.execute_params(frame[0], env_handle=hd["env"]), out)
+        st.reset = 0
+        frame[0] += 1
+
+    med, lo, hi = timed(trace_one)
+    res["trace_single_sample_ms_median"] = round(med, 4)
+    print("pt_trace %dx%d, one sample per pixel: median %.4f ms (min %.4f, max %.4f) of %d launches" % (w, h, med, lo, hi, a.calls), flush=True)
+    finish()
+
+
+if __name__ == "__main__":
+    main()

@@ -12,6 +12,9 @@ per-tile counts as a grey PNG (white = --spp).
 rgb / coverage, linear, 8 bit), PREFIX_normal.png ((n / |n| + 1) / 2 of the mean world-space shading normal where coverage > 0,
 black elsewhere) and PREFIX_depth.npy (float32 H x W: the mean of the camera rays' hit distances, a miss counting 0).
 
+--denoise [ITERATIONS]: the a-trous filter over the first-hit AOVs (pt_denoise, 5 passes unless given) on the accumulated frame before tone
+mapping; turns the AOVs on, and keeps the noisy frame beside the output as <out>_noisy.png (<out> without its extension).
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -39,6 +42,11 @@ def aov_images(albedo, normal_depth):
     return to8(alb), to8(enc), np.ascontiguousarray(normal_depth[..., 3], np.float32)
 
 
+def noisy_path(out):
+    """Where --denoise keeps the frame as it was before the filter."""
+    return os.path.splitext(out)[0] + "_noisy.png"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path")
@@ -56,6 +64,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="samples per pt_trace with --adaptive")
     ap.add_argument("--sample-map", default="")
     ap.add_argument("--aov", default="", metavar="PREFIX")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS")
     a = ap.parse_args()
 
     import torch
@@ -108,7 +117,7 @@ def main():
     p.environment_map = -1 if env is None else env
     p.tile_rank, p.tile_rank_count = 0, 1
     out = r.create_output(w, h)
-    if a.aov:
+    if a.aov or a.denoise is not None:
         aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
         r.set_aov(aov_albedo, aov_nd)
     if a.adaptive is None:
@@ -136,6 +145,12 @@ def main():
             grey = np.repeat(np.repeat((255.0 * samples / a.spp).astype(np.uint8), abi.TILE, 0), abi.TILE, 1)[:h, :w]
             gltf.write_png(a.sample_map, np.dstack([grey, grey, grey, np.full_like(grey, 255)]), 3)
     torch.cuda.synchronize()
+    if a.denoise is not None:
+        _, noisy8 = r.tonemap(out, want_rgba8=True)
+        gltf.write_png(noisy_path(a.out), noisy8, 3)
+        cfg = abi.PtDenoiseConfig.default()
+        cfg.iterations = a.denoise
+        r.denoise(out, aov_albedo, aov_nd, out=out, config=cfg)          # in place: the AOVs are only read
     _, rgba8 = r.tonemap(out, want_rgba8=True)
     if a.out.lower().endswith(".exr"):
         gltf.write_exr(a.out, r.readback(out)[..., :3], half=True)       # linear radiance
