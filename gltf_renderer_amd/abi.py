@@ -262,6 +262,22 @@ class PtDenoiseConfig(C.Structure):
         return cls(5, 1, 7, 0.02, 1.0)
 
 
+ACCUM_OUTPUT, ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE = 1, 2, 4, 8
+ACCUM_HEADER_BYTES = 160
+
+
+class PtAccumImages(C.Structure):
+    """pt_accum_images: the device images of an accumulation (pt_accum_save / pt_accum_load); None = not part of the state."""
+    _fields_ = [("output", C.c_void_p), ("albedo", C.c_void_p), ("normal_depth", C.c_void_p)]
+
+
+class PtAccumInfo(C.Structure):
+    """pt_accum_info: what a checkpoint blob holds (pt_accum_inspect)."""
+    _fields_ = [("sections", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("tile_rank", C.c_uint32),
+                ("tile_rank_count", C.c_uint32), ("accumulated_frames", C.c_int32), ("tiles", C.c_uint32),
+                ("next_frame", C.c_uint64), ("total_bytes", C.c_uint64), ("adaptive", PtAdaptiveConfig)]
+
+
 STAGE_NAMES = ("generate", "trace", "shade", "shadow", "resolve")
 EXCHANGE_GATHER, EXCHANGE_REDUCE = 0, 1
 BUILDER_LBVH, BUILDER_PLOC, BUILDER_PLOC_REINSERT = 0, 1, 2
@@ -280,3 +296,5 @@ assert C.sizeof(PtStats) == 152
 assert C.sizeof(PtAdaptiveConfig) == 16
 assert C.sizeof(PtAovConfig) == 24
 assert C.sizeof(PtDenoiseConfig) == 20
+assert C.sizeof(PtAccumImages) == 24
+assert C.sizeof(PtAccumInfo) == 64

@@ -21,6 +21,7 @@
 #include "pt_types.h"
 
 #include "pt_host.h"
+#include "host/accum_state.h"
 
 using namespace pt;
 
@@ -111,6 +112,8 @@ struct pt_ctx {
     uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
     bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
     int ad_frames = -1;                           // accumulated_frames the tile state stands for (-1: none)
+    // ---- pt_accum_save / pt_accum_load: the packed sections of one blob (one pt_tiles_pack image each), reused between calls
+    void* d_accum = nullptr; size_t accum_cap = 0;
     // ---- first-hit AOVs (pt_set_aov): the caller's targets
     pt_aov_config aov = {0, nullptr, nullptr};
     bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
@@ -686,6 +689,7 @@ void pt_destroy(pt_ctx* ctx) {
     hipFree(ctx->d_deep);
     hipFree(ctx->d_occ);
     hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
+    hipFree(ctx->d_accum);
     hipFree(ctx->d_denoise);
     for (int k = 0; k < StagingRing::kSlots; k++) {
         if (ctx->staging.host[k]) hipHostFree(ctx->staging.host[k]);
@@ -1413,6 +1417,142 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config, const void* color, 
     }
     float4* s = ctx->d_denoise;
     HIPOK(launch_denoise(cfg, (const float4*)color, (const float4*)albedo, (const float4*)normal_depth, width, height, (float4*)out, s, s + n, s + 2 * n, ctx->stream));
+    return PT_OK;
+}
+
+// ---- saving and resuming an accumulation (host/accum_state.h holds the format and its validator) ----------------------------------
+static int accum_scratch(pt_ctx* ctx, size_t need) {
+    if (need <= ctx->accum_cap) return PT_OK;
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->d_accum); ctx->d_accum = nullptr; ctx->accum_cap = 0;
+    if (hipMalloc(&ctx->d_accum, need) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "accumulation scratch: " + std::to_string(need) + " bytes"); }
+    ctx->accum_cap = need;
+    return PT_OK;
+}
+
+int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, uint32_t height, uint32_t tile_rank, uint32_t tile_rank_count,
+                  uint64_t next_frame, void* host_blob, size_t capacity, size_t* bytes_out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!bytes_out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: bytes_out is null");
+    if (!images || !images->output) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: images->output is null");
+    if (width == 0 || height == 0 || width > accum::kMaxExtent || height > accum::kMaxExtent) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: bad size");
+    const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
+    if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
+    if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
+    if (ctx->adaptive_restart || ctx->aov_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov since the last trace: the next trace starts anew");
+    // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
+    const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
+                          ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
+    pt_accum_info info;
+    memset(&info, 0, sizeof(info));
+    info.sections = PT_ACCUM_OUTPUT | (images->albedo ? PT_ACCUM_ALBEDO : 0) | (images->normal_depth ? PT_ACCUM_NORMAL_DEPTH : 0) | (adaptive ? PT_ACCUM_ADAPTIVE : 0);
+    info.width = width; info.height = height; info.tile_rank = tile_rank; info.tile_rank_count = world;
+    info.accumulated_frames = ctx->accumulated_frames;
+    info.tiles = tiles_of_rank(width, height, tile_rank, world);
+    info.next_frame = next_frame;
+    if (adaptive) info.adaptive = ctx->adaptive;
+    const accum::Layout l = accum::layout(info.sections, info.tiles);
+    info.total_bytes = l.total_bytes;
+    *bytes_out = (size_t)l.total_bytes;
+    if (!host_blob) return PT_OK;
+    if ((uint64_t)capacity < l.total_bytes) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: capacity below the " + std::to_string(l.total_bytes) + " bytes needed");
+    ENTER(ctx);
+    const void* src[4] = {images->output, images->albedo, images->normal_depth, adaptive ? ctx->d_ad_half : nullptr};
+    const uint64_t at[4] = {l.image[0], l.image[1], l.image[2], l.half};
+    const size_t P = (size_t)l.packed_bytes;
+    int slot[4], slots = 0;                       // one packed image of scratch per section present
+    for (int k = 0; k < 4; k++) slot[k] = src[k] ? slots++ : -1;
+    if (P) {
+        int r = accum_scratch(ctx, slots * P);
+        if (r) return r;
+        for (int k = 0; k < 4; k++)
+            if (src[k]) HIPOK(tiles_pack(src[k], width, height, tile_rank, world, (char*)ctx->d_accum + slot[k] * P, ctx->stream));
+    }
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    accum::write_header(host_blob, info, ctx->previous_world_to_clip);
+    for (int k = 0; k < 4 && P; k++)
+        if (src[k]) HIPOK(hipMemcpy((char*)host_blob + at[k], (char*)ctx->d_accum + slot[k] * P, P, hipMemcpyDeviceToHost));
+    if (adaptive && info.tiles) {
+        static_assert(sizeof(AdaptiveTile) == accum::kRecordBytes, "a tile record is an AdaptiveTile");
+        std::vector<AdaptiveTile> t(info.tiles);
+        HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
+        for (AdaptiveTile& x : t) x.pad = 0;
+        memcpy((char*)host_blob + l.records, t.data(), t.size() * sizeof(AdaptiveTile));
+    }
+    accum::seal(host_blob, l.total_bytes);
+    return PT_OK;
+}
+
+int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_accum_images* targets) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!targets) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: targets is null");
+    pt_accum_info info;
+    float world_to_clip[16];
+    std::string err;
+    if (!accum::validate(host_blob, bytes, info, world_to_clip, err)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: " + err);
+    void* dst[3] = {targets->output, targets->albedo, targets->normal_depth};
+    static const char* const names[3] = {"output", "albedo", "normal_depth"};
+    for (int k = 0; k < 3; k++) {
+        const bool section = (info.sections & (1u << k)) != 0;
+        if (section && !dst[k]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, std::string("accum_load: the blob holds ") + names[k] + " but no target is given");
+        if (!section && dst[k]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, std::string("accum_load: a target for ") + names[k] + " but the blob holds none");
+    }
+    const bool adaptive = (info.sections & PT_ACCUM_ADAPTIVE) != 0;
+    if (adaptive) {
+        const pt_adaptive_config& a = ctx->adaptive;
+        if (a.enable == 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: adaptive.enable: the blob is an adaptive accumulation, the context has adaptive sampling off");
+        if (a.enable != info.adaptive.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: adaptive.enable differs from the context's");
+        if (a.min_samples != info.adaptive.min_samples) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: adaptive.min_samples differs from the context's");
+        if (a.max_samples != info.adaptive.max_samples) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: adaptive.max_samples differs from the context's");
+        if (memcmp(&a.threshold, &info.adaptive.threshold, 4) != 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_load: adaptive.threshold differs from the context's");
+    }
+    if (adaptive && (uint64_t)info.width * info.height > SIZE_MAX / 16) return ctx->fail(PT_ERR_OUT_OF_MEMORY, "accum_load: half buffer of width x height float4");
+    ENTER(ctx);
+    const accum::Layout l = accum::layout(info.sections, info.tiles);
+    const size_t P = (size_t)l.packed_bytes, px = (size_t)info.width * info.height, tiles = info.tiles ? info.tiles : 1;
+    void* out[4] = {dst[0], dst[1], dst[2], adaptive ? (void*)1 : nullptr};        // [3]: the half buffer, once it is allocated
+    int slot[4], slots = 0;                       // one packed image of scratch per section present
+    for (int k = 0; k < 4; k++) slot[k] = out[k] ? slots++ : -1;
+    if (P) { int r = accum_scratch(ctx, slots * P); if (r) return r; }
+    if (adaptive && (tiles > ctx->ad_tiles_cap || px > ctx->ad_half_cap)) {         // grown as PathtraceScene grows them
+        HIPOK(hipStreamSynchronize(ctx->stream));
+        hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
+        ctx->d_ad_tiles = nullptr; ctx->d_ad_half = nullptr; ctx->ad_tiles_cap = ctx->ad_half_cap = 0; ctx->ad_ready = false;
+        if (hipMalloc((void**)&ctx->d_ad_tiles, tiles * sizeof(AdaptiveTile)) != hipSuccess || hipMalloc((void**)&ctx->d_ad_half, px * 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return ctx->fail(PT_ERR_OUT_OF_MEMORY, "adaptive tile state");
+        }
+        ctx->ad_tiles_cap = tiles; ctx->ad_half_cap = px;
+    }
+    // every check has passed.  The caller may free the blob on return: its bytes are on the device before that, the unpacking is enqueued.
+    const uint64_t at[4] = {l.image[0], l.image[1], l.image[2], l.half};
+    out[3] = adaptive ? (void*)ctx->d_ad_half : nullptr;
+    for (int k = 0; k < 4 && P; k++)
+        if (out[k]) HIPOK(hipMemcpyAsync((char*)ctx->d_accum + slot[k] * P, (const char*)host_blob + at[k], P, hipMemcpyHostToDevice, ctx->stream));
+    if (adaptive) {
+        if (info.tiles) HIPOK(hipMemcpyAsync(ctx->d_ad_tiles, (const char*)host_blob + l.records, info.tiles * sizeof(AdaptiveTile), hipMemcpyHostToDevice, ctx->stream));
+        HIPOK(hipMemsetAsync(ctx->d_ad_half, 0, px * 16, ctx->stream));            // other ranks' pixels: as a new accumulation leaves them
+    }
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 4 && P; k++)
+        if (out[k]) HIPOK(tiles_unpack((char*)ctx->d_accum + slot[k] * P, info.width, info.height, info.tile_rank, info.tile_rank_count, out[k], ctx->stream));
+    ctx->accumulated_frames = info.accumulated_frames;
+    memcpy(ctx->previous_world_to_clip, world_to_clip, 64);
+    if (adaptive) {
+        ctx->ad_w = info.width; ctx->ad_h = info.height; ctx->ad_rank = info.tile_rank; ctx->ad_rank_count = info.tile_rank_count;
+        ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
+    }
+    ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
+    ctx->adaptive_restart = false; ctx->aov_restart = false;
+    return PT_OK;
+}
+
+int pt_accum_inspect(const void* host_blob, size_t bytes, pt_accum_info* out) {
+    if (!host_blob || !out) return PT_ERR_INVALID_ARGUMENT;
+    std::string err;
+    pt_accum_info info;
+    if (!accum::validate(host_blob, bytes, info, nullptr, err)) return PT_ERR_INVALID_ARGUMENT;
+    *out = info;
     return PT_OK;
 }
 

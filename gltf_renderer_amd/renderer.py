@@ -29,7 +29,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # first-hit AOVs (additive likewise)
            "pt_set_aov",
            # the denoiser over them (additive likewise)
-           "pt_denoise"]
+           "pt_denoise",
+           # saving and resuming an accumulation (additive likewise)
+           "pt_accum_save", "pt_accum_load", "pt_accum_inspect"]
 
 
 class MiptError(RuntimeError):
@@ -105,6 +107,9 @@ def load_library():
     L.pt_adaptive_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.pt_set_aov.argtypes = [vp, vp]
     L.pt_denoise.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
+    L.pt_accum_save.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pt_accum_load.argtypes = [vp, vp, C.c_size_t, vp]
+    L.pt_accum_inspect.argtypes = [vp, C.c_size_t, vp]
     _LIB = L
     return L
 
@@ -274,6 +279,46 @@ class Renderer:
         self._check(self.L.pt_denoise(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
                                       C.c_void_p(albedo.data_ptr()), C.c_void_p(normal_depth.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
         return out
+
+    # ---- saving and resuming an accumulation (include/mipt.h pt_accum_save / pt_accum_load / pt_accum_inspect)
+    def _accum_images(self, output, albedo, normal_depth):
+        for t in (output, albedo, normal_depth):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4)
+        return abi.PtAccumImages(*[t.data_ptr() if t is not None else None for t in (output, albedo, normal_depth)])
+
+    def accum_save(self, width, height, output, albedo=None, normal_depth=None, rank=0, world=1, next_frame=0):
+        """The accumulation as one bytes blob: the images given (the output of trace() and, if AOVs are on, the targets of set_aov()), the
+        count and camera and, with adaptive sampling, the tile state.  rank / world: the tile shard traced (the blob holds the rank's
+        tiles).  next_frame: the frame number to continue with, kept for the caller.  Synchronises the stream."""
+        assert output is not None and tuple(output.shape[:2]) == (height, width)
+        img = self._accum_images(output, albedo, normal_depth)
+        need = C.c_size_t()
+        self._check(self.L.pt_accum_save(self.h, C.byref(img), width, height, rank, world, next_frame, None, 0, C.byref(need)))
+        blob = bytearray(need.value)
+        buf = (C.c_ubyte * need.value).from_buffer(blob)
+        self._check(self.L.pt_accum_save(self.h, C.byref(img), width, height, rank, world, next_frame, buf, need.value, C.byref(need)))
+        del buf
+        return bytes(blob)
+
+    def accum_load(self, blob, output, albedo=None, normal_depth=None):
+        """Puts a blob of accum_save() into this renderer and the given tensors (fresh ones, of the blob's size): call it after the scene
+        upload and set_adaptive() / set_aov() / set_samples_per_trace() as for a fresh run; trace() with the saved camera and reset = 0
+        then continues from the blob's next_frame.  Returns the blob's abi.PtAccumInfo."""
+        info = self.accum_inspect(blob)
+        for t in (output, albedo, normal_depth):
+            assert t is None or tuple(t.shape[:2]) == (info.height, info.width), "target size differs from the blob's"
+        img = self._accum_images(output, albedo, normal_depth)
+        self._check(self.L.pt_accum_load(self.h, bytes(blob), len(blob), C.byref(img)))
+        return info
+
+    @staticmethod
+    def accum_inspect(blob):
+        """What a blob holds (abi.PtAccumInfo); raises MiptError for one that is malformed.  No GPU call."""
+        info = abi.PtAccumInfo()
+        rc = load_library().pt_accum_inspect(bytes(blob), len(blob), C.byref(info))
+        if rc != 0:
+            raise MiptError("%d: not a valid accumulation blob" % rc)
+        return info
 
     def set_null_shadow_culling(self, on):
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""

@@ -496,6 +496,77 @@ typedef struct pt_denoise_config {
 int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config /* NULL = defaults */,
                const void* color, const void* albedo, const void* normal_depth,
                uint32_t width, uint32_t height, void* out);
+/* Saving and resuming an accumulation (absent upstream).  The state of a running accumulation is the caller's images (the output and, with
+ * pt_set_aov, the two AOV targets), the context's count and camera (accumulated_frames, the previous world_to_clip) and, with pt_set_adaptive,
+ * the per-tile records and the half buffer.  pt_accum_save writes all of it to one host blob; pt_accum_load puts it into another context --
+ * a new process, another day -- so that pt_trace continues: save, pt_destroy, pt_create, upload the scene, pt_set_adaptive / pt_set_aov /
+ * pt_set_samples_per_trace as for a fresh run, load, trace on with reset = 0 and the saved camera gives bit for bit the images and the
+ * tile state of the run that was never interrupted.  A rank of the tile-sharded renderer saves what it owns: its tiles, 1 / N of each image.
+ *
+ * The blob, little-endian.  Header, 160 bytes:
+ *     offset  0  char[8]   "MIPTACC1"
+ *             8  u32       version = 1
+ *            12  u32       header_bytes = 160
+ *            16  u64       total_bytes: the whole blob
+ *            24  u32       crc32 of bytes [28, total_bytes): the IEEE 802.3 polynomial, zlib's crc32
+ *            28  u32       sections: PT_ACCUM_* bits
+ *            32  u32       width
+ *            36  u32       height
+ *            40  u32       tile_rank
+ *            44  u32       tile_rank_count (>= 1; a 0 given to pt_accum_save is stored as 1)
+ *            48  i32       accumulated_frames (>= 1)
+ *            52  u32       tiles: the 16x16 tiles t of the ceil(width / 16) x ceil(height / 16) grid with t % tile_rank_count == tile_rank
+ *            56  u64       next_frame: the caller's value, the frame number to continue with
+ *            64  f32[16]   previous_world_to_clip, as pt_trace compares it
+ *           128  pt_adaptive_config {i32 enable, i32 min_samples, i32 max_samples, f32 threshold}; zeros without PT_ACCUM_ADAPTIVE
+ *           144  u32[4]    reserved = 0
+ * Payload, from offset 160, with P = pt_tiles_packed_bytes(width, height, tile_rank, tile_rank_count) = tiles * 256 * 16:
+ *     for each image bit present, in the order OUTPUT, ALBEDO, NORMAL_DEPTH: the rank's tiles in pt_tiles_pack's layout, P bytes;
+ *     with PT_ACCUM_ADAPTIVE: `tiles` records of 16 bytes {u32 active, u32 samples, f32 error, u32 0}, rank-local tile k being tile
+ *     tile_rank + k * tile_rank_count, then the half buffer packed like an image, P bytes.
+ * total_bytes = 160 + images * P + (ADAPTIVE ? tiles * 16 + P : 0). */
+enum { PT_ACCUM_OUTPUT = 1 << 0, PT_ACCUM_ALBEDO = 1 << 1, PT_ACCUM_NORMAL_DEPTH = 1 << 2, PT_ACCUM_ADAPTIVE = 1 << 3 };
+typedef struct pt_accum_images {      /* device pointers, W*H float4, caller-owned; NULL = not part of the state */
+    void* output; void* albedo; void* normal_depth;
+} pt_accum_images;
+typedef struct pt_accum_info {        /* what a blob holds; filled by pt_accum_inspect */
+    uint32_t sections;                /* PT_ACCUM_OUTPUT | _ALBEDO | _NORMAL_DEPTH | _ADAPTIVE = bits 0..3 */
+    uint32_t width, height, tile_rank, tile_rank_count;
+    int32_t  accumulated_frames;
+    uint32_t tiles;                   /* tiles of that rank */
+    uint64_t next_frame;              /* caller's value from save: the frame number to continue with */
+    uint64_t total_bytes;
+    pt_adaptive_config adaptive;      /* zeros without PT_ACCUM_ADAPTIVE */
+} pt_accum_info;                      /* 64 bytes */
+/* Writes the state to host_blob.  Synchronises the stream.  images->output is required; an AOV image is a section iff its pointer is given
+ * (the caller passes the targets of pt_set_aov, which hold the output's samples).  tile_rank / tile_rank_count as in pt_execute_params
+ * (a count of 0 means 1).  host_blob == NULL: only the size needed goes to *bytes_out.  PT_ERR_INVALID_ARGUMENT, with *bytes_out set, for
+ * a capacity below it.  PT_ERR_NOT_READY, with nothing written, while there is nothing to save: accumulated_frames is 0, or pt_set_adaptive /
+ * pt_set_aov was called after the last trace (the next trace starts a new accumulation anyway).  The ADAPTIVE section is present iff
+ * adaptive sampling is enabled and the tile state describes this accumulation (the last accumulating trace was adaptive, of this size and
+ * tile shard): exactly when the next adaptive pt_trace would continue rather than restart.  Otherwise the blob is a uniform one, and an
+ * adaptive trace after its load restarts as the uninterrupted one would.  The images are packed through device scratch that belongs to
+ * the context (one packed image per section; freed by pt_destroy). */
+int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, uint32_t height,
+                  uint32_t tile_rank, uint32_t tile_rank_count, uint64_t next_frame,
+                  void* host_blob, size_t capacity, size_t* bytes_out);
+/* Puts a blob's state into the context and the targets.  The order for a caller: pt_create, the scene, pt_set_adaptive / pt_set_aov as for a
+ * fresh run, then this.  The blob is validated as by pt_accum_inspect; then a target must be given for every image section and none without
+ * one, and with PT_ACCUM_ADAPTIVE the context's adaptive config must be enabled and equal the blob's field by field (the threshold by its
+ * bits).  Only then is anything written: any of these failures is PT_ERR_INVALID_ARGUMENT with a message naming the field, the context and
+ * the targets as they were.  The sections are unpacked into the targets -- the rank's tiles only, other pixels are not touched -- the tile
+ * records and the half buffer go into the context, accumulated_frames and the previous world_to_clip are set, and a pending restart from
+ * pt_set_adaptive / pt_set_aov is cleared.  The blob is consumed before the call returns (it waits for its own uploads); the unpacking is
+ * enqueued on the stream like pt_trace.  Afterwards a pt_trace with the saved camera and reset == 0 continues; another camera or reset
+ * starts anew as always.  The kernel mode is no part of the state: a uniform accumulation resumes in either. */
+int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_accum_images* targets);
+/* Parses and checks a blob: no context, no device call.  PT_ERR_INVALID_ARGUMENT for: bytes < 160, a wrong magic, version or header_bytes,
+ * total_bytes != bytes; unknown section bits, no OUTPUT, a non-zero reserved word; a width or height of 0 or above 2^30, tile_rank_count 0,
+ * tile_rank >= tile_rank_count; `tiles` other than the rank's tile count, accumulated_frames < 1; a total_bytes other than the formula
+ * above (64-bit arithmetic); with ADAPTIVE a config pt_set_adaptive refuses or one not enabled, without it a non-zero config byte; a crc
+ * mismatch; with ADAPTIVE a tile record with active > 1, samples > accumulated_frames, an active tile whose samples != accumulated_frames,
+ * a NaN error or a non-zero pad. */
+int pt_accum_inspect(const void* host_blob, size_t bytes, pt_accum_info* out);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -15,6 +15,12 @@ black elsewhere) and PREFIX_depth.npy (float32 H x W: the mean of the camera ray
 --denoise [ITERATIONS]: the a-trous filter over the first-hit AOVs (pt_denoise, 5 passes unless given) on the accumulated frame before tone
 mapping; turns the AOVs on, and keeps the noisy frame beside the output as <out>_noisy.png (<out> without its extension).
 
+--checkpoint FILE: after the last sample the accumulation (the frame, the AOVs, the adaptive tile state) is written to FILE
+(pt_accum_save).  --resume FILE: loads such a file (pt_accum_load) and continues from the frame number it holds; --spp is the TOTAL, so
+`--spp 64 --checkpoint a.acc` today and `--spp 256 --resume a.acc` tomorrow give the 256-sample frame of one uninterrupted run.  The file
+must fit the command line: the same --size, --aov / --denoise or neither, and the same --adaptive, --min-spp and --spp (an adaptive
+accumulation carries its sample cap); the scene, camera and --batch are the caller's to repeat.
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -47,6 +53,28 @@ def noisy_path(out):
     return os.path.splitext(out)[0] + "_noisy.png"
 
 
+def resume_mismatch(info, size, aov, adaptive, accum_flags):
+    """Why a checkpoint (its abi.PtAccumInfo) does not fit the command line, or None.  adaptive = (min_samples, max_samples, threshold) as
+    --min-spp / --spp / --adaptive give them, or None; accum_flags = (ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE)."""
+    a_alb, a_nd, a_ad = accum_flags
+    if (info.width, info.height) != tuple(size):
+        return "it holds a %d x %d frame, --size is %d x %d" % (info.width, info.height, size[0], size[1])
+    if (info.tile_rank, info.tile_rank_count) != (0, 1):
+        return "it holds tile shard %d of %d, this tool renders whole frames" % (info.tile_rank, info.tile_rank_count)
+    has_aov = bool(info.sections & (a_alb | a_nd))
+    if has_aov != bool(aov):
+        return "it holds AOVs, give --aov or --denoise" if has_aov else "it holds no AOVs, drop --aov / --denoise"
+    if bool(info.sections & a_ad) != (adaptive is not None):
+        return "it is an adaptive accumulation, give --adaptive" if info.sections & a_ad else "it is a uniform accumulation, drop --adaptive"
+    if adaptive is not None:
+        c = info.adaptive
+        have = (c.min_samples, c.max_samples, np.float32(c.threshold))
+        want = (adaptive[0], adaptive[1], np.float32(adaptive[2]))
+        if have != want:
+            return "it was rendered with --min-spp %d --spp %d --adaptive %.9g, not %d / %d / %.9g" % (have + want)
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path")
@@ -65,6 +93,8 @@ def main():
     ap.add_argument("--sample-map", default="")
     ap.add_argument("--aov", default="", metavar="PREFIX")
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS")
+    ap.add_argument("--checkpoint", default="", metavar="FILE", help="write the accumulation to FILE after the last sample")
+    ap.add_argument("--resume", default="", metavar="FILE", help="continue the accumulation of FILE; --spp is the total")
     a = ap.parse_args()
 
     import torch
@@ -117,23 +147,46 @@ def main():
     p.environment_map = -1 if env is None else env
     p.tile_rank, p.tile_rank_count = 0, 1
     out = r.create_output(w, h)
+    aov_albedo = aov_nd = None
     if a.aov or a.denoise is not None:
         aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
         r.set_aov(aov_albedo, aov_nd)
+    adaptive_cfg = None if a.adaptive is None else (min(a.min_spp, a.spp), a.spp, a.adaptive)
+    if adaptive_cfg is not None:
+        r.set_samples_per_trace(min(a.batch, 64))
+        r.set_adaptive(*adaptive_cfg)
+    first = 0
+    if a.resume:
+        # options first, as for a fresh run; then the state.  A file that does not fit is refused before anything is loaded.
+        blob = open(a.resume, "rb").read()
+        try:
+            info = Renderer.accum_inspect(blob)
+        except Exception:
+            sys.exit("--resume %s: not a valid accumulation checkpoint" % a.resume)
+        why = resume_mismatch(info, (w, h), aov_albedo is not None, adaptive_cfg, (abi.ACCUM_ALBEDO, abi.ACCUM_NORMAL_DEPTH, abi.ACCUM_ADAPTIVE))
+        if why:
+            sys.exit("--resume %s: %s" % (a.resume, why))
+        if info.accumulated_frames > a.spp:
+            sys.exit("--resume %s: it already holds %d samples, --spp (the total) is %d" % (a.resume, info.accumulated_frames, a.spp))
+        r.accum_load(blob, out, aov_albedo, aov_nd)
+        first = int(info.next_frame)
+        print("resumed %s: %d samples, continuing with frame %d" % (a.resume, info.accumulated_frames, first))
     if a.adaptive is None:
-        for frame in range(a.spp):
+        done = info.accumulated_frames if a.resume else 0
+        for frame in range(first, first + a.spp - done):
             p.frame = frame
             r.trace(st, p, out)
+        next_frame = first + a.spp - done
     else:
         # trace batches until no tile is active or every tile holds --spp samples
-        r.set_samples_per_trace(min(a.batch, 64))
-        r.set_adaptive(min(a.min_spp, a.spp), a.spp, a.adaptive)
-        frame, active = 0, 1
-        while active and frame < a.spp:
+        frame, active = first, (r.adaptive_read(w, h)[0] if a.resume else 1)
+        done = info.accumulated_frames if a.resume else 0
+        while active and frame - first < a.spp - done:
             p.frame = frame
             r.trace(st, p, out)
             frame += min(a.batch, 64)
             active = r.adaptive_read(w, h)[0]
+        next_frame = frame
         _, samples, _, _ = r.adaptive_read(w, h)
         pix = np.zeros((samples.shape[0] * abi.TILE, samples.shape[1] * abi.TILE), np.int64)
         pix[:h, :w] = 1
@@ -145,6 +198,11 @@ def main():
             grey = np.repeat(np.repeat((255.0 * samples / a.spp).astype(np.uint8), abi.TILE, 0), abi.TILE, 1)[:h, :w]
             gltf.write_png(a.sample_map, np.dstack([grey, grey, grey, np.full_like(grey, 255)]), 3)
     torch.cuda.synchronize()
+    if a.checkpoint:                                                     # before the denoiser: the state is the noisy accumulation
+        blob = r.accum_save(w, h, out, aov_albedo, aov_nd, next_frame=next_frame)
+        with open(a.checkpoint, "wb") as f:
+            f.write(blob)
+        print("checkpoint %s: %d bytes, %d samples, next frame %d" % (a.checkpoint, len(blob), Renderer.accum_inspect(blob).accumulated_frames, next_frame))
     if a.denoise is not None:
         _, noisy8 = r.tonemap(out, want_rgba8=True)
         gltf.write_png(noisy_path(a.out), noisy8, 3)
