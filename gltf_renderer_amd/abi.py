@@ -262,6 +262,12 @@ class PtDenoiseConfig(C.Structure):
         return cls(5, 1, 7, 0.02, 1.0)
 
 
+class PtLensConfig(C.Structure):
+    """pt_lens_config: thin-lens depth of field (pt_set_lens; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int32),
+                ("blade_rotation", C.c_float)]
+
+
 ACCUM_OUTPUT, ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE = 1, 2, 4, 8
 ACCUM_HEADER_BYTES = 160
 
@@ -296,5 +302,7 @@ assert C.sizeof(PtStats) == 152
 assert C.sizeof(PtAdaptiveConfig) == 16
 assert C.sizeof(PtAovConfig) == 24
 assert C.sizeof(PtDenoiseConfig) == 20
+assert C.sizeof(PtLensConfig) == 20
+assert [getattr(PtLensConfig, f).offset for f, _ in PtLensConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

@@ -117,6 +117,9 @@ struct pt_ctx {
     // ---- first-hit AOVs (pt_set_aov): the caller's targets
     pt_aov_config aov = {0, nullptr, nullptr};
     bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
+    // ---- thin lens (pt_set_lens)
+    pt_lens_config lens = {0, 0.0f, 1.0f, 0, 0.0f};
+    bool lens_restart = false;                    // pt_set_lens: the next pt_trace starts a new accumulation
     // ---- pt_denoise: two ping-pong signal images and the guide image, dn_pixels float4 each, for one image size
     float4* d_denoise = nullptr; size_t dn_pixels = 0;
 
@@ -192,8 +195,8 @@ void mat4_mul(const float* a, const float* b, float* out) {
             out[c * 4 + r] = s;
         }
 }
-bool mat4_inverse(const float* mf, float* out) {
-    double m[16], inv[16];
+bool mat4_inverse_d(const float* mf, double* inv) {
+    double m[16];
     for (int i = 0; i < 16; i++) m[i] = mf[i];
     double s0 = m[0] * m[5] - m[4] * m[1], s1 = m[0] * m[9] - m[8] * m[1], s2 = m[0] * m[13] - m[12] * m[1];
     double s3 = m[4] * m[9] - m[8] * m[5], s4 = m[4] * m[13] - m[12] * m[5], s5 = m[8] * m[13] - m[12] * m[9];
@@ -218,6 +221,11 @@ bool mat4_inverse(const float* mf, float* out) {
     inv[7] = (m[0] * c3 - m[4] * c1 + m[8] * c0) * id;
     inv[11] = (-m[3] * s3 + m[7] * s1 - m[11] * s0) * id;
     inv[15] = (m[2] * s3 - m[6] * s1 + m[10] * s0) * id;
+    return true;
+}
+bool mat4_inverse(const float* mf, float* out) {
+    double inv[16];
+    if (!mat4_inverse_d(mf, inv)) return false;
     for (int i = 0; i < 16; i++) out[i] = (float)inv[i];
     return true;
 }
@@ -258,6 +266,45 @@ void mark_buffer_users(pt_ctx* ctx, int handle) {
         }
     }
     if (any && ctx->accel_state == ACCEL_CLEAN) ctx->accel_state = ACCEL_REFIT;
+}
+
+// The camera of a call, from pt_execute_params and the lens config: world_to_clip as pt_trace compares it between calls, its inverse and
+// view_to_world (fp64, rounded once) and the lens as camera_ray takes it (include/mipt.h pt_set_lens).  PathtraceScene, pt_lens_focus_at
+// and the hook pt_debug_camera_rays all come through here, so that the rays they speak of are the same rays.
+struct CameraSetup {
+    float world_to_clip[16], clip_to_world[16], view_to_world[16];
+    LensArgs lens;
+};
+bool camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam) {
+    mat4_mul(ep->view_to_clip, ep->world_to_view, cam.world_to_clip);               // Pathtracer.cpp:262
+    double v2w[16];
+    if (!mat4_inverse_d(ep->world_to_view, v2w) || !mat4_inverse(cam.world_to_clip, cam.clip_to_world)) return false;
+    for (int i = 0; i < 16; i++) cam.view_to_world[i] = (float)v2w[i];
+    LensArgs& l = cam.lens;
+    memset(&l, 0, sizeof(l));
+    l.enable = (cfg.enable != 0 && cfg.aperture_radius > 0.0f) ? 1 : 0;
+    l.radius = cfg.aperture_radius; l.focus = cfg.focus_distance;
+    const int col[3] = {0, 1, 2};
+    float* dst[3] = {l.R, l.U, l.F};
+    for (int a = 0; a < 3; a++) {
+        const double* v = v2w + 4 * col[a];
+        const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), sgn = a == 2 ? -1.0 : 1.0;
+        for (int k = 0; k < 3; k++) dst[a][k] = (float)(sgn * v[k] / len);
+    }
+    for (int k = 0; k < 3; k++) l.c[k] = (float)v2w[12 + k];
+    l.blades = cfg.enable ? cfg.blades : 0;
+    if (l.blades < 3 || l.blades > kLensMaxBlades) l.blades = 0;                    // (pt_set_lens lets nothing else through)
+    for (int k = 0; k <= l.blades && l.blades; k++) {
+        const double ang = (double)cfg.blade_rotation + 2.0 * 3.14159265358979323846 * (double)(k % l.blades) / (double)l.blades;
+        l.vert[k][0] = (float)std::cos(ang); l.vert[k][1] = (float)std::sin(ang);
+    }
+    return true;
+}
+// What pinhole_ray reads of FrameConstants (the two camera hooks; PathtraceScene fills the rest as well)
+void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, FrameConstants& fc) {
+    memcpy(fc.clip_to_world, cam.clip_to_world, 64);
+    fc.camera_pos[0] = cam.view_to_world[12]; fc.camera_pos[1] = cam.view_to_world[13]; fc.camera_pos[2] = cam.view_to_world[14];
+    fc.res_x = ep->width; fc.res_y = ep->height;
 }
 
 }  // namespace
@@ -347,10 +394,9 @@ public:
 
     // Pathtracer::PathtraceScene (Source/Pathtracer.cpp:259-367)
     static int PathtraceScene(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* ep) {
-        float world_to_clip[16], clip_to_world[16], view_to_world[16];
-        mat4_mul(ep->view_to_clip, ep->world_to_view, world_to_clip);                   // :262
-        if (!mat4_inverse(ep->world_to_view, view_to_world) || !mat4_inverse(world_to_clip, clip_to_world))
-            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+        CameraSetup cam;
+        if (!camera_setup(ep, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+        const float* world_to_clip = cam.world_to_clip;                                  // :262
         bool reset = memcmp(world_to_clip, ctx->previous_world_to_clip, 64) != 0 || settings->reset;   // :267-271
         // Adaptive sampling (pt_set_adaptive) applies to accumulating calls without a debug output.  Its tile state describes the output
         // only if the last accumulation step was adaptive and of the same size and tile shard: otherwise the call starts a new one.
@@ -361,6 +407,7 @@ public:
         if (aov && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "AOVs are written in the wavefront mode only");
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
         if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
+        if (ctx->lens_restart) { reset = true; ctx->lens_restart = false; }
         if (adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
                          (ep->tile_rank_count ? ep->tile_rank_count : 1u) != ctx->ad_rank_count || ctx->accumulated_frames != ctx->ad_frames))
             reset = true;
@@ -393,10 +440,8 @@ public:
 
             FrameConstants fc;                                                          // :287-331
             memset(&fc, 0, sizeof(fc));
-            memcpy(fc.clip_to_world, clip_to_world, 64);
-            fc.camera_pos[0] = view_to_world[12]; fc.camera_pos[1] = view_to_world[13]; fc.camera_pos[2] = view_to_world[14];
+            camera_constants(cam, ep, fc);
             fc.num_of_lights = ep->light_count;
-            fc.res_x = ep->width; fc.res_y = ep->height;
             fc.seed = settings->use_frame_as_seed ? (uint32_t)ep->frame : settings->seed;   // :316
             fc.accumulated_frames = ctx->accumulated_frames;
             memcpy(fc.environment_color, settings->environment_color, 12);
@@ -461,7 +506,7 @@ public:
                     FrameConstants fk = fc;
                     fk.seed = fc.seed + (uint32_t)k * fc.seed_step;
                     fk.accumulated_frames = fc.accumulated_frames + k;
-                    launch_megakernel(sc, fk, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->stream);   // :344-353
+                    launch_megakernel(sc, fk, cam.lens, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->stream);   // :344-353
                 }
             } else {
                 fc.spp = (uint32_t)batch;
@@ -514,7 +559,7 @@ public:
                     ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
                 }
                 const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
-                HIPOK(launch_wavefront(sc, fc, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->d_workspace, stage_blocks,
+                HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->d_workspace, stage_blocks,
                                        ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, occ, adaptive ? &ad : nullptr, aov ? &av : nullptr));
             }
             HIPOK(hipGetLastError());
@@ -932,6 +977,37 @@ extern "C" int pt_debug_interleaved_emissive(const pt_ctx* ctx) {          // ..
     return n;
 }
 
+// the scene as a traversal-only kernel needs it (pt_debug_intersect, pt_lens_focus_at)
+static void scene_for_rays(pt_ctx* ctx, SceneRec& sc) {
+    memset(&sc, 0, sizeof(sc));
+    sc.rmats = ctx->d_rmats; sc.lights = ctx->d_lights; sc.instances = ctx->d_instances;
+    sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
+    sc.nodes = ctx->d_nodes; sc.tris = ctx->d_tris; sc.shade = ctx->d_shade; sc.root = ctx->root; sc.num_tris = ctx->n_tris;
+    sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
+}
+
+// test hook (not part of include/mipt.h): the camera rays pt_trace would generate for the queries {px, py, seed} under `params` and the context's
+// lens (pt_set_lens) -- camera_ray itself, one query per lane (pt_kernel.hip k_debug_camera_rays).  queries: 3 uint32 each, out: 8 floats each
+// (origin, tmin, direction, tmax), host arrays.  Needs no scene; leaves the accumulation and a pending restart as they are.
+extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
+    if (!ctx || !settings || !params || (n && (!queries || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
+    CameraSetup cam;
+    if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+    if (n == 0) return PT_OK;
+    ENTER(ctx);
+    FrameConstants fc;
+    memset(&fc, 0, sizeof(fc));
+    camera_constants(cam, params, fc);
+    uint32_t* d_q = nullptr; float* d_out = nullptr;
+    auto done = [&](int code, const std::string& why) { hipFree(d_q); hipFree(d_out); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
+    if (hipMalloc((void**)&d_q, (size_t)n * 12) != hipSuccess || hipMalloc((void**)&d_out, (size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_camera_rays: buffers"); }
+    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) { launch_debug_camera_rays(fc, cam.lens, d_q, n, d_out, ctx->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_camera_rays: ") + hipGetErrorString(e));
+}
+
 // test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
 // 8 floats per ray out, pt_kernel.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
 extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, uint32_t ray_flags, int mode, float* out) {
@@ -940,11 +1016,7 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
     if (n == 0) return PT_OK;
     SceneRec sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.rmats = ctx->d_rmats; sc.lights = ctx->d_lights; sc.instances = ctx->d_instances;
-    sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
-    sc.nodes = ctx->d_nodes; sc.tris = ctx->d_tris; sc.shade = ctx->d_shade; sc.root = ctx->root; sc.num_tris = ctx->n_tris;
-    sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
+    scene_for_rays(ctx, sc);
     const uint32_t lanes = (n + 255u) & ~255u;
     float *d_rays = nullptr, *d_out = nullptr; int32_t* d_deep = nullptr;
     auto done = [&](int code, const std::string& why) { hipFree(d_rays); hipFree(d_out); hipFree(d_deep); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
@@ -1268,6 +1340,54 @@ int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config) {
     return PT_OK;
 }
 
+int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: config is NULL");
+    if (config->enable) {
+        if (!std::isfinite(config->aperture_radius) || config->aperture_radius < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: aperture_radius must be finite and >= 0");
+        if (!std::isfinite(config->focus_distance) || config->focus_distance <= 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: focus_distance must be finite and > 0");
+        if (config->blades != 0 && (config->blades < 3 || config->blades > kLensMaxBlades)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: blades must be 0 or 3..16");
+        if (!std::isfinite(config->blade_rotation)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: blade_rotation must be finite");
+    }
+    ctx->lens = *config;
+    ctx->lens_restart = true;
+    return PT_OK;
+}
+
+int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, float px, float py, float* focus_distance_out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!settings || !params || !focus_distance_out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens_focus_at: NULL argument");
+    if (params->width == 0 || params->height == 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens_focus_at: zero resolution");
+    if (!(px >= 0.0f && px <= (float)params->width && py >= 0.0f && py <= (float)params->height))
+        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens_focus_at: position outside the image");
+    CameraSetup cam;
+    if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+    ENTER(ctx);
+    if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
+    SceneRec sc;
+    scene_for_rays(ctx, sc);
+    FrameConstants fc;
+    memset(&fc, 0, sizeof(fc));
+    camera_constants(cam, params, fc);
+    float* d_out = nullptr; int32_t* d_deep = nullptr;
+    auto done = [&](int code, const std::string& why) { hipFree(d_out); hipFree(d_deep); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
+    if (hipMalloc((void**)&d_out, 8) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: result buffer"); }
+    if ((int)ctx->stack_need > traversal_stack_capacity()) {
+        const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
+        if (hipMalloc((void**)&d_deep, (size_t)entries * 256 * 4) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: deep stack"); }
+        sc.deep_stack = d_deep; sc.deep_entries = entries; sc.deep_lanes = 256;
+    }
+    launch_lens_focus(sc, fc, cam.lens, px, py, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, d_out, ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
+    float res[2] = {0.0f, 0.0f};
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return done(PT_ERR_DEVICE, std::string("lens_focus_at: ") + hipGetErrorString(e));
+    if (res[0] == 0.0f) return done(PT_ERR_NOT_READY, "lens_focus_at: the ray hits nothing");
+    *focus_distance_out = res[1];
+    return done(PT_OK, "");
+}
+
 int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* active_tiles, uint32_t* tile_samples, float* tile_error, float* half_rgba32f) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->ad_ready) return ctx->fail(PT_ERR_NOT_READY, "no adaptive trace yet");
@@ -1439,7 +1559,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov since the last trace: the next trace starts anew");
+    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1543,7 +1663,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false;
+    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false;
     return PT_OK;
 }
 

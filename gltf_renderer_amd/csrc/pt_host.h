@@ -116,7 +116,10 @@ void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_sl
 void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
-void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream);
+void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream);
+// pt_debug_camera_rays / pt_lens_focus_at: d_out = 8 floats per query / 2 floats {hit, view-space depth}
+void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream);
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false);   // aov: with the two AOV record arrays behind the rest
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
@@ -142,11 +145,12 @@ struct AovArgs {
     float4* albedo;           // the caller's targets, res_x * res_y each; either may be nullptr
     float4* normal_depth;
 };
+// lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
 // occ_cache: the context's occluder cache (res_x * res_y * 8 words, persistent across calls; nullptr = none), see WfBuffers::occ_cache
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 // aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
-hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
+hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive = nullptr,
                             const AovArgs* aov = nullptr);
 

@@ -27,7 +27,7 @@ enum { KIND_CLOSEST = 0, KIND_SHADOW_ENV = 1, KIND_SHADOW_LIGHT = 2 };
 // =================================================================================================
 // MEGAKERNEL
 template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void pt_megakernel(SceneRec sc, FrameConstants fc, float4* __restrict__ output, Counters* __restrict__ counters) {
+__global__ __launch_bounds__(kBlock) void pt_megakernel(SceneRec sc, FrameConstants fc, float4* __restrict__ output, Counters* __restrict__ counters, LensArgs lens) {
     __shared__ int s_stack[kStackLds * kBlock];
     int* my_stack = s_stack + threadIdx.x;
     uint32_t px, py;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void pt_megakernel(SceneRec sc, FrameConsta
     fu.q_env = fu.q_light = fu.q_bounce = false;
     fu.pend_env = fu.pend_light = v3(0);
     if (alive) {
-        ray = camera_ray(fc, fc.seed, px, py, ps.rc);
+        ray = camera_ray(fc, lens, fc.seed, px, py, ps.rc);
         rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_BACK : 0;
         n_primary++;
     }
@@ -104,14 +104,14 @@ __global__ __launch_bounds__(kBlock) void pt_megakernel(SceneRec sc, FrameConsta
     if (st.deep) atomicAdd(&counters->deep_pushes, (unsigned long long)st.deep);
 }
 
-template __global__ void pt_megakernel<false>(SceneRec, FrameConstants, float4*, Counters*);
-template __global__ void pt_megakernel<true>(SceneRec, FrameConstants, float4*, Counters*);
+template __global__ void pt_megakernel<false>(SceneRec, FrameConstants, float4*, Counters*, LensArgs);
+template __global__ void pt_megakernel<true>(SceneRec, FrameConstants, float4*, Counters*, LensArgs);
 
-void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, hipStream_t stream) {
+void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream) {
     if (fc.my_tiles == 0) return;
     dim3 grid(fc.my_tiles), block(kBlock);
-    if (count) hipLaunchKernelGGL(pt_megakernel<true>, grid, block, 0, stream, sc, fc, output, counters);
-    else hipLaunchKernelGGL(pt_megakernel<false>, grid, block, 0, stream, sc, fc, output, counters);
+    if (count) hipLaunchKernelGGL(pt_megakernel<true>, grid, block, 0, stream, sc, fc, output, counters, lens);
+    else hipLaunchKernelGGL(pt_megakernel<false>, grid, block, 0, stream, sc, fc, output, counters, lens);
 }
 
 // Test hook (pt_debug_intersect): the product's traversal on caller-supplied rays, one ray per lane -- what TraceRay / TraceShadowRay find,
@@ -135,6 +135,38 @@ __global__ __launch_bounds__(kBlock) void k_debug_intersect(SceneRec sc, const f
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_rays, n, rf, mode, d_out);
+}
+
+// Test hook (pt_debug_camera_rays): the camera rays pt_trace generates, one query {px, py, seed} per lane, through camera_ray itself under the
+// context's lens.  out: 8 floats per query (origin, tmin, direction, tmax).
+__global__ __launch_bounds__(kBlock) void k_debug_camera_rays(FrameConstants fc, LensArgs lens, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    int rc = 0;
+    const Ray r = camera_ray(fc, lens, queries[3 * (size_t)i + 2], queries[3 * (size_t)i], queries[3 * (size_t)i + 1], rc);
+    float* o = out + (size_t)i * 8;
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
+}
+void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, lens, d_queries, n, d_out);
+}
+// Autofocus (pt_lens_focus_at): the pinhole ray through image position (sx, sy) -- no jitter, no lens -- and TraceRay's closest hit along it.
+// One lane works; out[0] = 1 for a hit, out[1] = its view-space depth zo + t * dn (include/mipt.h pt_set_lens; lens.c and lens.F are used).
+__global__ __launch_bounds__(kBlock) void k_lens_focus(SceneRec sc, FrameConstants fc, LensArgs lens, float sx, float sy, uint32_t rf, float* __restrict__ out) {
+    __shared__ int s_stack[kStackLds * kBlock];
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const Ray r = pinhole_ray(fc, sx, sy);
+    HitRec hit; LaneStats st = {0, 0, 0, 0, 0};
+    float transmission = 0.0f;
+    const bool got = traverse<false>(sc, s_stack + threadIdx.x, r, rf, 0xff, 0, hit, transmission, st);
+    const vec3 c = v3p(lens.c), F = v3p(lens.F);
+    const float zo = dot(r.o - c, F), dn = dot(r.d, F);
+    out[0] = got ? 1.0f : 0.0f;
+    out[1] = got ? zo + hit.t * dn : 0.0f;
+}
+void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_lens_focus, dim3(1), dim3(kBlock), 0, stream, sc, fc, lens, sx, sy, rf, d_out);
 }
 
 // Test hook (pt_debug_sample_texture, mipt_api.hip): the sampler as the megakernel runs it -- sRGB table and material records in global memory.

@@ -257,6 +257,17 @@ struct FrameConstants {
     FastDiv div_pixel_slots, div_tiles_x;   // divisions by pixel_slots / tiles_x (slot_pixel, slot_sample)
 };
 
+// Thin lens (pt_set_lens, include/mipt.h): what camera_ray takes beside FrameConstants.  Only the kernels that generate camera rays get it
+// (k_wf_generate, pt_megakernel, the two camera hooks): it is deliberately NOT part of FrameConstants, which every stage kernel takes.
+constexpr int kLensMaxBlades = 16;
+struct LensArgs {
+    int32_t enable;                       // 1: the lens branch runs (config enabled and aperture_radius > 0); wave-uniform
+    float radius, focus;                  // aperture_radius, focus_distance
+    float c[3], R[3], U[3], F[3];         // camera position, right, up, forward (view_to_world columns 3, 0, 1, -2; fp64, rounded once)
+    int32_t blades;                       // 0 = disc, else 3 .. kLensMaxBlades
+    float vert[kLensMaxBlades + 1][2];    // polygon vertices v_0 .. v_n (v_n = v_0), fp64 rounded once
+};
+
 struct Counters {
     unsigned long long rays_primary, rays_bounce, rays_shadow, nodes, tris, hits, taps, stack_overflow;
     unsigned long long nodes_shadow, tris_shadow;      // the occlusion stage's share (wavefront mode; the megakernel books everything above)

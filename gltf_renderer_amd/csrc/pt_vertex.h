@@ -283,11 +283,10 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
 }
 
 // RayGeneration prologue :744-758 (GenerateCameraRay :131-142)
-PT_DEV Ray camera_ray(const FrameConstants& fc, uint32_t seed, uint32_t px, uint32_t py, int& rc) {
-    vec4 r = next_random(px, py, seed, rc);
-    float jx = r.x - 0.5f, jy = r.y - 0.5f;
-    float cx = fdiv((float)px + 0.5f + jx, (float)fc.res_x) * 2 - 1;
-    float cy = fdiv((float)py + 0.5f + jy, (float)fc.res_y) * 2 - 1;
+// the pinhole ray through image position (sx, sy) in pixel units (pixel centres at + 0.5)
+PT_DEV Ray pinhole_ray(const FrameConstants& fc, float sx, float sy) {
+    float cx = fdiv(sx, (float)fc.res_x) * 2 - 1;
+    float cy = fdiv(sy, (float)fc.res_y) * 2 - 1;
     cy = -cy;
     vec4 s = mul4(fc.clip_to_world, vec4{cx, cy, 1, 1});
     vec4 e = mul4(fc.clip_to_world, vec4{cx, cy, 0, 1});
@@ -295,6 +294,41 @@ PT_DEV Ray camera_ray(const FrameConstants& fc, uint32_t seed, uint32_t px, uint
     vec3 d = xyz(e) / e.w - o;
     Ray ray;
     ray.o = o; ray.tmin = 0; ray.d = normalize(d); ray.tmax = length(d);
+    return ray;
+}
+// Thin lens (absent upstream; include/mipt.h pt_set_lens defines it operation by operation, tests/lens_ref.py restates it in float64):
+// the pinhole ray `ray` becomes the ray from lens sample L(u, v) through the pinhole ray's point on the plane in focus.
+PT_DEV vec2 lens_sample(const LensArgs& lens, float u, float v) {
+    if (lens.blades == 0) return square_to_disk(uv_to_square({u, v}));
+    const float s = u * (float)lens.blades;
+    const int k = min((int)s, lens.blades - 1);                                      // u may be exactly 1 (quirk q17)
+    const float a = sqrtf(s - (float)k);
+    // the two vertices by selects over the (wave-uniform) polygon: a per-lane index into the kernel argument would go through scratch
+    vec2 v0 = {lens.vert[0][0], lens.vert[0][1]}, v1 = {lens.vert[1][0], lens.vert[1][1]};
+    for (int j = 1; j < lens.blades; j++)
+        if (j == k) { v0 = {lens.vert[j][0], lens.vert[j][1]}; v1 = {lens.vert[j + 1][0], lens.vert[j + 1][1]}; }
+    return a * ((1 - v) * v0 + v * v1);
+}
+PT_DEV Ray lens_ray(const LensArgs& lens, const Ray& ray, float u, float v) {
+    const vec3 c = v3p(lens.c), R = v3p(lens.R), U = v3p(lens.U), F = v3p(lens.F);
+    const float zo = dot(ray.o - c, F), dn = dot(ray.d, F);
+    const vec3 P = ray.o + ray.d * fdiv(lens.focus - zo, dn);
+    const vec3 A = ray.o - ray.d * fdiv(zo, dn);
+    const vec2 l = lens.radius * lens_sample(lens, u, v);
+    const vec3 A2 = (A + l.x * R) + l.y * U;
+    Ray out;
+    out.d = normalize(P - A2);
+    out.o = A2 + out.d * fdiv(zo, dot(out.d, F));
+    out.tmin = 0; out.tmax = ray.tmax;
+    return out;
+}
+
+// RayGeneration prologue :744-758 (GenerateCameraRay :131-142); with pt_set_lens, the lens ray from the draw's two unused numbers
+PT_DEV Ray camera_ray(const FrameConstants& fc, const LensArgs& lens, uint32_t seed, uint32_t px, uint32_t py, int& rc) {
+    vec4 r = next_random(px, py, seed, rc);
+    float jx = r.x - 0.5f, jy = r.y - 0.5f;
+    const Ray ray = pinhole_ray(fc, (float)px + 0.5f + jx, (float)py + 0.5f + jy);
+    if (lens.enable) return lens_ray(lens, ray, r.z, r.w);                            // wave-uniform
     return ray;
 }
 

@@ -197,8 +197,11 @@ PT_DEV bool adaptive_tile_active(const FrameConstants& fc, const AdaptiveArgs& a
     const uint32_t local_tile = pair - slot_sample(fc, slot0) * fc.my_tiles;
     return ad.tiles[local_tile].active != 0;
 }
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad) {
+// LENS: the instantiations of calls with a thin lens (pt_set_lens); the others are compiled without the lens branch and its registers
+// (82 against 34 VGPRs), so that a pinhole call runs the kernel it always ran.
+template <bool ADAPTIVE, bool LENS>
+__global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, LensArgs lens) {
+    if (!LENS) lens.enable = 0;
     const ShardView sv = shard_view(wf);
     const uint32_t per_xcd = gridDim.x / kXcds;                       // the grid is a multiple of kShards, kShards of kXcds
     const uint32_t xcd = blockIdx.x % kXcds, member = blockIdx.x / kXcds;
@@ -235,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
         int rc = 0;
         Ray ray;
         ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
-        if (valid) ray = camera_ray(fc, sample_seed(fc, sample), px, py, rc);
+        if (valid) ray = camera_ray(fc, lens, sample_seed(fc, sample), px, py, rc);
         const uint32_t idx = queue_push(wf.cnt[0] + sv.shard * kCounterStride, valid);
         if (valid) {
             const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
@@ -1050,7 +1053,7 @@ static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
 int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
-hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4* output, Counters* counters, bool count, void* workspace,
+hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive, const AovArgs* aov) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
@@ -1084,8 +1087,11 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, float4
         av.rec_normal = av.rec_albedo + state_slots_for(slots);
     }
     AdaptiveArgs ad = {};
-    if (adaptive) { ad = *adaptive; hipLaunchKernelGGL(k_wf_generate<true>, stage, block, 0, stream, fc, wf, counters, ad); }
-    else hipLaunchKernelGGL(k_wf_generate<false>, stage, block, 0, stream, fc, wf, counters, ad);
+    if (adaptive) ad = *adaptive;
+    if (adaptive) { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<true, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
+                    else hipLaunchKernelGGL((k_wf_generate<true, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }
+    else { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<false, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
+           else hipLaunchKernelGGL((k_wf_generate<false, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }
     mark(STAGE_GENERATE);
     const uint32_t flags = fc.flags;
     const int iterations = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 1 : fc.max_bounces + 1;

@@ -31,7 +31,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # the denoiser over them (additive likewise)
            "pt_denoise",
            # saving and resuming an accumulation (additive likewise)
-           "pt_accum_save", "pt_accum_load", "pt_accum_inspect"]
+           "pt_accum_save", "pt_accum_load", "pt_accum_inspect",
+           # thin-lens depth of field (additive likewise)
+           "pt_set_lens", "pt_lens_focus_at"]
 
 
 class MiptError(RuntimeError):
@@ -110,6 +112,8 @@ def load_library():
     L.pt_accum_save.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.pt_accum_load.argtypes = [vp, vp, C.c_size_t, vp]
     L.pt_accum_inspect.argtypes = [vp, C.c_size_t, vp]
+    L.pt_set_lens.argtypes = [vp, vp]
+    L.pt_lens_focus_at.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.POINTER(C.c_float)]
     _LIB = L
     return L
 
@@ -319,6 +323,24 @@ class Renderer:
         if rc != 0:
             raise MiptError("%d: not a valid accumulation blob" % rc)
         return info
+
+    def set_lens(self, aperture_radius, focus_distance, blades=0, blade_rotation=0.0, enable=True):
+        """Thin-lens depth of field (include/mipt.h pt_set_lens): aperture_radius in world units (0 = the pinhole, bit for bit),
+        focus_distance = view-space depth of the plane in focus, blades = 0 for a circular aperture or 3..16 for a polygon whose vertex 0
+        sits at blade_rotation radians.  The next trace() starts a new accumulation.  The lens is not part of an accum_save() blob: set the
+        same lens before accum_load()."""
+        cfg = abi.PtLensConfig(int(bool(enable)), float(aperture_radius), float(focus_distance), int(blades), float(blade_rotation))
+        self._check(self.L.pt_set_lens(self.h, C.byref(cfg)))
+
+    def focus_at(self, settings, params, px, py):
+        """Autofocus (include/mipt.h pt_lens_focus_at): the view-space depth of what the pinhole ray through image position (px, py) sees
+        (pixel units, pixel centres at + 0.5) -- the focus_distance that puts it in focus -- or None where the ray hits nothing."""
+        out = C.c_float()
+        rc = self.L.pt_lens_focus_at(self.h, C.byref(settings), C.byref(params), float(px), float(py), C.byref(out))
+        if rc == -6:                                  # PT_ERR_NOT_READY: a miss
+            return None
+        self._check(rc)
+        return out.value
 
     def set_null_shadow_culling(self, on):
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""

@@ -567,6 +567,49 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
  * mismatch; with ADAPTIVE a tile record with active > 1, samples > accumulated_frames, an active tile whose samples != accumulated_frames,
  * a NaN error or a non-zero pad. */
 int pt_accum_inspect(const void* host_blob, size_t bytes, pt_accum_info* out);
+/* Thin-lens depth of field (absent upstream: the reference's camera is a pinhole).  Off by default; with enable == 0 or aperture_radius == 0
+ * none of the arithmetic below runs and the rays, the images, the AOVs and the ray counts are bit for bit those of the pinhole.  With the
+ * lens on it applies to the camera ray of every pt_trace: both kernel modes, every sample of a batch, calls with a debug output.  The lens
+ * sample comes from the two numbers of the camera ray's own random draw that the pixel jitter leaves unused (r.z, r.w of the draw whose
+ * r.x, r.y jitter the pixel): no extra draw, so the random sequence of every later vertex is what it is without a lens.
+ *   The host derives four vectors from view_to_world = inverse(world_to_view), computed in fp64, each component rounded once to float:
+ *     c = column 3 (the camera position), R, U, F = columns 0, 1 and MINUS column 2, each normalised in fp64 before the rounding.
+ *   Let (o, d, tmax) be the pinhole ray (o on the near plane, d unit, tmin = 0) and r its random draw.  All float32, in the order written:
+ *     zo = dot(o - c, F)                       the near distance           (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z)
+ *     dn = dot(d, F)
+ *     P  = o + d * ((focus_distance - zo) / dn)          the point in focus
+ *     A  = o - d * (zo / dn)                   where the ray crosses the lens plane: c for a perspective camera; the same definition
+ *                                              gives an orthographic camera a lens too
+ *     (lx, ly) = aperture_radius * L(r.z, r.w):
+ *         blades == 0:  L = square_to_disk(uv_to_square({r.z, r.w}))       (the reference's concentric mapping, Transforms.hlsli)
+ *         blades == n:  with v_k = (cos, sin)(blade_rotation + 2 pi k / n), k = 0 .. n, computed on the host in fp64 and rounded once
+ *                       (v_n = v_0):  s = r.z * n;  k = min((int)s, n - 1) (r.z may be exactly 1);  a = sqrt(s - k);
+ *                       L = a * ((1 - r.w) * v_k + r.w * v_{k+1})          uniform over the polygon inscribed in the unit circle
+ *     A' = (A + lx * R) + ly * U
+ *     d' = normalize(P - A')
+ *     o' = A' + d' * (zo / dot(d', F))         back on the near plane, so near clipping is kept
+ *     tmin = 0, tmax' = tmax
+ *   The divisions are correctly rounded (operands and quotients in the normal range); normalize(v) = v / sqrt(dot(v, v)).  The first-hit AOV depth (pt_set_aov) is t along this lens ray.
+ * The lens is a setting, like pt_settings: it is NOT part of the blob of pt_accum_save, whose format is unchanged -- a caller who resumes
+ * calls pt_set_lens with the same config before pt_accum_load. */
+typedef struct pt_lens_config {
+    int32_t enable;           /* 0 = pinhole (default) */
+    float   aperture_radius;  /* world units; finite, >= 0.  0 gives the pinhole ray bit for bit */
+    float   focus_distance;   /* view-space depth of the plane in focus; finite, > 0 */
+    int32_t blades;           /* 0 = circular aperture; 3..16 = regular polygon inscribed in the circle */
+    float   blade_rotation;   /* radians, finite: angle of polygon vertex 0 */
+} pt_lens_config;             /* 20 bytes */
+/* PT_ERR_INVALID_ARGUMENT for a NULL pointer or a bad config (checked only when enable != 0; the message names the field): the old config
+ * stays and no restart is pending.  A good config forces a new accumulation on the next pt_trace, as pt_set_aov does: until that trace
+ * pt_accum_save answers PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config);
+/* Autofocus: the view-space depth of what the pinhole ray through image position (px, py) sees -- pixel units, pixel centres at + 0.5, no
+ * jitter, no lens -- for pt_lens_config.focus_distance.  TraceRay's closest hit under the settings' cull flag (FLAG_CULL_BACKFACE); builds
+ * the acceleration structure if it is dirty; synchronises the stream; *focus_distance_out = zo + t * dn in float32 (zo, dn as above).
+ * PT_ERR_NOT_READY on a miss, with nothing written.  PT_ERR_INVALID_ARGUMENT for a NULL pointer, a zero size or a position outside
+ * [0, width] x [0, height].  Does not touch the accumulation. */
+int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params,
+                     float px, float py, float* focus_distance_out);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -21,6 +21,13 @@ mapping; turns the AOVs on, and keeps the noisy frame beside the output as <out>
 must fit the command line: the same --size, --aov / --denoise or neither, and the same --adaptive, --min-spp and --spp (an adaptive
 accumulation carries its sample cap); the scene, camera and --batch are the caller's to repeat.
 
+--aperture R: thin-lens depth of field (pt_set_lens) with aperture radius R in world units; --focus D gives the view-space depth of the plane
+in focus, --focus-pixel X,Y focuses on what that image position sees (pt_lens_focus_at; pixel units, the default is the image centre);
+--blades N (3..16) makes the aperture a regular polygon, --blade-rotation DEG turns it.  The lens is not part of a checkpoint: with
+--resume, give the same --aperture / --focus / --focus-pixel / --blades / --blade-rotation as the run that wrote it, or the accumulation
+continues with another lens (a --focus-pixel that now hits other geometry included).
+  python tools/render_gltf.py scene.glb --spp 256 --aperture 0.05 --focus-pixel 640,400 --blades 6
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -95,6 +102,12 @@ def main():
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS")
     ap.add_argument("--checkpoint", default="", metavar="FILE", help="write the accumulation to FILE after the last sample")
     ap.add_argument("--resume", default="", metavar="FILE", help="continue the accumulation of FILE; --spp is the total")
+    ap.add_argument("--aperture", type=float, default=0.0, metavar="R", help="thin-lens aperture radius in world units (0 = pinhole); with --resume, repeat the lens options of the run that wrote the checkpoint")
+    focus = ap.add_mutually_exclusive_group()
+    focus.add_argument("--focus", type=float, default=None, metavar="D", help="view-space depth of the plane in focus")
+    focus.add_argument("--focus-pixel", default=None, metavar="X,Y", help="focus on what this image position sees (default: the image centre)")
+    ap.add_argument("--blades", type=int, default=0, metavar="N", help="0 = circular aperture, 3..16 = polygon")
+    ap.add_argument("--blade-rotation", type=float, default=0.0, metavar="DEG")
     a = ap.parse_args()
 
     import torch
@@ -146,6 +159,16 @@ def main():
     p.width, p.height, p.light_count = w, h, lights
     p.environment_map = -1 if env is None else env
     p.tile_rank, p.tile_rank_count = 0, 1
+    if a.aperture > 0:
+        if a.focus is not None:
+            focus_distance = a.focus
+        else:
+            fx, fy = (float(v) for v in a.focus_pixel.split(",")) if a.focus_pixel else (w / 2, h / 2)
+            focus_distance = r.focus_at(st, p, fx, fy)
+            if focus_distance is None:
+                sys.exit("--focus-pixel %g,%g: nothing to focus on there, give another position or --focus D" % (fx, fy))
+            print("focus at pixel %g,%g: depth %.6g" % (fx, fy, focus_distance))
+        r.set_lens(a.aperture, focus_distance, a.blades, math.radians(a.blade_rotation))
     out = r.create_output(w, h)
     aov_albedo = aov_nd = None
     if a.aov or a.denoise is not None:
