@@ -1042,6 +1042,43 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
+// 2: the fused k_wf_traverse -- on queues the caller fills (pt_wavefront.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
+// (origin, tmin = 0: the queue format has none, direction, tmax) with the shard 0..255 each is queued in (the caller's order within a shard is
+// the queue's); shadow: n_s rays of 6 floats (origin, direction) with shard and is_light bit, one shadow_tmax for all.  flags: PT_FLAG_*;
+// bounce: of the closest rays (which 0, 2; the fused launch needs bounce >= 1 and takes the shadow rays of bounce - 1) or of the shadow rays
+// (which 1).  Ray flags, instance mask, kernel copy and counting are chosen by the code launch_wavefront runs.  out_closest: 8 floats per ray
+// as pt_debug_intersect's; out_shadow: the transmission written beside the ray's pending term; out_cnt: 256 x 7 counter words after the
+// launch; out_stray: 2 words, see pt_host.h.  Leaves the accumulation, the workspace and a pending restart of the context as they are.
+extern "C" int pt_debug_trace_queues(pt_ctx* ctx, const float* closest, const uint32_t* closest_shard, uint32_t n_c, const float* shadow, const uint32_t* shadow_shard,
+                                     const uint8_t* shadow_is_light, uint32_t n_s, float shadow_tmax, uint32_t flags, int bounce, uint32_t blocks_per_shard, int which,
+                                     float* out_closest, float* out_shadow, uint32_t* out_cnt, uint32_t* out_stray) {
+    if (which < 0 || which > 2 || blocks_per_shard < 1 || blocks_per_shard > 64 || bounce < 0 || (which == 2 && bounce < 1)) return PT_ERR_INVALID_ARGUMENT;
+    if ((n_c && (!closest || !closest_shard || !out_closest)) || (n_s && (!shadow || !shadow_shard || !shadow_is_light || !out_shadow)) || !out_cnt || !out_stray) return PT_ERR_INVALID_ARGUMENT;
+    if (n_c > 0x0fffffffu || n_s > 0x0fffffffu) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n_c; i++) if (closest_shard[i] > 255u || closest[(size_t)i * 8 + 3] != 0.0f) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n_s; i++) if (shadow_shard[i] > 255u) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
+    SceneRec sc;
+    scene_for_rays(ctx, sc);                                   // has_env = 0: the traversal stages draw no environment samples
+    int32_t* d_deep = nullptr;
+    if ((int)ctx->stack_need > traversal_stack_capacity()) {    // the deep stack as pt_trace sets it up, for this launch's grid
+        const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
+        const size_t lanes = (size_t)256 * blocks_per_shard * 256;
+        if (hipMalloc((void**)&d_deep, (size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: deep stack"); }
+        sc.deep_stack = d_deep; sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
+    }
+    const DebugQueues q = {closest, closest_shard, n_c, shadow, shadow_shard, shadow_is_light, n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
+                           out_closest, out_shadow, out_cnt, out_stray};
+    std::string why;
+    const hipError_t e = debug_trace_queues(sc, q, ctx->d_counters, ctx->counters_enabled, ctx->stream, why);
+    hipFree(d_deep);
+    if (e == hipErrorOutOfMemory) return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: " + why);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, "pt_debug_trace_queues: " + why);
+}
+
 // test hook (not part of include/mipt.h): the shade stage's texture sampler on caller-supplied queries, one per lane (pt_shading.h
 // debug_sample_query).  mat_slot: 2 per query (material, slot 0..14 or 16..19); tc: 4 per query (tc0.xy, tc1.xy); out_rgba: 4 per query;
 // out_taps (may be null): 5 per query (i0, i1, j0, j1, and ia: the first column of the texel pair loaded for each row).  unit 0: the wavefront stages' build (tables in LDS), 1: the megakernel's.

@@ -120,6 +120,18 @@ void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensA
 // pt_debug_camera_rays / pt_lens_focus_at: d_out = 8 floats per query / 2 floats {hit, view-space depth}
 void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
 void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream);
+// pt_debug_trace_queues (test hook): host arrays.  closest: 8 floats per ray (origin, tmin = 0, direction, tmax); shadow: 6 floats per ray (origin,
+// direction).  out_closest: 8 floats per ray as pt_debug_intersect writes them (all kDebugSentinel bits where the kernel wrote no hit record);
+// out_shadow: the transmission written beside ray i's pending term; out_cnt: the counter words [shard][0..6] after the launch;
+// out_stray: {hit entries, pending records} outside the rays' own that no longer hold the sentinel.
+struct DebugQueues {
+    const float* closest; const uint32_t* closest_shard; uint32_t n_closest;
+    const float* shadow; const uint32_t* shadow_shard; const uint8_t* shadow_is_light; uint32_t n_shadow;
+    float shadow_tmax;
+    uint32_t flags; int bounce; uint32_t blocks_per_shard; int which;
+    float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
+};
+hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false);   // aov: with the two AOV record arrays behind the rest
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.

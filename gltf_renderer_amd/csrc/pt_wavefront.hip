@@ -18,6 +18,9 @@
 // env-shadow term, then the light-shadow term of that vertex), independent of queue order, so frames are
 // bit-reproducible and N tile shards compose bit-exactly.
 #define PT_LUT_LDS 1          // every stage kernel of this file stages the sRGB table into LDS (pt_shading.h stage_luts)
+#include <algorithm>
+#include <cstring>
+
 #include "pt_vertex.h"
 #include "pt_host.h"
 
@@ -1053,6 +1056,41 @@ static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
 int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
+// ---- the traversal stages' ray flags, kernel copies and launches: ONE statement of each, used by launch_wavefront and by the test hook
+// debug_trace_queues below, so that the hook launches what a frame launches.
+// Ray flags and instance mask of the closest-hit rays of bounce b.
+static void traversal_ray_flags(uint32_t flags, int b, uint32_t& rf, uint32_t& rmask) {
+    rmask = 0xff;
+    if (b == 0) rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_BACK : 0;                              // RayGeneration :747
+    else {                                                                                            // TraceBounceRay :671-672
+        rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_FRONT : 0;
+        rmask = (flags & PT_FLAG_INDIRECT_ENVIRONMENT_ONLY) ? 0 : 0xff;
+    }
+}
+// the traversal kernels compiled for rays with no flags, if that is what the frame's settings give them
+static bool traversal_defaults(uint32_t flags) { return PT_TRAV_SPECIALISE && (flags & kTravFlagMask) == 0; }
+static void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
+                            uint32_t rmask, Counters* counters) {
+    const dim3 block(kBlock);
+    if (traversal_defaults(fc.flags)) { if (count) hipLaunchKernelGGL((k_wf_trace<true, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
+                                        else hipLaunchKernelGGL((k_wf_trace<false, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
+    else { if (count) hipLaunchKernelGGL((k_wf_trace<true, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
+           else hipLaunchKernelGGL((k_wf_trace<false, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
+}
+static void launch_wf_traverse(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int nxt, int b, uint32_t rf,
+                               uint32_t rmask, Counters* counters) {
+    const dim3 block(kBlock);
+    const uint32_t flags = fc.flags;
+    if (traversal_defaults(flags)) { if (count) hipLaunchKernelGGL((k_wf_traverse<true, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
+                                     else hipLaunchKernelGGL((k_wf_traverse<false, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
+    else { if (count) hipLaunchKernelGGL((k_wf_traverse<true, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
+           else hipLaunchKernelGGL((k_wf_traverse<false, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
+}
+static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const WfBuffers& w, int b, uint32_t flags, float tmax, Counters* counters) {
+    if (count) hipLaunchKernelGGL(k_wf_shadow<true>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters);
+    else hipLaunchKernelGGL(k_wf_shadow<false>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters);
+}
+
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive, const AovArgs* aov) {
     if (timers) timers->used = 0;
@@ -1095,28 +1133,11 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     mark(STAGE_GENERATE);
     const uint32_t flags = fc.flags;
     const int iterations = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 1 : fc.max_bounces + 1;
-    auto ray_flags = [&](int b, uint32_t& rf, uint32_t& rmask) {
-        rmask = 0xff;
-        if (b == 0) rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_BACK : 0;                          // RayGeneration :747
-        else {                                                                                        // TraceBounceRay :671-672
-            rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_FRONT : 0;
-            rmask = (flags & PT_FLAG_INDIRECT_ENVIRONMENT_ONLY) ? 0 : 0xff;
-        }
-    };
-    // the traversal kernels compiled for rays with no flags, if that is what this frame's settings give them
-    const bool trav_defaults = PT_TRAV_SPECIALISE && (flags & kTravFlagMask) == 0;
-    auto launch_trace = [&](dim3 grid, const WfBuffers& w, int cur, int b, uint32_t rf, uint32_t rmask) {
-        if (trav_defaults) { if (count) hipLaunchKernelGGL((k_wf_trace<true, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
-                             else hipLaunchKernelGGL((k_wf_trace<false, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
-        else { if (count) hipLaunchKernelGGL((k_wf_trace<true, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
-               else hipLaunchKernelGGL((k_wf_trace<false, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
-    };
-    auto launch_traverse = [&](dim3 grid, const WfBuffers& w, int nxt, int b, uint32_t rf, uint32_t rmask) {
-        if (trav_defaults) { if (count) hipLaunchKernelGGL((k_wf_traverse<true, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
-                             else hipLaunchKernelGGL((k_wf_traverse<false, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
-        else { if (count) hipLaunchKernelGGL((k_wf_traverse<true, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
-               else hipLaunchKernelGGL((k_wf_traverse<false, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
-    };
+    // ray flags, kernel copies and launches of the traversal stages: the functions above, shared with the test hook debug_trace_queues
+    auto ray_flags = [&](int b, uint32_t& rf, uint32_t& rmask) { traversal_ray_flags(flags, b, rf, rmask); };
+    auto launch_trace = [&](dim3 grid, const WfBuffers& w, int cur, int b, uint32_t rf, uint32_t rmask) { launch_wf_trace(grid, stream, count, sc, fc, w, cur, b, rf, rmask, counters); };
+    auto launch_traverse = [&](dim3 grid, const WfBuffers& w, int nxt, int b, uint32_t rf, uint32_t rmask) { launch_wf_traverse(grid, stream, count, sc, fc, w, nxt, b, rf, rmask, counters); };
+    auto launch_shadow = [&](dim3 grid, const WfBuffers& w, int b) { launch_wf_shadow(grid, stream, count, sc, w, b, flags, fc.max_ray_length, counters); };
     // the shade kernel compiled for this frame's flags, if there is one (k_wf_shade)
     const uint32_t shade_bits = flags & kShadeFlagMask;
     const int shade_variant = (!PT_SHADE_SPECIALISE || fc.debug_output != PT_DEBUG_OUTPUT_NONE) ? 0 : (shade_bits == kShadeDefaults ? 1 : (shade_bits == kShadeDefaultsNoLights ? 2 : 0));
@@ -1184,8 +1205,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         if (b + 1 < iterations) {
             launch_traverse(gt, wt, cur ^ 1, b, rf, rmask);
         } else {                                                                                      // the last vertex pushes no bounce ray
-            if (count) hipLaunchKernelGGL(k_wf_shadow<true>, gt, block, 0, stream, sc, wt, b, flags, fc.max_ray_length, counters);
-            else hipLaunchKernelGGL(k_wf_shadow<false>, gt, block, 0, stream, sc, wt, b, flags, fc.max_ray_length, counters);
+            launch_shadow(gt, wt, b);
         }
         mark(STAGE_SHADOW);
     }
@@ -1199,8 +1219,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         if (aov && b == 0) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }
         launch_shade(stage, wf, cur, b);
         mark(STAGE_SHADE);
-        if (count) hipLaunchKernelGGL(k_wf_shadow<true>, stage, block, 0, stream, sc, wf, b, flags, fc.max_ray_length, counters);
-        else hipLaunchKernelGGL(k_wf_shadow<false>, stage, block, 0, stream, sc, wf, b, flags, fc.max_ray_length, counters);
+        launch_shadow(stage, wf, b);
         mark(STAGE_SHADOW);
     }
 #endif
@@ -1210,6 +1229,143 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
            else hipLaunchKernelGGL((k_wf_resolve<false, false>), full, block, 0, stream, fc, wf, output, ad, av); }
     mark(STAGE_RESOLVE);
     return hipGetLastError();
+}
+
+// Test hook (pt_debug_trace_queues, mipt_api.hip): the traversal kernels of a frame -- k_wf_trace, k_wf_shadow or the fused k_wf_traverse, through
+// the launch functions above -- on queues the caller filled.  Owns a small WfBuffers: the seven counter arrays, one closest queue with its hit
+// array, the shadow queue and the pending records, nothing else (occ_cache = nullptr; sc.has_env must be 0, so no environment buffers are read).
+// Every output word holds kDebugSentinel before the launch and each shard's segment ends in a guard entry nobody may write.
+// `bounce` is the closest rays' bounce (which 0, 2) or the shadow rays' (which 1); the fused launch takes the shadow rays of bounce - 1 with it,
+// as in a frame.  Synchronises the stream.
+constexpr uint32_t kDebugSentinel = 0x7fc5a5a5u;           // a quiet NaN with a payload no kernel produces
+hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why) {
+    why.clear();
+    const int cur = q.bounce & 1;                                                       // the closest queue of that bounce (launch_wavefront)
+    const int shadow_bounce = q.which == 2 ? q.bounce - 1 : q.bounce;
+    const int scnt = (shadow_bounce & 1) ? 5 : 2;                                       // shadow_counter(), which is device code
+    std::vector<uint32_t> n_c(kShards, 0), n_s(kShards, 0);
+    for (uint32_t i = 0; i < q.n_closest; i++) n_c[q.closest_shard[i]]++;
+    for (uint32_t i = 0; i < q.n_shadow; i++) n_s[q.shadow_shard[i]]++;
+    uint32_t seg = 0;
+    for (uint32_t s = 0; s < kShards; s++) seg = std::max(seg, std::max(n_c[s], (n_s[s] + 1u) / 2u));
+    WfBuffers wf;
+    std::memset(&wf, 0, sizeof(wf));
+    wf.seg_cap = seg + 1u;                                                              // the guard entry (two for the shadow queue)
+    wf.blocks_per_shard = q.blocks_per_shard;
+    wf.capacity = q.n_shadow + 1u;                                                      // slots: one per shadow ray and a guard
+    wf.chunks_per_shard = chunks_per_shard_for(wf.capacity);
+    const size_t qn = (size_t)kShards * wf.seg_cap, slots = state_slots_for(wf.capacity), cnt_words = (size_t)kCounterArrays * kShards * kCounterStride;
+    auto host_sidx = [&](uint32_t slot) -> size_t {
+#if PT_STATE_BY_SHARD
+        const uint32_t c = slot >> 8;
+        return (((size_t)(c & (kShards - 1u)) * wf.chunks_per_shard + (c >> 8)) << 8) | (slot & 255u);
+#else
+        return slot;
+#endif
+    };
+    // host images of the buffers
+    std::vector<uint32_t> h_cnt(cnt_words, kDebugSentinel);
+    std::vector<float4> h_ro(qn), h_rd(qn), h_so(qn * 2), h_sd(qn * 2);
+    const float sentinel = *(const float*)&kDebugSentinel;
+    const float4 sent4 = make_float4(sentinel, sentinel, sentinel, sentinel);
+    std::vector<float4> h_hit(qn, sent4), h_pend(slots * 2, sent4);
+    std::memset(h_ro.data(), 0, qn * 16); std::memset(h_rd.data(), 0, qn * 16); std::memset(h_so.data(), 0, qn * 32); std::memset(h_sd.data(), 0, qn * 32);
+    std::vector<uint32_t> at_c(q.n_closest), at_s(q.n_shadow), fill(kShards, 0);
+    for (uint32_t i = 0; i < q.n_closest; i++) {
+        const uint32_t s = q.closest_shard[i];
+        const size_t e = (size_t)s * wf.seg_cap + fill[s]++;
+        const float* r = q.closest + (size_t)i * 8;
+        h_ro[e] = make_float4(r[0], r[1], r[2], r[7]);
+        h_rd[e] = make_float4(r[4], r[5], r[6], *(const float*)&i);                     // (d.w = the path's slot: unused by the traversal)
+        at_c[i] = (uint32_t)e;
+    }
+    std::fill(fill.begin(), fill.end(), 0u);
+    for (uint32_t i = 0; i < q.n_shadow; i++) {
+        const uint32_t s = q.shadow_shard[i];
+        const size_t e = (size_t)s * wf.seg_cap * 2 + fill[s]++;
+        const float* r = q.shadow + (size_t)i * 6;
+        const uint32_t bits = i | (q.shadow_is_light[i] ? 0x80000000u : 0u);
+        h_so[e] = make_float4(r[0], r[1], r[2], *(const float*)&bits);
+        h_sd[e] = make_float4(r[3], r[4], r[5], *(const float*)&kNoHint);
+        at_s[i] = (uint32_t)e;
+    }
+    for (uint32_t s = 0; s < kShards; s++) {
+        if (q.which != 1) h_cnt[(size_t)cur * kShards * kCounterStride + s * kCounterStride] = n_c[s];      // (a counter no launched kernel reads keeps the sentinel)
+        if (q.which != 0) h_cnt[(size_t)scnt * kShards * kCounterStride + s * kCounterStride] = n_s[s];
+        h_cnt[(size_t)3 * kShards * kCounterStride + s * kCounterStride] = 0;           // the fetch heads: in a frame the shade stage rewinds them
+        h_cnt[(size_t)4 * kShards * kCounterStride + s * kCounterStride] = 0;
+    }
+    char* d_all = nullptr;
+    const size_t b_cnt = cnt_words * 4, b_q = qn * 16;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t total = up(b_cnt) + 3 * up(b_q) + 2 * up(b_q * 2) + up(slots * 32);
+    if (hipMalloc((void**)&d_all, total) != hipSuccess) { (void)hipGetLastError(); why = "queue buffers"; return hipErrorOutOfMemory; }
+    char* p = d_all;
+    auto take = [&](size_t b) { char* r = p; p += up(b); return r; };
+    uint32_t* d_cnt = (uint32_t*)take(b_cnt);
+    for (int k = 0; k < kCounterArrays; k++) wf.cnt[k] = d_cnt + (size_t)k * kShards * kCounterStride;
+    wf.ray_o[cur] = (float4*)take(b_q); wf.ray_d[cur] = (float4*)take(b_q); wf.hit = (float4*)take(b_q);
+    wf.sh_o = (float4*)take(b_q * 2); wf.sh_d = (float4*)take(b_q * 2);
+    wf.pend = (float4*)take(slots * 32);
+    wf.occ_cache = nullptr;
+    hipError_t e = hipMemcpyAsync(d_cnt, h_cnt.data(), b_cnt, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.ray_o[cur], h_ro.data(), b_q, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.ray_d[cur], h_rd.data(), b_q, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.hit, h_hit.data(), b_q, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.sh_o, h_so.data(), b_q * 2, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.sh_d, h_sd.data(), b_q * 2, hipMemcpyHostToDevice, stream);
+    if (!e) e = hipMemcpyAsync(wf.pend, h_pend.data(), slots * 32, hipMemcpyHostToDevice, stream);
+    if (!e) {
+        FrameConstants fc;
+        std::memset(&fc, 0, sizeof(fc));
+        fc.flags = q.flags; fc.max_ray_length = q.shadow_tmax;
+        uint32_t rf, rmask;
+        traversal_ray_flags(q.flags, q.bounce, rf, rmask);
+        const dim3 grid(kShards * wf.blocks_per_shard);
+        if (q.which == 0) launch_wf_trace(grid, stream, count, sc, fc, wf, cur, q.bounce, rf, rmask, counters);
+        else if (q.which == 1) launch_wf_shadow(grid, stream, count, sc, wf, q.bounce, q.flags, q.shadow_tmax, counters);
+        else launch_wf_traverse(grid, stream, count, sc, fc, wf, cur, q.bounce - 1, rf, rmask, counters);
+        e = hipGetLastError();
+    }
+    std::vector<TriPacket> h_tris(sc.num_tris);
+    if (!e) e = hipMemcpyAsync(h_cnt.data(), d_cnt, b_cnt, hipMemcpyDeviceToHost, stream);
+    if (!e) e = hipMemcpyAsync(h_hit.data(), wf.hit, b_q, hipMemcpyDeviceToHost, stream);
+    if (!e) e = hipMemcpyAsync(h_pend.data(), wf.pend, slots * 32, hipMemcpyDeviceToHost, stream);
+    if (!e && sc.num_tris) e = hipMemcpyAsync(h_tris.data(), sc.tris, (size_t)sc.num_tris * sizeof(TriPacket), hipMemcpyDeviceToHost, stream);
+    if (!e) e = hipStreamSynchronize(stream);
+    hipFree(d_all);
+    if (e) { why = hipGetErrorString(e); return e; }
+    // ---- translate
+    auto is_sentinel = [](float v) { uint32_t b; std::memcpy(&b, &v, 4); return b == kDebugSentinel; };
+    auto untouched = [&](const float4& v) { return is_sentinel(v.x) && is_sentinel(v.y) && is_sentinel(v.z) && is_sentinel(v.w); };
+    std::vector<uint8_t> expected(qn, 0);
+    for (uint32_t i = 0; i < q.n_closest; i++) {
+        float* o = q.out_closest + (size_t)i * 8;
+        const float4 h = h_hit[at_c[i]];
+        expected[at_c[i]] = 1;
+        if (untouched(h)) { for (int k = 0; k < 8; k++) o[k] = sentinel; continue; }
+        uint32_t bits; std::memcpy(&bits, &h.w, 4);
+        const bool hit = bits != kMissTri && (bits & 0x7fffffffu) < sc.num_tris;
+        o[0] = hit ? 1.0f : 0.0f; o[1] = hit ? h.x : 0.0f; o[2] = hit ? h.y : 0.0f; o[3] = hit ? h.z : 0.0f;
+        if (hit) { const TriPacket& t = h_tris[bits & 0x7fffffffu]; o[4] = (float)t.inst; o[5] = (float)t.prim; o[6] = (bits >> 31) ? 1.0f : 0.0f; }
+        else { o[4] = -1.0f; o[5] = -1.0f; o[6] = 0.0f; if (bits != kMissTri) o[0] = sentinel; }                 // (a triangle index out of range: never a valid answer)
+        o[7] = 0.0f;
+    }
+    uint32_t stray_hit = 0, stray_pend = 0;
+    for (size_t k = 0; k < qn; k++) if (!expected[k] && !untouched(h_hit[k])) stray_hit++;
+    std::vector<uint8_t> target(slots * 2, 0);
+    for (uint32_t i = 0; i < q.n_shadow; i++) {
+        const size_t k = 2 * host_sidx(i) + (q.shadow_is_light[i] ? 1u : 0u);
+        target[k] = 1;
+        q.out_shadow[i] = h_pend[k].w;
+    }
+    for (size_t k = 0; k < slots * 2; k++) {
+        const float4& v = h_pend[k];
+        if (!is_sentinel(v.x) || !is_sentinel(v.y) || !is_sentinel(v.z) || (!target[k] && !is_sentinel(v.w))) stray_pend++;
+    }
+    q.out_stray[0] = stray_hit; q.out_stray[1] = stray_pend;
+    for (uint32_t s = 0; s < kShards; s++) for (int k = 0; k < kCounterArrays; k++) q.out_cnt[s * kCounterArrays + k] = h_cnt[(size_t)k * kShards * kCounterStride + s * kCounterStride];
+    return hipSuccess;
 }
 
 }  // namespace pt

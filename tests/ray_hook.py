@@ -1,4 +1,6 @@
-"""Test helper: the product's traversal on caller-supplied rays (pt_debug_intersect, a test hook of libmipt.so that is not part of include/mipt.h)."""
+"""Test helpers: the product's traversal on caller-supplied rays -- pt_debug_intersect (k_debug_intersect: traverse(), one ray per lane) and
+pt_debug_trace_queues (the wavefront stages' k_wf_trace / k_wf_shadow / k_wf_traverse on caller-filled queues), test hooks of libmipt.so that are
+not part of include/mipt.h."""
 import ctypes as C
 import numpy as np
 
@@ -20,6 +22,50 @@ def gpu_intersect(renderer, rays, ray_flags=0, mode=0):
     rc = f(renderer.h, rays.ctypes.data_as(C.c_void_p), len(rays), ray_flags, mode, out.ctypes.data_as(C.c_void_p))
     if rc != 0: raise RuntimeError("pt_debug_intersect: %d %s" % (rc, renderer.last_error() if hasattr(renderer, "last_error") else ""))
     return out
+
+
+TQ_TRACE, TQ_SHADOW, TQ_FUSED = 0, 1, 2                     # pt_debug_trace_queues `which`
+TQ_SENTINEL = 0x7fc5a5a5                                    # the bits every output word holds before the launch (a NaN no kernel produces)
+CNT_CLOSEST0, CNT_CLOSEST1, CNT_SHADOW_EVEN, CNT_HEAD_CLOSEST, CNT_HEAD_SHADOW, CNT_SHADOW_ODD, CNT_HEAD_SHADE = range(7)   # pt_wavefront.hip WfBuffers::cnt
+
+
+def shadow_counter(bounce):
+    return CNT_SHADOW_ODD if bounce & 1 else CNT_SHADOW_EVEN
+
+
+def trace_queues_rc(L, h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce, blocks_per_shard, which):
+    """The raw call: (return code, closest [n_c, 8] float32, shadow [n_s] float32, counters [256, 7] uint32, stray [2] uint32)."""
+    closest = np.ascontiguousarray(np.zeros((0, 8)) if closest is None else closest, np.float32).reshape(-1, 8)
+    shadow = np.ascontiguousarray(np.zeros((0, 6)) if shadow is None else shadow, np.float32).reshape(-1, 6)
+    n_c, n_s = len(closest), len(shadow)
+    cs = np.ascontiguousarray(np.zeros(n_c) if closest_shard is None else np.broadcast_to(closest_shard, (n_c,)), np.uint32)
+    ss = np.ascontiguousarray(np.zeros(n_s) if shadow_shard is None else np.broadcast_to(shadow_shard, (n_s,)), np.uint32)
+    il = np.ascontiguousarray(np.zeros(n_s) if is_light is None else np.broadcast_to(is_light, (n_s,)), np.uint8)
+    out_c = np.zeros((n_c, 8), np.float32); out_s = np.zeros(n_s, np.float32); cnt = np.zeros((256, 7), np.uint32); stray = np.zeros(2, np.uint32)
+    f = L.pt_debug_trace_queues
+    vp = C.c_void_p
+    f.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_float, C.c_uint32, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp]
+    f.restype = C.c_int
+    ptr = lambda a: a.ctypes.data_as(vp) if a.size else None
+    rc = f(h, ptr(closest), ptr(cs), n_c, ptr(shadow), ptr(ss), ptr(il), n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
+           ptr(out_c), ptr(out_s), cnt.ctypes.data_as(vp), stray.ctypes.data_as(vp))
+    return rc, out_c, out_s, cnt, stray
+
+
+def trace_queues(renderer, closest=None, closest_shard=None, shadow=None, shadow_shard=None, is_light=None, shadow_tmax=1000.0, flags=0, bounce=0,
+                 blocks_per_shard=1, which=TQ_TRACE):
+    """closest [n_c, 8] float32 (origin, 0, direction, tmax) and shadow [n_s, 6] float32 (origin, direction) rays with the shard (0..255, an array
+    or one number) each is queued in -> (closest results [n_c, 8] as gpu_intersect's, shadow transmissions [n_s], counter words [256, 7], stray [2])."""
+    rc, out_c, out_s, cnt, stray = trace_queues_rc(renderer.L, renderer.h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce,
+                                                   blocks_per_shard, which)
+    if rc != 0: raise RuntimeError("pt_debug_trace_queues: %d %s" % (rc, renderer.L.pt_last_error(renderer.h).decode()))
+    return out_c, out_s, cnt, stray
+
+
+def shadow_rays_of(rays):
+    """[n, 8] rays (origin, tmin, direction, tmax) -> the [n, 6] (origin, direction) records of the shadow queue."""
+    rays = np.asarray(rays, np.float32).reshape(-1, 8)
+    return np.ascontiguousarray(np.concatenate([rays[:, 0:3], rays[:, 4:7]], axis=1))
 
 
 def surface_rays(o, s, n, seed):

@@ -339,42 +339,7 @@ def test_bench_launches_its_own_ranks_when_started_plainly(tmp_path):
 
 
 # ---- trees deeper than the 64-entry on-chip stack are rendered, not refused ----------------------------------------------------------
-def _deep_chain_scene(dups=4096, size=32):
-    """A legal scene whose radix tree needs more traversal-stack entries than a lane holds on chip, and whose rays really use them.
-    57 thin sheets perpendicular to the view direction (+x) whose bounding-box centres are (C,0,0), (0,C,0) or (0,0,C) with
-    C = (2^j + 1/4) 2^-10, j = 0..18 -- long thin triangles for the y and z kinds: every Morton code has a different highest bit, so the
-    radix tree is one chain, 57 binary levels deep -- plus `dups` coincident copies of the nearest sheet (equal codes: a subtree balanced by
-    index below the chain's end).  Each chain level's sheet lies farther along the ray than everything below it, so a ray enters the inner
-    child first and leaves the sheets on its stack: ~3 entries per wide level all the way down, then 3 more per level of the copies."""
-    from gltf_renderer_amd import camera, meshgen
-    f32 = np.float32
-    u, h, w, eps = 2.0 ** -10, 2.0 ** -10, 2.0 ** -11, 2.0 ** -20
-    tris = [[(-eps, -h, -h), (-eps, h, -h), (-eps, 0, h)]] * dups                 # the nearest sheet, `dups` times
-    k = 0
-    for j in range(19):
-        C = (2.0 ** j + 0.25) * u
-        xk = (k + 1) * eps; k += 1
-        tris.append([(xk, -h, -w), (xk, -h, 2 * C + w), (xk, h, -w)])             # centre (~0, 0, C): long along z
-        xk = (k + 1) * eps; k += 1
-        tris.append([(xk, -w, -h), (xk, 2 * C + w, -h), (xk, -w, h)])             # centre (~0, C, 0): long along y
-        k += 1
-        tris.append([(C, -h, -h), (C, h, -h), (C, 0, h)])                         # centre (C, 0, 0)
-    pos = np.array(tris, f32)[:, [0, 2, 1], :].reshape(-1, 3)                     # wound so that the geometric normal faces the camera (-x)
-    n = len(pos) // 3
-    mesh = meshgen.Mesh(pos, np.arange(3 * n), normals=np.tile(np.array([[-1, 0, 0]], f32), (3 * n, 1)),
-                        uv0=np.tile(np.array([[0, 1], [1, 1], [0.5, 0]], f32), (n, 1)))
-    s = scenes.single_triangle(size)
-    s.instances.clear(); s.mesh_records.clear(); s.buffers.clear(); s.triangles = 0
-    m = s.add_material(scenes.material(base_color_factor=(0.8, 0.6, 0.4, 1.0), flags=abi.MATERIAL_FLAG_DOUBLE_SIDED))
-    s.add_mesh(mesh, None, m)
-    s.world_to_view = camera.free_world_to_view((-0.5, 0.0, 0.0), yaw=-np.pi / 2)
-    assert np.allclose(s.world_to_view @ np.array([1.0, 0, 0, 0]), [0, 0, -1, 0], atol=1e-12)          # looking along +x
-    s.ortho = (1.0 / (0.15 * h), 1.0 / (0.15 * h))                                # half extents 1 / mag: every ray inside every sheet
-    st = abi.PtSettings.app_defaults(); st.min_bounces, st.max_bounces = 1, 2
-    st.flags &= ~(abi.FLAG_ENVIRONMENT_MAP | abi.FLAG_ENVIRONMENT_MIS)            # no map: the constant colour lights the scene
-    st.environment_color[:] = (1.0, 1.0, 1.0)
-    s.settings = st
-    return s, n
+from traversal_scenes import _deep_chain_scene            # shared with tests/test_gpu_traversal_driver.py
 
 
 @pytest.mark.parametrize("mode", [abi.MODE_WAVEFRONT, abi.MODE_MEGAKERNEL], ids=["wavefront", "megakernel"])

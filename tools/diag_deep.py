@@ -1,4 +1,4 @@
-import sys; sys.path.insert(0, '.')
+import sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import numpy as np
 from tests.test_gpu_round3 import _deep_chain_scene, copy_settings
 from gltf_renderer_amd import abi

@@ -4,7 +4,9 @@ Each trial: 1-4 instances (random rotation / non-uniform scale / mirroring / tra
 (50-4000 triangles, sizes over six orders of magnitude, some degenerate -- repeated or collinear vertices --, some exact coplanar duplicates so
 that equal-distance ties occur, some axis-aligned sheets whose boxes have no thickness); all three builders in turn; rays between random points
 of the scene's box, along the axes, from points ON triangles, grazing; closest-hit with and without culling and occlusion.  A sample of the rays
-also goes through the oracle's exhaustive search.   usage: python tools/geometry_fuzz.py [trials] [seed]"""
+also goes through the oracle's exhaustive search.   usage: python tools/geometry_fuzz.py [trials] [seed] [--driver wavefront]
+--driver wavefront sends the same rays (with tmin = 0: the queue format has none) through the wavefront stages' kernels too (pt_debug_trace_queues:
+k_wf_trace for the closest-hit rows, k_wf_shadow for the occlusion row), dealt over the 256 shards, and compares those with the oracle as well."""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
@@ -70,9 +72,28 @@ def random_rays(rng, o, tris, n):
     return np.concatenate([rays, surf, ax, short])
 
 
+def wavefront_intersect(r, rays, flags, mode, shards):
+    """The rows of the main loop through the wavefront kernels.  Ray flags 0 / RF_CULL_BACK / RF_CULL_FRONT are what a frame gives its closest rays at
+    bounce 0 without culling, at bounce 0 with PT_FLAG_CULL_BACKFACE and at bounce 1 with it.  The shadow queue has ONE tmax for all its rays:
+    the caller passes occlusion rays that share theirs."""
+    from ray_hook import trace_queues, shadow_rays_of, TQ_TRACE, TQ_SHADOW     # (only this option needs the queue hook's wrapper)
+    if mode == 0:
+        pt_flags, bounce = {0: (0, 0), RF_CULL_BACK: (abi.FLAG_CULL_BACKFACE, 0), RF_CULL_FRONT: (abi.FLAG_CULL_BACKFACE, 1)}[flags]
+        return trace_queues(r, rays, shards, flags=pt_flags, bounce=bounce, blocks_per_shard=2, which=TQ_TRACE)[0]
+    v = trace_queues(r, None, None, shadow_rays_of(rays), shards, 1, shadow_tmax=float(rays[0, 7]), flags=0, bounce=0, blocks_per_shard=2, which=TQ_SHADOW)[1]
+    out = np.zeros((len(rays), 8), f32); out[:, 0] = v == 0
+    return out
+
+
 if __name__ == "__main__":
-    trials = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+    args = list(sys.argv[1:])
+    wavefront = False
+    if "--driver" in args:
+        k = args.index("--driver"); wavefront = args[k + 1] == "wavefront"
+        if args[k + 1] not in ("wavefront", "traverse"): sys.exit("--driver wavefront | traverse")
+        del args[k:k + 2]
+    trials = int(args[0]) if len(args) > 0 else 40
+    rng = np.random.default_rng(int(args[1]) if len(args) > 1 else 3)
     n_rays = n_bad = n_hit = n_closest = 0; t0 = time.time()
     for t in range(trials):
         s = random_scene(rng)
@@ -88,6 +109,17 @@ if __name__ == "__main__":
                 d = np.nonzero((g[:, :7].view(np.uint32) != c[:, :7].view(np.uint32)).any(axis=1) if mode == 0 else g[:, 0] != c[:, 0])[0]
                 n_bad += len(d)
                 print("trial %d (builder %d, %d triangles, flags %d mode %d): %d of %d rays differ; first: ray %s gpu %s oracle %s" % (t, t % 3, s.triangles, flags, mode, len(d), len(rays), rays[d[0]], g[d[0]], c[d[0]]), flush=True)
+        if wavefront:
+            wrays = rays.copy(); wrays[:, 3] = 0
+            shards = rng.integers(0, 256, len(wrays)).astype(np.uint32)
+            for flags, mode in ((0, 0), (RF_CULL_BACK, 0), (RF_CULL_FRONT, 0), (RF_ACCEPT_FIRST, 1)):
+                if mode == 1: wrays[:, 7] = np.median(rays[:, 7])
+                g = wavefront_intersect(r, wrays, flags, mode, shards); c = o.intersect_many(wrays, dxr_flags(flags), mode)
+                d = np.nonzero(g[:, 0] != c[:, 0] if mode == 1 else (g[:, :7].view(np.uint32) != c[:, :7].view(np.uint32)).any(axis=1))[0]
+                n_rays += len(wrays)
+                if len(d):
+                    n_bad += len(d)
+                    print("trial %d (builder %d, wavefront driver, flags %d mode %d): %d of %d rays differ; first: ray %s gpu %s oracle %s" % (t, t % 3, flags, mode, len(d), len(wrays), wrays[d[0]], g[d[0]], c[d[0]]), flush=True)
         sub = rays[rng.integers(0, len(rays), 1500)]
         o.set_brute_force(True); b = o.intersect_many(sub, 0, 0); o.set_brute_force(False)
         if not np.array_equal(b.view(np.uint32), o.intersect_many(sub, 0, 0).view(np.uint32)):
