@@ -644,8 +644,16 @@ public:
             a.bones = (const pt_bone*)dst;
             a.bone_count = bone_count;
         }
+        // k_skin_mfma multiplies every bone into every vertex (weight 0 where the vertex does not list it), and 0 * NaN = NaN: one non-finite
+        // bone -- the inverse_transpose of a joint scaled to zero is all NaN -- would reach every vertex of the mesh.  Such a call takes k_skin,
+        // which like the shader reads only the four bones a vertex lists.  The bones are still on the host here: 32 floats each.
+        bool use_mfma = p->use_mfma != 0;
+        if (use_mfma && a.bones) {
+            const float* f = (const float*)bones;
+            for (size_t i = 0, n = (size_t)bone_count * 32; i < n; i++) if (!std::isfinite(f[i])) { use_mfma = false; break; }
+        }
         HIPOK(hipEventRecord(ctx->ev_skin[0], ctx->stream));
-        launch_skin(a, p->use_mfma != 0, ctx->stream);
+        launch_skin(a, use_mfma, ctx->stream);
         HIPOK(hipGetLastError());
         HIPOK(hipEventRecord(ctx->ev_skin[1], ctx->stream));
         if (a.bones) { HIPOK(hipEventRecord(ctx->bones_fence, ctx->stream)); ctx->bones_fence_pending = true; }

@@ -9,6 +9,9 @@
 //             the 4 (joint, weight) pairs per vertex; then position/normal/tangent are transformed by the
 //             blended 3x4 matrices.  Blending matrices first and transforming once differs from the
 //             reference's "transform four times, then blend" only by fp32 re-association (~1 ulp).
+//             FINITE BONES ONLY: the product is dense, so a vertex meets every bone with weight 0 and 0 * NaN = 0 * inf = NaN would
+//             carry one bad bone into every vertex, where the shader confines it to the vertices that list it.  GpuSkin::Run scans
+//             the bones on the host and gives a call with a non-finite value in any of them to k_skin.
 // k_tonemap:  Source/Shaders/ToneMapper.ps.hlsl:30-101 (exposure, AgX or clamp, sRGB OETF, optional dither).
 #include "pt_shading.h"
 #include "pt_host.h"
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(64) void k_skin(SkinArgs a) {
 // (row = joint, col = one of 12 affine entries; the 3x3 of inverse_transpose go in a second pass).
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
+// Rule: every float of a.bones is finite (see the head of this file); launch_skin's caller keeps non-finite bones away from this kernel.
 __global__ __launch_bounds__(64) void k_skin_mfma(SkinArgs a) {
     __shared__ float s_m[2][16][16];                       // blended matrices: [0] transform (12 used), [1] inverse_transpose (9 used)
     const uint32_t lane = threadIdx.x, row = lane & 15, kq = lane >> 4;

@@ -288,7 +288,11 @@ typedef struct pt_skin_params {
     float    morph_weights[PT_MAX_SIMULTANEOUS_MORPH_TARGETS];
     int32_t  morph_position[PT_MAX_SIMULTANEOUS_MORPH_TARGETS];       /* handles, -1 = absent */
     int32_t  morph_tangent_space[PT_MAX_SIMULTANEOUS_MORPH_TARGETS];
-    int32_t  use_mfma;                 /* 0: per-vertex VALU blend; 1: v_mfma_f32_16x16x4_f32 blend */
+    int32_t  use_mfma;                 /* 0: per-vertex VALU blend; 1: v_mfma_f32_16x16x4_f32 blend.  The matrix-core blend is used
+                                          only for a call whose bones are all finite: with a NaN or an infinity in any of the
+                                          bone_count * 32 floats the call takes the per-vertex blend, which like the shader confines
+                                          the damage to the vertices that list the bad bone (a joint scaled to zero has an all-NaN
+                                          inverse_transpose) */
 } pt_skin_params;
 
 /* ---- ToneMapper::Config (Source/ToneMapper.h:11-20) ---------------------------------------- */
