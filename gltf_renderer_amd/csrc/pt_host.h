@@ -158,12 +158,11 @@ struct AovArgs {
     float4* normal_depth;
 };
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
-// occ_cache: the context's occluder cache (res_x * res_y * 8 words, persistent across calls; nullptr = none), see WfBuffers::occ_cache
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 // aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive = nullptr,
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
                             const AovArgs* aov = nullptr);
 
 // ---- sort_scan.hip: the build's two data-parallel primitives, hand-written (stable LSD radix sort of (u64, u32) pairs over 63 key bits; u32 exclusive scan)

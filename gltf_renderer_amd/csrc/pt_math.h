@@ -59,31 +59,18 @@ PT_DEV vec3 xyz(vec4 v) { return {v.x, v.y, v.z}; }
 // tests/test_gpu_math.py pins them).  On the path that reaches contrib / light_pdf, the MIS ratios and the luminance clamp a subnormal pdf is
 // already a degenerate sample that sanitize_sample zeroes either way (NaN and Inf alike, PathTracer.lib.hlsl:760-766).  Where such operands
 // can occur by construction (1 / direction of the ray set-up) the code keeps the compiler's sequence.
-// A vector divided by one scalar corrects the reciprocal once.  PT_EXACT_DIV=1 restores the compiler's sequence everywhere (A/B).
-#ifndef PT_EXACT_DIV
-#define PT_EXACT_DIV 0
-#endif
+// A vector divided by one scalar corrects the reciprocal once.
 PT_DEV float frcp_refined(float b) {                 // 1 / b to within half an ulp (not always the rounded reciprocal; fdiv_with corrects the quotient)
     float r = __builtin_amdgcn_rcpf(b);
     const float e = __builtin_fmaf(-b, r, 1.0f);
     return __builtin_fmaf(e, r, r);
 }
 PT_DEV float fdiv_with(float a, float b, float r) {  // a / b given r = frcp_refined(b), or the rounded 1 / b of a constant b
-#if PT_EXACT_DIV
-    return a / b;
-#else
     const float q = a * r;
     const float m = __builtin_fmaf(-b, q, a);
     return __builtin_amdgcn_div_fixupf(__builtin_fmaf(m, r, q), b, a);
-#endif
 }
-PT_DEV float fdiv(float a, float b) {
-#if PT_EXACT_DIV
-    return a / b;
-#else
-    return fdiv_with(a, b, frcp_refined(b));
-#endif
-}
+PT_DEV float fdiv(float a, float b) { return fdiv_with(a, b, frcp_refined(b)); }
 
 PT_DEV vec2 operator+(vec2 a, vec2 b) { return {a.x + b.x, a.y + b.y}; }
 PT_DEV vec2 operator-(vec2 a, vec2 b) { return {a.x - b.x, a.y - b.y}; }
@@ -133,32 +120,16 @@ PT_DEV vec3 reflect(vec3 i, vec3 n) { return i - 2 * dot(n, i) * n; }
 // 64 spp with them, 4.9e-3 without).  The cost is not measurable: the hardware's approximate v_sin_f32 / v_cos_f32 in their place
 // (PT_PROBE_FAST_SINCOS, wrong images) save 0.05 ms of a 23-ms launch -- two calls a hit.  The other transcendentals (atan2, log2, exp2,
 // exp, pow) are float kernels defined below: through double THEY are expensive (7.7 ms a launch).
-// PT_F64_TRANSCENDENTALS=0: the fp32 library sinf / cosf (A/B).
-#ifndef PT_F64_TRANSCENDENTALS
-#define PT_F64_TRANSCENDENTALS 1
-#endif
-#if PT_F64_TRANSCENDENTALS
 PT_DEV float pt_sin(float x) { return (float)sin((double)x); }
 PT_DEV float pt_cos(float x) { return (float)cos((double)x); }
-#else
-PT_DEV float pt_sin(float x) { return sinf(x); }
-PT_DEV float pt_cos(float x) { return cosf(x); }
-#endif
-// both of one angle: one argument reduction in double for the pair (PT_SINCOS_PAIR=0: two separate calls, for A/B)
-#ifndef PT_SINCOS_PAIR
-#define PT_SINCOS_PAIR 1
-#endif
+// both of one angle: one argument reduction in double for the pair
 PT_DEV void pt_sincos(float x, float& s, float& c) {
 #ifdef PT_PROBE_FAST_SINCOS      // PROBE ONLY: the hardware's approximate v_sin_f32 / v_cos_f32 -- what an ideal sincos would save
     s = __sinf(x); c = __cosf(x); return;
 #endif
-#if PT_F64_TRANSCENDENTALS && PT_SINCOS_PAIR
     double ds, dc;
     sincos((double)x, &ds, &dc);
     s = (float)ds; c = (float)dc;
-#else
-    s = pt_sin(x); c = pt_cos(x);
-#endif
 }
 // atan2, log2, exp2 -- and through them pow and exp -- are DEFINED here, as short float kernels made of IEEE multiplies, adds and divisions in
 // a fixed order (no fused multiply-add: these translation units are compiled without contraction), which the CPU oracle states operation for
@@ -170,11 +141,7 @@ PT_DEV void pt_sincos(float x, float& s, float& c) {
 // they cost 7.7 ms of a 22.6 ms launch (measured: ocml's double atan2, log2, exp2 are long).  These: atan2 nothing measurable; pow / exp
 // 0.35 ms on the Sponza-class scene, whose curtains (3 % of the hits) put a sheen lane into most waves of the shade stage -- v_log_f32 /
 // v_exp_f32 were 3 instructions per pow, this is ~55 (0.8 ms before the view-dependent half of the sheen lobe was hoisted out of the three
-// evaluations a hit makes, pt_shading.h prepare_sheen; as real calls instead of inlined code 1.0 ms).  PT_CO_TRANSCENDENTALS / PT_CO_ATAN2 /
-// PT_CO_POW = 0: the library routines (A/B).
-#ifndef PT_CO_TRANSCENDENTALS
-#define PT_CO_TRANSCENDENTALS 1
-#endif
+// evaluations a hit makes, pt_shading.h prepare_sheen; as real calls instead of inlined code 1.0 ms).
 PT_DEV float co_atan2(float y, float x) {
     if (!(x == x) || !(y == y)) return __builtin_nanf("");
     const float ax = fabsf(x), ay = fabsf(y), mx = fmaxf(ax, ay), mn = fminf(ax, ay);
@@ -224,25 +191,10 @@ PT_DEV float co_exp(float x) {
     const float r = (x - n * 0.693145751953125f) - n * 1.42860677e-06f;
     return co_scale2(co_exp2_reduced(r * 1.44269504f), n);
 }
-#ifndef PT_CO_ATAN2
-#define PT_CO_ATAN2 PT_CO_TRANSCENDENTALS
-#endif
-#ifndef PT_CO_POW
-#define PT_CO_POW PT_CO_TRANSCENDENTALS
-#endif
-#if PT_CO_ATAN2
 PT_DEV float pt_atan2(float y, float x) { return co_atan2(y, x); }
-#else
-PT_DEV float pt_atan2(float y, float x) { return atan2f(y, x); }
-#endif
 // pow(x, y) = exp2(y * log2 x): NaN for a negative base, pow(0, y > 0) = 0.
-#if PT_CO_POW
 PT_DEV float pt_exp(float x) { return co_exp(x); }
 PT_DEV float hpow(float x, float y) { return co_exp2(y * co_log2(x)); }
-#else
-PT_DEV float pt_exp(float x) { return expf(x); }
-PT_DEV float hpow(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
-#endif
 // pow with the CONSTANT integer exponents the path uses -- Schlick's (1 - |c|)^5, the punctual lights' (d / cutoff)^4 -- as products: x^2 * x^2 (* x),
 // each product correctly rounded, NaN for a negative base like the exp2 / log2 form.  HLSL leaves pow's precision to the implementation and
 // shader compilers expand such pows themselves; what matters here is that this is a definition the CPU oracle evaluates to the SAME BITS

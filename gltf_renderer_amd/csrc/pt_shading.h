@@ -144,13 +144,6 @@ PT_DEV RTex load_rtex(const RTex* p) {                      // 3 x dwordx4, issu
 }
 // The four texel addresses + weights of one Texture2D.SampleLevel(sampler, uv, 0): D3D texel-centre rule.
 // TransformUv (Material.hlsli:68-88) is folded in: rows (c*sx, s*sy, ox), (-s*sx, c*sy, oy) were formed on the host in fp32.
-#ifndef PT_TEX_PAIRS
-#define PT_TEX_PAIRS 1      // the two texels of a row in ONE 8-byte load (0: four dword gathers per fetch)
-#endif
-#ifndef PT_TEX_TRIO
-#define PT_TEX_TRIO 1       // materials flagged RM_TRIO fetch albedo + normal + metal-rough from the interleaved copy (0: never; needs PT_TEX_PAIRS)
-#endif
-#if PT_TEX_PAIRS
 // Both texels of a row come from one 8-byte load at the pair's base column ia = clamp(i0, 0, width - 2): element i - ia of it.  Only
 // a tap whose second column wrapped or mirrored off the pair (i0 = width - 1 with WRAP) needs its own loads, and the whole wave
 // skips those unless some lane is there.  (Textures are allocated 4 bytes long so that a width-1 texture's pair stays inside.)
@@ -206,54 +199,13 @@ PT_DEV vec4 resolve_taps(const TexTaps& k, uint32_t t00, uint32_t t10, uint32_t 
            unpack_texel(t01, k.srgb, srgb_lut) * k.w01 + unpack_texel(t11, k.srgb, srgb_lut) * k.w11;
 }
 PT_DEV vec4 resolve_taps(const TexTaps& k, const TexQuad& q, const float* srgb_lut) { return resolve_taps(k, q.t00, q.t10, q.t01, q.t11, srgb_lut); }
-#else
-struct TexTaps { const uint32_t *p00, *p10, *p01, *p11; float w00, w10, w01, w11; uint32_t srgb; };
-PT_DEV TexTaps texture_taps(const RTex& t, const vec2 tc[2]) {
-    // No fused multiply-add in here: the compiler contracts each inlined copy of this function on its own, and two textures with the
-    // same transform and size must get the same texels and weights to the bit (a material's interleaved footprint is fetched with the
-    // albedo texture's taps).  Plain products and sums are also what the CPU oracle computes.
-#pragma clang fp contract(off)
-    const vec2 uv = (t.flags & RT_TEXCOORD1) ? tc[1] : tc[0];
-    const float tu = t.m00 * uv.x + t.m01 * uv.y + t.ox;
-    const float tv = t.m10 * uv.x + t.m11 * uv.y + t.oy;
-    const int au = (int)((t.flags >> 1) & 3u), av = (int)((t.flags >> 3) & 3u);
-    float x = finite_coord(tu * (float)t.width), y = finite_coord(tv * (float)t.height);
-    TexTaps k;
-    k.srgb = t.flags & RT_SRGB;
-    if (t.flags & RT_POINT) {
-        int i = wrap_addr((int)floorf(x), t.width, au), j = wrap_addr((int)floorf(y), t.height, av);
-        k.p00 = k.p10 = k.p01 = k.p11 = t.texels + (size_t)j * t.width + i;
-        k.w00 = 1; k.w10 = k.w01 = k.w11 = 0;
-        return k;
-    }
-    x -= 0.5f; y -= 0.5f;
-    float fx0 = floorf(x), fy0 = floorf(y);
-    float fx = x - fx0, fy = y - fy0;
-    int i0 = wrap_addr((int)fx0, t.width, au), i1 = wrap_addr((int)fx0 + 1, t.width, au);
-    int j0 = wrap_addr((int)fy0, t.height, av), j1 = wrap_addr((int)fy0 + 1, t.height, av);
-    const uint32_t* r0 = t.texels + (size_t)j0 * t.width;
-    const uint32_t* r1 = t.texels + (size_t)j1 * t.width;
-    k.p00 = r0 + i0; k.p10 = r0 + i1; k.p01 = r1 + i0; k.p11 = r1 + i1;
-    k.w00 = (1 - fx) * (1 - fy); k.w10 = fx * (1 - fy); k.w01 = (1 - fx) * fy; k.w11 = fx * fy;
-    return k;
-}
-PT_DEV vec4 resolve_taps(const TexTaps& k, uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, const float* srgb_lut) {
-    if (k.w10 == 0 && k.w01 == 0 && k.w11 == 0 && k.w00 == 1) return unpack_texel(t00, k.srgb, srgb_lut);      // point filter
-    return unpack_texel(t00, k.srgb, srgb_lut) * k.w00 + unpack_texel(t10, k.srgb, srgb_lut) * k.w10 +
-           unpack_texel(t01, k.srgb, srgb_lut) * k.w01 + unpack_texel(t11, k.srgb, srgb_lut) * k.w11;
-}
-#endif
 // SampleTexture (Material.hlsli:90-96) of one material slot.
 PT_DEV vec4 sample_slot(const SceneRec& sc, const RMat* m, int slot, const vec2 tc[2], unsigned& taps) {
     const RTex t = load_rtex(&m->tex[slot]);
     const TexTaps k = texture_taps(t, tc);
     taps++;
-#if PT_TEX_PAIRS
     const uint2 r0 = tap_row(k, 0), r1 = tap_row(k, 1);
     return resolve_taps(k, tap_quad(k, r0, r1), sc.srgb_lut);
-#else
-    return resolve_taps(k, gload(k.p00), gload(k.p10), gload(k.p01), gload(k.p11), sc.srgb_lut);
-#endif
 }
 
 // ---------------------------------------------------------------- vertex fetch (PathTracer.lib.hlsl:176-302)
@@ -480,9 +432,7 @@ PT_DEV vec3 normal_from_sample(vec4 s, float scale, vec3 gn, vec3 t, vec3 b) {  
 // `fetched`: the filtered emissive texel when it came with the interleaved footprint (RM_TRIO_EMISSIVE, get_surface), else ignored
 PT_DEV vec3 emissive_of(const SceneRec& sc, const RMat* m, const MatHeader& h, const vec2 tc[2], unsigned& taps, vec3 fetched) {   // :151-159
     vec3 e = h.emissive_factor;
-#if PT_TEX_PAIRS && PT_TEX_TRIO
     if (h.bound_mask & RM_TRIO_EMISSIVE) { taps++; return e * fetched; }
-#endif
     if (slot_bound(h.bound_mask, SLOT_EMISSIVE)) e = e * xyz(sample_slot(sc, m, SLOT_EMISSIVE, tc, taps));
     return e;
 }
@@ -505,7 +455,6 @@ struct PbrTexels {
 PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHeader& h, const vec2 tc[2]) {
     PbrTexels f;
     f.emissive = vec4{0, 0, 0, 0};
-#if PT_TEX_PAIRS && PT_TEX_TRIO
     // Materials whose three textures share one footprint (RM_TRIO, the usual glTF PBR set) read it from the interleaved copy: one set
     // of addresses and weights, two dwordx4 per texel row.  Both paths are wave-uniform branches; a wave of trio materials only (every
     // wave of the bench scene) never enters the general one.
@@ -546,21 +495,6 @@ PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHea
             m00 = qm.t00; m10 = qm.t10; m01 = qm.t01; m11 = qm.t11;
         }
     }
-#else
-    const RTex t_alb = material_slot012(sc, mid, SLOT_ALBEDO), t_nrm = material_slot012(sc, mid, SLOT_NORMAL), t_mr = material_slot012(sc, mid, SLOT_METALLIC_ROUGHNESS);
-    const TexTaps k_alb = texture_taps(t_alb, tc), k_nrm = texture_taps(t_nrm, tc), k_mr = texture_taps(t_mr, tc);
-#if PT_TEX_PAIRS
-    const uint2 ar0 = tap_row(k_alb, 0), ar1 = tap_row(k_alb, 1), nr0 = tap_row(k_nrm, 0), nr1 = tap_row(k_nrm, 1), mr0 = tap_row(k_mr, 0), mr1 = tap_row(k_mr, 1);
-    const TexQuad qa = tap_quad(k_alb, ar0, ar1), qn = tap_quad(k_nrm, nr0, nr1), qm = tap_quad(k_mr, mr0, mr1);
-    const uint32_t a00 = qa.t00, a10 = qa.t10, a01 = qa.t01, a11 = qa.t11;
-    const uint32_t n00 = qn.t00, n10 = qn.t10, n01 = qn.t01, n11 = qn.t11;
-    const uint32_t m00 = qm.t00, m10 = qm.t10, m01 = qm.t01, m11 = qm.t11;
-#else
-    const uint32_t a00 = gload(k_alb.p00), a10 = gload(k_alb.p10), a01 = gload(k_alb.p01), a11 = gload(k_alb.p11);
-    const uint32_t n00 = gload(k_nrm.p00), n10 = gload(k_nrm.p10), n01 = gload(k_nrm.p01), n11 = gload(k_nrm.p11);
-    const uint32_t m00 = gload(k_mr.p00), m10 = gload(k_mr.p10), m01 = gload(k_mr.p01), m11 = gload(k_mr.p11);
-#endif
-#endif
     f.k_alb = k_alb; f.k_nrm = k_nrm; f.k_mr = k_mr;
     f.a00 = a00; f.a10 = a10; f.a01 = a01; f.a11 = a11;
     f.n00 = n00; f.n10 = n10; f.n01 = n01; f.n11 = n11;
@@ -655,11 +589,7 @@ PT_DEV vec4 debug_sample_query(const SceneRec& sc, uint32_t mid, int slot, const
         const MatHeader h = material_header(sc, mid);
         const PbrTexels f = fetch_pbr_texels(sc, mid, h, tc);
         const int s = slot == 16 ? SLOT_ALBEDO : slot == 17 ? SLOT_NORMAL : slot == 18 ? SLOT_METALLIC_ROUGHNESS : SLOT_EMISSIVE;
-#if PT_TEX_PAIRS && PT_TEX_TRIO
         const bool trio = (h.bound_mask & RM_TRIO) != 0;
-#else
-        const bool trio = false;
-#endif
         const RTex t = load_rtex(&m->tex[trio ? SLOT_ALBEDO : s]);  // the texture whose rows the footprint's pointers index
         base = t.texels;
         if (slot == 16) { k = f.k_alb; r = resolve_taps(k, f.a00, f.a10, f.a01, f.a11, sc.srgb_lut); }
@@ -668,13 +598,9 @@ PT_DEV vec4 debug_sample_query(const SceneRec& sc, uint32_t mid, int slot, const
         else if (trio && (h.bound_mask & RM_TRIO_EMISSIVE)) { k = f.k_alb; r = f.emissive; }
         else { const RTex te = load_rtex(&m->tex[SLOT_EMISSIVE]); k = texture_taps(te, tc); base = te.texels; r = sample_slot(sc, m, SLOT_EMISSIVE, tc, taps); }
     }
-#if PT_TEX_PAIRS
     taps5[0] = k.i0; taps5[1] = k.i1;
     taps5[2] = (int32_t)((k.p0 - base) / k.width); taps5[3] = (int32_t)((k.p1 - base) / k.width);
     taps5[4] = k.ia;
-#else
-    (void)k; (void)base; taps5[0] = taps5[1] = taps5[2] = taps5[3] = taps5[4] = -1;     // (the four-gather build keeps no columns)
-#endif
     return r;
 }
 
@@ -765,7 +691,7 @@ PT_DEV vec3 gltf_bsdf(const float* lut, const Surface& s, vec3 v, vec3 l, int mo
     float hdl = dot(h, l), hdv = dot(h, v);
     float h_dot_abs_l = dot(normalize(v3(ll.x, ll.y, fabsf(ll.z)) + vl), vl);
     bool refl = mode != 2, trans = mode != 1;
-    // the coat first (PT_COAT_FIRST; it is the LAST term of the shader's expression, :318-324): its inputs are the world-space n, v, h, l, which
+    // the coat first (it is the LAST term of the shader's expression, :318-324): its inputs are the world-space n, v, h, l, which
     // nothing after it needs -- evaluated at the end they stayed live through the whole function in a kernel that has no register to spare
     float cndv = dot(n, v), cndh = dot(n, h), cndl = dot(n, l);                    // (sic) shading normal
 #ifndef PT_PROBE_BASE_ONLY
@@ -797,16 +723,13 @@ PT_DEV vec3 gltf_bsdf(const float* lut, const Surface& s, vec3 v, vec3 l, int mo
     vec3 material = lerp3(dielectric, metal, s.metalness);
     float sa = sheen_alpha(s);
     float ms = max3(s.sheen_color);                                               // SheenMix :210-214
-#ifndef PT_SHEEN_SKIP
-#define PT_SHEEN_SKIP 1
-#endif
     // A material WITHOUT sheen (sheen colour exactly (0,0,0): every material that does not use KHR_materials_sheen) in a wave that holds no
     // sheen material skips the sheen BRDF -- two pow, three SheenL, the exponentials: ~150 instructions, three evaluations a hit -- and gets
     // the SAME bits: the layer term is 0 * sheen_brdf, which is +0 whenever sheen_brdf is finite and NaN otherwise, and sheen_brdf =
     // saturate(.) * D * V with V clamped to [0, 1] (a NaN clamps to 0) and D = (2 + 1/a) pow(1 - ndh^2, 1/(2a)) / 2 pi, finite unless the pow's
     // base is negative or NaN (|ndh| a rounding above 1, a NaN normal); the albedo scaling is 1 - 0 * E = 1 exactly.
     const bool no_sheen = s.sheen_color.x == 0.0f && s.sheen_color.y == 0.0f && s.sheen_color.z == 0.0f;
-    if (PT_SHEEN_SKIP && !__any(!no_sheen)) {
+    if (!__any(!no_sheen)) {
         const float sin2h = 1 - hl.z * hl.z;
         const float layer = (refl && !(sin2h >= 0.0f)) ? __builtin_nanf("") : 0.0f;
         material = v3(layer) + material * 1.0f;

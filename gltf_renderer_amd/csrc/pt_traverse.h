@@ -2,7 +2,7 @@
 //
 // One lane = one ray.  Traversal of 64-B 4-wide nodes with 8-bit quantised child boxes (3 x dwordx4 + 1 x dwordx2
 // loads per node; each word holds one bound of all four children, the near and the far word of each axis are picked by the sign of the
-// ray's inverse direction (PT_SLAB_SELECT), dequantised with v_cvt_f32_ubyte + v_fma, then
+// ray's inverse direction, dequantised with v_cvt_f32_ubyte + v_fma, then
 // the slab test of the four boxes is straight VALU on registers.  Measured: an extra dwordx4 load per node step
 // costs 6 % of the frame, 110 extra VALU instructions per node step cost 1 %), children visited near-to-far (4-key sorting network on (entry distance | slot) packed in one uint), 48-B world-space
 // triangle packets (3 x dwordx4), a per-lane stack held in LDS ([depth][lane] layout: conflict-free
@@ -25,44 +25,17 @@
 
 namespace pt {
 
-#ifndef PT_OCC_SLOT_ORDER
-#define PT_OCC_SLOT_ORDER 0
-#endif
-#ifndef PT_LEAF_SINGLE
-#define PT_LEAF_SINGLE 0
-#endif
 #ifndef PT_STACK_LDS
 #define PT_STACK_LDS 24
 #endif
-// Distance to a box plane.  1 (default): (plane - origin) * inv, the subtraction first: its rounding error is RELATIVE to the distance, which
-// the 1.0000004 on the exit distance covers, so a box that the ray enters is never culled.  0: plane * inv - origin * inv as one fused
-// multiply-add (six VALU instructions fewer per child): its error is ABSOLUTE, half an ulp of |origin * inv|, and for a short ray that starts
+// Distance to a box plane: (plane - origin) * inv, the subtraction first: its rounding error is RELATIVE to the distance, which
+// the 1.0000004 on the exit distance covers, so a box that the ray enters is never culled.  plane * inv - origin * inv as one fused
+// multiply-add (six VALU instructions fewer per child) has an ABSOLUTE error, half an ulp of |origin * inv|, and for a short ray that starts
 // far from the coordinate origin that is more than the padding -- measured at 1920x1080 on the Sponza-class scene, about one ray in ten
 // million then missed a box whose triangle it hits (a wall's box has no thickness), left the scene through the wall and came back as a
 // firefly: 43 pixels of a 64-sample frame beyond 1e-2 of the CPU oracle's, image metric 7.9e-4 of the 1e-3 allowed; subtracting first: 2 pixels,
 // 4.0e-5, and the frame time is the same (22.7 against 22.8 ms: the traversal waits on its node loads, not on these instructions).
-#ifndef PT_TIE_BREAK
-#define PT_TIE_BREAK 1
-#endif
-#ifndef PT_BOX_GATE
-#define PT_BOX_GATE 1
-#endif
-#ifndef PT_SLAB_SUBTRACT_FIRST
-#define PT_SLAB_SUBTRACT_FIRST 1
-#endif
-// 1 (default): a 4-wide node step picks, per axis, the NEAR and the FAR plane word of all four children by the sign of the ray's inv BEFORE it
-// dequantises them (two selects per axis), and the slab test uses them directly instead of fminf / fmaxf of every pair of plane distances: 15
-// vector instructions fewer in every copy of the step (tools/kernel_sizes.sh).  The values are the same: lo <= hi per child (the builder's quantisation keeps the order) and inv is
-// finite and not NaN for every finite direction (trav_init clamps it to +-1e30), so (near - o) * inv <= (far - o) * inv and no 0 * inf occurs;
-// only the sign of a zero distance can differ, which can change a visiting order but never a hit (candidate_stands).  Measured: EXPERIMENTS.md.
-#ifndef PT_SLAB_SELECT
-#define PT_SLAB_SELECT 1
-#endif
-#if PT_SLAB_SUBTRACT_FIRST
 #define PT_SLAB_T(P, A) (((P) - t.o.A) * t.inv.A)
-#else
-#define PT_SLAB_T(P, A) ((P) * t.inv.A - t.ood.A)
-#endif
 constexpr int kStackLds = PT_STACK_LDS;       // entries per lane in LDS  (24 * 4 B * 256 lanes = 24 KiB per workgroup)
 constexpr int kStackSpill = 40;     // further entries in scratch
 constexpr int kBlock = 256;
@@ -88,13 +61,12 @@ PT_DEV void candidate_alpha(const SceneRec& sc, uint32_t inst, int tri, float u,
 
 // Per-lane traversal state.
 struct Trav {
-    vec3 o, d, inv, ood;
+    vec3 o, d, inv;
     float tmin, tmax;          // original interval
     uint32_t rf, mask;
     int mode;                  // 0 closest hit, 1 occlusion
     bool all_candidates;       // alpha-shadow rays visit every candidate of the ORIGINAL interval (quirk q12)
     int cur, sp;
-    int post;                  // a leaf this lane reached but has not tested yet (kTravDone: none): trace_persistent's postponed leaf
     HitRec best;
     float transmission;        // ShadowPayload
     bool committed;
@@ -109,14 +81,12 @@ PT_DEV void trav_init(Trav& t, const SceneRec& sc, const Ray& r, uint32_t rf, ui
     // beyond any ray interval with the sign it should have, for every plane farther than |origin| * 2^-24 from the origin's coordinate.
     const float kInvMax = 1.0e30f;
     t.inv = v3(clampf(1.0f / r.d.x, -kInvMax, kInvMax), clampf(1.0f / r.d.y, -kInvMax, kInvMax), clampf(1.0f / r.d.z, -kInvMax, kInvMax));
-    t.ood = v3(r.o.x * t.inv.x, r.o.y * t.inv.y, r.o.z * t.inv.z);
     t.rf = rf; t.mask = mask; t.mode = mode;
     t.all_candidates = (mode == 1) && (rf & RF_FORCE_NON_OPAQUE);
     t.best.t = r.tmax; t.best.tri = -1; t.best.u = 0; t.best.v = 0; t.best.front = true;
     t.transmission = transmission0;
     t.committed = false;
     t.sp = 0;
-    t.post = kTravDone;
     t.cur = (mask == 0 || sc.num_tris == 0) ? kTravDone : sc.root;
 }
 
@@ -148,67 +118,6 @@ PT_DEV void trav_pop(Trav& t, const SceneRec& sc, const int* lds_stack, const in
 
 #define PT_CSWAP(a, b) { uint32_t _lo = min(a, b), _hi = max(a, b); a = _lo; b = _hi; }
 
-#if PT_BVH_WIDTH == 8
-// One inner-node step over an 8-wide node (pt_types.h): six dwordx4 loads, eight slab tests.  Each hit child becomes a 64-bit
-// (entry distance, child reference) pair; closest-hit rays enter the nearest and push the rest (a full 19-exchange sort of the
-// pairs was slower still: 4146 against 4200 Mrays/s).
-// On exit t.cur is the nearest hit child, or the popped entry, or kTravDone.
-template <bool COUNT, bool ORDERED = true>
-PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spill, LaneStats& st) {
-#pragma clang fp contract(fast)       // box tests only decide the visiting order: fused multiply-adds here cannot change a hit (csrc/Makefile)
-    const float4* np = (const float4*)sc.nodes + (size_t)t.cur * kNodeFloat4;
-    const float4 hd = np[0], ca = np[1], cb = np[2], qx = np[3], qy = np[4], qz = np[5];
-    if (COUNT) st.nodes++;
-    const float limit = t.all_candidates ? t.tmax : t.best.t;
-    const uint32_t ex = __float_as_uint(hd.w);
-    const float sx = bvh_step(ex & 0xffu), sy = bvh_step((ex >> 8) & 0xffu), sz = bvh_step((ex >> 16) & 0xffu);
-    const int c[8] = {__float_as_int(ca.x), __float_as_int(ca.y), __float_as_int(ca.z), __float_as_int(ca.w),
-                      __float_as_int(cb.x), __float_as_int(cb.y), __float_as_int(cb.z), __float_as_int(cb.w)};
-    // words: q?.x = lo of children 0-3, q?.y = lo of 4-7, q?.z = hi of 0-3, q?.w = hi of 4-7 (byte k & 3 = child k)
-    const uint32_t lx[2] = {__float_as_uint(qx.x), __float_as_uint(qx.y)}, hx[2] = {__float_as_uint(qx.z), __float_as_uint(qx.w)};
-    const uint32_t ly[2] = {__float_as_uint(qy.x), __float_as_uint(qy.y)}, hy[2] = {__float_as_uint(qy.z), __float_as_uint(qy.w)};
-    const uint32_t lz[2] = {__float_as_uint(qz.x), __float_as_uint(qz.y)}, hz[2] = {__float_as_uint(qz.z), __float_as_uint(qz.w)};
-    unsigned long long e[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const int w = k >> 2, sh = 8 * (k & 3);
-        const float LX = bvh_dequant((lx[w] >> sh) & 0xffu, sx, hd.x), HX = bvh_dequant((hx[w] >> sh) & 0xffu, sx, hd.x);
-        const float LY = bvh_dequant((ly[w] >> sh) & 0xffu, sy, hd.y), HY = bvh_dequant((hy[w] >> sh) & 0xffu, sy, hd.y);
-        const float LZ = bvh_dequant((lz[w] >> sh) & 0xffu, sz, hd.z), HZ = bvh_dequant((hz[w] >> sh) & 0xffu, sz, hd.z);
-        const float a0 = PT_SLAB_T(LX, x), b0 = PT_SLAB_T(HX, x), a1 = PT_SLAB_T(LY, y), b1 = PT_SLAB_T(HY, y);
-        const float a2 = PT_SLAB_T(LZ, z), b2 = PT_SLAB_T(HZ, z);
-        const float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));
-        const float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), limit)) * 1.0000004f;
-        const bool hit = tn <= tx && c[k] != kEmptyChild;
-        // tn >= 0, so its bit pattern orders like the float; a miss sorts behind every hit
-        e[k] = hit ? (((unsigned long long)__float_as_uint(tn) << 32) | (uint32_t)c[k]) : ~0ull;
-    }
-    // a step pushes at most seven entries: if no active lane is within seven of the LDS part's end, every push is a plain ds_write
-    const bool shallow = __ballot(t.sp + 7 > kStackLds) == 0;
-    if (!ORDERED) {
-        // occlusion rays accept any hit: visiting order is irrelevant, skip the sort
-        int next = kTravDone;
-#define PT_PUSH_UNORDERED(F)                                                                                                        \
-        _Pragma("unroll") for (int k = 0; k < 8; k++)                                                                               \
-            if (e[k] != ~0ull) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, (int)(uint32_t)e[k], st); else next = (int)(uint32_t)e[k]; }
-        if (shallow) { PT_PUSH_UNORDERED(true) } else { PT_PUSH_UNORDERED(false) }
-#undef PT_PUSH_UNORDERED
-        if (next != kTravDone) t.cur = next; else trav_pop(t, sc, lds_stack, spill);
-        return;
-    }
-    // nearest child first, the other hit children pushed as they come (their order only affects how soon a later box is culled)
-    unsigned long long best = e[0];
-#pragma unroll
-    for (int k = 1; k < 8; k++) best = e[k] < best ? e[k] : best;
-    if (best != ~0ull) {
-#define PT_PUSH_REST(F)                                                                                                             \
-        _Pragma("unroll") for (int k = 0; k < 8; k++) if (e[k] != ~0ull && e[k] != best) trav_push<F>(t, sc, lds_stack, spill, (int)(uint32_t)e[k], st);
-        if (shallow) { PT_PUSH_REST(true) } else { PT_PUSH_REST(false) }
-#undef PT_PUSH_REST
-        t.cur = (int)(uint32_t)best;
-    } else trav_pop(t, sc, lds_stack, spill);
-}
-#else
 // One inner-node step: t.cur >= 0 on entry; on exit t.cur is the nearest hit child, or the popped entry, or kTravDone.
 template <bool COUNT, bool ORDERED = true>
 PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spill, LaneStats& st) {
@@ -232,27 +141,24 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     const uint32_t wlx = __float_as_uint(qxy.x), whx = __float_as_uint(qxy.y), wly = __float_as_uint(qxy.z), why = __float_as_uint(qxy.w);
     const uint32_t wlz = __float_as_uint(qz.x), whz = __float_as_uint(qz.y);
 #define PT_DQ4(W, S, O) make_float4(bvh_dequant((W) & 0xffu, S, O), bvh_dequant(((W) >> 8) & 0xffu, S, O), bvh_dequant(((W) >> 16) & 0xffu, S, O), bvh_dequant((W) >> 24, S, O))
-#if PT_SLAB_SELECT
-    // lo? / hi? hold the planes the ray meets first / last on each axis (hi / lo swapped where it runs towards minus)
+    // lo? / hi? hold the planes the ray meets first / last on each axis (hi / lo swapped where it runs towards minus): the near and the far
+    // plane word of all four children are picked by the sign of the ray's inv BEFORE they are dequantised (two selects per axis), and the slab
+    // test uses them directly instead of fminf / fmaxf of every pair of plane distances: 15 vector instructions fewer in every copy of the
+    // step (tools/kernel_sizes.sh).  The values are the same: lo <= hi per child (the builder's quantisation keeps the order) and inv is
+    // finite and not NaN for every finite direction (trav_init clamps it to +-1e30), so (near - o) * inv <= (far - o) * inv and no 0 * inf
+    // occurs; only the sign of a zero distance can differ, which can change a visiting order but never a hit (candidate_stands).
+    // Measured: EXPERIMENTS.md.
     const bool nx = t.inv.x < 0.0f, ny = t.inv.y < 0.0f, nz = t.inv.z < 0.0f;
     const float4 lox = PT_DQ4(nx ? whx : wlx, sx, hd.x), hix = PT_DQ4(nx ? wlx : whx, sx, hd.x), loy = PT_DQ4(ny ? why : wly, sy, hd.y), hiy = PT_DQ4(ny ? wly : why, sy, hd.y);
     const float4 loz = PT_DQ4(nz ? whz : wlz, sz, hd.z), hiz = PT_DQ4(nz ? wlz : whz, sz, hd.z);
-#define PT_SLAB_NEAR(A, B) (A)
-#define PT_SLAB_FAR(A, B) (B)
-#else
-    const float4 lox = PT_DQ4(wlx, sx, hd.x), hix = PT_DQ4(whx, sx, hd.x), loy = PT_DQ4(wly, sy, hd.y), hiy = PT_DQ4(why, sy, hd.y);
-    const float4 loz = PT_DQ4(wlz, sz, hd.z), hiz = PT_DQ4(whz, sz, hd.z);
-#define PT_SLAB_NEAR(A, B) fminf(A, B)
-#define PT_SLAB_FAR(A, B) fmaxf(A, B)
-#endif
 #undef PT_DQ4
     uint32_t key[4];
 #define PT_SLAB(K, CH, LX, LY, LZ, HX, HY, HZ)                                                                            \
     {                                                                                                                     \
         float a0 = PT_SLAB_T(LX, x), b0 = PT_SLAB_T(HX, x), a1 = PT_SLAB_T(LY, y), b1 = PT_SLAB_T(HY, y);                   \
         float a2 = PT_SLAB_T(LZ, z), b2 = PT_SLAB_T(HZ, z);                                                                \
-        float tn = fmaxf(fmaxf(PT_SLAB_NEAR(a0, b0), PT_SLAB_NEAR(a1, b1)), fmaxf(PT_SLAB_NEAR(a2, b2), t.tmin));          \
-        float tx = fminf(fminf(PT_SLAB_FAR(a0, b0), PT_SLAB_FAR(a1, b1)), fminf(PT_SLAB_FAR(a2, b2), limit)) * 1.0000004f; \
+        float tn = fmaxf(fmaxf(a0, a1), fmaxf(a2, t.tmin));                                                                \
+        float tx = fminf(fminf(b0, b1), fminf(b2, limit)) * 1.0000004f;                                                    \
         key[K] = (tn <= tx && CH != kEmptyChild) ? ((__float_as_uint(tn) & ~3u) | (uint32_t)K) : 0xffffffffu;              \
     }
     PT_SLAB(0, c0, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x)
@@ -260,28 +166,16 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     PT_SLAB(2, c2, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z)
     PT_SLAB(3, c3, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w)
 #undef PT_SLAB
-#undef PT_SLAB_NEAR
-#undef PT_SLAB_FAR
     // a step pushes at most three entries: if no active lane is within three of the LDS part's end, every push is a plain ds_write
     const bool shallow = __ballot(t.sp + 3 > kStackLds) == 0;
     if (!ORDERED) {
         // occlusion rays accept any hit: visiting order is irrelevant, skip the sort
         int next = kTravDone;
-#if PT_OCC_SLOT_ORDER
-        // the hit children in SLOT order (the builder stores them in decreasing surface area): the first is entered, the others are
-        // pushed last-slot-first so that they pop in slot order too
-        if (key[3] != 0xffffffffu) next = c3;
-#define PT_PUSH_UNORDERED(F)                                                                                                        \
-        if (key[2] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, next, st); next = c2; }               \
-        if (key[1] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, next, st); next = c1; }               \
-        if (key[0] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, next, st); next = c0; }
-#else
         if (key[0] != 0xffffffffu) next = c0;
 #define PT_PUSH_UNORDERED(F)                                                                                                        \
         if (key[1] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c1, st); else next = c1; }           \
         if (key[2] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c2, st); else next = c2; }           \
         if (key[3] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c3, st); else next = c3; }
-#endif
         if (shallow) { PT_PUSH_UNORDERED(true) } else { PT_PUSH_UNORDERED(false) }
 #undef PT_PUSH_UNORDERED
         if (next != kTravDone) t.cur = next; else trav_pop(t, sc, lds_stack, spill);
@@ -300,7 +194,6 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
         t.cur = child_of(key[0]);
     } else trav_pop(t, sc, lds_stack, spill);
 }
-#endif
 
 // What makes the answer independent of the TREE (rare path: only for a triangle the float Moeller-Trumbore test has just accepted).
 //  (1) The box gate.  The float test does not decide "inside" exactly: it accepts rays that pass a few ulp (of the ray's length, more at
@@ -314,35 +207,27 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
 //      walk; here the lower (instance, primitive) wins.
 // The oracle states both the same way (oracle.cpp Tracer::intersect), and its exhaustive search over all triangles finds the same hits.
 PT_DEV bool candidate_stands(const Trav& t, const SceneRec& sc, vec3 v0, vec3 e1, vec3 e2, float tt, float limit, uint32_t inst, uint32_t prim) {
-    if (PT_BOX_GATE) {
-        const vec3 v1 = v0 + e1, v2 = v0 + e2;                                          // the builder's expression for the box (accel.hip k_seg_pass)
-        const vec3 lo = hmin(hmin(v0, v1), v2), hi = hmax(hmax(v0, v1), v2);
-        const float a0 = (lo.x - t.o.x) * t.inv.x, b0 = (hi.x - t.o.x) * t.inv.x, a1 = (lo.y - t.o.y) * t.inv.y, b1 = (hi.y - t.o.y) * t.inv.y;
-        const float a2 = (lo.z - t.o.z) * t.inv.z, b2 = (hi.z - t.o.z) * t.inv.z;
-        const float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));
-        const float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fmaxf(a2, b2));
-        if (!(tn <= tx * 1.0000004f && tn <= tt * 1.0000004f)) return false;
-    }
+    // (1) the box gate
+    const vec3 v1 = v0 + e1, v2 = v0 + e2;                                          // the builder's expression for the box (accel.hip k_seg_pass)
+    const vec3 lo = hmin(hmin(v0, v1), v2), hi = hmax(hmax(v0, v1), v2);
+    const float a0 = (lo.x - t.o.x) * t.inv.x, b0 = (hi.x - t.o.x) * t.inv.x, a1 = (lo.y - t.o.y) * t.inv.y, b1 = (hi.y - t.o.y) * t.inv.y;
+    const float a2 = (lo.z - t.o.z) * t.inv.z, b2 = (hi.z - t.o.z) * t.inv.z;
+    const float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));
+    const float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fmaxf(a2, b2));
+    if (!(tn <= tx * 1.0000004f && tn <= tt * 1.0000004f)) return false;
     if (tt < limit) return true;
-    if (!(PT_TIE_BREAK && t.mode == 0 && t.best.tri >= 0)) return false;                // tt == limit: the interval's end, or a tie with the hit held
+    if (!(t.mode == 0 && t.best.tri >= 0)) return false;                // tt == limit: the interval's end, or a tie with the hit held
     const uint4 h0 = *(const uint4*)((const float4*)sc.tris + (size_t)t.best.tri * kTriFloat4), h1 = *(const uint4*)((const float4*)sc.tris + (size_t)t.best.tri * kTriFloat4 + 1);
     return inst < h0.w || (inst == h0.w && prim < h1.w);
 }
 
 // One leaf step: t.cur = leaf reference (1..kLeafMax contiguous triangles) on entry; on exit the popped entry or kTravDone.
-// `keep` != kTravDone: the leaf tested is a POSTPONED one (trace_persistent): instead of popping, the lane goes on with `keep`, the entry it
-// had already moved on to -- unless the ray ended in this leaf.
 template <bool COUNT>
-PT_DEV void trav_leaf_step(Trav& t, const SceneRec& sc, const int* lds_stack, const int* spill, LaneStats& st, bool keep_next = false, int keep = kTravDone) {
+PT_DEV void trav_leaf_step(Trav& t, const SceneRec& sc, const int* lds_stack, const int* spill, LaneStats& st) {
     const uint32_t leaf = (uint32_t)~t.cur;
     const int first = (int)(leaf & kLeafFirstMask), count = (int)(leaf >> 28) + 1;
     bool stop = false;
-#if PT_LEAF_SINGLE
-  const int n_here = 1;                                       // one triangle per call: a lane with more of the leaf left stays at the (shortened) leaf
-#else
-  const int n_here = count;
-#endif
-  for (int k = 0; k < n_here && !stop; k++) {
+  for (int k = 0; k < count && !stop; k++) {
     const int tri = first + k;
     const float4* tp = (const float4*)sc.tris + (size_t)tri * kTriFloat4;
     float4 q0 = tp[0], q1 = tp[1], q2 = tp[2];
@@ -387,10 +272,6 @@ PT_DEV void trav_leaf_step(Trav& t, const SceneRec& sc, const int* lds_stack, co
     }
   }
     if (stop) t.cur = kTravDone;
-#if PT_LEAF_SINGLE
-    else if (count > 1) t.cur = ~(int)(((uint32_t)(first + 1) & kLeafFirstMask) | ((uint32_t)(count - 2) << 28));
-#endif
-    else if (keep_next) t.cur = keep;
     else trav_pop(t, sc, lds_stack, spill);
 }
 

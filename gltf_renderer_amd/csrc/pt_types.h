@@ -99,14 +99,7 @@ static_assert(sizeof(BvhNode) == 64, "BvhNode");
 // 16-bit cell indices on a per-tree grid, 5-bit step exponents below the root's: three dwordx4 loads, explicit child references kept) was
 // built and measured: bit-identical images, 0.6 % more node visits, traversal stage 14.05 against 13.84 ms -- the fourth load of a line
 // the step has already asked for is not what a step waits for.  Not kept (profiles/EXPERIMENTS.md).
-#ifndef PT_BVH_WIDTH
-#define PT_BVH_WIDTH 4          // children per wide node: 4 (64-B node, 4 loads per step) or 8 (96-B node, 6 loads per step).  Measured:
-                                // 8-wide takes 10.4 node steps per ray instead of 15.4 with the same loads per ray and is 7 % SLOWER
-                                // (4200 against 4530 Mrays/s: eight dequantised slab tests per step are no longer free)
-#endif
-constexpr int kBvhWidth = PT_BVH_WIDTH;
-static_assert(kBvhWidth == 4 || kBvhWidth == 8, "PT_BVH_WIDTH");
-#if PT_BVH_WIDTH == 4
+constexpr int kBvhWidth = 4;    // children per wide node (an 8-wide, 96-B node was measured 7 % slower: profiles/EXPERIMENTS.md)
 struct __attribute__((aligned(64))) Bvh4Node {
     float origin[3];                // lo corner of the union of the children
     uint8_t exp[3], _e;             // biased exponents of the per-axis grid step
@@ -116,21 +109,10 @@ struct __attribute__((aligned(64))) Bvh4Node {
     uint32_t _pad[2];
 };
 static_assert(sizeof(Bvh4Node) == 64, "Bvh4Node");
-#else
-// 8-wide: the same encoding with eight children, 96 B = six dwordx4 loads.  A ray takes about half as many node steps, and a
-// step is one dependent round trip to memory whatever it fetches.
-struct __attribute__((aligned(16))) Bvh4Node {
-    float origin[3];
-    uint8_t exp[3], _e;
-    int32_t child[8];
-    uint8_t qlox[8], qhix[8], qloy[8], qhiy[8], qloz[8], qhiz[8];     // byte k & 3 of word k >> 2 of each bound = child k
-};
-static_assert(sizeof(Bvh4Node) == 96, "Bvh4Node");
-#endif
 constexpr int kNodeFloat4 = (int)(sizeof(Bvh4Node) / 16);
 // Per wide node, the contiguous range [first, first + count) of Morton-sorted triangles under each child (count 0: unused slot).
 // Written by the collapse, read by the refit: a child's box is a range query over the triangles' boxes.
-struct __attribute__((aligned(16))) WideRanges { uint32_t first[PT_BVH_WIDTH], count[PT_BVH_WIDTH]; };
+struct __attribute__((aligned(16))) WideRanges { uint32_t first[kBvhWidth], count[kBvhWidth]; };
 constexpr int32_t kEmptyChild = 0x7fffffff;
 // the plane a quantised coordinate stands for; build and traversal must use this one expression
 __host__ __device__ __forceinline__ float bvh_dequant(uint32_t q, float step, float origin) { return __builtin_fmaf((float)q, step, origin); }
@@ -145,21 +127,16 @@ __host__ __device__ __forceinline__ float bvh_step(uint32_t biased_exp) {
 constexpr int kLeafMax = PT_LEAF_MAX;
 constexpr uint32_t kLeafFirstMask = 0x0fffffffu;
 
-// 48-B triangle packet in world space: v0, e1 = v1-v0, e2 = v2-v0 + ids -- stored one per 64-B line (PT_TRI_STRIDE64 = 1): packed at 48 B a
+// 48-B triangle packet in world space: v0, e1 = v1-v0, e2 = v2-v0 + ids -- stored one per 64-B line: packed at 48 B a
 // packet straddles two lines a third of the time, and a leaf test then waits for two cache lines; one per line measured 13.9 against 14.05 ms
 // of traversal per launch (+1 % rays/s) for 4 MB more on the bench scene (257 k triangles: 16.4 instead of 12.3 MB).  Bit-identical images.
-#ifndef PT_TRI_STRIDE64
-#define PT_TRI_STRIDE64 1
-#endif
 struct __attribute__((aligned(16))) TriPacket {
     float v0[3]; uint32_t inst;
     float e1[3]; uint32_t prim;
     float e2[3]; uint32_t flags;   // copy of InstanceRec::mask_flags
-#if PT_TRI_STRIDE64
     uint32_t _line_pad[4];
-#endif
 };
-static_assert(sizeof(TriPacket) == (PT_TRI_STRIDE64 ? 64 : 48), "TriPacket");
+static_assert(sizeof(TriPacket) == 64, "TriPacket");
 constexpr int kTriFloat4 = (int)(sizeof(TriPacket) / 16);
 
 // 128-B shading packet of one triangle, same (Morton) order as the TriPacket array: everything GetVertexAttributes gathers for the
@@ -252,8 +229,7 @@ struct FrameConstants {
     // `spp` consecutive PathtraceScene calls: sample k uses seed + k * seed_step and blends with accumulated_frames + k.
     uint32_t spp, pixel_slots, seed_step;
     uint32_t cull_null_shadow;       // pt_set_null_shadow_culling: do not trace a shadow ray whose pending term is exactly zero
-    uint32_t defer_rare;             // the shade stage sets hits on rare materials aside and shades them together (k_wf_shade; set by the host
-                                     // when a FEW of the scene's materials have the feature: with none there is nothing to gain, with many nothing either)
+    uint32_t defer_rare;             // unused, always 0: no kernel reads it; kept for the kernel-argument layout (profiles/EXPERIMENTS.md)
     FastDiv div_pixel_slots, div_tiles_x;   // divisions by pixel_slots / tiles_x (slot_pixel, slot_sample)
 };
 

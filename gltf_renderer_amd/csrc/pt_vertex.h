@@ -26,8 +26,11 @@ struct Followups {
     float b_pdf;
     bool b_mis;
     unsigned counted_shadow;   // shadow rays the reference traces but whose result a debug mode discards
-    uint32_t light_index;      // the punctual light the light-NEE sample picked (occluder cache key)
-    uint32_t hint_env, hint_light;   // occluder-cache words of the two shadow rays (fetched here, early, so that the push does not wait for them)
+    // DEAD: left from the rejected occluder cache.  light_index is written (shade_closest_hit), the hints are initialised, nothing reads
+    // any of the three; they stay because removing them changes pt_megakernel's register assignment (profiles/EXPERIMENTS.md, "The
+    // rejected compile-time alternatives removed": step 2).
+    uint32_t light_index;
+    uint32_t hint_env, hint_light;
 };
 
 // The environment-map branch of Miss, in three parts (shade_miss and the test hook pt_debug_env_query call them): the radiance along
@@ -108,11 +111,9 @@ extern __device__ unsigned long long pt_timing[12];
 // the in-place code, its LDS tables and its registers are not compiled in); otherwise it is drawn here.
 template <bool PRE = false>
 PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint32_t seed, uint32_t px, uint32_t py, const Ray& ray, const HitRec& hit,
-                              const RawPacket& packet_in, const ShadePacket* packet_at, PathState& ps, Followups& fu, unsigned& taps, const EnvSample* pre = nullptr,
-                              const uint32_t* occ_row = nullptr) {
+                              const RawPacket& packet_in, const ShadePacket* packet_at, PathState& ps, Followups& fu, unsigned& taps, const EnvSample* pre = nullptr) {
     const uint32_t flags = fc.flags;
     fu.add = v3(0); fu.overwrite = false; fu.counted_shadow = 0; fu.light_index = 0; fu.hint_env = fu.hint_light = 0xffffffffu;
-    if (occ_row) fu.hint_env = occ_row[0];
     fu.q_env = fu.q_light = fu.q_bounce = false;
 #ifdef PT_TIMING
     unsigned long long _sec[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, _t = __builtin_readcyclecounter();
@@ -176,7 +177,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
     }
     const Lobes lobes = lobe_probabilities(sp, view);
     sp.sheen_lh = sp.sheen_sv = 0.0f;
-    if (!PT_SHEEN_SKIP || __any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition)
+    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition)
     vec3 c = emissive_of(sc, mat, mh, va.tc, taps, sp.emissive_texel);                                                     // :925-926
     fu.origin_above = o_above;
     PT_TICK(2)
@@ -213,8 +214,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
         float u = next_random(px, py, seed, ps.rc).x;
         uint32_t li = f2u(u * (float)fc.num_of_lights);
         li = min(li, (uint32_t)(fc.num_of_lights - 1));                                              // u may be exactly 1 (quirk q17)
-        fu.light_index = li;
-        if (occ_row) fu.hint_light = occ_row[1u + li % 7u];
+        fu.light_index = li;                                                                         // (dead store, see Followups)
         float pdf = fdiv(1.0f, (float)fc.num_of_lights);
         vec3 ldir, lcol;
         bool cone_terms_staged;

@@ -50,109 +50,62 @@ namespace pt {
 constexpr uint32_t kShards = 256;
 constexpr uint32_t kMissTri = 0x7fffffffu;
 constexpr uint32_t kNoHint = 0xffffffffu;
-#ifndef PT_OCC_CACHE
-#define PT_OCC_CACHE 0        // 1: occluder cache for the shadow rays of first path vertices (WfBuffers::occ_cache).  MEASURED (round 3, images
-                              // bit-identical): node visits per ray 12.6 -> 10.9, traversal 13.85 -> 13.6 ms, shade +1.5 % (the hint fetches):
-                              // no gain -- the rays it shortens are the coherent, cheap ones, and a wave still lasts as long as its longest ray.
-                              // Off; kept as a build option for the record (profiles/EXPERIMENTS.md).
-#endif
 constexpr uint32_t kCounterStride = 16;      // one 64-B line per shard counter
 constexpr int kCounterArrays = 7;
 
 struct WfBuffers {
     // per slot (one path per pixel of this rank)
     float4* L;            // xyz radiance so far; w = bits: bit 0 env term pending, bit 1 light term pending
-    float4* beta_pdf;     // beta.xyz, prev_pdf
-    float4* thr_misc;     // thr.xyz, bits: rc | bounce << 16 | prev_mis << 31
+    float4* beta_pdf;     // unused (beta and throughput travel in q_beta / q_thr): no kernel reads or writes these two; they keep the
+    float4* thr_misc;     // kernel-argument layout
     float4* pend;         // [2 * slot] xyz pending env-NEE term (beta-weighted), w = its shadow transmission (written by the shadow stage);
                           // [2 * slot + 1] the same for the punctual-light term: one 32-B piece per path
     // closest-ray queues (ping-pong), kShards segments of seg_cap entries: (o.xyz, tmax), (d.xyz, slot)
     float4* ray_o[2];
     float4* ray_d[2];
-    float4* q_beta[2];    // PT_BT_IN_QUEUE: the path's (beta, prev_pdf) and (throughput, misc bits) travel with its closest-ray entry -- written
-    float4* q_thr[2];     // compacted, read coalesced -- instead of living in the slot-indexed arrays beta_pdf / thr_misc above
+    float4* q_beta[2];    // the path's (beta, prev_pdf) and (throughput, misc bits) travel with its closest-ray entry -- written
+    float4* q_thr[2];     // compacted, read coalesced -- instead of living in slot-indexed arrays
     float4* hit;          // per entry of the current queue: t, u, v, bits: tri | front << 31 (kMissTri: miss)
     float4* env_a;        // per entry of the current closest queue: the vertex's environment light sample, drawn by the traversal stage that
     float4* env_b;        // traces the entry (env_prepass): (direction, pdf), (radiance, -)
     // shadow queue, kShards segments of 2 * seg_cap entries: (o.xyz, bits: slot | is_light << 31), (d.xyz, tmax)
     float4* sh_o;
-    float4* sh_d;         // (d.xyz, bits: occluder hint -- a triangle index, kNoHint for none; the rays' tmax is the constant max_ray_length)
-    uint32_t* sh_c;       // per shadow entry: where the ray's occluder goes in occ_cache (kNoHint: nowhere)
-    // Occluder cache (PT_OCC_CACHE): per pixel, eight triangle indices -- [0] the last triangle that occluded an environment shadow ray of the
-    // pixel's FIRST path vertex, [1 + light % 7] the same for that punctual light.  A hint, never a result: the shadow ray tests the hinted
-    // triangle first, with the same intersection routine and flags; if it hits, the ray is occluded exactly as the traversal would have found,
-    // by whichever triangle.  Persists across pt_trace calls (the next samples of a pixel meet the occluders of the last ones).
-    uint32_t* occ_cache;
+    float4* sh_d;         // (d.xyz, kNoHint; the rays' tmax is the constant max_ray_length)
+    uint32_t* sh_c;       // unused, nullptr (kernel-argument layout)
+    uint32_t* occ_cache;  // unused, nullptr (kernel-argument layout)
     uint32_t* cnt[7];     // per shard (stride kCounterStride): entry counts of closest queue 0, closest queue 1, shadow queue (even bounces);
                           // [3], [4]: dynamic-fetch heads of the closest / shadow trace stages; [5]: shadow-queue count of odd bounces
                           // (the shadow count ping-pongs so that the fused traversal stage can zero the one the NEXT shade stage fills
                           // while it still reads the current one); [6]: dynamic-fetch head of the shade stage
     uint32_t capacity;    // slots
-    uint32_t chunks_per_shard;   // path-state arrays: 256-slot chunks per shard (state_index)
+    uint32_t chunks_per_shard;   // path-state arrays: 256-slot chunks per shard (unused by the kernels)
     uint32_t seg_cap;     // entries per closest-queue segment
     uint32_t blocks_per_shard;
-    uint32_t gen_region_tiles, gen_rounds;     // k_wf_generate: tiles per XCD band, workgroup-rounds to cover a band's (tile, sample) pairs
+    uint32_t gen_region_tiles, gen_rounds;     // k_wf_generate: (unused, 0), workgroup-rounds to cover the (tile, sample) pairs
 };
 
 
-// Queue entries and path-state records are written once and read once, a stage apart, by then long evicted from the 4-MiB L2s: they
-// are moved with the non-temporal hint so that they do not push the tree's nodes and triangle packets out on their way through
-// (PT_STREAM: 0 plain, 1 the ray / hit / shadow queues, 2 the per-path state records too).
-#ifndef PT_STREAM
-#define PT_STREAM 1       // (measured 0 / 1 / 2, Sponza class: 5073 / 5100 / 5099 Mrays/s at 8 spp, 4.66 / 4.59 / 4.57 ms per 1-spp launch)
-#endif
+// Queue entries are written once and read once, a stage apart, by then long evicted from the 4-MiB L2s: they are moved with the
+// non-temporal hint (QLD / QST) so that they do not push the tree's nodes and triangle packets out on their way through.  The per-path
+// state records are accessed plainly.
 typedef float nt_v4f __attribute__((ext_vector_type(4)));
 PT_DEV float4 nt_load(const float4& p) { const nt_v4f v = __builtin_nontemporal_load((const nt_v4f*)&p); return make_float4(v.x, v.y, v.z, v.w); }
 PT_DEV uint32_t nt_load(const uint32_t& p) { return __builtin_nontemporal_load(&p); }
 PT_DEV void nt_store(float4& p, const float4 v) { nt_v4f q; q.x = v.x; q.y = v.y; q.z = v.z; q.w = v.w; __builtin_nontemporal_store(q, (nt_v4f*)&p); }
 PT_DEV void nt_store(uint32_t& p, const uint32_t v) { __builtin_nontemporal_store(v, &p); }
-#if PT_STREAM >= 1
 #define QLD(p) nt_load(p)
 #define QST(p, v) nt_store((p), (v))
-#else
-#define QLD(p) (p)
-#define QST(p, v) ((p) = (v))
-#endif
-#if PT_STREAM >= 2
-#define SLD(p) nt_load(p)
-#define SST(p, v) nt_store((p), (v))
-#else
-#define SLD(p) (p)
-#define SST(p, v) ((p) = (v))
-#endif
 
-// Where the state of path `slot` lives.  Generate workgroup b takes the 256-slot chunks {b, b + grid, ...} and belongs to shard b % 256,
-// so in slot order a shard's paths are 4-KB pieces 1 MB apart in each of the six state arrays, and 33 MB apart from sample to sample:
-// a shade workgroup touched hundreds of pages (0.7 UTCL1 misses per hit, profiles/r02e_memside_counters.txt).  PT_STATE_BY_SHARD stores
-// chunk c of shard s at (s * chunks_per_shard + c / 256): everything a shard reads and writes is one contiguous piece of each array.
-#ifndef PT_STATE_BY_SHARD
-#define PT_STATE_BY_SHARD 0      // (measured on MI355X: 5082 against 5081 Mrays/s, no effect -- kept as a build option)
-#endif
-PT_DEV uint32_t state_index(const WfBuffers& wf, uint32_t slot) {
-#if PT_STATE_BY_SHARD
-    const uint32_t c = slot >> 8;
-    return (((c & (kShards - 1u)) * wf.chunks_per_shard + (c >> 8)) << 8) | (slot & 255u);
-#else
-    return slot;
-#endif
-}
-#define SIDX(s) state_index(wf, (s))
-#define PEND_ENV(s) wf.pend[2u * SIDX(s)]
-#define PEND_LIGHT(s) wf.pend[2u * SIDX(s) + 1u]
+#define PEND_ENV(s) wf.pend[2u * (s)]
+#define PEND_LIGHT(s) wf.pend[2u * (s) + 1u]
 // The random-sequence counter every path holds after its camera ray (camera_ray draws once): the state of a path at its FIRST vertex is a
 // constant -- L = 0, beta = 1, pdf = 0, throughput = 1, rc = kRcAfterCamera, nothing pending -- so the generate stage writes no state and
-// the first shade stage reads none (PT_FIRST_VERTEX_STATELESS).
+// the first shade stage reads none.
 constexpr int kRcAfterCamera = 1;
 // The shade stage is bound by the divergent vector-memory instructions it issues (tools/pmc_shade_attribution.sh: taking the radiance /
 // pending records away -- 3 loads, 3 stores, 13 % of its fabric bytes -- made it 10 % faster).  beta / throughput are read by exactly one
-// consumer, the shade stage of the next vertex, which already reads the path's queue entry: with PT_BT_IN_QUEUE they ride in two more
-// arrays parallel to the closest-ray queue (coalesced both ways) instead of two slot-indexed arrays (a divergent load and store each).
-#ifndef PT_BT_IN_QUEUE
-#define PT_BT_IN_QUEUE 1
-#endif
-#ifndef PT_FIRST_VERTEX_STATELESS
-#define PT_FIRST_VERTEX_STATELESS 1
-#endif
+// consumer, the shade stage of the next vertex, which already reads the path's queue entry: they ride in two more arrays parallel to the
+// closest-ray queue (q_beta / q_thr, coalesced both ways) instead of two slot-indexed arrays (a divergent load and store each).
 
 // wave64 ballot compaction into a shard counter: lanes with `pred` get consecutive indices; one atomic per wave.
 PT_DEV uint32_t queue_push(uint32_t* counter, bool pred) {
@@ -179,19 +132,10 @@ PT_DEV ShardView shard_view(const WfBuffers& wf) {
 
 // Which pixel tiles a workgroup generates.  Workgroups are dispatched to the eight XCDs round-robin (XCD = blockIdx % 8), every later
 // stage launch has the same grid, and shard s = blockIdx % kShards is only ever touched by workgroups with blockIdx % 8 == s % 8:
-// a path lives its whole life on ONE XCD.  Each XCD has its own 4-MiB L2, and the scene (BVH + packets, tens of MB) fits none of
-// them.  PT_GEN_XCD_BANDS = 1 / 2 gives each XCD a CONTIGUOUS range of this rank's tiles (a row band / a column band of the
-// screen), so that its primary rays, their shadow rays and most first bounces walk one part of the scene and its L2 holds that part
-// instead of a 1/8 sample of everything.  Within the band, consecutive workgroups of the XCD take consecutive (tile, sample)
-// pairs.  Slots keep their meaning (slot = sample * pixel_slots + tile * 256 + lane), only the workgroup that generates a slot
-// changes: images are bit-identical (tested).  MEASURED: both band shapes are 3-4 % SLOWER than dealing tiles round-robin over all
-// workgroups (the default, 0): a path never leaves its XCD, so the XCD whose band holds the expensive part of the picture finishes
-// last while the others idle, and that costs more than the locality buys.  Kept as a build option for the record.
+// a path lives its whole life on ONE XCD.  Tiles are dealt round-robin over all workgroups, so every XCD sees the whole screen: giving
+// each XCD a contiguous band of tiles was slower, because the XCD whose band holds the expensive part of the picture finishes last
+// while the others idle (profiles/EXPERIMENTS.md).
 constexpr uint32_t kXcds = 8;
-#ifndef PT_GEN_XCD_BANDS
-#define PT_GEN_XCD_BANDS 0      // measured on MI355X (Sponza-class 1080p, 8 spp / launch): 0 (tiles dealt round-robin) 4473 Mrays/s,
-                                // 1 (row bands) 4339, 2 (column bands) 4274 -- see the comment above and DESIGN.md section 4
-#endif
 // Adaptive sampling (pt_set_adaptive): is the tile of a workgroup-round's (tile, sample) pair still active?  `slot0` = the round's first
 // slot (workgroup-uniform), so the state is read once per round; a retired tile pushes no ray and every later stage is unchanged.
 PT_DEV bool adaptive_tile_active(const FrameConstants& fc, const AdaptiveArgs& ad, uint32_t slot0) {
@@ -206,38 +150,21 @@ template <bool ADAPTIVE, bool LENS>
 __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, LensArgs lens) {
     if (!LENS) lens.enable = 0;
     const ShardView sv = shard_view(wf);
-    const uint32_t per_xcd = gridDim.x / kXcds;                       // the grid is a multiple of kShards, kShards of kXcds
+    // DEAD: the next four lines are left from the rejected per-XCD tile bands; nothing below reads them (gen_region_tiles is always 0).
+    // They stay because removing them changes k_wf_generate's code generation (operand order of three scalar multiplies), which puts the
+    // removal under the measurement rule of profiles/EXPERIMENTS.md ("The rejected compile-time alternatives removed": step 2).
+    const uint32_t per_xcd = gridDim.x / kXcds;
     const uint32_t xcd = blockIdx.x % kXcds, member = blockIdx.x / kXcds;
     uint32_t first_tile = xcd * wf.gen_region_tiles;
     uint32_t n_tiles = first_tile < fc.my_tiles ? min(wf.gen_region_tiles, fc.my_tiles - first_tile) : 0u;
-#if PT_GEN_XCD_BANDS == 2
-    // column bands (whole frames only; a tile shard of a frame keeps the ranges of its own tile list): XCD x owns the tile columns
-    // [c0, c1) over all rows -- every band holds sky, walls and floor alike, so the eight XCDs finish together
-    const bool columns = fc.tile_rank_count == 1;
-    const uint32_t c0 = xcd * fc.tiles_x / kXcds, band_w = (xcd + 1u) * fc.tiles_x / kXcds - c0;
-    if (columns) n_tiles = band_w * fc.tiles_y;
-#endif
     unsigned n_primary = 0;
     for (uint32_t rnd = 0; rnd < wf.gen_rounds; rnd++) {
         // a workgroup-round is one 16x16 tile of one sample: primary rays stay coherent per wave (8x8 quadrant)
-#if PT_GEN_XCD_BANDS
-        const uint32_t q = rnd * per_xcd + member;
-        const uint32_t tile_in_region = q / fc.spp, sample = q - tile_in_region * fc.spp;
-        uint32_t tile = first_tile + tile_in_region;
-#if PT_GEN_XCD_BANDS == 2
-        if (columns) { const uint32_t brow = band_w ? tile_in_region / band_w : 0u; tile = brow * fc.tiles_x + c0 + (tile_in_region - brow * band_w); }
-#endif
-        const uint32_t slot = sample * fc.pixel_slots + tile * kBlock + threadIdx.x;
-        uint32_t px = 0, py = 0;
-        bool valid = tile_in_region < n_tiles && slot_pixel(fc, slot, px, py);
-        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, sample * fc.pixel_slots + tile * kBlock); valid = valid && tile_on; }
-#else       // A/B: tiles dealt round-robin over all workgroups (every XCD sees the whole screen); rounds are sized for either
         const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
         const uint32_t sample = slot_sample(fc, slot);
         uint32_t px = 0, py = 0;
         bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
         if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
-#endif
         int rc = 0;
         Ray ray;
         ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
@@ -247,16 +174,6 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
             const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
             QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
             QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
-#if !PT_FIRST_VERTEX_STATELESS
-            SST(wf.L[SIDX(slot)], make_float4(0, 0, 0, 0));
-#if PT_BT_IN_QUEUE
-            QST(wf.q_beta[0][e], make_float4(1, 1, 1, 0));
-            QST(wf.q_thr[0][e], make_float4(1, 1, 1, __uint_as_float((uint32_t)rc)));
-#else
-            SST(wf.beta_pdf[SIDX(slot)], make_float4(1, 1, 1, 0));
-            SST(wf.thr_misc[SIDX(slot)], make_float4(1, 1, 1, __uint_as_float((uint32_t)rc)));
-#endif
-#endif
             n_primary++;
         }
     }
@@ -272,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
 PT_DEV int shadow_counter(int bounce) { return (bounce & 1) ? 5 : 2; }
 template <bool COUNT, int MODE>
 PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_stack, const ShardView& sv, int cur, uint32_t rf_closest, uint32_t rmask,
-                             uint32_t flags, LaneStats& st, float shadow_tmax = 0.0f, bool use_occ_cache = false) {
+                             uint32_t flags, LaneStats& st, float shadow_tmax = 0.0f) {
     // MODE 0: `cur` = closest queue (0 / 1).  MODE 1: `cur` = index of the shadow-queue counter (shadow_counter(bounce)).
     const uint32_t n = wf.cnt[cur][sv.shard * kCounterStride];
     uint32_t* head = wf.cnt[MODE == 0 ? 3 : 4] + sv.shard * kCounterStride;
@@ -282,7 +199,7 @@ PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_st
     Trav t;
     t.cur = kTravDone; t.sp = 0;
     bool has = false, exhausted = (n == 0);
-    uint32_t entry = 0, slot_bits = 0, occ_at = kNoHint;
+    uint32_t entry = 0, slot_bits = 0;
 #ifdef PT_UTIL_PROBE
     unsigned long long u_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // wave-level: [0] node iterations [1] lanes stepping [2] leaf iterations [3] lanes testing [4] refills [5] lanes refilled [6] lanes holding a ray, summed over node iterations
 #endif
@@ -312,16 +229,6 @@ PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_st
                         uint32_t srf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_BACK : 0;
                         srf |= alpha_shadow ? RF_FORCE_NON_OPAQUE : RF_ACCEPT_FIRST;
                         trav_init(t, sc, ray, srf, 0xff, 1, alpha_shadow ? 1.0f : 0.0f);
-#if PT_OCC_CACHE
-                        // occluder cache: an accept-first ray whose pixel remembers an occluder tests that triangle FIRST -- as a one-triangle leaf,
-                        // with the root waiting on the stack -- and ends there if it still occludes
-                        occ_at = kNoHint;
-                        if (use_occ_cache) {
-                            const uint32_t hint = __float_as_uint(d.w);
-                            occ_at = alpha_shadow ? kNoHint : QLD(wf.sh_c[base + i]);
-                            if (occ_at != kNoHint && hint < sc.num_tris && hint < kLeafFirstMask && t.cur >= 0) { my_stack[0] = t.cur; t.sp = 1; t.cur = ~(int)hint; }
-                        }
-#endif
                     }
                     entry = i;
                     has = true;
@@ -338,48 +245,18 @@ PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_st
 #define PT_NODE_MIN 16        // (swept 4..32 at 8 samples per launch: 16) leave the node phase early when fewer lanes than this hold an inner node AND some lane waits at a leaf
                               // (swept 1/4/8/12/16/32 on MI355X: 2195/2326/2359/2360/2356/2294 Mrays/s)
 #endif
-#ifndef PT_POSTPONE_LEAF
-#define PT_POSTPONE_LEAF 0    // 1: a lane that reaches a leaf while others still step nodes sets the leaf aside and goes on with its next stack entry.
-                              // MEASURED (round 3, bit-identical images): lanes stepping per node iteration 42.6 -> 44.5 of 64, but 25 % more node
-                              // visits (12.6 -> 15.8 per ray; occlusion rays +36 %: the postponed leaf is usually the hit that ends them) --
-                              // traversal 13.9 -> 16.1 ms per 8-spp launch.  Off; kept as a build option for the record.
-#endif
         for (;;) {
-#if PT_POSTPONE_LEAF
-            // Speculative traversal (Aila & Laine): a third of the lanes of a node iteration used to sit at a leaf, waiting for the wave's leaf
-            // phase (tools/util_probe.py: 42.6 of 59 lanes stepping).  Such a lane now POSTPONES its leaf -- one at a time, and only if its
-            // stack holds something to go on with -- and keeps stepping; the leaf phase tests the postponed leaf FIRST, so triangles are
-            // tested in the order they were reached and every ray finds the hit it found before.  The node steps taken meanwhile used the
-            // older, longer interval: a superset of the nodes, never a different hit.
-            if (has && t.cur < 0 && t.cur != kTravDone && t.post == kTravDone && t.sp > 0) { t.post = t.cur; trav_pop(t, sc, my_stack, spill); }
-#endif
             const unsigned long long at_node = __ballot(has && t.cur >= 0);
             if (at_node == 0) break;
-            if (PT_NODE_MIN > 1 && (int)__popcll(at_node) < PT_NODE_MIN && __ballot(has && t.cur < 0 && (t.cur != kTravDone || t.post != kTravDone)) != 0) break;
+            if (PT_NODE_MIN > 1 && (int)__popcll(at_node) < PT_NODE_MIN && __ballot(has && t.cur < 0 && t.cur != kTravDone) != 0) break;
             PT_UTIL(0, 1); PT_UTIL(1, __popcll(at_node)); PT_UTIL(6, __popcll(__ballot(has)));
             if (has && t.cur >= 0) trav_node_step<COUNT, MODE == 0>(t, sc, my_stack, spill, st);
         }
         // ---- leaf phase
 #ifdef PT_UTIL_PROBE
-        { const unsigned long long at_leaf = __ballot(has && ((t.cur != kTravDone && t.cur < 0) || t.post != kTravDone)); if (at_leaf) { PT_UTIL(2, 1); PT_UTIL(3, __popcll(at_leaf)); } }
+        { const unsigned long long at_leaf = __ballot(has && t.cur != kTravDone && t.cur < 0); if (at_leaf) { PT_UTIL(2, 1); PT_UTIL(3, __popcll(at_leaf)); } }
 #endif
-#if PT_POSTPONE_LEAF
-        // the postponed leaf first (the lane then goes on with the entry it had moved on to, unless the ray ended there), then the leaf the
-        // lane stands at: ONE copy of the leaf code, run at most twice
-#pragma nounroll
-        for (int pass = 0; pass < 2; pass++) {
-            const bool first_pass = pass == 0;
-            const bool mine = has && (first_pass ? t.post != kTravDone : (t.cur != kTravDone && t.cur < 0));
-            if (!__any(mine)) continue;
-            if (mine) {
-                const int keep = t.cur;
-                if (first_pass) { t.cur = t.post; t.post = kTravDone; }
-                trav_leaf_step<COUNT>(t, sc, my_stack, spill, st, first_pass, keep);
-            }
-        }
-#else
         if (has && t.cur != kTravDone && t.cur < 0) trav_leaf_step<COUNT>(t, sc, my_stack, spill, st);
-#endif
         // ---- retire finished rays
         if (has && t.cur == kTravDone) {
             if (MODE == 0) {
@@ -388,9 +265,6 @@ PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_st
             } else {
                 const float tr = t.committed ? t.transmission : 1.0f;                                              // ShadowMiss :1081-1085
                 const uint32_t slot = slot_bits & 0x7fffffffu;
-#if PT_OCC_CACHE
-                if (use_occ_cache && occ_at != kNoHint && t.committed) wf.occ_cache[occ_at] = (uint32_t)t.best.tri;   // remember the occluder
-#endif
                 float* w = (slot_bits >> 31) ? &PEND_LIGHT(slot).w : &PEND_ENV(slot).w;
                 *w = tr;
             }
@@ -414,12 +288,8 @@ PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_st
 // much here as there (+0.8 % overall, and 17 KB of LDS a shade workgroup no longer needs).  Handing the samples to dedicated workgroups
 // prepended to the traversal launch (1-3 per shard), so that their arithmetic would fill the issue slots of the memory-bound traversal
 // waves beside them, was slower still (traversal 14.9-15.0 ms): those slots are not idle.
-#ifndef PT_ENV_PREPASS
-#define PT_ENV_PREPASS 1
-#endif
-
 PT_DEV bool env_prepass_wanted(const SceneRec& sc, const FrameConstants& fc, int vertex_bounce) {
-    return PT_ENV_PREPASS && sc.has_env && (fc.flags & PT_FLAG_ENVIRONMENT_MAP) && (fc.flags & PT_FLAG_ENVIRONMENT_MIS) && vertex_bounce < fc.max_bounces;
+    return sc.has_env && (fc.flags & PT_FLAG_ENVIRONMENT_MAP) && (fc.flags & PT_FLAG_ENVIRONMENT_MIS) && vertex_bounce < fc.max_bounces;
 }
 PT_DEV void env_prepass(const SceneRec& sc, const FrameConstants& fc, const WfBuffers& wf, int* stack_lds, const ShardView& sv, int cur, bool first_vertex) {
     static_assert((size_t)kStackLds * kBlock * sizeof(int) >= (size_t)kImpLdsFloat4 * sizeof(float4), "the traversal stack's LDS must hold the importance pyramid's coarse levels");
@@ -430,11 +300,7 @@ PT_DEV void env_prepass(const SceneRec& sc, const FrameConstants& fc, const WfBu
     for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
         const uint32_t slot = QLD(*((const uint32_t*)&wf.ray_d[cur][base + i] + 3));
         int rc = kRcAfterCamera;
-#if PT_BT_IN_QUEUE
-        if (!(PT_FIRST_VERTEX_STATELESS && first_vertex)) rc = (int)(QLD(*((const uint32_t*)&wf.q_thr[cur][base + i] + 3)) & 0xffffu);
-#else
-        if (!(PT_FIRST_VERTEX_STATELESS && first_vertex)) rc = (int)(SLD(*((const uint32_t*)&wf.thr_misc[SIDX(slot)] + 3)) & 0xffffu);
-#endif
+        if (!first_vertex) rc = (int)(QLD(*((const uint32_t*)&wf.q_thr[cur][base + i] + 3)) & 0xffffu);
         uint32_t px, py;
         slot_pixel(fc, slot, px, py);
         const vec4 r = next_random(px, py, sample_seed(fc, slot_sample(fc, slot)), rc);
@@ -448,20 +314,11 @@ PT_DEV void env_prepass(const SceneRec& sc, const FrameConstants& fc, const WfBu
 #ifndef PT_TRACE_WAVES
 #define PT_TRACE_WAVES 1
 #endif
-#ifndef PT_LATE_GRID
-#define PT_LATE_GRID 1        // smaller stage grids for the thin late bounces (launch_wavefront)
-#endif
-#ifndef PT_FUSE_TRAVERSAL
-#define PT_FUSE_TRAVERSAL 1   // the shadow rays of a bounce and the closest-hit rays of the next in one launch (k_wf_traverse)
-#endif
 // `bounce` = the bounce whose shade stage follows: it fills closest queue cur ^ 1 and the shadow counter of that bounce.
 // DEFAULTS (k_wf_trace, k_wf_traverse): a copy compiled for the settings that leave the rays' flags alone -- no back-face culling, no alpha
 // shadows, no indirect-environment-only mask (the application's defaults): ray flags 0, mask 0xff and an accept-first shadow search as
 // constants take the other searches' code out of the loop (13.87 against 14.04 ms of traversal per launch).  launch_wavefront picks it.
 constexpr uint32_t kTravFlagMask = PT_FLAG_CULL_BACKFACE | PT_FLAG_ALPHA_SHADOWS | PT_FLAG_INDIRECT_ENVIRONMENT_ONLY;
-#ifndef PT_TRAV_SPECIALISE
-#define PT_TRAV_SPECIALISE 1
-#endif
 template <bool COUNT, bool DEFAULTS>
 __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_trace(SceneRec sc, FrameConstants fc, WfBuffers wf, int cur, int bounce, uint32_t rf, uint32_t rmask, Counters* __restrict__ counters) {
     if (DEFAULTS) { rf = 0; rmask = 0xff; }
@@ -492,7 +349,7 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_traverse(SceneRec
     if (env_prepass_wanted(sc, fc, bounce + 1)) env_prepass(sc, fc, wf, s_stack, sv, nxt, false);
     if (sv.member == 0 && threadIdx.x == 0) { wf.cnt[nxt ^ 1][sv.shard * kCounterStride] = 0; wf.cnt[shadow_counter(bounce + 1)][sv.shard * kCounterStride] = 0; wf.cnt[6][sv.shard * kCounterStride] = 0; }
     LaneStats st_shadow = {0, 0, 0, 0}, st = {0, 0, 0, 0};
-    trace_persistent<COUNT, 1>(sc, wf, s_stack + threadIdx.x, sv, shadow_counter(bounce), 0, 0xff, flags, st_shadow, fc.max_ray_length, wf.occ_cache != nullptr && bounce == 0);
+    trace_persistent<COUNT, 1>(sc, wf, s_stack + threadIdx.x, sv, shadow_counter(bounce), 0, 0xff, flags, st_shadow, fc.max_ray_length);
     trace_persistent<COUNT, 0>(sc, wf, s_stack + threadIdx.x, sv, nxt, rf, rmask, 0, st);
     if (COUNT) {
         flush_counters(counters, threadIdx.x & 63, 0, 0, 0, 0, st_shadow, true); flush_counters(counters, threadIdx.x & 63, 0, 0, 0, 0, st);
@@ -506,44 +363,16 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_traverse(SceneRec
 // the flags first and the records behind them.
 // `pf` = the pending bits that travel in L.w.
 PT_DEV void apply_pending(const WfBuffers& wf, uint32_t slot, uint32_t pf, vec3& L) {
-    const float4 pe = SLD(PEND_ENV(slot)), pl = SLD(PEND_LIGHT(slot));
+    const float4 pe = PEND_ENV(slot), pl = PEND_LIGHT(slot);
     if ((pf & 1u) && pe.w > 0.0f) L += v3(pe.x, pe.y, pe.z) * pe.w;
     if ((pf & 2u) && pl.w > 0.0f) L += v3(pl.x, pl.y, pl.z) * pl.w;
 }
 
-// Material features whose hits the shade stage sets aside and shades together (k_wf_shade): 1 sheen, 2 clearcoat, 4 transmission, 8 anisotropy;
-// 0 (the default): none, the code is not compiled in.  MEASURED with 1 (sheen) on the bench scene, where 3 % of the hits put a sheen lane into
-// nearly every wave: shade stage 9.06 -> 8.80 ms per 8-sample launch (+1 % rays/s), but a single-sample launch 4.00 -> 4.05 ms (a wave rarely
-// collects enough notes before its queue ends, and the last iteration over the few it has is an iteration more), the material grid -1 %
-// (a sixth of its hits are sheen: the extra iterations cost more than the shared code saves) and a scene without sheen -0.8 % (the test
-// itself).  The noted hits cost a full iteration per 60 while the lanes they left idle shorten nothing, which eats most of what the
-// shared lobe code saves.  Enabled per scene by the host (FrameConstants::defer_rare) when compiled in.  profiles/EXPERIMENTS.md.
-#ifndef PT_DEFER_FEATURES
-#define PT_DEFER_FEATURES 0
-#endif
-#ifndef PT_DEFER_FLUSH
-#define PT_DEFER_FLUSH 60
-#endif
-#ifndef PT_DEFER_MAJORITY
-#define PT_DEFER_MAJORITY 4
-#endif
+// Constants of the dead set-aside scaffolding in k_wf_shade (see the comment there): "no note held", notes in a wave that triggered the
+// iteration over them, rare hits in a chunk from which it was shaded in place.
 constexpr uint32_t kNoHeld = 0xffffffffu;
-constexpr int kDeferFlush = PT_DEFER_FLUSH;        // notes in a wave that trigger the iteration over them
-constexpr uint32_t kDeferMajority = PT_DEFER_MAJORITY; // a chunk with this many rare hits is shaded in place
-PT_DEV bool material_is_rare(const SceneRec& sc, uint32_t inst_id) {
-    const ShadeInst inst = load_shade_inst(sc, inst_id);
-    const MatHeader mh = material_header(sc, inst.material_id);
-    bool rare = false;
-    if (PT_DEFER_FEATURES & 1) rare = rare || mh.sheen_color_factor.x != 0.0f || mh.sheen_color_factor.y != 0.0f || mh.sheen_color_factor.z != 0.0f;
-    if (PT_DEFER_FEATURES & 2) rare = rare || mh.clearcoat_factor != 0.0f;
-    if (PT_DEFER_FEATURES & 4) rare = rare || mh.transmission_factor != 0.0f;
-    if (PT_DEFER_FEATURES & 8) rare = rare || mh.anisotropy_strength != 0.0f;
-    return rare;
-}
-
-#ifndef PT_SHADE_DYNAMIC
-#define PT_SHADE_DYNAMIC 1    // shade-stage waves pull 64-entry chunks from the shard's head counter (0: static rounds over the grid's stride)
-#endif
+constexpr int kDeferFlush = 60;
+constexpr uint32_t kDeferMajority = 4;
 #ifndef PT_SHADE_WAVES
 #define PT_SHADE_WAVES 2      // waves per SIMD the register allocator must leave room for (2 -> <= 256 VGPR+AGPR)
 #endif
@@ -557,9 +386,6 @@ constexpr uint32_t kShadeFlagMask = PT_FLAG_MATERIAL_DIFFUSE_WHITE | PT_FLAG_MAT
 constexpr uint32_t kShadeSpecialised = 0x80000000u;          // marks a non-zero SPECIAL (a flag set could be 0)
 constexpr uint32_t kShadeDefaultsNoLights = PT_FLAG_SHADOW_RAYS | PT_FLAG_ENVIRONMENT_MAP | PT_FLAG_ENVIRONMENT_MIS | PT_FLAG_MATERIAL_MIS | PT_FLAG_SHADING_NORMAL_ADAPTATION;
 constexpr uint32_t kShadeDefaults = kShadeDefaultsNoLights | PT_FLAG_POINT_LIGHTS;
-#ifndef PT_SHADE_SPECIALISE
-#define PT_SHADE_SPECIALISE 1
-#endif
 // SMALL: the scene's instance rows, materials and lights all fit the LDS copies (<= 128 / 96 / 32: every BASELINE config): as a constant this
 // removes the global-memory branch of every table lookup (shade stage 8.70 -> 8.52 ms per launch).
 template <uint32_t SPECIAL, bool SMALL>
@@ -574,9 +400,6 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     }
     stage_luts(sc);
     stage_tangent_lut(sc);
-#if !PT_ENV_PREPASS
-    stage_importance_top(sc);
-#endif
     stage_lights(sc, fc.num_of_lights);
     stage_instances(sc);
     stage_materials(sc);
@@ -590,7 +413,6 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     if (sv.member == 0 && threadIdx.x == 0) { wf.cnt[3][sv.shard * kCounterStride] = 0; wf.cnt[4][sv.shard * kCounterStride] = 0; }
     unsigned n_bounce = 0, n_shadow = 0, n_hits = 0;
     LaneStats st = {0, 0, 0, 0};
-#if PT_SHADE_DYNAMIC
     // Every WAVE pulls the next 64 entries of its shard's queue from the shard's head counter (one atomic per wave and chunk, the next
     // chunk requested before the current one is shaded, so its round trip is hidden).  Hits differ in cost and a queue is rarely a
     // multiple of the grid's stride: with static rounds a launch ran as long as the workgroups that had one chunk more (a 1-spp
@@ -600,13 +422,13 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     uint32_t chunk = 0;
     if (lane64 == 0) chunk = atomicAdd(shade_head, 64u);
     chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);
-    // Hits on RARE materials (PT_DEFER_FEATURES: sheen, ...) are set aside and shaded together.  A wave executes a lobe's code if ONE of its
-    // lanes needs it, and 3 % of the bench scene's hits (its curtains) put a sheen lane into nearly every wave: the lobe's ~600 instructions
-    // a hit ran in almost every wave with two or three lanes active.  Instead, a lane that meets a rare hit only notes the queue entry
-    // (`held`: one note per lane, handed to any free lane of the wave through LDS so that the notes pack densely) and does not shade it;
-    // once most lanes hold a note -- or the queue is empty -- the wave shades the noted entries in one iteration, all lanes in the rare
-    // code together.  Only the order of the follow-up queues changes: images are bit-identical (tools/compare_builds.py).
-    const bool defer_on = PT_DEFER_FEATURES != 0 && fc.defer_rare != 0;
+    // DEAD CODE, kept on purpose: `defer_on`, `held`, `flush`, `s_hand` and `set_aside` are what is left of an experiment that set hits on
+    // rare materials (sheen) aside and shaded them together, a wave's notes packed onto free lanes through LDS.  It was measured and
+    // rejected, and its switch is gone: defer_on is false, so flush and set_aside are always false, held is always kNoHeld, and the block
+    // under "2." below never runs.  The variables stay only because k_wf_shade sits at its register limit and taking them out changes its
+    // code generation; that removal was measured too and fell below the parent's range (profiles/EXPERIMENTS.md, "The rejected
+    // compile-time alternatives removed": step 2).  Read the loop as: every wave shades chunk after chunk until its shard's queue is empty.
+    const bool defer_on = false;
     uint32_t held = kNoHeld;
     __shared__ uint32_t s_hand[kBlock];                              // the hand-over slots, 64 per wave
     uint32_t* hand = s_hand + (threadIdx.x & ~63u);
@@ -620,16 +442,7 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         const uint32_t i = flush ? held : chunk + lane64;
         const bool active = flush ? held != kNoHeld : i < n;
         if (flush) held = kNoHeld;
-#else
-    const bool flush = true;                                          // (no setting aside in this mode)
-    const unsigned long long held_mask = 0; uint32_t held = kNoHeld; uint32_t* hand = nullptr; const uint32_t lane64 = threadIdx.x & 63u;
-    const uint32_t rounds = (n + sv.stride - 1) / sv.stride;      // uniform per workgroup: ballots inside stay wave-uniform
-    for (uint32_t rnd = 0; rnd < rounds; rnd++) {
-        const uint32_t i = rnd * sv.stride + sv.member * kBlock + threadIdx.x;
-        const bool active = i < n;
-#endif
         bool push_env = false, push_light = false, push_bounce = false;
-        uint32_t occ_pixel = kNoHint;                       // first-vertex hits: the pixel's row of the occluder cache
         Followups fu;
         fu.q_env = fu.q_light = fu.q_bounce = false;
         uint32_t slot = 0;
@@ -640,21 +453,17 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         uint32_t hb = kMissTri;
         const ShadePacket* packet_at = sc.shade;
         RawPacket packet;
-#if PT_ENV_PREPASS
         EnvSample es;
         es.dir = v3(0, 0, 1); es.pdf = 1; es.color = v3(0);
-#endif
-        const bool with_state = !(PT_FIRST_VERTEX_STATELESS && bounce == 0);          // (wave-uniform: `bounce` is a kernel argument)
+        const bool with_state = bounce != 0;          // (wave-uniform: `bounce` is a kernel argument)
         if (active) {
             o = QLD(wf.ray_o[cur][base + i]); d = QLD(wf.ray_d[cur][base + i]); h = QLD(wf.hit[base + i]);
-#if PT_ENV_PREPASS
             // the vertex's environment light sample, drawn by the traversal stage (env_prepass); without an environment the sample is
             // the constant the in-place code produces.  Fetched with the entry whether or not this vertex will use it: no extra round trip.
             if (env_prepass_wanted(sc, fc, bounce)) {
                 const float4 ea = QLD(wf.env_a[base + i]), eb = QLD(wf.env_b[base + i]);
                 es.dir = v3(ea.x, ea.y, ea.z); es.pdf = ea.w; es.color = v3(eb.x, eb.y, eb.z);
             }
-#endif
             slot = __float_as_uint(d.w);
             // the hit's shading packet depends on the queue entry only, like the path state below: one round trip for both
             hb = __float_as_uint(h.w);
@@ -665,21 +474,16 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
 #endif
             packet = load_shade_packet_raw(packet_at);
             if (with_state) {
-#if PT_BT_IN_QUEUE
                 bp = QLD(wf.q_beta[cur][base + i]); tm = QLD(wf.q_thr[cur][base + i]);
-#else
-                bp = SLD(wf.beta_pdf[SIDX(slot)]); tm = SLD(wf.thr_misc[SIDX(slot)]);
-#endif
 #ifndef PT_PROBE_NO_LP        // PROBE ONLY: the radiance and pending-term records are neither read nor written -- black image, same paths: what that class of state costs
-                Lq = SLD(wf.L[SIDX(slot)]); pe = SLD(PEND_ENV(slot)); pl = SLD(PEND_LIGHT(slot));
+                Lq = wf.L[slot]; pe = PEND_ENV(slot); pl = PEND_LIGHT(slot);
 #endif
             }
         }
-        // ---- 2. rare hits are set aside (wave-uniform control flow)
+        // ---- 2. (dead: defer_on is false; the rejected set-aside of rare hits, kept for k_wf_shade's code generation -- see above)
         bool set_aside = false;
-#if PT_SHADE_DYNAMIC
         if (defer_on && !flush) {
-            const bool rare = active && hb != kMissTri && material_is_rare(sc, raw_packet_inst(packet));
+            const bool rare = false;                              // (was: the hit's material has a rare feature)
             const unsigned long long R = __ballot(rare), F = ~held_mask;
             const uint32_t nR = (uint32_t)__popcll(R), nF = (uint32_t)__popcll(F);
             if (nR != 0 && nR < kDeferMajority) {                 // (a chunk made mostly of rare hits is shaded as it is: nothing to gain)
@@ -692,7 +496,6 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
                 if (held == kNoHeld && rf < min(nR, nF)) held = hand[rf];
             }
         }
-#endif
         // ---- 3. shade
         if (active && !set_aside) {
             Ray ray;
@@ -718,58 +521,33 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
                 uint32_t px, py;
                 slot_pixel(fc, slot, px, py);
                 n_hits++;
-#if PT_OCC_CACHE
-                if (bounce == 0 && wf.occ_cache) occ_pixel = (py * fc.res_x + px) * 8u;
-                const uint32_t* occ_row = occ_pixel != kNoHint ? wf.occ_cache + occ_pixel : nullptr;
-#else
-                const uint32_t* occ_row = nullptr;
-#endif
-#if PT_ENV_PREPASS
-                const bool done = shade_closest_hit<true>(sc, fc, sample_seed(fc, slot_sample(fc, slot)), px, py, ray, hit, packet, packet_at, ps, fu, st.taps, &es, occ_row);
-#else
-                const bool done = shade_closest_hit(sc, fc, sample_seed(fc, slot_sample(fc, slot)), px, py, ray, hit, packet, packet_at, ps, fu, st.taps, nullptr, occ_row);
-#endif
+                const bool done = shade_closest_hit<true>(sc, fc, sample_seed(fc, slot_sample(fc, slot)), px, py, ray, hit, packet, packet_at, ps, fu, st.taps, &es);
                 if (fu.overwrite) L = v3(0);
                 L += fu.add;
                 n_shadow += fu.counted_shadow;
                 if (!done) {
                     push_env = fu.q_env; push_light = fu.q_light; push_bounce = fu.q_bounce;
 #ifndef PT_PROBE_NO_LP
-                    if (push_env) { pf |= 1u; SST(PEND_ENV(slot), make_float4(fu.pend_env.x, fu.pend_env.y, fu.pend_env.z, 0.0f)); }
-                    if (push_light) { pf |= 2u; SST(PEND_LIGHT(slot), make_float4(fu.pend_light.x, fu.pend_light.y, fu.pend_light.z, 0.0f)); }
+                    if (push_env) { pf |= 1u; PEND_ENV(slot) = make_float4(fu.pend_env.x, fu.pend_env.y, fu.pend_env.z, 0.0f); }
+                    if (push_light) { pf |= 2u; PEND_LIGHT(slot) = make_float4(fu.pend_light.x, fu.pend_light.y, fu.pend_light.z, 0.0f); }
 #endif
                 }
             }
 #ifndef PT_PROBE_NO_LP
-            SST(wf.L[SIDX(slot)], make_float4(L.x, L.y, L.z, __uint_as_float(pf)));
+            wf.L[slot] = make_float4(L.x, L.y, L.z, __uint_as_float(pf));
 #endif
         }
         // ---- compaction into this shard's shadow segment and next closest-ray segment (wave-uniform control flow)
-        // occluder hints of a first-vertex hit's two shadow rays: both cache words of the pixel fetched together (a wave's pixels are an 8x8 block:
-        // eight 256-B runs), only by the stage that shades first vertices
-        uint32_t at_env = kNoHint, at_light = kNoHint, hint_env = kNoHint, hint_light = kNoHint;
-#if PT_OCC_CACHE
-        if (bounce == 0 && occ_pixel != kNoHint) {         // (the two cache words were fetched inside shade_closest_hit, well before this point)
-            at_env = occ_pixel; at_light = occ_pixel + 1u + fu.light_index % 7u;
-            hint_env = fu.hint_env; hint_light = fu.hint_light;
-        }
-#endif
         const uint32_t ie = queue_push(cnt_shadow, push_env);
         if (push_env) {
             QST(wf.sh_o[sbase + ie], make_float4(fu.origin_above.x, fu.origin_above.y, fu.origin_above.z, __uint_as_float(slot)));
-            QST(wf.sh_d[sbase + ie], make_float4(fu.env_dir.x, fu.env_dir.y, fu.env_dir.z, __uint_as_float(hint_env)));
-#if PT_OCC_CACHE
-            if (bounce == 0 && wf.occ_cache) QST(wf.sh_c[sbase + ie], at_env);
-#endif
+            QST(wf.sh_d[sbase + ie], make_float4(fu.env_dir.x, fu.env_dir.y, fu.env_dir.z, __uint_as_float(kNoHint)));
             n_shadow++;
         }
         const uint32_t il = queue_push(cnt_shadow, push_light);
         if (push_light) {
             QST(wf.sh_o[sbase + il], make_float4(fu.origin_above.x, fu.origin_above.y, fu.origin_above.z, __uint_as_float(slot | 0x80000000u)));
-            QST(wf.sh_d[sbase + il], make_float4(fu.light_dir.x, fu.light_dir.y, fu.light_dir.z, __uint_as_float(hint_light)));
-#if PT_OCC_CACHE
-            if (bounce == 0 && wf.occ_cache) QST(wf.sh_c[sbase + il], at_light);
-#endif
+            QST(wf.sh_d[sbase + il], make_float4(fu.light_dir.x, fu.light_dir.y, fu.light_dir.z, __uint_as_float(kNoHint)));
             n_shadow++;
         }
         const uint32_t ib = queue_push(cnt_next, push_bounce);
@@ -777,18 +555,11 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
             QST(wf.ray_o[nxt][base + ib], make_float4(fu.b_o.x, fu.b_o.y, fu.b_o.z, fc.max_ray_length));
             QST(wf.ray_d[nxt][base + ib], make_float4(fu.b_d.x, fu.b_d.y, fu.b_d.z, __uint_as_float(slot)));
             const uint32_t misc = ((uint32_t)ps.rc & 0xffffu) | ((uint32_t)(ps.bounce + 1) << 16) | (fu.b_mis ? 0x80000000u : 0u);
-#if PT_BT_IN_QUEUE
             QST(wf.q_beta[nxt][base + ib], make_float4(fu.b_beta.x, fu.b_beta.y, fu.b_beta.z, fu.b_pdf));
             QST(wf.q_thr[nxt][base + ib], make_float4(fu.b_thr.x, fu.b_thr.y, fu.b_thr.z, __uint_as_float(misc)));
-#else
-            SST(wf.beta_pdf[SIDX(slot)], make_float4(fu.b_beta.x, fu.b_beta.y, fu.b_beta.z, fu.b_pdf));
-            SST(wf.thr_misc[SIDX(slot)], make_float4(fu.b_thr.x, fu.b_thr.y, fu.b_thr.z, __uint_as_float(misc)));
-#endif
             n_bounce++;
         }
-#if PT_SHADE_DYNAMIC
         if (!flush) chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_chunk);
-#endif
     }
     flush_counters(counters, threadIdx.x & 63, 0, n_bounce, n_shadow, n_hits, st);
 }
@@ -800,7 +571,7 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_shadow(SceneRec s
     stage_luts(sc);
     const ShardView sv = shard_view(wf);
     LaneStats st = {0, 0, 0, 0};
-    trace_persistent<COUNT, 1>(sc, wf, s_stack + threadIdx.x, sv, shadow_counter(bounce), 0, 0xff, flags, st, tmax, wf.occ_cache != nullptr && bounce == 0);
+    trace_persistent<COUNT, 1>(sc, wf, s_stack + threadIdx.x, sv, shadow_counter(bounce), 0, 0xff, flags, st, tmax);
     if (COUNT) { flush_counters(counters, threadIdx.x & 63, 0, 0, 0, 0, st, true); if (st.deep) atomicAdd(&counters->deep_pushes, (unsigned long long)st.deep); }
     else if (st.overflow | st.deep) flush_rare(counters, st);
 }
@@ -878,8 +649,8 @@ __global__ __launch_bounds__(kBlock) void k_wf_aov(SceneRec sc_in, FrameConstant
             if (!aov_finite(ra)) ra = make_float4(0, 0, 0, 0);
             if (!aov_finite(rn)) rn = make_float4(0, 0, 0, 0);
         }
-        if (av.albedo) QST(av.rec_albedo[SIDX(slot)], ra);
-        if (av.normal_depth) QST(av.rec_normal[SIDX(slot)], rn);
+        if (av.albedo) QST(av.rec_albedo[slot], ra);
+        if (av.normal_depth) QST(av.rec_normal[slot], rn);
     }
 }
 // the running mean of a four-component AOV record: blend_sample's weight on every component
@@ -893,7 +664,7 @@ PT_DEV void resolve_aov_target(const FrameConstants& fc, const WfBuffers& wf, co
     float4 pixel = make_float4(0, 0, 0, 0);
     if (first > 0) pixel = target[at];
     for (uint32_t k = 0; k < fc.spp; k++) {
-        const float4 v = QLD(rec[SIDX(k * fc.pixel_slots + pslot)]);
+        const float4 v = QLD(rec[k * fc.pixel_slots + pslot]);
         const int n = first + (int)k;
         pixel = n > 0 ? blend_aov(pixel, n, v) : v;
     }
@@ -930,7 +701,7 @@ PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, floa
         if (fc.accumulated_frames != 0) { pixel = output[at]; half = ad.half[at]; }
         for (uint32_t k = 0; k < fc.spp; k++) {
             const uint32_t slot = k * fc.pixel_slots + pslot;
-            float4 Lq = SLD(wf.L[SIDX(slot)]);
+            float4 Lq = wf.L[slot];
             vec3 L = v3(Lq.x, Lq.y, Lq.z);
             apply_pending(wf, slot, __float_as_uint(Lq.w), L);
             L = sanitize_sample(fc, L);
@@ -976,7 +747,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuff
     if (accumulate && fc.accumulated_frames != 0) pixel = *outp;
     for (uint32_t k = 0; k < fc.spp; k++) {
         const uint32_t slot = k * fc.pixel_slots + pslot;
-        float4 Lq = SLD(wf.L[SIDX(slot)]);
+        float4 Lq = wf.L[slot];
         vec3 L = v3(Lq.x, Lq.y, Lq.z);
         apply_pending(wf, slot, __float_as_uint(Lq.w), L);
         L = sanitize_sample(fc, L);
@@ -992,16 +763,11 @@ static uint32_t blocks_per_shard_for(int stage_blocks) {
     uint32_t b = (uint32_t)(stage_blocks > 0 ? stage_blocks : 1536) / kShards;
     return b < 1 ? 1 : b;
 }
-// k_wf_generate: every XCD covers its band of tiles x spp samples with its kShards * blocks_per_shard / 8 workgroups
-static uint32_t gen_region_tiles_for(const FrameConstants& fc) {
-#if PT_GEN_XCD_BANDS == 2
-    if (fc.tile_rank_count == 1) return ((fc.tiles_x + kXcds - 1) / kXcds) * fc.tiles_y;      // the widest column band
-#endif
-    return (fc.my_tiles + kXcds - 1) / kXcds;
-}
+// k_wf_generate: workgroup-rounds that cover the (tile, sample) pairs.  Counted per XCD -- an eighth of the tiles, rounded up, against an
+// eighth of the kShards * blocks_per_shard workgroups -- which is what sizes the queue segments and the workspace.
 static uint32_t gen_rounds_for(const FrameConstants& fc, uint32_t blocks_per_shard) {
     const uint32_t per_xcd = kShards * blocks_per_shard / kXcds;
-    const uint32_t pairs = gen_region_tiles_for(fc) * fc.spp;
+    const uint32_t pairs = (fc.my_tiles + kXcds - 1) / kXcds * fc.spp;
     return (pairs + per_xcd - 1) / per_xcd;
 }
 static uint32_t seg_cap_for(const FrameConstants& fc, uint32_t blocks_per_shard) {
@@ -1009,7 +775,7 @@ static uint32_t seg_cap_for(const FrameConstants& fc, uint32_t blocks_per_shard)
     return gen_rounds_for(fc, blocks_per_shard) * blocks_per_shard * kBlock;
 }
 
-// entries of each path-state array: whole 256-slot chunks, the same number for every shard (state_index)
+// entries of each path-state array: whole 256-slot chunks, the same number for every shard
 static uint32_t chunks_per_shard_for(size_t slots) { return (uint32_t)(((slots + kBlock - 1) / kBlock + kShards - 1) / kShards); }
 static size_t state_slots_for(size_t slots) { return (size_t)chunks_per_shard_for(slots) * kShards * kBlock; }
 
@@ -1020,7 +786,7 @@ size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, boo
     const size_t slots = state_slots_for((size_t)fc.my_tiles * kBlock * fc.spp);
     if (aov) return aov_records_offset(fc, stage_blocks) + slots * (2 * 16);
     const size_t q = (size_t)kShards * seg_cap_for(fc, bps);
-    return slots * (5 * 16) + q * (4 * 16 + 4 * 16 + 16 + 2 * 16 + 2 * 2 * 16 + (PT_OCC_CACHE ? 2 * 4 : 0)) + kCounterArrays * kShards * kCounterStride * 4 + 52 * 256;
+    return slots * (5 * 16) + q * (4 * 16 + 4 * 16 + 16 + 2 * 16 + 2 * 2 * 16) + kCounterArrays * kShards * kCounterStride * 4 + 52 * 256;
 }
 
 static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
@@ -1032,7 +798,7 @@ static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
     auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
     wf.blocks_per_shard = blocks_per_shard_for(stage_blocks);
     wf.seg_cap = seg_cap_for(fc, wf.blocks_per_shard);
-    wf.gen_region_tiles = gen_region_tiles_for(fc);
+    wf.gen_region_tiles = 0;
     wf.gen_rounds = gen_rounds_for(fc, wf.blocks_per_shard);
     const size_t q = (size_t)kShards * wf.seg_cap;
     for (int k = 0; k < kCounterArrays; k++) wf.cnt[k] = (uint32_t*)take((size_t)kShards * kCounterStride * 4);
@@ -1047,7 +813,7 @@ static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
     wf.env_b = (float4*)take(q * 16);
     wf.sh_o = (float4*)take(q * 2 * 16);
     wf.sh_d = (float4*)take(q * 2 * 16);
-    wf.sh_c = PT_OCC_CACHE ? (uint32_t*)take(q * 2 * 4) : nullptr;
+    wf.sh_c = nullptr;
     wf.occ_cache = nullptr;
     wf.capacity = slots;
     return wf;
@@ -1068,7 +834,7 @@ static void traversal_ray_flags(uint32_t flags, int b, uint32_t& rf, uint32_t& r
     }
 }
 // the traversal kernels compiled for rays with no flags, if that is what the frame's settings give them
-static bool traversal_defaults(uint32_t flags) { return PT_TRAV_SPECIALISE && (flags & kTravFlagMask) == 0; }
+static bool traversal_defaults(uint32_t flags) { return (flags & kTravFlagMask) == 0; }
 static void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
                             uint32_t rmask, Counters* counters) {
     const dim3 block(kBlock);
@@ -1092,7 +858,7 @@ static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const Sc
 }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, uint32_t* occ_cache, const AdaptiveArgs* adaptive, const AovArgs* aov) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -1113,7 +879,6 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     };
     const uint32_t slots = fc.my_tiles * kBlock * fc.spp;
     WfBuffers wf = carve(workspace, fc, stage_blocks);
-    wf.occ_cache = PT_OCC_CACHE ? occ_cache : nullptr;
     hipError_t e = hipMemsetAsync(wf.cnt[0], 0, (size_t)kCounterArrays * kShards * kCounterStride * 4, stream);     // the counter arrays are contiguous
     if (e) return e;
     const dim3 block(kBlock), full(fc.my_tiles), stage(kShards * wf.blocks_per_shard);
@@ -1140,15 +905,14 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     auto launch_shadow = [&](dim3 grid, const WfBuffers& w, int b) { launch_wf_shadow(grid, stream, count, sc, w, b, flags, fc.max_ray_length, counters); };
     // the shade kernel compiled for this frame's flags, if there is one (k_wf_shade)
     const uint32_t shade_bits = flags & kShadeFlagMask;
-    const int shade_variant = (!PT_SHADE_SPECIALISE || fc.debug_output != PT_DEBUG_OUTPUT_NONE) ? 0 : (shade_bits == kShadeDefaults ? 1 : (shade_bits == kShadeDefaultsNoLights ? 2 : 0));
-    const bool small_tables = PT_SHADE_SPECIALISE && sc.n_instances <= kInstCacheMax && sc.n_materials <= kMatCacheMax && fc.num_of_lights <= kLightCacheMax;
+    const int shade_variant = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 0 : (shade_bits == kShadeDefaults ? 1 : (shade_bits == kShadeDefaultsNoLights ? 2 : 0));
+    const bool small_tables = sc.n_instances <= kInstCacheMax && sc.n_materials <= kMatCacheMax && fc.num_of_lights <= kLightCacheMax;
     auto launch_shade = [&](dim3 grid, const WfBuffers& w, int cur, int b) {
         if (small_tables && shade_variant == 1) hipLaunchKernelGGL((k_wf_shade<kShadeSpecialised | kShadeDefaults, true>), grid, block, 0, stream, sc, fc, w, cur, b, counters);
         else if (small_tables && shade_variant == 2) hipLaunchKernelGGL((k_wf_shade<kShadeSpecialised | kShadeDefaultsNoLights, true>), grid, block, 0, stream, sc, fc, w, cur, b, counters);
         else if (small_tables) hipLaunchKernelGGL((k_wf_shade<0u, true>), grid, block, 0, stream, sc, fc, w, cur, b, counters);
         else hipLaunchKernelGGL((k_wf_shade<0u, false>), grid, block, 0, stream, sc, fc, w, cur, b, counters);
     };
-#if PT_LATE_GRID
     // Late bounces carry few paths (Russian roulette starts after min_bounces and the reference's throughput drives the continuation
     // probability to its floor): a launch sized for the full queue then mostly starts workgroups that find nothing and, in the shade
     // stage, would stage 67 KB of tables for it.  The grid of a bounce follows the EXPECTED queue (a quarter of the paths per bounce
@@ -1166,38 +930,21 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         }
         return dim3(kShards * bps);
     };
-#define PT_GRID(b) grid_of(b)
-#define PT_WF(b) wf_for(b)
-    auto wf_for = [&](int b) { WfBuffers w = wf; w.blocks_per_shard = grid_of(b).x / kShards; return w; };
     auto cap = [&](dim3 g, int env) { if (env > 0 && (uint32_t)env * kShards < g.x) g.x = (uint32_t)env * kShards; return g; };
     auto wf_of = [&](dim3 g) { WfBuffers w = wf; w.blocks_per_shard = g.x / kShards; return w; };
-#else
-#define PT_GRID(b) stage
-#define PT_WF(b) wf
-#endif
-#if PT_FUSE_TRAVERSAL
     // generate -> trace(0) -> [shade(b) -> shadow(b) + trace(b + 1)] x (bounces) -> resolve: two grid-wide synchronisations per bounce
     {
         uint32_t rf, rmask;
         ray_flags(0, rf, rmask);
-#if PT_LATE_GRID
         const dim3 g0 = cap(stage, env_trace_bps);
         launch_trace(g0, wf_of(g0), 0, 0, rf, rmask);
-#else
-        launch_trace(stage, wf, 0, 0, rf, rmask);
-#endif
         mark(STAGE_TRACE);
     }
     if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
     for (int b = 0; b < iterations; b++) {
         const int cur = b & 1;
-#if PT_LATE_GRID
         const dim3 gs = cap(grid_of(b), env_shade_bps), gt = cap(grid_of(b), env_trace_bps);
         const WfBuffers ws = wf_of(gs), wt = wf_of(gt);
-#else
-        const dim3 gs = stage, gt = stage;
-        const WfBuffers& ws = wf; const WfBuffers& wt = wf;
-#endif
         launch_shade(gs, ws, cur, b);
         mark(STAGE_SHADE);
         uint32_t rf, rmask;
@@ -1209,20 +956,6 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         }
         mark(STAGE_SHADOW);
     }
-#else
-    for (int b = 0; b < iterations; b++) {
-        const int cur = b & 1;
-        uint32_t rf, rmask;
-        ray_flags(b, rf, rmask);
-        launch_trace(stage, wf, cur, b, rf, rmask);
-        mark(STAGE_TRACE);
-        if (aov && b == 0) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }
-        launch_shade(stage, wf, cur, b);
-        mark(STAGE_SHADE);
-        launch_shadow(stage, wf, b);
-        mark(STAGE_SHADOW);
-    }
-#endif
     if (aov) { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, true>), full, block, 0, stream, fc, wf, output, ad, av);
                else hipLaunchKernelGGL((k_wf_resolve<false, true>), full, block, 0, stream, fc, wf, output, ad, av); }
     else { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, false>), full, block, 0, stream, fc, wf, output, ad, av);
@@ -1233,7 +966,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
 
 // Test hook (pt_debug_trace_queues, mipt_api.hip): the traversal kernels of a frame -- k_wf_trace, k_wf_shadow or the fused k_wf_traverse, through
 // the launch functions above -- on queues the caller filled.  Owns a small WfBuffers: the seven counter arrays, one closest queue with its hit
-// array, the shadow queue and the pending records, nothing else (occ_cache = nullptr; sc.has_env must be 0, so no environment buffers are read).
+// array, the shadow queue and the pending records, nothing else (sc.has_env must be 0, so no environment buffers are read).
 // Every output word holds kDebugSentinel before the launch and each shard's segment ends in a guard entry nobody may write.
 // `bounce` is the closest rays' bounce (which 0, 2) or the shadow rays' (which 1); the fused launch takes the shadow rays of bounce - 1 with it,
 // as in a frame.  Synchronises the stream.
@@ -1253,16 +986,7 @@ hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters
     wf.seg_cap = seg + 1u;                                                              // the guard entry (two for the shadow queue)
     wf.blocks_per_shard = q.blocks_per_shard;
     wf.capacity = q.n_shadow + 1u;                                                      // slots: one per shadow ray and a guard
-    wf.chunks_per_shard = chunks_per_shard_for(wf.capacity);
     const size_t qn = (size_t)kShards * wf.seg_cap, slots = state_slots_for(wf.capacity), cnt_words = (size_t)kCounterArrays * kShards * kCounterStride;
-    auto host_sidx = [&](uint32_t slot) -> size_t {
-#if PT_STATE_BY_SHARD
-        const uint32_t c = slot >> 8;
-        return (((size_t)(c & (kShards - 1u)) * wf.chunks_per_shard + (c >> 8)) << 8) | (slot & 255u);
-#else
-        return slot;
-#endif
-    };
     // host images of the buffers
     std::vector<uint32_t> h_cnt(cnt_words, kDebugSentinel);
     std::vector<float4> h_ro(qn), h_rd(qn), h_so(qn * 2), h_sd(qn * 2);
@@ -1307,7 +1031,6 @@ hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters
     wf.ray_o[cur] = (float4*)take(b_q); wf.ray_d[cur] = (float4*)take(b_q); wf.hit = (float4*)take(b_q);
     wf.sh_o = (float4*)take(b_q * 2); wf.sh_d = (float4*)take(b_q * 2);
     wf.pend = (float4*)take(slots * 32);
-    wf.occ_cache = nullptr;
     hipError_t e = hipMemcpyAsync(d_cnt, h_cnt.data(), b_cnt, hipMemcpyHostToDevice, stream);
     if (!e) e = hipMemcpyAsync(wf.ray_o[cur], h_ro.data(), b_q, hipMemcpyHostToDevice, stream);
     if (!e) e = hipMemcpyAsync(wf.ray_d[cur], h_rd.data(), b_q, hipMemcpyHostToDevice, stream);
@@ -1355,7 +1078,7 @@ hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters
     for (size_t k = 0; k < qn; k++) if (!expected[k] && !untouched(h_hit[k])) stray_hit++;
     std::vector<uint8_t> target(slots * 2, 0);
     for (uint32_t i = 0; i < q.n_shadow; i++) {
-        const size_t k = 2 * host_sidx(i) + (q.shadow_is_light[i] ? 1u : 0u);
+        const size_t k = 2 * (size_t)i + (q.shadow_is_light[i] ? 1u : 0u);
         target[k] = 1;
         q.out_shadow[i] = h_pend[k].w;
     }

@@ -564,7 +564,7 @@ def test_traversal_finds_the_oracles_hit_for_every_ray(R, scene):
     """pt_debug_intersect (the product's traversal, no shading) against the oracle's traversal: two different trees (4-wide quantised PLOC
     against a binary float LBVH), the same triangle test, and DXR's rule that the closest hit wins -- so every ray must report the same
     triangle with bit-identical t, u, v.  This is the test that would have caught the box test that lost rays starting far from the
-    coordinate origin (pt_traverse.h PT_SLAB_SUBTRACT_FIRST).  Two rules, stated the same way on both sides, make the hit independent of the
+    coordinate origin (pt_traverse.h PT_SLAB_T: the subtraction comes first).  Two rules, stated the same way on both sides, make the hit independent of the
     tree (pt_traverse.h candidate_stands): a candidate must pass the box test of its own box (the float triangle test accepts rays a few ulp
     outside the triangle, which a tree may or may not have culled), and of two triangles at exactly the same distance (the stand-in scenes
     have coplanar, overlapping surfaces: 7 rays in 10 000 here) the lower (instance, primitive) wins."""
