@@ -7,139 +7,18 @@
 //   class GpuSkin      <- Source/GpuSkin.{h,cpp}: Create / Run
 //   class EnvironmentMap <- Source/EnvironmentMap.{h,cpp}: CreateEnvironmentMap (cube + importance only)
 //   ResourceTable      <- the bindless descriptor heap (DescriptorAllocator.h), as raw device pointers
+// This file is the product: context lifetime, resources, scene tables, trace, skin, post, accumulation, exchange.  The context itself is
+// in pt_ctx.h, the owner of its device arrays in dev_buf.h, the test hooks (pt_debug_*) in mipt_debug.hip.
 // There is no CPU fallback anywhere in this file: every compute entry point launches HIP kernels.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "pt_types.h"
-
-#include "pt_host.h"
+#include "pt_ctx.h"
 #include "host/accum_state.h"
 
 using namespace pt;
-
-// Pinned upload slots for the per-frame tables (materials, lights, instances, bones, vertex updates).  The reference hands those
-// over in a transient upload heap that stays valid for the frame (Source/Renderer.cpp:490,496); here the caller's memory may be
-// reused as soon as the call returns, so the bytes are copied into a pinned slot and go to the device asynchronously.  The host
-// only ever waits when it comes round to a slot whose copy is still in flight -- not once per call.
-struct StagingRing {
-    static constexpr int kSlots = 8;
-    void* host[kSlots] = {};
-    size_t cap[kSlots] = {};
-    hipEvent_t done[kSlots] = {};
-    bool pending[kSlots] = {};
-    int next = 0;
-};
-
-enum AccelState { ACCEL_CLEAN = 0, ACCEL_REFIT = 1, ACCEL_REBUILD = 2 };
-
-
-struct pt_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
-    StagingRing staging;
-
-    // ---- ResourceTable ("descriptor heap")
-    std::vector<BufferRec> buffers;
-    std::vector<TextureRec> textures;
-    std::vector<SamplerRec> samplers;
-    BufferRec* d_buffers = nullptr; size_t d_buffers_cap = 0; bool buffers_dirty = true;   // device copy: BVH build only
-    uint32_t* d_white = nullptr;                                   // 1x1 white texel behind every unbound material slot
-    // interleaved albedo / normal / metal-rough texels of the materials whose three textures share one footprint (pt_types.h RM_TRIO),
-    // keyed by the three texel pointers (nullptr = slot unbound); owned here, rebuilt / released by pt_scene_set_materials
-    struct TrioRec { const uint32_t *a, *n, *m, *e; uint4* ptr; };
-    std::vector<TrioRec> trios;
-
-    // ---- per-frame arrays (Renderer::GatherMaterials / GatherLights)
-    RMat* d_rmats = nullptr; int n_materials = 0; size_t rmats_cap = 0;    // resolved on the host in pt_scene_set_materials
-    std::vector<RMat> rmats_host;                                          // what was uploaded (pt_texture_destroy checks it)
-    pt_light* d_lights = nullptr; int n_lights = 0; size_t lights_cap = 0;
-
-    // ---- instance table + acceleration structure
-    std::vector<InstanceRec> instances;
-    InstanceRec* d_instances = nullptr; size_t instances_cap = 0;
-    uint32_t n_tris = 0;
-    Bvh4Node* d_nodes = nullptr; TriPacket* d_tris = nullptr; ShadePacket* d_shade = nullptr; size_t accel_cap = 0;
-    uint32_t wide_nodes = 0, stack_need = 0;
-    int32_t root = 0;
-    AccelScratch scratch;
-    // What the next pt_build_accel / pt_trace has to do: nothing, a refit of the instances marked in `touched` (vertices or
-    // transform changed: UpdateDynamicBlas + the per-frame TLAS rebuild upstream), or a full build (topology changed).
-    int accel_state = ACCEL_REBUILD;
-    bool accel_built = false;                 // a full build of the current instance table exists (a refit needs one)
-    bool instances_dirty = true;              // the device copy of the instance table is stale
-    std::vector<uint8_t> touched;             // per instance
-    uint8_t* d_touched = nullptr; size_t touched_cap = 0;
-    uint32_t accel_refits = 0, accel_builds = 0;
-    std::vector<int> free_buffers, free_textures, free_envs;      // destroyed handles, reused by the next create
-
-    std::vector<EnvDevice*> envs;
-    float* d_sheen = nullptr;
-    float* d_srgb = nullptr;
-    float2* d_tangent_lut = nullptr;
-    Counters* d_counters = nullptr;
-    void* d_bones = nullptr; size_t bones_cap = 0, bones_used = 0;   // bone arena: one slice per pt_skin_run, wraps behind a fence
-    hipEvent_t bones_fence = nullptr; bool bones_fence_pending = false;
-    void* d_workspace = nullptr; size_t workspace_cap = 0;     // wavefront ray / hit / path-state arrays
-    void* d_tonemap = nullptr; size_t tonemap_cap = 0;         // pt_tonemap's device scratch (float RGB + RGBA8), reused
-    pt::ExchangeState* exchange = nullptr;                         // pt_exchange_* (exchange.hip)
-    int32_t* d_deep = nullptr; size_t deep_cap = 0;                // deep traversal stack (SceneRec::deep_stack), only for trees that need > 64 entries
-    bool stage_timing = false;                                 // pt_enable_stage_timing
-    StageTimers timers;
-    int kernel_mode = PT_MODE_WAVEFRONT;
-    int stage_blocks = 0;         // workgroups per stage launch; 0 = by the size of the launch (stage_blocks_for)
-    hipEvent_t ev_trace[2] = {nullptr, nullptr}, ev_accel[2] = {nullptr, nullptr}, ev_skin[2] = {nullptr, nullptr};
-    bool have_trace = false, have_accel = false, have_skin = false;
-    int bounce_limit = PT_REFERENCE_MAX_BOUNCES;
-    int samples_per_trace = 1;
-    bool cull_null_shadow = false;
-    bool counters_enabled = false;
-    // ---- adaptive sampling (pt_set_adaptive): per rank-local tile state and the half buffer, for one size and tile shard
-    pt_adaptive_config adaptive = {0, 2, 2, 0.0f};
-    bool adaptive_restart = false;                // pt_set_adaptive: the next pt_trace starts a new accumulation
-    AdaptiveTile* d_ad_tiles = nullptr; size_t ad_tiles_cap = 0;
-    float4* d_ad_half = nullptr; size_t ad_half_cap = 0;
-    uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
-    bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
-    int ad_frames = -1;                           // accumulated_frames the tile state stands for (-1: none)
-    // ---- pt_accum_save / pt_accum_load: the packed sections of one blob (one pt_tiles_pack image each), reused between calls
-    void* d_accum = nullptr; size_t accum_cap = 0;
-    // ---- first-hit AOVs (pt_set_aov): the caller's targets
-    pt_aov_config aov = {0, nullptr, nullptr};
-    bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
-    // ---- thin lens (pt_set_lens)
-    pt_lens_config lens = {0, 0.0f, 1.0f, 0, 0.0f};
-    bool lens_restart = false;                    // pt_set_lens: the next pt_trace starts a new accumulation
-    // ---- pt_denoise: two ping-pong signal images and the guide image, dn_pixels float4 each, for one image size
-    float4* d_denoise = nullptr; size_t dn_pixels = 0;
-
-    // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
-    float previous_world_to_clip[16] = {0};
-    int accumulated_frames = 0;
-
-    int fail(int code, const std::string& msg) { error = msg; return code; }
-};
-
-#define HIPOK(call)                                                                                          \
-    do {                                                                                                     \
-        hipError_t _e = (call);                                                                              \
-        if (_e != hipSuccess) return ctx->fail(PT_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-// Every entry point that touches the device makes the context's device current first: two contexts on two GPUs in one process
-// (one per rank thread, or a host that drives several GPUs itself) must not launch or allocate on each other's device.
-#define ENTER(ctx)                                                                                           \
-    do {                                                                                                     \
-        hipError_t _e = hipSetDevice((ctx)->device);                                                         \
-        if (_e != hipSuccess) return (ctx)->fail(PT_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
-    } while (0)
 
 namespace {
 
@@ -167,21 +46,28 @@ hipError_t staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes) 
 }
 
 template <typename T>
-hipError_t upload_table(pt_ctx* ctx, T*& d, size_t& cap, const std::vector<T>& h) {
-    size_t n = h.size() ? h.size() : 1;
-    if (n > cap) {
-        // kernels already enqueued may still read the old table
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e) return e;
-        hipFree(d);
-        d = nullptr; cap = 0;
-        size_t nc = n + n / 2 + 8;
-        e = hipMalloc((void**)&d, nc * sizeof(T));
-        if (e) return e;
-        cap = nc;
-    }
-    if (h.empty()) return hipSuccess;
-    return staged_upload(ctx, d, h.data(), h.size() * sizeof(T));
+hipError_t upload_table(pt_ctx* ctx, DevBuf& d, const std::vector<T>& h) {
+    const size_t n = h.size() ? h.size() : 1;
+    const hipError_t e = d.reserve(ctx->stream, n * sizeof(T), (n + n / 2 + 8) * sizeof(T));
+    if (e || h.empty()) return e;
+    return staged_upload(ctx, d.ptr, h.data(), h.size() * sizeof(T));
+}
+
+// What a grow that answers an exhausted device with PT_ERR_OUT_OF_MEMORY and its own text returns (anything else DevBuf::realloc
+// fails with is its synchronise)
+int grow_failed(pt_ctx* ctx, hipError_t e, const std::string& what) {
+    if (e != hipErrorOutOfMemory) return ctx->fail(PT_ERR_DEVICE, std::string("hipStreamSynchronize(ctx->stream): ") + hipGetErrorString(e));
+    (void)hipGetLastError();
+    return ctx->fail(PT_ERR_OUT_OF_MEMORY, what);
+}
+// The adaptive tile state (`tiles` AdaptiveTile) and half buffer (`px` float4), reallocated together when either is too small; what they
+// held is gone then, and with it what pt_adaptive_read could show (PathtraceScene and pt_accum_load fill them next)
+int adaptive_state(pt_ctx* ctx, size_t tiles, size_t px) {
+    if (tiles * sizeof(AdaptiveTile) <= ctx->d_ad_tiles.cap && px * 16 <= ctx->d_ad_half.cap) return PT_OK;
+    ctx->ad_ready = false;
+    hipError_t e = ctx->d_ad_tiles.realloc(ctx->stream, tiles * sizeof(AdaptiveTile));
+    if (e == hipSuccess) e = ctx->d_ad_half.realloc(ctx->stream, px * 16);
+    return e == hipSuccess ? PT_OK : grow_failed(ctx, e, "adaptive tile state");
 }
 
 // glm closed forms.  Inverses in fp64, rounded once.
@@ -251,14 +137,16 @@ int stage_blocks_for(size_t slots) { return slots >= 1200000 ? 1536 : (slots >= 
 // A vertex stream was rewritten (pt_skin_run, pt_buffer_update): the instances that read it need their packets rebuilt (refit);
 // a rewritten index stream changes which vertices form a triangle, which the refit also handles (it re-reads the indices), but
 // the Morton order was made for the old triangles -- still correct, only slower -- so that stays a refit too.
+bool reads_buffer(const InstanceRec& r, const void* ptr) {
+    return r.p_index == ptr || r.p_position == ptr || r.p_tangent_space == ptr || r.p_texcoord[0] == ptr || r.p_texcoord[1] == ptr || r.p_color == ptr;
+}
 void mark_buffer_users(pt_ctx* ctx, int handle) {
     if (handle < 0) return;
     if (ctx->touched.size() != ctx->instances.size()) ctx->touched.assign(ctx->instances.size(), 0);
     const void* ptr = ctx->buffers[handle].ptr;
     bool any = false;
     for (size_t i = 0; i < ctx->instances.size(); i++) {
-        const InstanceRec& r = ctx->instances[i];
-        if (r.p_index == ptr || r.p_position == ptr || r.p_tangent_space == ptr || r.p_texcoord[0] == ptr || r.p_texcoord[1] == ptr || r.p_color == ptr) {
+        if (reads_buffer(ctx->instances[i], ptr)) {
             ctx->touched[i] = 1;
             any = true;
         }
@@ -266,14 +154,10 @@ void mark_buffer_users(pt_ctx* ctx, int handle) {
     if (any && ctx->accel_state == ACCEL_CLEAN) ctx->accel_state = ACCEL_REFIT;
 }
 
-// The camera of a call, from pt_execute_params and the lens config: world_to_clip as pt_trace compares it between calls, its inverse and
-// view_to_world (fp64, rounded once) and the lens as camera_ray takes it (include/mipt.h pt_set_lens).  PathtraceScene, pt_lens_focus_at
-// and the hook pt_debug_camera_rays all come through here, so that the rays they speak of are the same rays.
-struct CameraSetup {
-    float world_to_clip[16], clip_to_world[16], view_to_world[16];
-    LensArgs lens;
-};
-bool camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam) {
+}  // namespace
+
+// (pt_ctx.h)
+bool pt::camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam) {
     mat4_mul(ep->view_to_clip, ep->world_to_view, cam.world_to_clip);               // Pathtracer.cpp:262
     double v2w[16];
     if (!mat4_inverse_d(ep->world_to_view, v2w) || !mat4_inverse(cam.world_to_clip, cam.clip_to_world)) return false;
@@ -298,14 +182,12 @@ bool camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, Camera
     }
     return true;
 }
-// What pinhole_ray reads of FrameConstants (the two camera hooks; PathtraceScene fills the rest as well)
-void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, FrameConstants& fc) {
+void pt::camera_constants(const CameraSetup& cam, const pt_execute_params* ep, FrameConstants& fc) {
+    memset(&fc, 0, sizeof(fc));
     memcpy(fc.clip_to_world, cam.clip_to_world, 64);
     fc.camera_pos[0] = cam.view_to_world[12]; fc.camera_pos[1] = cam.view_to_world[13]; fc.camera_pos[2] = cam.view_to_world[14];
     fc.res_x = ep->width; fc.res_y = ep->height;
 }
-
-}  // namespace
 
 // =================================================================================================
 // class Pathtracer (Source/Pathtracer.h:16-157)
@@ -317,39 +199,29 @@ public:
     // small TLAS every frame.  Here: ONE full build of the flattened soup when the set of triangles changes, and a refit -- packets
     // of the touched instances rewritten in place, every box re-derived -- when only vertices or transforms moved.
     static int BuildAccel(pt_ctx* ctx) {
-        if (ctx->buffers_dirty) { HIPOK(upload_table(ctx, ctx->d_buffers, ctx->d_buffers_cap, ctx->buffers)); ctx->buffers_dirty = false; }
-        if (ctx->instances_dirty) { HIPOK(upload_table(ctx, ctx->d_instances, ctx->instances_cap, ctx->instances)); ctx->instances_dirty = false; }
+        if (ctx->buffers_dirty) { HIPOK(upload_table(ctx, ctx->d_buffers, ctx->buffers)); ctx->buffers_dirty = false; }
+        if (ctx->instances_dirty) { HIPOK(upload_table(ctx, ctx->d_instances, ctx->instances)); ctx->instances_dirty = false; }
         if (ctx->accel_state == ACCEL_CLEAN && ctx->accel_built) return PT_OK;
         const bool refit = ctx->accel_built && ctx->accel_state == ACCEL_REFIT;
         if (!refit) {
-            size_t need = ctx->n_tris ? ctx->n_tris : 1;
-            if (need > ctx->accel_cap) {
-                HIPOK(hipStreamSynchronize(ctx->stream));
-                hipFree(ctx->d_nodes); hipFree(ctx->d_tris); hipFree(ctx->d_shade);
-                ctx->d_nodes = nullptr; ctx->d_tris = nullptr; ctx->d_shade = nullptr; ctx->accel_cap = 0;
-                size_t cap = need + need / 8 + 64;
-                HIPOK(hipMalloc((void**)&ctx->d_nodes, cap * sizeof(Bvh4Node)));
-                HIPOK(hipMalloc((void**)&ctx->d_tris, cap * sizeof(TriPacket)));
-                HIPOK(hipMalloc((void**)&ctx->d_shade, cap * sizeof(ShadePacket)));
-                ctx->accel_cap = cap;
-            }
+            const size_t need = ctx->n_tris ? ctx->n_tris : 1, cap = need + need / 8 + 64;
+            HIPOK(ctx->d_nodes.reserve(ctx->stream, need * sizeof(Bvh4Node), cap * sizeof(Bvh4Node)));
+            HIPOK(ctx->d_tris.reserve(ctx->stream, need * sizeof(TriPacket), cap * sizeof(TriPacket)));
+            HIPOK(ctx->d_shade.reserve(ctx->stream, need * sizeof(ShadePacket), cap * sizeof(ShadePacket)));
         }
+        const InstanceRec* d_instances = ctx->d_instances.as<InstanceRec>();
+        Bvh4Node* d_nodes = ctx->d_nodes.as<Bvh4Node>(); TriPacket* d_tris = ctx->d_tris.as<TriPacket>(); ShadePacket* d_shade = ctx->d_shade.as<ShadePacket>();
         HIPOK(hipEventRecord(ctx->ev_accel[0], ctx->stream));
         if (refit) {
             const size_t n = ctx->instances.size();
-            if (n > ctx->touched_cap) {
-                HIPOK(hipStreamSynchronize(ctx->stream));
-                hipFree(ctx->d_touched); ctx->d_touched = nullptr; ctx->touched_cap = 0;
-                HIPOK(hipMalloc((void**)&ctx->d_touched, n + 64));
-                ctx->touched_cap = n + 64;
-            }
-            HIPOK(staged_upload(ctx, ctx->d_touched, ctx->touched.data(), n));
-            HIPOK(accel_refit(ctx->scratch, ctx->d_instances, ctx->d_touched, ctx->n_tris, ctx->wide_nodes, ctx->d_nodes, ctx->d_tris, ctx->d_shade, ctx->stream));
+            HIPOK(ctx->d_touched.reserve(ctx->stream, n, n + 64));
+            HIPOK(staged_upload(ctx, ctx->d_touched.ptr, ctx->touched.data(), n));
+            HIPOK(accel_refit(ctx->scratch, d_instances, ctx->d_touched.as<uint8_t>(), ctx->n_tris, ctx->wide_nodes, d_nodes, d_tris, d_shade, ctx->stream));
             ctx->accel_refits++;
         } else {
             ctx->scratch.why.clear();
-            const hipError_t be = accel_build(ctx->scratch, ctx->d_buffers, ctx->d_instances, (int)ctx->instances.size(), ctx->n_tris, ctx->d_nodes, ctx->d_tris,
-                                              ctx->d_shade, &ctx->root, &ctx->wide_nodes, &ctx->stack_need, ctx->stream);
+            const hipError_t be = accel_build(ctx->scratch, ctx->d_buffers.as<BufferRec>(), d_instances, (int)ctx->instances.size(), ctx->n_tris, d_nodes, d_tris,
+                                              d_shade, &ctx->root, &ctx->wide_nodes, &ctx->stack_need, ctx->stream);
             if (be != hipSuccess) {
                 ctx->accel_built = false; ctx->accel_state = ACCEL_REBUILD;
                 return ctx->fail(PT_ERR_DEVICE, std::string("acceleration-structure build: ") + (ctx->scratch.why.empty() ? hipGetErrorString(be) : ctx->scratch.why.c_str()));
@@ -372,8 +244,8 @@ public:
             ctx->scratch.builder = 0;
             ctx->scratch.fallbacks++;
             ctx->scratch.fallback_why = "clustered tree needs a traversal stack of " + std::to_string(ctx->stack_need) + " entries";
-            const hipError_t be = accel_build(ctx->scratch, ctx->d_buffers, ctx->d_instances, (int)ctx->instances.size(), ctx->n_tris, ctx->d_nodes, ctx->d_tris,
-                                              ctx->d_shade, &ctx->root, &ctx->wide_nodes, &ctx->stack_need, ctx->stream);
+            const hipError_t be = accel_build(ctx->scratch, ctx->d_buffers.as<BufferRec>(), d_instances, (int)ctx->instances.size(), ctx->n_tris, d_nodes, d_tris,
+                                              d_shade, &ctx->root, &ctx->wide_nodes, &ctx->stack_need, ctx->stream);
             ctx->scratch.builder = chosen;
             if (be != hipSuccess) {
                 ctx->accel_built = false; ctx->accel_state = ACCEL_REBUILD;
@@ -413,30 +285,15 @@ public:
         const int frame_cap = adaptive ? std::min(ctx->adaptive.max_samples, settings->max_accumulated_frames) : settings->max_accumulated_frames;
         if (ctx->accumulated_frames < frame_cap) {                                       // :273
             if (ep->light_count > ctx->n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "light_count exceeds uploaded lights");
-            if (ep->environment_map >= 0 && (ep->environment_map >= (int)ctx->envs.size() || !ctx->envs[ep->environment_map]))
+            if (ep->environment_map >= 0 && !live_env(ctx, ep->environment_map))
                 return ctx->fail(PT_ERR_BAD_HANDLE, "bad environment map handle");
             if (!ep->output) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "output is null");
-            if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = BuildAccel(ctx); if (r) return r; }
+            if (int r = ensure_accel(ctx)) return r;
 
-            SceneRec sc;
-            memset(&sc, 0, sizeof(sc));
-            sc.rmats = ctx->d_rmats; sc.lights = ctx->d_lights; sc.instances = ctx->d_instances;
-            sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
-            sc.nodes = ctx->d_nodes; sc.tris = ctx->d_tris; sc.shade = ctx->d_shade; sc.root = ctx->root; sc.num_tris = ctx->n_tris;
-            sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
-            sc.has_env = 0;
-            if (ep->environment_map >= 0) {
-                const EnvDevice& ed = *ctx->envs[ep->environment_map];
-                sc.env.cube = ed.cube; sc.env.cube_n = ed.mip_n[0]; sc.env.importance = ed.importance;
-                for (int i = 0; i < 12; i++) sc.env.level_offset[i] = ed.level_offset[i];
-                sc.env.imp_res = ed.imp_res; sc.env.imp_levels = ed.levels; sc.env.imp_total = ed.total;
-                sc.env.blocked = ed.blocked;
-                for (int i = 0; i < 5; i++) sc.env.blocked_offset[i] = ed.blocked_offset[i];
-                sc.has_env = 1;
-            }
+            SceneRec sc = scene_fill(ctx);
+            if (ep->environment_map >= 0) scene_set_env(sc, *ctx->envs[ep->environment_map]);
 
             FrameConstants fc;                                                          // :287-331
-            memset(&fc, 0, sizeof(fc));
             camera_constants(cam, ep, fc);
             fc.num_of_lights = ep->light_count;
             fc.seed = settings->use_frame_as_seed ? (uint32_t)ep->frame : settings->seed;   // :316
@@ -477,19 +334,13 @@ public:
 
             // deep traversal stack (trees that need more than the 64 on-chip entries): (need - 64) entries for every lane of the widest
             // traversal launch of this call
-            if ((int)ctx->stack_need > traversal_stack_capacity()) {
-                const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
+            if (const uint32_t entries = deep_stack_entries(ctx)) {
                 size_t lanes;
                 if (ctx->kernel_mode == PT_MODE_MEGAKERNEL) lanes = (size_t)fc.my_tiles * 256;
                 else lanes = (size_t)traversal_grid_lanes(ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * (size_t)batch));
                 const size_t need = (size_t)entries * lanes * 4;
-                if (need > ctx->deep_cap) {
-                    HIPOK(hipStreamSynchronize(ctx->stream));
-                    hipFree(ctx->d_deep); ctx->d_deep = nullptr; ctx->deep_cap = 0;
-                    if (hipMalloc((void**)&ctx->d_deep, need) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "deep traversal stack: " + std::to_string(need) + " bytes"); }
-                    ctx->deep_cap = need;
-                }
-                sc.deep_stack = ctx->d_deep; sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
+                if (const hipError_t e = ctx->d_deep.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "deep traversal stack: " + std::to_string(need) + " bytes");
+                sc.deep_stack = ctx->d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
             }
             HIPOK(hipEventRecord(ctx->ev_trace[0], ctx->stream));
             if (ctx->kernel_mode == PT_MODE_MEGAKERNEL) {
@@ -497,46 +348,32 @@ public:
                     FrameConstants fk = fc;
                     fk.seed = fc.seed + (uint32_t)k * fc.seed_step;
                     fk.accumulated_frames = fc.accumulated_frames + k;
-                    launch_megakernel(sc, fk, cam.lens, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->stream);   // :344-353
+                    launch_megakernel(sc, fk, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->stream);   // :344-353
                 }
             } else {
                 fc.spp = (uint32_t)batch;
                 if ((unsigned long long)fc.pixel_slots * fc.spp > 0x7fffffffull) return ctx->fail(PT_ERR_CAPACITY, "sample batch too large for this resolution");
                 const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * fc.spp);
-                size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov);
-                if (need > ctx->workspace_cap) {
-                    HIPOK(hipStreamSynchronize(ctx->stream));
-                    hipFree(ctx->d_workspace); ctx->d_workspace = nullptr; ctx->workspace_cap = 0;
-                    HIPOK(hipMalloc(&ctx->d_workspace, need));
-                    ctx->workspace_cap = need;
-                }
+                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov);
+                HIPOK(ctx->d_workspace.reserve(ctx->stream, need, need));
                 AdaptiveArgs ad = {};
                 if (adaptive) {
                     // tile state (rank-local tiles) and half buffer; a new accumulation makes every tile active with 0 samples
                     const size_t px = (size_t)ep->width * ep->height, tiles = fc.my_tiles ? fc.my_tiles : 1;
-                    if (tiles > ctx->ad_tiles_cap || px > ctx->ad_half_cap) {
-                        HIPOK(hipStreamSynchronize(ctx->stream));
-                        hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
-                        ctx->d_ad_tiles = nullptr; ctx->d_ad_half = nullptr; ctx->ad_tiles_cap = ctx->ad_half_cap = 0; ctx->ad_ready = false;
-                        if (hipMalloc((void**)&ctx->d_ad_tiles, tiles * sizeof(AdaptiveTile)) != hipSuccess || hipMalloc((void**)&ctx->d_ad_half, px * 16) != hipSuccess) {
-                            (void)hipGetLastError();
-                            return ctx->fail(PT_ERR_OUT_OF_MEMORY, "adaptive tile state");
-                        }
-                        ctx->ad_tiles_cap = tiles; ctx->ad_half_cap = px;
-                    }
+                    if (int r = adaptive_state(ctx, tiles, px)) return r;
                     if (ctx->accumulated_frames == 0) {
                         const AdaptiveTile fresh = {1u, 0u, 0.0f, 0u};
                         const std::vector<AdaptiveTile> init(tiles, fresh);
-                        HIPOK(staged_upload(ctx, ctx->d_ad_tiles, init.data(), tiles * sizeof(AdaptiveTile)));
-                        HIPOK(hipMemsetAsync(ctx->d_ad_half, 0, px * 16, ctx->stream));
+                        HIPOK(staged_upload(ctx, ctx->d_ad_tiles.ptr, init.data(), tiles * sizeof(AdaptiveTile)));
+                        HIPOK(hipMemsetAsync(ctx->d_ad_half.ptr, 0, px * 16, ctx->stream));
                     }
-                    ad.tiles = ctx->d_ad_tiles; ad.half = ctx->d_ad_half;
+                    ad.tiles = ctx->d_ad_tiles.as<AdaptiveTile>(); ad.half = ctx->d_ad_half.as<float4>();
                     ad.min_samples = ctx->adaptive.min_samples; ad.cap = frame_cap; ad.threshold = ctx->adaptive.threshold;
                     ctx->ad_w = ep->width; ctx->ad_h = ep->height; ctx->ad_rank = fc.tile_rank; ctx->ad_rank_count = fc.tile_rank_count;
                     ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
                 }
                 const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
-                HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters, ctx->counters_enabled, ctx->d_workspace, stage_blocks,
+                HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
                                        ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr));
             }
             HIPOK(hipGetLastError());
@@ -605,17 +442,12 @@ public:
             size_t bytes = (size_t)bone_count * sizeof(pt_bone);
             // Each call gets its own slice of the bone arena: a frame skins several primitives back to back on one stream, and the
             // kernel of the previous call may not have read its bones yet (they live in the caller's transient heap, Renderer.cpp:411).
-            if (ctx->bones_used + bytes > ctx->bones_cap) {
-                if (bytes > ctx->bones_cap) {
-                    HIPOK(hipStreamSynchronize(ctx->stream));
-                    hipFree(ctx->d_bones); ctx->d_bones = nullptr; ctx->bones_cap = 0;
-                    const size_t nc = bytes * 8 + 4096;
-                    HIPOK(hipMalloc(&ctx->d_bones, nc));
-                    ctx->bones_cap = nc;
-                } else if (ctx->bones_fence_pending) HIPOK(hipEventSynchronize(ctx->bones_fence));      // wrap: the arena's earlier readers must be done
+            if (ctx->bones_used + bytes > ctx->d_bones.cap) {
+                if (bytes > ctx->d_bones.cap) HIPOK(ctx->d_bones.realloc(ctx->stream, bytes * 8 + 4096));
+                else if (ctx->bones_fence_pending) HIPOK(hipEventSynchronize(ctx->bones_fence));      // wrap: the arena's earlier readers must be done
                 ctx->bones_used = 0;
             }
-            void* dst = (char*)ctx->d_bones + ctx->bones_used;
+            void* dst = ctx->d_bones.as<char>() + ctx->bones_used;
             ctx->bones_used += (bytes + 255) & ~(size_t)255;
             HIPOK(staged_upload(ctx, dst, bones, bytes));
             a.bones = (const pt_bone*)dst;
@@ -642,6 +474,9 @@ public:
         return PT_OK;
     }
 };
+int ensure_accel(pt_ctx* ctx) {
+    return ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty ? Pathtracer::BuildAccel(ctx) : PT_OK;
+}
 }  // namespace pt
 
 static int exchange_frame_checked(pt_ctx* ctx, const void* local, void* frame, uint32_t w, uint32_t h, int mode, int dst, std::string& err) {
@@ -669,14 +504,14 @@ int pt_create(int device, void* hip_stream, const float* sheen_e_16x16, pt_ctx**
         double c = i / 255.0;
         srgb[i] = (float)(c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4));
     }
-    bool ok = hipMalloc((void**)&ctx->d_sheen, 256 * 4) == hipSuccess && hipMalloc((void**)&ctx->d_srgb, 256 * 4) == hipSuccess &&
-              hipMalloc((void**)&ctx->d_counters, sizeof(Counters)) == hipSuccess && hipMalloc((void**)&ctx->d_white, 16) == hipSuccess &&
-              hipMemset(ctx->d_white, 0xff, 16) == hipSuccess &&
-              hipMemcpy(ctx->d_sheen, sheen_e_16x16, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(ctx->d_srgb, srgb, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemset(ctx->d_counters, 0, sizeof(Counters)) == hipSuccess &&
-              hipMalloc((void**)&ctx->d_tangent_lut, 1024 * sizeof(float2)) == hipSuccess &&
-              build_tangent_lut(ctx->d_tangent_lut, ctx->stream) == hipSuccess;
+    bool ok = ctx->d_sheen.realloc(ctx->stream, 256 * 4) == hipSuccess && ctx->d_srgb.realloc(ctx->stream, 256 * 4) == hipSuccess &&
+              ctx->d_counters.realloc(ctx->stream, sizeof(Counters)) == hipSuccess && ctx->d_white.realloc(ctx->stream, 16) == hipSuccess &&
+              hipMemset(ctx->d_white.ptr, 0xff, 16) == hipSuccess &&
+              hipMemcpy(ctx->d_sheen.ptr, sheen_e_16x16, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(ctx->d_srgb.ptr, srgb, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemset(ctx->d_counters.ptr, 0, sizeof(Counters)) == hipSuccess &&
+              ctx->d_tangent_lut.realloc(ctx->stream, 1024 * sizeof(float2)) == hipSuccess &&
+              build_tangent_lut(ctx->d_tangent_lut.as<float2>(), ctx->stream) == hipSuccess;
     for (int i = 0; i < 2 && ok; i++)
         ok = hipEventCreate(&ctx->ev_trace[i]) == hipSuccess && hipEventCreate(&ctx->ev_accel[i]) == hipSuccess && hipEventCreate(&ctx->ev_skin[i]) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->bones_fence, hipEventDisableTiming) == hipSuccess;
@@ -707,18 +542,8 @@ void pt_destroy(pt_ctx* ctx) {
     for (auto& t : ctx->textures) hipFree((void*)t.texels);
     for (auto& t : ctx->trios) hipFree((void*)t.ptr);
     for (auto* e : ctx->envs) if (e) { env_free(*e); delete e; }
-    hipFree(ctx->d_buffers); hipFree(ctx->d_white); hipFree(ctx->d_rmats); hipFree(ctx->d_lights);
-    hipFree(ctx->d_instances); hipFree(ctx->d_nodes); hipFree(ctx->d_tris); hipFree(ctx->d_shade); hipFree(ctx->d_sheen); hipFree(ctx->d_srgb); hipFree(ctx->d_tangent_lut); hipFree(ctx->d_counters);
     accel_scratch_free(ctx->scratch);
-    hipFree(ctx->d_bones);
-    hipFree(ctx->d_workspace);
-    hipFree(ctx->d_tonemap);
-    hipFree(ctx->d_touched);
     exchange_free(ctx->exchange);
-    hipFree(ctx->d_deep);
-    hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
-    hipFree(ctx->d_accum);
-    hipFree(ctx->d_denoise);
     for (int k = 0; k < StagingRing::kSlots; k++) {
         if (ctx->staging.host[k]) hipHostFree(ctx->staging.host[k]);
         if (ctx->staging.done[k]) hipEventDestroy(ctx->staging.done[k]);
@@ -730,7 +555,7 @@ void pt_destroy(pt_ctx* ctx) {
         if (ctx->ev_accel[i]) hipEventDestroy(ctx->ev_accel[i]);
         if (ctx->ev_skin[i]) hipEventDestroy(ctx->ev_skin[i]);
     }
-    delete ctx;
+    delete ctx;                 // ... and every DevBuf with it: the device is current, the stream drained
 }
 
 const char* pt_last_error(const pt_ctx* ctx) { return ctx ? ctx->error.c_str() : "null context"; }
@@ -744,8 +569,7 @@ int pt_buffer_create(pt_ctx* ctx, const void* host, size_t bytes, int format, in
     hipError_t e = host ? hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) : hipMemset(d, 0, bytes);
     if (e) { hipFree(d); return ctx->fail(PT_ERR_DEVICE, std::string("pt_buffer_create: ") + hipGetErrorString(e)); }
     const BufferRec rec = {d, (uint32_t)format, (uint32_t)bytes};
-    if (!ctx->free_buffers.empty()) { *handle_out = ctx->free_buffers.back(); ctx->free_buffers.pop_back(); ctx->buffers[*handle_out] = rec; }
-    else { ctx->buffers.push_back(rec); *handle_out = (int)ctx->buffers.size() - 1; }
+    *handle_out = take_slot(ctx->buffers, ctx->free_buffers, rec);
     ctx->buffers_dirty = true;
     return PT_OK;
 }
@@ -779,7 +603,7 @@ int pt_buffer_destroy(pt_ctx* ctx, int handle) {
     if (!live_buffer(ctx, handle)) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_buffer_destroy");
     const void* ptr = ctx->buffers[handle].ptr;
     for (const InstanceRec& r : ctx->instances)
-        if (r.p_index == ptr || r.p_position == ptr || r.p_tangent_space == ptr || r.p_texcoord[0] == ptr || r.p_texcoord[1] == ptr || r.p_color == ptr)
+        if (reads_buffer(r, ptr))
             return ctx->fail(PT_ERR_NOT_READY, "pt_buffer_destroy: the buffer is used by the current instance table (replace it with pt_scene_set_instances first)");
     ENTER(ctx);
     HIPOK(hipStreamSynchronize(ctx->stream));                // enqueued kernels (skinning, an earlier trace) may still read or write it
@@ -799,8 +623,7 @@ int pt_texture_create(pt_ctx* ctx, const uint8_t* rgba8, int width, int height, 
     hipError_t e = hipMemcpy(d, rgba8, bytes, hipMemcpyHostToDevice);
     if (e) { hipFree(d); return ctx->fail(PT_ERR_DEVICE, std::string("pt_texture_create: ") + hipGetErrorString(e)); }
     const TextureRec rec = {(const uint32_t*)d, width, height, srgb ? 1u : 0u, 0u};
-    if (!ctx->free_textures.empty()) { *handle_out = ctx->free_textures.back(); ctx->free_textures.pop_back(); ctx->textures[*handle_out] = rec; }
-    else { ctx->textures.push_back(rec); *handle_out = (int)ctx->textures.size() - 1; }
+    *handle_out = take_slot(ctx->textures, ctx->free_textures, rec);
     return PT_OK;
 }
 
@@ -876,7 +699,7 @@ int pt_scene_set_materials(pt_ctx* ctx, const pt_material* m, int count) {
             const pt_texture_sample& a = *slots[k];
             RTex& t = r.tex[k];
             if (a.descriptor == -1) {                     // unbound: a 1x1 white texel keeps the batched fetch branch-free
-                t.texels = ctx->d_white; t.width = 1; t.height = 1; t.flags = RT_POINT;
+                t.texels = ctx->d_white.as<uint32_t>(); t.width = 1; t.height = 1; t.flags = RT_POINT;
                 t.m00 = 0; t.m01 = 0; t.ox = 0; t.m10 = 0; t.m11 = 0; t.oy = 0;
                 continue;
             }
@@ -932,7 +755,7 @@ int pt_scene_set_materials(pt_ctx* ctx, const pt_material* m, int count) {
         r.bound_mask |= RM_TRIO | ((bn && (N.flags & RT_SRGB)) ? RM_TRIO_SRGB_N : 0u) | ((bm && (M.flags & RT_SRGB)) ? RM_TRIO_SRGB_M : 0u) |
                         (be ? (RM_TRIO_EMISSIVE | ((E.flags & RT_SRGB) ? RM_TRIO_SRGB_E : 0u)) : 0u);
     }
-    HIPOK(upload_table(ctx, ctx->d_rmats, ctx->rmats_cap, rm));
+    HIPOK(upload_table(ctx, ctx->d_rmats, rm));
     ctx->rmats_host.swap(rm);
     ctx->n_materials = count;
     // copies the new table no longer names: enqueued frames may still read them, so drain the stream first (a scene change, not a per-frame event)
@@ -947,222 +770,11 @@ int pt_scene_set_materials(pt_ctx* ctx, const pt_material* m, int count) {
     return PT_OK;
 }
 
-// diagnostic (not part of include/mipt.h): how many materials of the current table read the interleaved footprint
-extern "C" int pt_debug_interleaved_materials(const pt_ctx* ctx) {
-    int n = 0;
-    if (ctx) for (const RMat& r : ctx->rmats_host) n += (r.bound_mask & RM_TRIO) ? 1 : 0;
-    return n;
-}
-
-extern "C" int pt_debug_interleaved_emissive(const pt_ctx* ctx) {          // ... and how many of them carry their emissive texture in it
-    int n = 0;
-    if (ctx) for (const RMat& r : ctx->rmats_host) n += (r.bound_mask & RM_TRIO_EMISSIVE) ? 1 : 0;
-    return n;
-}
-
-// the scene as a traversal-only kernel needs it (pt_debug_intersect, pt_lens_focus_at)
-static void scene_for_rays(pt_ctx* ctx, SceneRec& sc) {
-    memset(&sc, 0, sizeof(sc));
-    sc.rmats = ctx->d_rmats; sc.lights = ctx->d_lights; sc.instances = ctx->d_instances;
-    sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
-    sc.nodes = ctx->d_nodes; sc.tris = ctx->d_tris; sc.shade = ctx->d_shade; sc.root = ctx->root; sc.num_tris = ctx->n_tris;
-    sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
-}
-
-// test hook (not part of include/mipt.h): the camera rays pt_trace would generate for the queries {px, py, seed} under `params` and the context's
-// lens (pt_set_lens) -- camera_ray itself, one query per lane (pt_kernel.hip k_debug_camera_rays).  queries: 3 uint32 each, out: 8 floats each
-// (origin, tmin, direction, tmax), host arrays.  Needs no scene; leaves the accumulation and a pending restart as they are.
-extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
-    if (!ctx || !settings || !params || (n && (!queries || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
-    CameraSetup cam;
-    if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
-    if (n == 0) return PT_OK;
-    ENTER(ctx);
-    FrameConstants fc;
-    memset(&fc, 0, sizeof(fc));
-    camera_constants(cam, params, fc);
-    uint32_t* d_q = nullptr; float* d_out = nullptr;
-    auto done = [&](int code, const std::string& why) { hipFree(d_q); hipFree(d_out); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
-    if (hipMalloc((void**)&d_q, (size_t)n * 12) != hipSuccess || hipMalloc((void**)&d_out, (size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_camera_rays: buffers"); }
-    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_camera_rays(fc, cam.lens, d_q, n, d_out, ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_camera_rays: ") + hipGetErrorString(e));
-}
-
-// test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
-// 8 floats per ray out, pt_kernel.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
-extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, uint32_t ray_flags, int mode, float* out) {
-    if (!ctx || (n && (!rays || !out)) || mode < 0 || mode > 1) return PT_ERR_INVALID_ARGUMENT;
-    ENTER(ctx);
-    if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
-    if (n == 0) return PT_OK;
-    SceneRec sc;
-    scene_for_rays(ctx, sc);
-    const uint32_t lanes = (n + 255u) & ~255u;
-    float *d_rays = nullptr, *d_out = nullptr; int32_t* d_deep = nullptr;
-    auto done = [&](int code, const std::string& why) { hipFree(d_rays); hipFree(d_out); hipFree(d_deep); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
-    if (hipMalloc((void**)&d_rays, (size_t)n * 32) != hipSuccess || hipMalloc((void**)&d_out, (size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: ray buffers"); }
-    if ((int)ctx->stack_need > traversal_stack_capacity()) {
-        const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
-        if (hipMalloc((void**)&d_deep, (size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: deep stack"); }
-        sc.deep_stack = d_deep; sc.deep_entries = entries; sc.deep_lanes = lanes;
-    }
-    hipError_t e = hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess && getenv("MIPT_DEBUG_INTERSECT_TIMING")) {           // probe (tools/ray_order_probe.py): the same launch timed, 5 repeats
-        hipEvent_t ev[2]; hipEventCreate(&ev[0]); hipEventCreate(&ev[1]);
-        hipEventRecord(ev[0], ctx->stream);
-        for (int k = 0; k < 5; k++) launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream);
-        hipEventRecord(ev[1], ctx->stream); hipEventSynchronize(ev[1]);
-        float ms = 0; hipEventElapsedTime(&ms, ev[0], ev[1]);
-        fprintf(stderr, "pt_debug_intersect: %u rays, %.3f ms per launch, %.1f Mrays/s\n", n, ms / 5, n / (ms / 5) * 1e-3);
-        hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
-}
-
-// test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
-// 2: the fused k_wf_traverse -- on queues the caller fills (pt_wavefront.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
-// (origin, tmin = 0: the queue format has none, direction, tmax) with the shard 0..255 each is queued in (the caller's order within a shard is
-// the queue's); shadow: n_s rays of 6 floats (origin, direction) with shard and is_light bit, one shadow_tmax for all.  flags: PT_FLAG_*;
-// bounce: of the closest rays (which 0, 2; the fused launch needs bounce >= 1 and takes the shadow rays of bounce - 1) or of the shadow rays
-// (which 1).  Ray flags, instance mask, kernel copy and counting are chosen by the code launch_wavefront runs.  out_closest: 8 floats per ray
-// as pt_debug_intersect's; out_shadow: the transmission written beside the ray's pending term; out_cnt: 256 x 7 counter words after the
-// launch; out_stray: 2 words, see pt_host.h.  Leaves the accumulation, the workspace and a pending restart of the context as they are.
-extern "C" int pt_debug_trace_queues(pt_ctx* ctx, const float* closest, const uint32_t* closest_shard, uint32_t n_c, const float* shadow, const uint32_t* shadow_shard,
-                                     const uint8_t* shadow_is_light, uint32_t n_s, float shadow_tmax, uint32_t flags, int bounce, uint32_t blocks_per_shard, int which,
-                                     float* out_closest, float* out_shadow, uint32_t* out_cnt, uint32_t* out_stray) {
-    if (which < 0 || which > 2 || blocks_per_shard < 1 || blocks_per_shard > 64 || bounce < 0 || (which == 2 && bounce < 1)) return PT_ERR_INVALID_ARGUMENT;
-    if ((n_c && (!closest || !closest_shard || !out_closest)) || (n_s && (!shadow || !shadow_shard || !shadow_is_light || !out_shadow)) || !out_cnt || !out_stray) return PT_ERR_INVALID_ARGUMENT;
-    if (n_c > 0x0fffffffu || n_s > 0x0fffffffu) return PT_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < n_c; i++) if (closest_shard[i] > 255u || closest[(size_t)i * 8 + 3] != 0.0f) return PT_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < n_s; i++) if (shadow_shard[i] > 255u) return PT_ERR_INVALID_ARGUMENT;
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    ENTER(ctx);
-    if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
-    SceneRec sc;
-    scene_for_rays(ctx, sc);                                   // has_env = 0: the traversal stages draw no environment samples
-    int32_t* d_deep = nullptr;
-    if ((int)ctx->stack_need > traversal_stack_capacity()) {    // the deep stack as pt_trace sets it up, for this launch's grid
-        const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
-        const size_t lanes = (size_t)256 * blocks_per_shard * 256;
-        if (hipMalloc((void**)&d_deep, (size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: deep stack"); }
-        sc.deep_stack = d_deep; sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
-    }
-    const DebugQueues q = {closest, closest_shard, n_c, shadow, shadow_shard, shadow_is_light, n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
-                           out_closest, out_shadow, out_cnt, out_stray};
-    std::string why;
-    const hipError_t e = debug_trace_queues(sc, q, ctx->d_counters, ctx->counters_enabled, ctx->stream, why);
-    hipFree(d_deep);
-    if (e == hipErrorOutOfMemory) return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: " + why);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, "pt_debug_trace_queues: " + why);
-}
-
-// test hook (not part of include/mipt.h): the shade stage's texture sampler on caller-supplied queries, one per lane (pt_shading.h
-// debug_sample_query).  mat_slot: 2 per query (material, slot 0..14 or 16..19); tc: 4 per query (tc0.xy, tc1.xy); out_rgba: 4 per query;
-// out_taps (may be null): 5 per query (i0, i1, j0, j1, and ia: the first column of the texel pair loaded for each row).  unit 0: the wavefront stages' build (tables in LDS), 1: the megakernel's.
-extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* mat_slot, const float* tc, uint32_t n, float* out_rgba, int32_t* out_taps) {
-    if (!ctx || unit < 0 || unit > 1 || (n && (!mat_slot || !tc || !out_rgba))) return PT_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t mat = mat_slot[2 * i], slot = mat_slot[2 * i + 1];
-        if (mat >= (uint32_t)ctx->n_materials || !(slot < (uint32_t)SLOT_COUNT || (slot >= 16u && slot <= 19u)))
-            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_sample_texture: query " + std::to_string(i) + " names material " + std::to_string(mat) +
-                                                      " slot " + std::to_string(slot) + " (" + std::to_string(ctx->n_materials) + " materials)");
-    }
-    ENTER(ctx);
-    if (n == 0) return PT_OK;
-    SceneRec sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.rmats = ctx->d_rmats; sc.n_materials = (uint32_t)ctx->n_materials;
-    sc.sheen_e = ctx->d_sheen; sc.srgb_lut = ctx->d_srgb; sc.tangent_lut = ctx->d_tangent_lut;
-    uint32_t* d_ms = nullptr; float *d_tc = nullptr, *d_out = nullptr; int32_t* d_taps = nullptr;
-    auto done = [&](int code, const std::string& why) { hipFree(d_ms); hipFree(d_tc); hipFree(d_out); hipFree(d_taps); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
-    if (hipMalloc((void**)&d_ms, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_tc, (size_t)n * 16) != hipSuccess ||
-        hipMalloc((void**)&d_out, (size_t)n * 16) != hipSuccess || hipMalloc((void**)&d_taps, (size_t)n * 20) != hipSuccess) {
-        (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_sample_texture: query buffers");
-    }
-    hipError_t e = hipMemcpyAsync(d_ms, mat_slot, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tc, tc, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_sample_texture_wf(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
-        else launch_debug_sample_texture_mk(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && out_taps) e = hipMemcpyAsync(out_taps, d_taps, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_sample_texture: ") + hipGetErrorString(e));
-}
-
-// test hook (not part of include/mipt.h): the environment light on caller-supplied queries, one per lane (pt_vertex.h debug_env_query:
-// op 0 SAMPLE, 1 PDF, 2 CUBE, 3 MISS; 8 input and 16 output floats per query).  unit 0: the wavefront stages' build (the coarse pyramid
-// levels staged into LDS as env_prepass stages them), 1: the megakernel's (global memory).
-extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const float* in, uint32_t n, float* out) {
-    if (!ctx || unit < 0 || unit > 1 || op < 0 || op > 3 || (n && (!in || !out))) return PT_ERR_INVALID_ARGUMENT;
-    if (env < 0 || env >= (int)ctx->envs.size() || !ctx->envs[env]) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_query: environment " + std::to_string(env));
-    ENTER(ctx);
-    if (n == 0) return PT_OK;
-    const EnvDevice& ed = *ctx->envs[env];
-    SceneRec sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.env.cube = ed.cube; sc.env.cube_n = ed.mip_n[0]; sc.env.importance = ed.importance;
-    for (int i = 0; i < 12; i++) sc.env.level_offset[i] = ed.level_offset[i];
-    sc.env.imp_res = ed.imp_res; sc.env.imp_levels = ed.levels; sc.env.imp_total = ed.total;
-    sc.env.blocked = ed.blocked;
-    for (int i = 0; i < 5; i++) sc.env.blocked_offset[i] = ed.blocked_offset[i];
-    sc.has_env = 1;
-    const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 16 * 4;
-    float *d_in = nullptr, *d_out = nullptr;
-    auto done = [&](int code, const std::string& why) { hipFree(d_in); hipFree(d_out); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
-    if (hipMalloc((void**)&d_in, in_bytes) != hipSuccess || hipMalloc((void**)&d_out, out_bytes) != hipSuccess) {
-        (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "pt_debug_env_query: query buffers");
-    }
-    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, ctx->stream);      // unused outputs keep the caller's values
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in, n, d_out, ctx->stream);
-        else launch_debug_env_query_mk(sc, op, d_in, n, d_out, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return done(e == hipSuccess ? PT_OK : PT_ERR_DEVICE, std::string("pt_debug_env_query: ") + hipGetErrorString(e));
-}
-
-// test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid
-// (level 0 first), as the oracle's orc_env_create_raw takes them -- so both sides can sample a crafted pyramid.
-extern "C" int pt_debug_env_create_raw(pt_ctx* ctx, int cube_n, const uint16_t* cube_rgba16f, const float* pyramid, int* env_out) {
-    if (!ctx || cube_n < 1 || cube_n > 16384 || !cube_rgba16f || !pyramid || !env_out) return PT_ERR_INVALID_ARGUMENT;
-    ENTER(ctx);
-    EnvDevice* env = new EnvDevice();
-    hipError_t e = env_build_raw(*env, cube_n, cube_rgba16f, pyramid, ctx->stream);
-    if (e) { env_free(*env); delete env; return ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_create_raw: ") + hipGetErrorString(e)); }
-    if (!ctx->free_envs.empty()) { *env_out = ctx->free_envs.back(); ctx->free_envs.pop_back(); ctx->envs[*env_out] = env; }
-    else { ctx->envs.push_back(env); *env_out = (int)ctx->envs.size() - 1; }
-    return PT_OK;
-}
-
-// test hook (not part of include/mipt.h): the five 4x4-blocked copies of pyramid levels 8, 6, 4, 2, 0 (EnvRec::blocked: 4^2 + 16^2 + 64^2 +
-// 256^2 + 1024^2 = 1118480 floats, coarsest first), as the sampler reads them.
-extern "C" int pt_debug_env_read_blocked(pt_ctx* ctx, int env, float* out) {
-    if (!ctx || !out) return PT_ERR_INVALID_ARGUMENT;
-    if (env < 0 || env >= (int)ctx->envs.size() || !ctx->envs[env]) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_read_blocked: environment " + std::to_string(env));
-    ENTER(ctx);
-    HIPOK(hipStreamSynchronize(ctx->stream));
-    const EnvDevice& ed = *ctx->envs[env];
-    HIPOK(hipMemcpy(out, ed.blocked, (size_t)(ed.blocked_offset[4] + 1024u * 1024u) * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
 int pt_scene_set_lights(pt_ctx* ctx, const pt_light* l, int count) {
     if (!ctx || (count > 0 && !l) || count < 0) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);
     std::vector<pt_light> h(l, l + count);
-    HIPOK(upload_table(ctx, ctx->d_lights, ctx->lights_cap, h));
+    HIPOK(upload_table(ctx, ctx->d_lights, h));
     ctx->n_lights = count;
     return PT_OK;
 }
@@ -1260,12 +872,9 @@ int pt_env_create(pt_ctx* ctx, const float* rgb, int width, int height, int* env
     if (!e) e = hipStreamSynchronize(ctx->stream);
     hipFree(d);
     if (e) { env_free(*env); delete env; return ctx->fail(PT_ERR_DEVICE, std::string("pt_env_create: ") + hipGetErrorString(e)); }
-    if (!ctx->free_envs.empty()) { *env_out = ctx->free_envs.back(); ctx->free_envs.pop_back(); ctx->envs[*env_out] = env; }
-    else { ctx->envs.push_back(env); *env_out = (int)ctx->envs.size() - 1; }
+    *env_out = take_slot(ctx->envs, ctx->free_envs, env);
     return PT_OK;
 }
-
-static bool live_env(const pt_ctx* ctx, int env) { return env >= 0 && env < (int)ctx->envs.size() && ctx->envs[env] != nullptr; }
 
 // EnvironmentMap::Destroy: the maps of one environment (the reference replaces its single environment map in place when a new
 // image is loaded, Source/EnvironmentMap.cpp:84-130).
@@ -1383,29 +992,25 @@ int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_
     CameraSetup cam;
     if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
     ENTER(ctx);
-    if (ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty) { int r = Pathtracer::BuildAccel(ctx); if (r) return r; }
-    SceneRec sc;
-    scene_for_rays(ctx, sc);
+    if (int r = ensure_accel(ctx)) return r;
+    SceneRec sc = scene_fill(ctx);
     FrameConstants fc;
-    memset(&fc, 0, sizeof(fc));
     camera_constants(cam, params, fc);
-    float* d_out = nullptr; int32_t* d_deep = nullptr;
-    auto done = [&](int code, const std::string& why) { hipFree(d_out); hipFree(d_deep); return code == PT_OK ? PT_OK : ctx->fail(code, why); };
-    if (hipMalloc((void**)&d_out, 8) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: result buffer"); }
-    if ((int)ctx->stack_need > traversal_stack_capacity()) {
-        const uint32_t entries = (ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u;
-        if (hipMalloc((void**)&d_deep, (size_t)entries * 256 * 4) != hipSuccess) { (void)hipGetLastError(); return done(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: deep stack"); }
-        sc.deep_stack = d_deep; sc.deep_entries = entries; sc.deep_lanes = 256;
+    TempBuf d_out, d_deep;
+    if (d_out.alloc(8) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: result buffer"); }
+    if (const uint32_t entries = deep_stack_entries(ctx)) {
+        if (d_deep.alloc((size_t)entries * 256 * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: deep stack"); }
+        sc.deep_stack = d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = 256;
     }
-    launch_lens_focus(sc, fc, cam.lens, px, py, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, d_out, ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
+    launch_lens_focus(sc, fc, cam.lens, px, py, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, d_out.as<float>(), ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
     float res[2] = {0.0f, 0.0f};
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(res, d_out.ptr, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(PT_ERR_DEVICE, std::string("lens_focus_at: ") + hipGetErrorString(e));
-    if (res[0] == 0.0f) return done(PT_ERR_NOT_READY, "lens_focus_at: the ray hits nothing");
+    if (e != hipSuccess) return ctx->fail(PT_ERR_DEVICE, std::string("lens_focus_at: ") + hipGetErrorString(e));
+    if (res[0] == 0.0f) return ctx->fail(PT_ERR_NOT_READY, "lens_focus_at: the ray hits nothing");
     *focus_distance_out = res[1];
-    return done(PT_OK, "");
+    return PT_OK;
 }
 
 int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* active_tiles, uint32_t* tile_samples, float* tile_error, float* half_rgba32f) {
@@ -1415,7 +1020,7 @@ int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* acti
     ENTER(ctx);
     HIPOK(hipStreamSynchronize(ctx->stream));
     std::vector<AdaptiveTile> t(ctx->ad_my_tiles);
-    if (!t.empty()) HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
+    if (!t.empty()) HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles.ptr, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
     const size_t ntiles = (size_t)((width + PT_TILE - 1) / PT_TILE) * ((height + PT_TILE - 1) / PT_TILE);
     if (tile_samples) memset(tile_samples, 0, ntiles * sizeof(uint32_t));
     if (tile_error) memset(tile_error, 0, ntiles * sizeof(float));
@@ -1428,7 +1033,7 @@ int pt_adaptive_read(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* acti
         active += t[l].active ? 1 : 0;
     }
     if (active_tiles) *active_tiles = active;
-    if (half_rgba32f) HIPOK(hipMemcpy(half_rgba32f, ctx->d_ad_half, (size_t)width * height * 16, hipMemcpyDeviceToHost));
+    if (half_rgba32f) HIPOK(hipMemcpy(half_rgba32f, ctx->d_ad_half.ptr, (size_t)width * height * 16, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -1461,7 +1066,7 @@ int pt_enable_stage_timing(pt_ctx* ctx, int enable) {
 int pt_reset_stats(pt_ctx* ctx) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);
-    HIPOK(hipMemsetAsync(ctx->d_counters, 0, sizeof(Counters), ctx->stream));
+    HIPOK(hipMemsetAsync(ctx->d_counters.ptr, 0, sizeof(Counters), ctx->stream));
     return PT_OK;
 }
 
@@ -1470,7 +1075,7 @@ int pt_get_stats(pt_ctx* ctx, pt_stats* out) {
     ENTER(ctx);
     HIPOK(hipStreamSynchronize(ctx->stream));
     Counters c;
-    HIPOK(hipMemcpy(&c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(&c, ctx->d_counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
     memset(out, 0, sizeof(*out));
     out->rays_primary = c.rays_primary; out->rays_bounce = c.rays_bounce; out->rays_shadow = c.rays_shadow;
     out->rays = c.rays_primary + c.rays_bounce + c.rays_shadow;
@@ -1487,8 +1092,7 @@ int pt_get_stats(pt_ctx* ctx, pt_stats* out) {
     out->bvh_nodes = ctx->wide_nodes;
     out->bvh_triangles = ctx->n_tris;
     out->bvh_stack_need = ctx->stack_need;
-    out->bvh_stack_capacity = (int)ctx->stack_need > traversal_stack_capacity() ? ((ctx->stack_need - (uint32_t)traversal_stack_capacity() + 7u) & ~7u) + (uint32_t)traversal_stack_capacity()
-                                                                               : (uint32_t)traversal_stack_capacity();
+    out->bvh_stack_capacity = deep_stack_entries(ctx) + (uint32_t)traversal_stack_capacity();
     out->accel_builder_fallbacks = ctx->scratch.fallbacks;
     out->deep_stack_pushes = c.deep_pushes;
     out->accel_builds = ctx->accel_builds; out->accel_refits = ctx->accel_refits;
@@ -1508,14 +1112,9 @@ int pt_tonemap(pt_ctx* ctx, const pt_tonemap_config* cfg, const void* device_rgb
     if (!ctx || !cfg || !device_rgba32f || width == 0 || height == 0) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);
     const size_t n = (size_t)width * height, need = n * 16;      // float RGB (12 B) + RGBA8 (4 B) per pixel, kept between calls
-    if (need > ctx->tonemap_cap) {
-        HIPOK(hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->d_tonemap); ctx->d_tonemap = nullptr; ctx->tonemap_cap = 0;
-        HIPOK(hipMalloc(&ctx->d_tonemap, need));
-        ctx->tonemap_cap = need;
-    }
-    float* d_rgb = host_rgb ? (float*)ctx->d_tonemap : nullptr;
-    uint32_t* d_q = host_rgba8 ? (uint32_t*)((char*)ctx->d_tonemap + n * 12) : nullptr;
+    HIPOK(ctx->d_tonemap.reserve(ctx->stream, need, need));
+    float* d_rgb = host_rgb ? ctx->d_tonemap.as<float>() : nullptr;
+    uint32_t* d_q = host_rgba8 ? (uint32_t*)(ctx->d_tonemap.as<char>() + n * 12) : nullptr;
     launch_tonemap((const float4*)device_rgba32f, width, height, *cfg, d_rgb, d_q, ctx->stream);
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(ctx->stream));
@@ -1549,25 +1148,16 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config, const void* color, 
         if (out != color) HIPOK(hipMemcpyAsync(out, color, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         return PT_OK;
     }
-    if (n != ctx->dn_pixels) {
-        HIPOK(hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->d_denoise); ctx->d_denoise = nullptr; ctx->dn_pixels = 0;
-        HIPOK(hipMalloc(&ctx->d_denoise, 3 * bytes));
-        ctx->dn_pixels = n;
-    }
-    float4* s = ctx->d_denoise;
+    if (3 * bytes != ctx->d_denoise.cap) HIPOK(ctx->d_denoise.realloc(ctx->stream, 3 * bytes));      // for this size alone: a smaller image reallocates too
+    float4* s = ctx->d_denoise.as<float4>();
     HIPOK(launch_denoise(cfg, (const float4*)color, (const float4*)albedo, (const float4*)normal_depth, width, height, (float4*)out, s, s + n, s + 2 * n, ctx->stream));
     return PT_OK;
 }
 
 // ---- saving and resuming an accumulation (host/accum_state.h holds the format and its validator) ----------------------------------
 static int accum_scratch(pt_ctx* ctx, size_t need) {
-    if (need <= ctx->accum_cap) return PT_OK;
-    HIPOK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->d_accum); ctx->d_accum = nullptr; ctx->accum_cap = 0;
-    if (hipMalloc(&ctx->d_accum, need) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "accumulation scratch: " + std::to_string(need) + " bytes"); }
-    ctx->accum_cap = need;
-    return PT_OK;
+    const hipError_t e = ctx->d_accum.reserve(ctx->stream, need, need);
+    return e == hipSuccess ? PT_OK : grow_failed(ctx, e, "accumulation scratch: " + std::to_string(need) + " bytes");
 }
 
 int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, uint32_t height, uint32_t tile_rank, uint32_t tile_rank_count,
@@ -1597,7 +1187,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     if (!host_blob) return PT_OK;
     if ((uint64_t)capacity < l.total_bytes) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: capacity below the " + std::to_string(l.total_bytes) + " bytes needed");
     ENTER(ctx);
-    const void* src[4] = {images->output, images->albedo, images->normal_depth, adaptive ? ctx->d_ad_half : nullptr};
+    const void* src[4] = {images->output, images->albedo, images->normal_depth, adaptive ? ctx->d_ad_half.ptr : nullptr};
     const uint64_t at[4] = {l.image[0], l.image[1], l.image[2], l.half};
     const size_t P = (size_t)l.packed_bytes;
     int slot[4], slots = 0;                       // one packed image of scratch per section present
@@ -1606,16 +1196,16 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
         int r = accum_scratch(ctx, slots * P);
         if (r) return r;
         for (int k = 0; k < 4; k++)
-            if (src[k]) HIPOK(tiles_pack(src[k], width, height, tile_rank, world, (char*)ctx->d_accum + slot[k] * P, ctx->stream));
+            if (src[k]) HIPOK(tiles_pack(src[k], width, height, tile_rank, world, ctx->d_accum.as<char>() + slot[k] * P, ctx->stream));
     }
     HIPOK(hipStreamSynchronize(ctx->stream));
     accum::write_header(host_blob, info, ctx->previous_world_to_clip);
     for (int k = 0; k < 4 && P; k++)
-        if (src[k]) HIPOK(hipMemcpy((char*)host_blob + at[k], (char*)ctx->d_accum + slot[k] * P, P, hipMemcpyDeviceToHost));
+        if (src[k]) HIPOK(hipMemcpy((char*)host_blob + at[k], ctx->d_accum.as<char>() + slot[k] * P, P, hipMemcpyDeviceToHost));
     if (adaptive && info.tiles) {
         static_assert(sizeof(AdaptiveTile) == accum::kRecordBytes, "a tile record is an AdaptiveTile");
         std::vector<AdaptiveTile> t(info.tiles);
-        HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
+        HIPOK(hipMemcpy(t.data(), ctx->d_ad_tiles.ptr, t.size() * sizeof(AdaptiveTile), hipMemcpyDeviceToHost));
         for (AdaptiveTile& x : t) x.pad = 0;
         memcpy((char*)host_blob + l.records, t.data(), t.size() * sizeof(AdaptiveTile));
     }
@@ -1654,28 +1244,19 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
     int slot[4], slots = 0;                       // one packed image of scratch per section present
     for (int k = 0; k < 4; k++) slot[k] = out[k] ? slots++ : -1;
     if (P) { int r = accum_scratch(ctx, slots * P); if (r) return r; }
-    if (adaptive && (tiles > ctx->ad_tiles_cap || px > ctx->ad_half_cap)) {         // grown as PathtraceScene grows them
-        HIPOK(hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->d_ad_tiles); hipFree(ctx->d_ad_half);
-        ctx->d_ad_tiles = nullptr; ctx->d_ad_half = nullptr; ctx->ad_tiles_cap = ctx->ad_half_cap = 0; ctx->ad_ready = false;
-        if (hipMalloc((void**)&ctx->d_ad_tiles, tiles * sizeof(AdaptiveTile)) != hipSuccess || hipMalloc((void**)&ctx->d_ad_half, px * 16) != hipSuccess) {
-            (void)hipGetLastError();
-            return ctx->fail(PT_ERR_OUT_OF_MEMORY, "adaptive tile state");
-        }
-        ctx->ad_tiles_cap = tiles; ctx->ad_half_cap = px;
-    }
+    if (adaptive) { int r = adaptive_state(ctx, tiles, px); if (r) return r; }                     // grown as PathtraceScene grows them
     // every check has passed.  The caller may free the blob on return: its bytes are on the device before that, the unpacking is enqueued.
     const uint64_t at[4] = {l.image[0], l.image[1], l.image[2], l.half};
-    out[3] = adaptive ? (void*)ctx->d_ad_half : nullptr;
+    out[3] = adaptive ? ctx->d_ad_half.ptr : nullptr;
     for (int k = 0; k < 4 && P; k++)
-        if (out[k]) HIPOK(hipMemcpyAsync((char*)ctx->d_accum + slot[k] * P, (const char*)host_blob + at[k], P, hipMemcpyHostToDevice, ctx->stream));
+        if (out[k]) HIPOK(hipMemcpyAsync(ctx->d_accum.as<char>() + slot[k] * P, (const char*)host_blob + at[k], P, hipMemcpyHostToDevice, ctx->stream));
     if (adaptive) {
-        if (info.tiles) HIPOK(hipMemcpyAsync(ctx->d_ad_tiles, (const char*)host_blob + l.records, info.tiles * sizeof(AdaptiveTile), hipMemcpyHostToDevice, ctx->stream));
-        HIPOK(hipMemsetAsync(ctx->d_ad_half, 0, px * 16, ctx->stream));            // other ranks' pixels: as a new accumulation leaves them
+        if (info.tiles) HIPOK(hipMemcpyAsync(ctx->d_ad_tiles.ptr, (const char*)host_blob + l.records, info.tiles * sizeof(AdaptiveTile), hipMemcpyHostToDevice, ctx->stream));
+        HIPOK(hipMemsetAsync(ctx->d_ad_half.ptr, 0, px * 16, ctx->stream));        // other ranks' pixels: as a new accumulation leaves them
     }
     HIPOK(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 4 && P; k++)
-        if (out[k]) HIPOK(tiles_unpack((char*)ctx->d_accum + slot[k] * P, info.width, info.height, info.tile_rank, info.tile_rank_count, out[k], ctx->stream));
+        if (out[k]) HIPOK(tiles_unpack(ctx->d_accum.as<char>() + slot[k] * P, info.width, info.height, info.tile_rank, info.tile_rank_count, out[k], ctx->stream));
     ctx->accumulated_frames = info.accumulated_frames;
     memcpy(ctx->previous_world_to_clip, world_to_clip, 64);
     if (adaptive) {

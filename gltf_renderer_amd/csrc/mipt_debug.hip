@@ -1,0 +1,192 @@
+// mipt_debug.hip -- the test hooks of libmipt.so (pt_debug_*, not part of include/mipt.h): the product's own device code run on the
+// caller's queries, for tests/ and tools/ to compare with the oracle.  Host code only: this file has no kernel; what the hooks launch is in
+// pt_kernel.hip and pt_wavefront.hip.  The product itself is mipt_api.hip.
+#include <cstdio>
+#include <cstdlib>
+
+#include "pt_ctx.h"
+
+using namespace pt;
+
+// diagnostic (not part of include/mipt.h): how many materials of the current table read the interleaved footprint
+extern "C" int pt_debug_interleaved_materials(const pt_ctx* ctx) {
+    int n = 0;
+    if (ctx) for (const RMat& r : ctx->rmats_host) n += (r.bound_mask & RM_TRIO) ? 1 : 0;
+    return n;
+}
+
+extern "C" int pt_debug_interleaved_emissive(const pt_ctx* ctx) {          // ... and how many of them carry their emissive texture in it
+    int n = 0;
+    if (ctx) for (const RMat& r : ctx->rmats_host) n += (r.bound_mask & RM_TRIO_EMISSIVE) ? 1 : 0;
+    return n;
+}
+
+// test hook (not part of include/mipt.h): the camera rays pt_trace would generate for the queries {px, py, seed} under `params` and the context's
+// lens (pt_set_lens) -- camera_ray itself, one query per lane (pt_kernel.hip k_debug_camera_rays).  queries: 3 uint32 each, out: 8 floats each
+// (origin, tmin, direction, tmax), host arrays.  Needs no scene; leaves the accumulation and a pending restart as they are.
+extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
+    if (!ctx || !settings || !params || (n && (!queries || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
+    CameraSetup cam;
+    if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+    if (n == 0) return PT_OK;
+    ENTER(ctx);
+    FrameConstants fc;
+    camera_constants(cam, params, fc);
+    TempBuf d_q, d_out;
+    if (d_q.alloc((size_t)n * 12) != hipSuccess || d_out.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_camera_rays: buffers"); }
+    hipError_t e = hipMemcpyAsync(d_q.ptr, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) { launch_debug_camera_rays(fc, cam.lens, d_q.as<uint32_t>(), n, d_out.as<float>(), ctx->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_camera_rays: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
+// 8 floats per ray out, pt_kernel.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
+extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, uint32_t ray_flags, int mode, float* out) {
+    if (!ctx || (n && (!rays || !out)) || mode < 0 || mode > 1) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    if (n == 0) return PT_OK;
+    SceneRec sc = scene_fill(ctx);
+    const uint32_t lanes = (n + 255u) & ~255u;
+    TempBuf rays_buf, out_buf, deep_buf;
+    if (rays_buf.alloc((size_t)n * 32) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: ray buffers"); }
+    if (const uint32_t entries = deep_stack_entries(ctx)) {
+        if (deep_buf.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: deep stack"); }
+        sc.deep_stack = deep_buf.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = lanes;
+    }
+    float *d_rays = rays_buf.as<float>(), *d_out = out_buf.as<float>();
+    hipError_t e = hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) { launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream); e = hipGetLastError(); }
+    if (e == hipSuccess && getenv("MIPT_DEBUG_INTERSECT_TIMING")) {           // probe (tools/ray_order_probe.py): the same launch timed, 5 repeats
+        hipEvent_t ev[2]; hipEventCreate(&ev[0]); hipEventCreate(&ev[1]);
+        hipEventRecord(ev[0], ctx->stream);
+        for (int k = 0; k < 5; k++) launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream);
+        hipEventRecord(ev[1], ctx->stream); hipEventSynchronize(ev[1]);
+        float ms = 0; hipEventElapsedTime(&ms, ev[0], ev[1]);
+        fprintf(stderr, "pt_debug_intersect: %u rays, %.3f ms per launch, %.1f Mrays/s\n", n, ms / 5, n / (ms / 5) * 1e-3);
+        hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
+// 2: the fused k_wf_traverse -- on queues the caller fills (pt_wavefront.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
+// (origin, tmin = 0: the queue format has none, direction, tmax) with the shard 0..255 each is queued in (the caller's order within a shard is
+// the queue's); shadow: n_s rays of 6 floats (origin, direction) with shard and is_light bit, one shadow_tmax for all.  flags: PT_FLAG_*;
+// bounce: of the closest rays (which 0, 2; the fused launch needs bounce >= 1 and takes the shadow rays of bounce - 1) or of the shadow rays
+// (which 1).  Ray flags, instance mask, kernel copy and counting are chosen by the code launch_wavefront runs.  out_closest: 8 floats per ray
+// as pt_debug_intersect's; out_shadow: the transmission written beside the ray's pending term; out_cnt: 256 x 7 counter words after the
+// launch; out_stray: 2 words, see pt_host.h.  Leaves the accumulation, the workspace and a pending restart of the context as they are.
+extern "C" int pt_debug_trace_queues(pt_ctx* ctx, const float* closest, const uint32_t* closest_shard, uint32_t n_c, const float* shadow, const uint32_t* shadow_shard,
+                                     const uint8_t* shadow_is_light, uint32_t n_s, float shadow_tmax, uint32_t flags, int bounce, uint32_t blocks_per_shard, int which,
+                                     float* out_closest, float* out_shadow, uint32_t* out_cnt, uint32_t* out_stray) {
+    if (which < 0 || which > 2 || blocks_per_shard < 1 || blocks_per_shard > 64 || bounce < 0 || (which == 2 && bounce < 1)) return PT_ERR_INVALID_ARGUMENT;
+    if ((n_c && (!closest || !closest_shard || !out_closest)) || (n_s && (!shadow || !shadow_shard || !shadow_is_light || !out_shadow)) || !out_cnt || !out_stray) return PT_ERR_INVALID_ARGUMENT;
+    if (n_c > 0x0fffffffu || n_s > 0x0fffffffu) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n_c; i++) if (closest_shard[i] > 255u || closest[(size_t)i * 8 + 3] != 0.0f) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n_s; i++) if (shadow_shard[i] > 255u) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    SceneRec sc = scene_fill(ctx);                         // has_env = 0: the traversal stages draw no environment samples
+    TempBuf d_deep;
+    if (const uint32_t entries = deep_stack_entries(ctx)) {    // the deep stack as pt_trace sets it up, for this launch's grid
+        const size_t lanes = (size_t)256 * blocks_per_shard * 256;
+        if (d_deep.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: deep stack"); }
+        sc.deep_stack = d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
+    }
+    const DebugQueues q = {closest, closest_shard, n_c, shadow, shadow_shard, shadow_is_light, n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
+                           out_closest, out_shadow, out_cnt, out_stray};
+    std::string why;
+    const hipError_t e = debug_trace_queues(sc, q, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->stream, why);
+    if (e == hipErrorOutOfMemory) return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: " + why);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, "pt_debug_trace_queues: " + why);
+}
+
+// test hook (not part of include/mipt.h): the shade stage's texture sampler on caller-supplied queries, one per lane (pt_shading.h
+// debug_sample_query).  mat_slot: 2 per query (material, slot 0..14 or 16..19); tc: 4 per query (tc0.xy, tc1.xy); out_rgba: 4 per query;
+// out_taps (may be null): 5 per query (i0, i1, j0, j1, and ia: the first column of the texel pair loaded for each row).  unit 0: the wavefront stages' build (tables in LDS), 1: the megakernel's.
+extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* mat_slot, const float* tc, uint32_t n, float* out_rgba, int32_t* out_taps) {
+    if (!ctx || unit < 0 || unit > 1 || (n && (!mat_slot || !tc || !out_rgba))) return PT_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t mat = mat_slot[2 * i], slot = mat_slot[2 * i + 1];
+        if (mat >= (uint32_t)ctx->n_materials || !(slot < (uint32_t)SLOT_COUNT || (slot >= 16u && slot <= 19u)))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_sample_texture: query " + std::to_string(i) + " names material " + std::to_string(mat) +
+                                                      " slot " + std::to_string(slot) + " (" + std::to_string(ctx->n_materials) + " materials)");
+    }
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    const SceneRec sc = scene_fill(ctx);                   // (the sampler reads the materials and the lookup tables)
+    TempBuf ms_buf, tc_buf, out_buf, taps_buf;
+    if (ms_buf.alloc((size_t)n * 8) != hipSuccess || tc_buf.alloc((size_t)n * 16) != hipSuccess || out_buf.alloc((size_t)n * 16) != hipSuccess ||
+        taps_buf.alloc((size_t)n * 20) != hipSuccess) {
+        (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_sample_texture: query buffers");
+    }
+    uint32_t* d_ms = ms_buf.as<uint32_t>(); float *d_tc = tc_buf.as<float>(), *d_out = out_buf.as<float>(); int32_t* d_taps = taps_buf.as<int32_t>();
+    hipError_t e = hipMemcpyAsync(d_ms, mat_slot, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tc, tc, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_sample_texture_wf(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
+        else launch_debug_sample_texture_mk(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && out_taps) e = hipMemcpyAsync(out_taps, d_taps, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_sample_texture: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): the environment light on caller-supplied queries, one per lane (pt_vertex.h debug_env_query:
+// op 0 SAMPLE, 1 PDF, 2 CUBE, 3 MISS; 8 input and 16 output floats per query).  unit 0: the wavefront stages' build (the coarse pyramid
+// levels staged into LDS as env_prepass stages them), 1: the megakernel's (global memory).
+extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const float* in, uint32_t n, float* out) {
+    if (!ctx || unit < 0 || unit > 1 || op < 0 || op > 3 || (n && (!in || !out))) return PT_ERR_INVALID_ARGUMENT;
+    if (!live_env(ctx, env)) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_query: environment " + std::to_string(env));
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    SceneRec sc;
+    memset(&sc, 0, sizeof(sc));
+    scene_set_env(sc, *ctx->envs[env]);
+    const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 16 * 4;
+    TempBuf in_buf, out_buf;
+    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_env_query: query buffers"); }
+    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
+    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, ctx->stream);      // unused outputs keep the caller's values
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in, n, d_out, ctx->stream);
+        else launch_debug_env_query_mk(sc, op, d_in, n, d_out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_query: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid
+// (level 0 first), as the oracle's orc_env_create_raw takes them -- so both sides can sample a crafted pyramid.
+extern "C" int pt_debug_env_create_raw(pt_ctx* ctx, int cube_n, const uint16_t* cube_rgba16f, const float* pyramid, int* env_out) {
+    if (!ctx || cube_n < 1 || cube_n > 16384 || !cube_rgba16f || !pyramid || !env_out) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    EnvDevice* env = new EnvDevice();
+    hipError_t e = env_build_raw(*env, cube_n, cube_rgba16f, pyramid, ctx->stream);
+    if (e) { env_free(*env); delete env; return ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_create_raw: ") + hipGetErrorString(e)); }
+    *env_out = take_slot(ctx->envs, ctx->free_envs, env);
+    return PT_OK;
+}
+
+// test hook (not part of include/mipt.h): the five 4x4-blocked copies of pyramid levels 8, 6, 4, 2, 0 (EnvRec::blocked: 4^2 + 16^2 + 64^2 +
+// 256^2 + 1024^2 = 1118480 floats, coarsest first), as the sampler reads them.
+extern "C" int pt_debug_env_read_blocked(pt_ctx* ctx, int env, float* out) {
+    if (!ctx || !out) return PT_ERR_INVALID_ARGUMENT;
+    if (!live_env(ctx, env)) return ctx->fail(PT_ERR_BAD_HANDLE, "pt_debug_env_read_blocked: environment " + std::to_string(env));
+    ENTER(ctx);
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const EnvDevice& ed = *ctx->envs[env];
+    HIPOK(hipMemcpy(out, ed.blocked, (size_t)(ed.blocked_offset[4] + 1024u * 1024u) * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}

@@ -1,0 +1,176 @@
+// pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what both of its translation units need of it: mipt_api.hip (the product)
+// and mipt_debug.hip (the test hooks).  Internal to those two.
+#pragma once
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "dev_buf.h"
+#include "pt_host.h"
+
+// Pinned upload slots for the per-frame tables (materials, lights, instances, bones, vertex updates).  The reference hands those
+// over in a transient upload heap that stays valid for the frame (Source/Renderer.cpp:490,496); here the caller's memory may be
+// reused as soon as the call returns, so the bytes are copied into a pinned slot and go to the device asynchronously.  The host
+// only ever waits when it comes round to a slot whose copy is still in flight -- not once per call.
+struct StagingRing {
+    static constexpr int kSlots = 8;
+    void* host[kSlots] = {};
+    size_t cap[kSlots] = {};
+    hipEvent_t done[kSlots] = {};
+    bool pending[kSlots] = {};
+    int next = 0;
+};
+
+enum AccelState { ACCEL_CLEAN = 0, ACCEL_REFIT = 1, ACCEL_REBUILD = 2 };
+
+// Every device array below that is not handle-indexed is a DevBuf: it carries its capacity and goes with the context (pt_destroy).
+struct pt_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string error;
+    StagingRing staging;
+
+    // ---- ResourceTable ("descriptor heap")
+    std::vector<pt::BufferRec> buffers;
+    std::vector<pt::TextureRec> textures;
+    std::vector<pt::SamplerRec> samplers;
+    pt::DevBuf d_buffers; bool buffers_dirty = true;               // device copy (BufferRec): BVH build only
+    pt::DevBuf d_white;                                            // 1x1 white texel behind every unbound material slot
+    // interleaved albedo / normal / metal-rough texels of the materials whose three textures share one footprint (pt_types.h RM_TRIO),
+    // keyed by the three texel pointers (nullptr = slot unbound); owned here, rebuilt / released by pt_scene_set_materials
+    struct TrioRec { const uint32_t *a, *n, *m, *e; uint4* ptr; };
+    std::vector<TrioRec> trios;
+
+    // ---- per-frame arrays (Renderer::GatherMaterials / GatherLights)
+    pt::DevBuf d_rmats; int n_materials = 0;                       // RMat, resolved on the host in pt_scene_set_materials
+    std::vector<pt::RMat> rmats_host;                              // what was uploaded (pt_texture_destroy checks it)
+    pt::DevBuf d_lights; int n_lights = 0;                         // pt_light
+
+    // ---- instance table + acceleration structure
+    std::vector<pt::InstanceRec> instances;
+    pt::DevBuf d_instances;                                        // InstanceRec
+    uint32_t n_tris = 0;
+    pt::DevBuf d_nodes, d_tris, d_shade;                           // Bvh4Node, TriPacket, ShadePacket: one capacity in triangles for the three
+    uint32_t wide_nodes = 0, stack_need = 0;
+    int32_t root = 0;
+    pt::AccelScratch scratch;
+    // What the next pt_build_accel / pt_trace has to do: nothing, a refit of the instances marked in `touched` (vertices or
+    // transform changed: UpdateDynamicBlas + the per-frame TLAS rebuild upstream), or a full build (topology changed).
+    int accel_state = ACCEL_REBUILD;
+    bool accel_built = false;                 // a full build of the current instance table exists (a refit needs one)
+    bool instances_dirty = true;              // the device copy of the instance table is stale
+    std::vector<uint8_t> touched;             // per instance
+    pt::DevBuf d_touched;
+    uint32_t accel_refits = 0, accel_builds = 0;
+    std::vector<int> free_buffers, free_textures, free_envs;      // destroyed handles, reused by the next create
+
+    std::vector<pt::EnvDevice*> envs;
+    pt::DevBuf d_sheen, d_srgb, d_tangent_lut, d_counters;        // float[256] twice, float2[1024], Counters: allocated by pt_create
+    pt::DevBuf d_bones; size_t bones_used = 0;                     // bone arena: one slice per pt_skin_run, wraps behind a fence
+    hipEvent_t bones_fence = nullptr; bool bones_fence_pending = false;
+    pt::DevBuf d_workspace;                                        // wavefront ray / hit / path-state arrays
+    pt::DevBuf d_tonemap;                                          // pt_tonemap's device scratch (float RGB + RGBA8), reused
+    pt::ExchangeState* exchange = nullptr;                         // pt_exchange_* (exchange.hip)
+    pt::DevBuf d_deep;                                             // deep traversal stack (SceneRec::deep_stack), only for trees that need > 64 entries
+    bool stage_timing = false;                                 // pt_enable_stage_timing
+    pt::StageTimers timers;
+    int kernel_mode = PT_MODE_WAVEFRONT;
+    int stage_blocks = 0;         // workgroups per stage launch; 0 = by the size of the launch (stage_blocks_for)
+    hipEvent_t ev_trace[2] = {nullptr, nullptr}, ev_accel[2] = {nullptr, nullptr}, ev_skin[2] = {nullptr, nullptr};
+    bool have_trace = false, have_accel = false, have_skin = false;
+    int bounce_limit = PT_REFERENCE_MAX_BOUNCES;
+    int samples_per_trace = 1;
+    bool cull_null_shadow = false;
+    bool counters_enabled = false;
+    // ---- adaptive sampling (pt_set_adaptive): per rank-local tile state and the half buffer, for one size and tile shard
+    pt_adaptive_config adaptive = {0, 2, 2, 0.0f};
+    bool adaptive_restart = false;                // pt_set_adaptive: the next pt_trace starts a new accumulation
+    pt::DevBuf d_ad_tiles, d_ad_half;             // AdaptiveTile per tile, float4 per pixel
+    uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
+    bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
+    int ad_frames = -1;                           // accumulated_frames the tile state stands for (-1: none)
+    // ---- pt_accum_save / pt_accum_load: the packed sections of one blob (one pt_tiles_pack image each), reused between calls
+    pt::DevBuf d_accum;
+    // ---- first-hit AOVs (pt_set_aov): the caller's targets
+    pt_aov_config aov = {0, nullptr, nullptr};
+    bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
+    // ---- thin lens (pt_set_lens)
+    pt_lens_config lens = {0, 0.0f, 1.0f, 0, 0.0f};
+    bool lens_restart = false;                    // pt_set_lens: the next pt_trace starts a new accumulation
+    // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
+    pt::DevBuf d_denoise;
+
+    // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
+    float previous_world_to_clip[16] = {0};
+    int accumulated_frames = 0;
+
+    int fail(int code, const std::string& msg) { error = msg; return code; }
+};
+
+#define HIPOK(call)                                                                                          \
+    do {                                                                                                     \
+        hipError_t _e = (call);                                                                              \
+        if (_e != hipSuccess) return ctx->fail(PT_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+// Every entry point that touches the device makes the context's device current first: two contexts on two GPUs in one process
+// (one per rank thread, or a host that drives several GPUs itself) must not launch or allocate on each other's device.
+#define ENTER(ctx)                                                                                           \
+    do {                                                                                                     \
+        hipError_t _e = hipSetDevice((ctx)->device);                                                         \
+        if (_e != hipSuccess) return (ctx)->fail(PT_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
+    } while (0)
+
+namespace pt {
+
+// The camera of a call, from pt_execute_params and the lens config: world_to_clip as pt_trace compares it between calls, its inverse and
+// view_to_world (fp64, rounded once) and the lens as camera_ray takes it (include/mipt.h pt_set_lens).  PathtraceScene, pt_lens_focus_at
+// and the hook pt_debug_camera_rays all come through here, so that the rays they speak of are the same rays.  (mipt_api.hip)
+struct CameraSetup {
+    float world_to_clip[16], clip_to_world[16], view_to_world[16];
+    LensArgs lens;
+};
+bool camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam);
+// What pinhole_ray reads of FrameConstants, the rest zero (the two camera hooks; PathtraceScene fills the rest as well)
+void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, FrameConstants& fc);
+
+// Pathtracer::BuildAccel (mipt_api.hip) if the tree does not stand for the current tables, as every call that traces rays begins
+int ensure_accel(pt_ctx* ctx);
+
+inline bool live_env(const pt_ctx* ctx, int env) { return env >= 0 && env < (int)ctx->envs.size() && ctx->envs[env] != nullptr; }
+
+// A handle for `rec`: one a destroy gave back, else a new one at the end of the table.
+template <typename T>
+int take_slot(std::vector<T>& table, std::vector<int>& free_list, const T& rec) {
+    if (free_list.empty()) { table.push_back(rec); return (int)table.size() - 1; }
+    const int h = free_list.back();
+    free_list.pop_back();
+    table[h] = rec;
+    return h;
+}
+
+// The scene as the kernels take it: tables, tree and lookup tables, no environment and no deep stack (the caller adds those)
+inline SceneRec scene_fill(const pt_ctx* ctx) {
+    SceneRec sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.rmats = ctx->d_rmats.as<RMat>(); sc.lights = ctx->d_lights.as<pt_light>(); sc.instances = ctx->d_instances.as<InstanceRec>();
+    sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
+    sc.nodes = ctx->d_nodes.as<Bvh4Node>(); sc.tris = ctx->d_tris.as<TriPacket>(); sc.shade = ctx->d_shade.as<ShadePacket>(); sc.root = ctx->root; sc.num_tris = ctx->n_tris;
+    sc.sheen_e = ctx->d_sheen.as<float>(); sc.srgb_lut = ctx->d_srgb.as<float>(); sc.tangent_lut = ctx->d_tangent_lut.as<float2>();
+    return sc;
+}
+inline void scene_set_env(SceneRec& sc, const EnvDevice& ed) {
+    sc.env.cube = ed.cube; sc.env.cube_n = ed.mip_n[0]; sc.env.importance = ed.importance;
+    for (int i = 0; i < 12; i++) sc.env.level_offset[i] = ed.level_offset[i];
+    sc.env.imp_res = ed.imp_res; sc.env.imp_levels = ed.levels; sc.env.imp_total = ed.total;
+    sc.env.blocked = ed.blocked;
+    for (int i = 0; i < 5; i++) sc.env.blocked_offset[i] = ed.blocked_offset[i];
+    sc.has_env = 1;
+}
+
+// Entries a lane's deep stack holds in memory, beyond those on chip (SceneRec::deep_entries); 0: the tree needs none
+inline uint32_t deep_stack_entries(const pt_ctx* ctx) {
+    const uint32_t on_chip = (uint32_t)traversal_stack_capacity();
+    return ctx->stack_need > on_chip ? (ctx->stack_need - on_chip + 7u) & ~7u : 0u;
+}
+
+}  // namespace pt

@@ -169,7 +169,7 @@ void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensA
     hipLaunchKernelGGL(k_lens_focus, dim3(1), dim3(kBlock), 0, stream, sc, fc, lens, sx, sy, rf, d_out);
 }
 
-// Test hook (pt_debug_sample_texture, mipt_api.hip): the sampler as the megakernel runs it -- sRGB table and material records in global memory.
+// Test hook (pt_debug_sample_texture, mipt_debug.hip): the sampler as the megakernel runs it -- sRGB table and material records in global memory.
 __global__ __launch_bounds__(kBlock) void k_debug_sample_texture_mk(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
                                                                  uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -184,7 +184,7 @@ void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_sl
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_sample_texture_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
 }
-// Test hook (pt_debug_env_query, mipt_api.hip): the environment light as the megakernel runs it -- the whole pyramid in global memory.
+// Test hook (pt_debug_env_query, mipt_debug.hip): the environment light as the megakernel runs it -- the whole pyramid in global memory.
 __global__ __launch_bounds__(kBlock) void k_debug_env_query_mk(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;

@@ -576,7 +576,7 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_shadow(SceneRec s
     else if (st.overflow | st.deep) flush_rare(counters, st);
 }
 
-// Test hook (pt_debug_sample_texture, mipt_api.hip): the sampler as this file's stages run it -- sRGB table and material records in LDS.
+// Test hook (pt_debug_sample_texture, mipt_debug.hip): the sampler as this file's stages run it -- sRGB table and material records in LDS.
 __global__ __launch_bounds__(kBlock) void k_debug_sample_texture_wf(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
                                                                  uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
     stage_luts(sc);
@@ -593,7 +593,7 @@ void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_sl
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_sample_texture_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
 }
-// Test hook (pt_debug_env_query, mipt_api.hip): the environment light as this file's stages run it -- the three coarsest level pairs of the
+// Test hook (pt_debug_env_query, mipt_debug.hip): the environment light as this file's stages run it -- the three coarsest level pairs of the
 // importance pyramid staged, as env_prepass stages them, into LDS of the traversal stack's type and size.  Every lane stages before any
 // lane without a query leaves.
 __global__ __launch_bounds__(kBlock) void k_debug_env_query_wf(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
@@ -964,7 +964,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     return hipGetLastError();
 }
 
-// Test hook (pt_debug_trace_queues, mipt_api.hip): the traversal kernels of a frame -- k_wf_trace, k_wf_shadow or the fused k_wf_traverse, through
+// Test hook (pt_debug_trace_queues, mipt_debug.hip): the traversal kernels of a frame -- k_wf_trace, k_wf_shadow or the fused k_wf_traverse, through
 // the launch functions above -- on queues the caller filled.  Owns a small WfBuffers: the seven counter arrays, one closest queue with its hit
 // array, the shadow queue and the pending records, nothing else (sc.has_env must be 0, so no environment buffers are read).
 // Every output word holds kDebugSentinel before the launch and each shard's segment ends in a guard entry nobody may write.
