@@ -268,6 +268,11 @@ class PtLensConfig(C.Structure):
                 ("blade_rotation", C.c_float)]
 
 
+class PtBakeConfig(C.Structure):
+    """pt_bake_config: texture-space baking (pt_set_bake; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("tex_coord", C.c_int32), ("instance", C.c_int32), ("surface_offset", C.c_float)]
+
+
 ACCUM_OUTPUT, ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE = 1, 2, 4, 8
 ACCUM_HEADER_BYTES = 160
 
@@ -304,5 +309,7 @@ assert C.sizeof(PtAovConfig) == 24
 assert C.sizeof(PtDenoiseConfig) == 20
 assert C.sizeof(PtLensConfig) == 20
 assert [getattr(PtLensConfig, f).offset for f, _ in PtLensConfig._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtBakeConfig) == 16
+assert [getattr(PtBakeConfig, f).offset for f, _ in PtBakeConfig._fields_] == [0, 4, 8, 12]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

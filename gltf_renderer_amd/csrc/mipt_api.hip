@@ -274,7 +274,13 @@ public:
         // First-hit AOVs (pt_set_aov) are written by every call without a debug output, under the output's counts and resets.
         const bool aov = ctx->aov.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
         if (aov && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "AOVs are written in the wavefront mode only");
+        // Texture-space baking (pt_set_bake): the generate stage starts the paths on the atlas's texels; everything else is this function as it is.
+        const bool bake = ctx->bake.enable != 0;
+        if (bake && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "a bake runs in the wavefront mode only");
+        if (bake && ctx->bake.instance >= (int)ctx->instances.size())
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance " + std::to_string(ctx->bake.instance) + " of " + std::to_string(ctx->instances.size()));
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (ctx->bake_restart) { reset = true; ctx->bake_restart = false; }
         if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
         if (ctx->lens_restart) { reset = true; ctx->lens_restart = false; }
         if (adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
@@ -289,6 +295,8 @@ public:
                 return ctx->fail(PT_ERR_BAD_HANDLE, "bad environment map handle");
             if (!ep->output) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "output is null");
             if (int r = ensure_accel(ctx)) return r;
+            BakeArgs bk = {};
+            if (bake) { if (int r = bake_setup(ctx, ep->width, ep->height, bk)) return r; }
 
             SceneRec sc = scene_fill(ctx);
             if (ep->environment_map >= 0) scene_set_env(sc, *ctx->envs[ep->environment_map]);
@@ -374,7 +382,7 @@ public:
                 }
                 const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
                 HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
-                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr));
+                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
@@ -474,6 +482,27 @@ public:
         return PT_OK;
     }
 };
+int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake) {
+    const uint64_t accel = (uint64_t)ctx->accel_builds + ctx->accel_refits;
+    const size_t texels = (size_t)width * height;
+    if (!ctx->bake_ready || ctx->bake_w != width || ctx->bake_h != height || memcmp(&ctx->bake_built, &ctx->bake, sizeof(pt_bake_config)) != 0 || ctx->bake_accel != accel) {
+        ctx->bake_ready = false;
+        hipError_t e = ctx->d_bake_keys.reserve(ctx->stream, texels * 8, texels * 8);
+        if (e == hipSuccess) e = ctx->d_bake_owner.reserve(ctx->stream, texels * 4, texels * 4);
+        const size_t scratch = bake_coverage_scratch_bytes(ctx->n_tris);
+        if (e == hipSuccess) e = ctx->d_bake_scratch.reserve(ctx->stream, scratch, scratch + scratch / 8);
+        if (e != hipSuccess) return grow_failed(ctx, e, "bake coverage map: " + std::to_string(texels * 12 + scratch) + " bytes");
+        const BakeRaster r = {ctx->d_tris.as<TriPacket>(), ctx->d_shade.as<ShadePacket>(), ctx->d_instances.as<InstanceRec>(), ctx->n_tris, width, height,
+                              ctx->bake.tex_coord, ctx->bake.instance};
+        std::string why;
+        e = bake_coverage_build(r, ctx->d_bake_keys.as<unsigned long long>(), ctx->d_bake_owner.as<uint32_t>(), ctx->d_bake_scratch.ptr, ctx->stream, why);
+        if (e != hipSuccess) return why.empty() ? ctx->fail(PT_ERR_DEVICE, std::string("bake coverage map: ") + hipGetErrorString(e)) : ctx->fail(PT_ERR_CAPACITY, "bake coverage map: " + why);
+        ctx->bake_w = width; ctx->bake_h = height; ctx->bake_built = ctx->bake; ctx->bake_accel = accel; ctx->bake_ready = true;
+    }
+    bake.owner = ctx->d_bake_owner.as<uint32_t>(); bake.tris = ctx->d_tris.as<TriPacket>(); bake.shade = ctx->d_shade.as<ShadePacket>();
+    bake.surface_offset = ctx->bake.surface_offset; bake.tex_coord = ctx->bake.tex_coord;
+    return PT_OK;
+}
 int ensure_accel(pt_ctx* ctx) {
     return ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty ? Pathtracer::BuildAccel(ctx) : PT_OK;
 }
@@ -983,6 +1012,51 @@ int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config) {
     return PT_OK;
 }
 
+int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: config is NULL");
+    if (config->enable) {
+        if (config->tex_coord != 0 && config->tex_coord != 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: tex_coord must be 0 or 1");
+        if (config->instance < -1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance must be -1 or a row of the instance table");
+        if (!std::isfinite(config->surface_offset) || !(config->surface_offset > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: surface_offset must be finite and > 0");
+    }
+    ctx->bake = *config;
+    ctx->bake_restart = true;
+    return PT_OK;
+}
+
+int pt_bake_coverage(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* instance_out, uint32_t* primitive_out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
+    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_coverage: size differs from the coverage map's");
+    ENTER(ctx);
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const size_t n = (size_t)width * height;
+    std::vector<unsigned long long> keys(n);
+    HIPOK(hipMemcpy(keys.data(), ctx->d_bake_keys.ptr, n * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        const bool none = keys[i] == ~0ull;
+        if (instance_out) instance_out[i] = none ? -1 : (int32_t)(keys[i] >> 32);
+        if (primitive_out) primitive_out[i] = none ? 0xffffffffu : (uint32_t)keys[i];
+    }
+    return PT_OK;
+}
+
+int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, int passes) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!image) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: null image");
+    if (width == 0 || height == 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: bad size");
+    if (passes < 1 || passes > 64) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: passes outside 1..64");
+    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
+    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: size differs from the coverage map's");
+    ENTER(ctx);
+    const size_t n = (size_t)width * height, need = n * 16 + 2 * n;
+    if (const hipError_t e = ctx->d_bake_dilate.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "bake_dilate scratch: " + std::to_string(need) + " bytes");
+    HIPOK(launch_bake_dilate((float4*)image, ctx->d_bake_owner.as<uint32_t>(), width, height, passes, ctx->d_bake_dilate.as<float4>(),
+                             ctx->d_bake_dilate.as<uint8_t>() + n * 16, ctx->stream));
+    return PT_OK;
+}
+
 int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, float px, float py, float* focus_distance_out) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     if (!settings || !params || !focus_distance_out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens_focus_at: NULL argument");
@@ -1169,7 +1243,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens since the last trace: the next trace starts anew");
+    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1264,7 +1338,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false;
+    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false;
     return PT_OK;
 }
 

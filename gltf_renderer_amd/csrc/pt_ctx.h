@@ -97,6 +97,16 @@ struct pt_ctx {
     // ---- thin lens (pt_set_lens)
     pt_lens_config lens = {0, 0.0f, 1.0f, 0, 0.0f};
     bool lens_restart = false;                    // pt_set_lens: the next pt_trace starts a new accumulation
+    // ---- texture-space baking (pt_set_bake): the config, and the coverage map of one atlas size, config and state of the tree
+    pt_bake_config bake = {0, 0, -1, 0.0f};
+    bool bake_restart = false;                    // pt_set_bake: the next pt_trace starts a new accumulation
+    pt::DevBuf d_bake_keys, d_bake_owner;         // per texel: the owner's (instance << 32 | primitive); its index into d_tris / d_shade (BakeArgs::owner)
+    pt::DevBuf d_bake_scratch;                    // the rasteriser's bin counts and scan (bake.hip)
+    pt::DevBuf d_bake_dilate;                     // pt_bake_dilate: one image and two fill masks
+    bool bake_ready = false;                      // the map stands for (bake_w, bake_h, bake_built, bake_accel)
+    uint32_t bake_w = 0, bake_h = 0;
+    pt_bake_config bake_built = {0, 0, -1, 0.0f};
+    uint64_t bake_accel = 0;                      // accel_builds + accel_refits when the map was built: the packets it was rasterised from
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
 
@@ -132,6 +142,11 @@ struct CameraSetup {
 bool camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam);
 // What pinhole_ray reads of FrameConstants, the rest zero (the two camera hooks; PathtraceScene fills the rest as well)
 void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, FrameConstants& fc);
+
+// The bake of a call (pt_set_bake): the coverage map for a width x height atlas -- built now unless it stands for this size, config and
+// state of the tree -- and what k_wf_generate_bake takes.  After ensure_accel.  pt_trace and the hook pt_debug_bake_rays both come through
+// here.  (mipt_api.hip)
+int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake);
 
 // Pathtracer::BuildAccel (mipt_api.hip) if the tree does not stand for the current tables, as every call that traces rays begins
 int ensure_accel(pt_ctx* ctx);

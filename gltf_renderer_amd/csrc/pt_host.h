@@ -157,13 +157,38 @@ struct AovArgs {
     float4* albedo;           // the caller's targets, res_x * res_y each; either may be nullptr
     float4* normal_depth;
 };
+// Texture-space baking (pt_set_bake): what k_wf_generate_bake takes as its own argument, beside the tree's two packet arrays.
+constexpr uint32_t kBakeNone = 0xffffffffu;
+struct BakeArgs {
+    const uint32_t* owner;    // res_x * res_y: the coverage map -- per texel the owner's index into tris / shade, kBakeNone where none covers
+    const TriPacket* tris;
+    const ShadePacket* shade;
+    float surface_offset;
+    int32_t tex_coord;
+};
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
+// bake: nullptr = camera rays (k_wf_generate); else k_wf_generate_bake starts the paths on the atlas's texels and `lens` is not looked at
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 // aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
-                            const AovArgs* aov = nullptr);
+                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr);
+// pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
+void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+
+// ---- bake.hip: the coverage map of pt_set_bake and pt_bake_dilate's passes ---------------------------------------------------
+// The UV rasteriser over the built tree's packets.  keys: w * h (instance << 32 | primitive of the owner, all ones where none covers);
+// owner: w * h (BakeArgs::owner).  scratch: bake_coverage_scratch_bytes(n_tris).  Synchronises the stream once (the bin count).
+struct BakeRaster {
+    const TriPacket* tris; const ShadePacket* shade; const InstanceRec* instances;
+    uint32_t n_tris, w, h;
+    int32_t tex_coord, instance;      // instance -1: every instance that has the UV set
+};
+size_t bake_coverage_scratch_bytes(uint32_t n_tris);
+hipError_t bake_coverage_build(const BakeRaster& r, unsigned long long* keys, uint32_t* owner, void* scratch, hipStream_t stream, std::string& why);
+// `passes` dilation passes over image (w * h float4) from the coverage `owner`; pong: w * h float4, mask: 2 * w * h bytes.  Asynchronous.
+hipError_t launch_bake_dilate(float4* image, const uint32_t* owner, uint32_t w, uint32_t h, int passes, float4* pong, uint8_t* mask, hipStream_t stream);
 
 // ---- sort_scan.hip: the build's two data-parallel primitives, hand-written (stable LSD radix sort of (u64, u32) pairs over 63 key bits; u32 exclusive scan)
 size_t radix_sort_temp_bytes(size_t n);

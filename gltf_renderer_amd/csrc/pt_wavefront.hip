@@ -23,6 +23,7 @@
 
 #include "pt_vertex.h"
 #include "pt_host.h"
+#include "pt_bake.h"
 
 #ifdef PT_TIMING                 // diagnostic build only (tools/shade_sections.py); not part of the C-ABI
 namespace pt { __device__ unsigned long long pt_timing[12]; }
@@ -179,6 +180,59 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
     }
     LaneStats st = {0, 0, 0, 0};
     flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+}
+
+// Texture-space baking (pt_set_bake): the generate stage of an image whose "camera" is a surface.  Slots, tiles, shards and the queue are
+// k_wf_generate's; the ray of a (texel, sample) is bake_ray's (pt_bake.h) -- one coverage word, one ShadePacket and one TriPacket per covered
+// sample -- and everything behind this launch is the code a camera frame runs.  An uncovered texel pushes no ray and counts none: no later
+// stage would write its slot, so its records are written here -- radiance 0 with nothing pending and, with AOVs on, zero records (`av` as
+// k_wf_aov takes it, all null without AOVs) -- and the unchanged resolve blends a defined value.
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_generate_bake(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, BakeArgs bk, AovArgs av) {
+    const ShardView sv = shard_view(wf);
+    unsigned n_primary = 0;
+    for (uint32_t rnd = 0; rnd < wf.gen_rounds; rnd++) {
+        const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+        const uint32_t sample = slot_sample(fc, slot);
+        uint32_t px = 0, py = 0;
+        bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
+        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
+        int rc = 0;
+        Ray ray;
+        ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
+        bool covered = false;
+        if (valid) covered = bake_ray(fc, bk, sample_seed(fc, sample), px, py, rc, ray);
+        const uint32_t idx = queue_push(wf.cnt[0] + sv.shard * kCounterStride, covered);
+        if (covered) {
+            const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
+            QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
+            QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
+            n_primary++;
+        } else if (valid) {
+            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            wf.L[slot] = zero;
+            if (av.albedo) QST(av.rec_albedo[slot], zero);
+            if (av.normal_depth) QST(av.rec_normal[slot], zero);
+        }
+    }
+    LaneStats st = {0, 0, 0, 0};
+    flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+}
+// Test hook (pt_debug_bake_rays, mipt_debug.hip): bake_ray itself, one query {px, py, seed} per lane
+__global__ __launch_bounds__(kBlock) void k_debug_bake_rays(FrameConstants fc, BakeArgs bk, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t px = queries[3 * (size_t)i], py = queries[3 * (size_t)i + 1];
+    int rc = 0;
+    Ray r;
+    r.o = v3(0); r.d = v3(0); r.tmin = 0; r.tmax = -1.0f;
+    if (px < fc.res_x && py < fc.res_y) bake_ray(fc, bk, queries[3 * (size_t)i + 2], px, py, rc, r);
+    float* o = out + (size_t)i * 8;
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
+}
+void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_bake_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, bake, d_queries, n, d_out);
 }
 
 // Wave-persistent "while-while" traversal of one shard segment with dynamic ray fetch (pt_traverse.h).
@@ -858,7 +912,7 @@ static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const Sc
 }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -891,7 +945,9 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     }
     AdaptiveArgs ad = {};
     if (adaptive) ad = *adaptive;
-    if (adaptive) { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<true, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
+    if (bake) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_bake<true>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av);
+                else hipLaunchKernelGGL((k_wf_generate_bake<false>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av); }
+    else if (adaptive) { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<true, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
                     else hipLaunchKernelGGL((k_wf_generate<true, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }
     else { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<false, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
            else hipLaunchKernelGGL((k_wf_generate<false, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }

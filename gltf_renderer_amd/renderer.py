@@ -33,7 +33,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # saving and resuming an accumulation (additive likewise)
            "pt_accum_save", "pt_accum_load", "pt_accum_inspect",
            # thin-lens depth of field (additive likewise)
-           "pt_set_lens", "pt_lens_focus_at"]
+           "pt_set_lens", "pt_lens_focus_at",
+           # texture-space baking (additive likewise)
+           "pt_set_bake", "pt_bake_coverage", "pt_bake_dilate"]
 
 
 class MiptError(RuntimeError):
@@ -114,6 +116,9 @@ def load_library():
     L.pt_accum_inspect.argtypes = [vp, C.c_size_t, vp]
     L.pt_set_lens.argtypes = [vp, vp]
     L.pt_lens_focus_at.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.pt_set_bake.argtypes = [vp, vp]
+    L.pt_bake_coverage.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.pt_bake_dilate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci]
     _LIB = L
     return L
 
@@ -331,6 +336,27 @@ class Renderer:
         same lens before accum_load()."""
         cfg = abi.PtLensConfig(int(bool(enable)), float(aperture_radius), float(focus_distance), int(blades), float(blade_rotation))
         self._check(self.L.pt_set_lens(self.h, C.byref(cfg)))
+
+    def set_bake(self, surface_offset, tex_coord=0, instance=-1, enable=True):
+        """Texture-space baking (include/mipt.h pt_set_bake): trace() renders into the width x height atlas addressed by UV set tex_coord
+        of every instance that has it (instance = -1) or of one instance-table row; every ray starts surface_offset (world units) above
+        its texel's surface point.  The next trace() starts a new accumulation.  Wavefront mode only.  The bake is not part of an
+        accum_save() blob: set the same bake before accum_load()."""
+        cfg = abi.PtBakeConfig(int(bool(enable)), int(tex_coord), int(instance), float(surface_offset))
+        self._check(self.L.pt_set_bake(self.h, C.byref(cfg)))
+
+    def bake_coverage(self, width, height):
+        """The coverage map of the last bake trace() (pt_bake_coverage): (instance [H, W] int32, -1 where no triangle covers;
+        primitive [H, W] uint32, the triangle within the instance)."""
+        inst = np.zeros((height, width), np.int32)
+        prim = np.zeros((height, width), np.uint32)
+        self._check(self.L.pt_bake_coverage(self.h, width, height, _p(inst), _p(prim)))
+        return inst, prim
+
+    def bake_dilate(self, image, passes):
+        """pt_bake_dilate: fills the uncovered texels of a device image (create_output) from their covered neighbours, `passes` texels
+        deep, in place; for the atlas size of the last bake trace()."""
+        self._check(self.L.pt_bake_dilate(self.h, image.data_ptr(), image.shape[1], image.shape[0], int(passes)))
 
     def focus_at(self, settings, params, px, py):
         """Autofocus (include/mipt.h pt_lens_focus_at): the view-space depth of what the pinhole ray through image position (px, py) sees

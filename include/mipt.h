@@ -614,6 +614,70 @@ int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config);
  * [0, width] x [0, height].  Does not touch the accumulation. */
 int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params,
                      float px, float py, float* focus_distance_out);
+/* Texture-space baking (absent upstream).  With a bake on, pt_trace renders into a UV atlas instead of through a camera: params->width x
+ * height is the atlas, and every (texel, sample) whose texel a triangle covers starts a path on that triangle's surface.  Only the first ray
+ * differs -- from its first closest hit on, a path is the path of a camera frame -- so sample batches, tile shards, adaptive sampling, AOVs,
+ * pt_denoise, pt_accum_save / load and pt_exchange_frame apply to the atlas as to any W x H image, bit for bit.  With the bake off (the
+ * default) every image, ray count and stat is what it is without this section.  world_to_view / view_to_clip generate no rays under a bake
+ * but must still be valid (identity will do) and still drive the reset comparison; the lens (pt_set_lens) does not apply, pt_lens_focus_at
+ * is unaffected; debug outputs work, the first vertex being the texel's surface point.  Wavefront mode only: a bake call in
+ * PT_MODE_MEGAKERNEL fails with PT_ERR_INVALID_ARGUMENT and writes nothing.  An `instance` >= the current instance table's count is
+ * reported by the pt_trace that meets it (PT_ERR_INVALID_ARGUMENT, nothing written).
+ *   The coverage map (owned by the context, the whole atlas on every rank) is built by the pt_trace that needs it and rebuilt after
+ * pt_build_accel had work to do (a build or a refit), after pt_set_bake and after a change of size.  float32 throughout, every operation in
+ * the order written, products and sums not fused:
+ *     texel (x, y) has the centre p = (x + 0.5, y + 0.5), in texel units
+ *     a triangle's UV vertices (set tex_coord) are A, B, C = (u * (float)W, v * (float)H): no wrap, no flip; UVs outside [0, 1] fall off the atlas
+ *     E(P, Q, p) = (Q.x - P.x)(p.y - P.y) - (Q.y - P.y)(p.x - P.x)        area2 = E(A, B, C)
+ *     a triangle takes part if its instance is selected (instance == -1, or that row) and has the UV stream, and unless
+ *         area2 == 0 or one of the six coordinates is not finite, or
+ *         n = cross(e1, e2) of its world-space edges (e1 = v1 - v0, e2 = v2 - v0) has sqrt(dot(n, n)) zero or not finite
+ *     it covers p iff each of E(B, C, p), E(C, A, p), E(A, B, p) is zero or has area2's sign
+ *     the texel's owner is the covering triangle with the least (instance, primitive) pair -- whatever the builder (PT_BUILDER_*), the
+ *     order of the triangles or the scheduling.  (The rasteriser visits a triangle's bounding box widened by a texel.)
+ *   The sample of texel (px, py) with seed s (divisions and sqrt correctly rounded):
+ *     r = the draw the camera ray would make: next_random(px, py, s, 0).  It is the sample's only draw here too, so every later vertex sees
+ *         the random sequence it sees in a camera frame.
+ *     p = (px + 0.5 + (r.x - 0.5), py + 0.5 + (r.y - 0.5))               the camera ray's jittered position
+ *     uncovered texel: no ray, no primary ray counted; the sample is radiance (0, 0, 0) and, with pt_set_aov, zero AOV records: the
+ *         output holds exactly (0, 0, 0, 1) and the AOV targets zeros, after any number of samples.
+ *     covered texel, owner (v0, e1, e2; A, B, C):
+ *     b1 = E(C, A, p) / area2,  b2 = E(A, B, p) / area2
+ *     b1 = max(b1, 0),  b2 = max(b2, 0),  b0 = max((1 - b1) - b2, 0),  s = (b0 + b1) + b2,  b1 = b1 / s,  b2 = b2 / s      (a jitter outside
+ *         the triangle is clamped onto it)
+ *     b1 = b1 * (1 - 2^-10) + (float)(2^-10 / 3), b2 likewise          strictly inside, so that the ray cannot slip past an edge
+ *     P  = (v0 + b1 * e1) + b2 * e2
+ *     n  = cross(e1, e2), negated for a mirrored instance;  Ng = n / sqrt(dot(n, n)), component by component: the side the traversal
+ *         reports as the front face
+ *     o = P + Ng * surface_offset,  d = -Ng,  tmin = 0,  tmax = 2 * surface_offset
+ *   The first closest hit is the surface itself at t ~ surface_offset, or whatever lies closer than that above it; the image holds the
+ * radiance that leaves each texel along its front normal under the call's settings and flags -- for a diffuse surface, the lightmap.  With
+ * pt_set_aov, albedo.w is the coverage, albedo.rgb demodulates the lightmap and normal_depth.w ~ surface_offset.  An ambient-occlusion map:
+ * PT_FLAG_MATERIAL_DIFFUSE_WHITE, a constant white environment, max_bounces = 1, no lights.
+ * The bake is a setting, like the lens: it is NOT part of the blob of pt_accum_save, whose format is unchanged -- a caller who resumes calls
+ * pt_set_bake with the same config before pt_accum_load. */
+typedef struct pt_bake_config {
+    int32_t enable;           /* 0 = camera (default) */
+    int32_t tex_coord;        /* 0 or 1: the UV set that addresses the atlas */
+    int32_t instance;         /* -1 = every instance that has that UV set, else one row of the instance table */
+    float   surface_offset;   /* world units, finite, > 0: the ray starts this far above the surface */
+} pt_bake_config;             /* 16 bytes */
+/* PT_ERR_INVALID_ARGUMENT for a NULL pointer or a bad config (checked only when enable != 0; the message names the field): the old config
+ * stays and no restart is pending.  A good config forces a new accumulation on the next pt_trace, as pt_set_lens does: until that trace
+ * pt_accum_save answers PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config);
+/* Copies the coverage map's owners out (host arrays of width * height, either may be NULL): instance_out the instance row, -1 where no
+ * triangle covers; primitive_out the triangle within the instance (0xffffffff where none).  Synchronises the stream.  PT_ERR_NOT_READY
+ * before the first bake trace, PT_ERR_INVALID_ARGUMENT for a size other than the map's. */
+int pt_bake_coverage(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* instance_out, uint32_t* primitive_out);
+/* Fills the uncovered texels of a W*H float4 device image from the coverage map of that size, in place, enqueued on the stream.  A texel
+ * is `filled` if it has an owner.  In each of the `passes` (1..64) passes an unfilled texel looks at its 8 neighbours, dy = -1..1 outer,
+ * dx = -1..1 inner, the centre skipped, and counts those inside the atlas that were filled at the start of the pass; with count > 0 it
+ * becomes (the sequential float32 sum of those neighbours, all four channels) / (float)count and is filled from the next pass on.
+ * Filled texels are never changed and unfilled ones never read as neighbours.  The scratch (one image, two masks) belongs to the context.
+ * PT_ERR_INVALID_ARGUMENT, with nothing written: a NULL ctx (answered before any device call), a NULL image, a zero width or height, passes
+ * outside 1..64, a size other than the map's.  PT_ERR_NOT_READY before the first bake trace. */
+int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, int passes);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

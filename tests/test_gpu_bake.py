@@ -1,0 +1,618 @@
+"""Texture-space baking (include/mipt.h pt_set_bake, pt_bake_coverage, pt_bake_dilate) on the MI355X.
+
+The coverage map is held to tests/bake_ref.py texel for texel (float32 in numpy, exact); the rays come out of the test hook pt_debug_bake_rays,
+which runs the generate kernel's own ray function, and are held to the float64 restatement within the bound counted in tests/bake_ref.py
+(18 roundings for the origin, 7 for the direction, times the condition of the chart).  Everything else is bit for bit: that pt_trace traces
+exactly the hook's rays, that uncovered texels are exactly (0, 0, 0, 1), that a bake composes with batches, tile shards, checkpoints and
+adaptive sampling, and pt_bake_dilate against its restatement.  The radiance of a baked quad is compared with the oracle's orthographic camera
+looking straight down on it, with the project's bar: tone-mapped relative L2 <= 1e-3."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from gltf_renderer_amd import abi, camera, meshgen, scenes
+from gltf_renderer_amd.renderer import MiptError
+from tests import bake_ref as br
+from tests import lens_ref as lr
+from tests import ray_hook
+
+pytestmark = pytest.mark.gpu
+f32, f64 = np.float32, np.float64
+SIZES = [(32, 32), (48, 20), (17, 33)]      # ragged 16 x 16 tiles in both directions
+OFFSET = 1.0 / 64
+N = 8
+
+
+def copy_settings(s):
+    return abi.PtSettings.from_buffer_copy(bytes(s))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+class Mesh32(meshgen.Mesh):
+    """A small mesh with a 32-bit index stream."""
+
+    def index_stream(self):
+        return self.indices.astype(np.uint32), abi.FORMAT_R32_UINT
+
+
+def rot(uv, deg, centre):
+    a = np.deg2rad(deg)
+    R = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+    return ((np.asarray(uv, f64) - centre) @ R.T + centre).astype(f32)
+
+
+def base_settings():
+    st = abi.PtSettings.app_defaults()
+    st.flags &= ~(abi.FLAG_ENVIRONMENT_MAP | abi.FLAG_ENVIRONMENT_MIS)
+    st.environment_color[:] = (0.25, 0.5, 0.75)
+    st.use_frame_as_seed = 1
+    st.max_accumulated_frames = 64
+    return st
+
+
+def mixed_scene():
+    """26 triangles on four instances, no two surfaces coincident (the sheets lie a unit apart, the offset is 1 / 64):
+      0  non-indexed, z = 0: primitive 0 is degenerate in world space (three collinear points) with a UV triangle over the whole atlas -- it must
+         own nothing although its pair is the least; primitive 1 has a zero-area UV triangle; primitives 2, 3 are a quad whose UV set 0 is a
+         chart inside the atlas and whose set 1 runs off it on two sides
+      1  indexed-16, z = 1, 12 triangles: set 0 a rotated chart that overlaps instance 0's; no set 1
+      2  indexed-32, z = 2, mirrored (x -> -x), 8 triangles: set 0 overlaps instance 0's chart and runs off the top; set 1 a rotated chart
+      3  no UV stream at all, z = 3"""
+    s = scenes.SceneData("bake_mixed")
+    up = np.repeat([[0.0, 0.0, 1.0]], 12, axis=0)
+    pos = [(0, 0, 0), (1, 0, 0), (2, 0, 0),   (4, 0, 0), (6, 0, 0), (6, 2, 0),   (0, 0, 0), (2, 0, 0), (2, 2, 0),   (0, 0, 0), (2, 2, 0), (0, 2, 0)]
+    quad0 = np.array([(0.05, 0.05), (0.65, 0.05), (0.65, 0.65), (0.05, 0.05), (0.65, 0.65), (0.05, 0.65)])
+    quad1 = np.array([(-0.25, 0.6), (0.5, 0.6), (0.5, 1.3), (-0.25, 0.6), (0.5, 1.3), (-0.25, 1.3)])
+    whole = [(0, 0), (2, 0), (0, 2)]
+    line = [(0.3, 0.3), (0.3, 0.3), (0.7, 0.7)]                # two equal vertices: area2 is exactly 0 at every atlas size
+    m0 = meshgen.Mesh(pos, None, normals=up, uv0=np.concatenate([whole, line, quad0]), uv1=np.concatenate([whole, line, quad1]))
+    s.add_mesh(m0)
+    m1 = meshgen.grid(3, 2, (0, 0, 0), (3, 0, 0), (0, 2, 0))
+    m1.uv0 = rot(m1.uv0 * [0.55, 0.6] + [0.4, 0.3], 20.0, (0.65, 0.6))
+    s.add_mesh(m1, camera.translate((0, 0, 1)))
+    g = meshgen.grid(2, 2, (0, 0, 0), (2, 0, 0), (0, 2, 0))
+    m2 = Mesh32(g.positions, g.indices, g.normals, g.tangents, uv0=(g.uv0 * [0.5, 0.65] + [0.0, 0.55]).astype(f32), uv1=rot(g.uv0 * 0.5 + 0.3, 30.0, (0.55, 0.55)))
+    T = np.diag([-1.0, 1.0, 1.0, 1.0]); T[2, 3] = 2.0
+    s.add_mesh(m2, T)
+    m3 = meshgen.grid(1, 1, (0, 0, 0), (2, 0, 0), (0, 2, 0))
+    m3.uv0 = None
+    s.add_mesh(m3, camera.translate((0, 0, 3)))
+    s.world_to_view = np.eye(4)
+    s.settings = base_settings()
+    return s
+
+
+def lit_scene(occluder=True, chart=1.0):
+    """A quad in the plane z = 0 over [-1, 1]^2 whose UVs map it onto chart * the atlas exactly as the orthographic camera of
+    ortho_camera() maps it onto its pixel grid (u = (x + 1) / 2, v = (1 - y) / 2), an occluder box above it, a point light and a constant
+    environment."""
+    s = scenes.SceneData("bake_lit")
+    quad = meshgen.Mesh([(-1, -1, 0), (1, -1, 0), (1, 1, 0), (-1, 1, 0)], [0, 1, 2, 0, 2, 3], normals=np.repeat([[0.0, 0.0, 1.0]], 4, axis=0),
+                        uv0=np.array([(0, 1), (1, 1), (1, 0), (0, 0)], f64) * chart)
+    s.add_mesh(quad)
+    if occluder:
+        s.add_mesh(meshgen.box((-0.3, -0.35, 0.4), (0.35, 0.3, 0.6)))
+    s.add_light(abi.LIGHT_POINT, position=(0.3, 0.2, 1.5), color=(1.0, 0.9, 0.8), intensity=4.0)
+    s.settings = base_settings()
+    ortho_camera(s)
+    return s
+
+
+def ortho_camera(s):
+    """Looks along -z from above the quad: x_mag = y_mag = 1 shows [-1, 1]^2, and the near plane lies OFFSET above z = 0."""
+    s.ortho = (1.0, 1.0)
+    s.world_to_view = camera.translate((0.0, 0.0, -(OFFSET + s.z_near)))
+
+
+class Ctx:
+    """A renderer with the scene uploaded and, per atlas size, an output and the two AOV targets."""
+
+    def __init__(self, s, bake=(OFFSET,), aov=False, mode=None):
+        from gltf_renderer_amd.renderer import Renderer
+        self.s, self.aov = s, aov
+        self.r = Renderer(0)
+        self.handles = s.upload(self.r)
+        self.img = {}
+        self.size = None
+        if mode is not None:
+            self.r.set_kernel_mode(mode)
+        if bake is not None:
+            self.r.set_bake(*bake)
+
+    def use(self, W, H):
+        if (W, H) not in self.img:
+            self.img[(W, H)] = tuple(self.r.create_output(W, H) for _ in range(3))
+        if self.size != (W, H) and self.aov:
+            self.r.set_aov(self.img[(W, H)][1], self.img[(W, H)][2])
+        self.size = (W, H)
+        self.out, self.alb, self.nd = self.img[(W, H)]
+
+    def params(self, frame=0, **kw):
+        self.s.width, self.s.height = self.size
+        return self.s.execute_params(frame, **kw)
+
+    def trace(self, st, frame, **kw):
+        self.r.trace(st, self.params(frame, **kw), self.out)
+
+    def read(self):
+        return tuple(self.r.readback(t) for t in ((self.out, self.alb, self.nd) if self.aov else (self.out,)))
+
+    def close(self):
+        self.r.close()
+
+
+def hook_rays(c, st, queries):
+    """pt_debug_bake_rays: queries [n, 3] uint32 {px, py, seed} -> [n, 8] float32 (origin, tmin, direction, tmax)."""
+    q = np.ascontiguousarray(queries, np.uint32).reshape(-1, 3)
+    out = np.zeros((len(q), 8), f32)
+    f = c.r.L.pt_debug_bake_rays
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    f.restype = C.c_int
+    params = c.params(0)
+    rc = f(c.r.h, C.byref(st), C.byref(params), q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p))
+    assert rc == 0, (rc, c.r.L.pt_last_error(c.r.h))
+    return out
+
+
+def texel_queries(W, H, seeds):
+    sd, y, x = np.meshgrid(np.asarray(list(seeds), np.uint32), np.arange(H, dtype=np.uint32), np.arange(W, dtype=np.uint32), indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), sd.ravel()], axis=1)
+
+
+def once(st):
+    st = copy_settings(st)
+    st.flags &= ~abi.FLAG_ACCUMULATE
+    return st
+
+
+def rel_l2(a, b):
+    """The project's image metric (tests/test_gpu_parity.py): relative L2 over the pixels finite on both sides."""
+    a = a.astype(f64); b = b.astype(f64)
+    fa, fb = np.isfinite(a), np.isfinite(b)
+    assert (fa != fb).mean() < 1e-3, float((fa != fb).mean())
+    ok = fa & fb
+    return float(np.sqrt(((a[ok] - b[ok]) ** 2).sum() / max((b[ok] ** 2).sum(), 1e-30)))
+
+
+def rf_of(st):
+    return ray_hook.RF_CULL_BACK if st.flags & abi.FLAG_CULL_BACKFACE else 0
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    return mixed_scene()
+
+
+@pytest.fixture(scope="module")
+def mixed_tris(mixed):
+    return br.scene_triangles(mixed)
+
+
+@pytest.fixture(scope="module")
+def rnd(oracle_lib):
+    """orc_random(px, py, seed, 0) on the 32 x 32 atlas for seeds 0 .. 7 (bit-identical to the product's by tests/test_gpu_parity.py)."""
+    return lr.randoms(oracle_lib, 32, 32, range(N))
+
+
+# ---- 1. coverage -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W,H", SIZES)
+def test_coverage_equals_the_restatement_texel_for_texel(mixed, mixed_tris, W, H):
+    """UV set 0 against 1, every instance against one row, under both builders, then after a pt_buffer_update of a UV stream."""
+    c = Ctx(mixed, bake=None)
+    c.use(W, H)
+    st = once(mixed.settings)
+    seen = []
+    for builder in (abi.BUILDER_LBVH, abi.BUILDER_PLOC_REINSERT):
+        c.r.set_accel_builder(builder)
+        for tc in (0, 1):
+            for inst in (-1, 0, 2):
+                c.r.set_bake(OFFSET, tc, inst)
+                c.trace(st, 0)
+                got = c.r.bake_coverage(W, H)
+                want = br.coverage(mixed_tris, W, H, tc, inst)
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (builder, tc, inst)
+                seen.append(want[0])
+    whole = br.coverage(mixed_tris, W, H, 0, -1)
+    assert {0, 1, 2} <= set(np.unique(whole[0]).tolist()) and (whole[0] == -1).any() and 3 not in whole[0]     # overlapping charts, gaps, no stream
+    assert not ((whole[0] == 0) & (whole[1] < 2)).any()                  # the two skipped triangles own nothing
+    assert sum(1 for a in seen for b in seen if not np.array_equal(a, b)) > 0
+    # a UV stream rewritten in place: the refit's packets, a new map
+    new_uv = rot(mixed.mesh_records[1][0].uv0, -35.0, (0.5, 0.5))
+    c.r.buffer_update(c.handles["instances"][1].gpu.texcoord_descriptors[0], new_uv)
+    c.r.set_bake(OFFSET, 0, -1)
+    c.trace(st, 0)
+    got = c.r.bake_coverage(W, H)
+    want = br.coverage(br.scene_triangles(mixed, {(1, 0): new_uv}), W, H, 0, -1)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert not np.array_equal(want[0], whole[0])
+    c.r.buffer_update(c.handles["instances"][1].gpu.texcoord_descriptors[0], mixed.mesh_records[1][0].uv0)
+    # without a new pt_set_bake: the map follows the tree
+    c.trace(st, 0)
+    got = c.r.bake_coverage(W, H)
+    assert np.array_equal(got[0], whole[0]) and np.array_equal(got[1], whole[1])
+    with pytest.raises(MiptError):
+        c.r.bake_coverage(W + 1, H)
+    c.close()
+
+
+def test_coverage_is_not_ready_before_the_first_bake_trace(mixed):
+    c = Ctx(mixed)
+    inst = np.full(4, 7, np.int32)
+    assert c.r.L.pt_bake_coverage(c.r.h, 2, 2, inst.ctypes.data_as(C.c_void_p), None) == -6 and (inst == 7).all()
+    img = c.r.create_output(2, 2)
+    assert c.r.L.pt_bake_dilate(c.r.h, C.c_void_p(img.data_ptr()), 2, 2, 1) == -6
+    c.close()
+
+
+# ---- 2. the rays are the definition ----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mixed_rays(mixed, mixed_tris):
+    """The hook's rays of every texel of the 32 x 32 atlas at seeds 0 .. 7 (UV set 0, every instance) and the coverage they stand on."""
+    W, H = 32, 32
+    c = Ctx(mixed)
+    c.use(W, H)
+    q = texel_queries(W, H, range(N))
+    rays = hook_rays(c, mixed.settings, q)
+    cov = c.r.bake_coverage(W, H)
+    yield c, q, rays, cov
+    c.close()
+
+
+def test_hook_rays_are_the_definition(mixed, mixed_tris, mixed_rays, rnd, oracle_lib):
+    W, H = 32, 32
+    c, q, rays, cov = mixed_rays
+    inst, prim, which = br.coverage(mixed_tris, W, H)
+    assert np.array_equal(cov[0], inst) and np.array_equal(cov[1], prim)
+    covered = (which >= 0)[q[:, 1], q[:, 0]]
+    assert 0.2 < covered.mean() < 0.9
+    # an uncovered texel gives the sentinel
+    assert (rays[~covered, 0:7] == 0).all() and (rays[~covered, 7] == -1).all()
+    worst_o, worst_d = 0.0, 0.0
+    for k in np.nonzero(covered)[0]:
+        px, py, seed = (int(v) for v in q[k])
+        t = mixed_tris[which[py, px]]
+        o, d, tmax, bo, bd = br.ray(t, 0, W, H, px, py, rnd[seed, py, px], OFFSET)
+        eo, ed = np.abs(rays[k, 0:3].astype(f64) - o).max(), np.abs(rays[k, 4:7].astype(f64) - d).max()
+        worst_o, worst_d = max(worst_o, eo / bo), max(worst_d, ed / bd)
+        assert eo <= bo and ed <= bd, (px, py, seed, eo, bo, ed, bd)
+        # d is bit for bit -Ng of the float32 normal
+        n = br.cross(t.e1, t.e2)
+        n = -n if t.mirrored else n
+        Ng = n / np.sqrt(br.dot(n, n))
+        assert same(rays[k, 4:7], -Ng), (px, py, seed)
+    print("largest error / bound: origin %.3f, direction %.3f" % (worst_o, worst_d))
+    assert (bits(rays[covered, 7]) == bits(f32(2) * f32(OFFSET))).all() and (rays[covered, 3] == 0).all()
+    assert len(np.unique(bits(rays[covered, 0:3]), axis=0)) > 0.9 * covered.sum()       # the jitter moves the start: not one ray per texel
+    # every covered texel-sample finds its owner as the closest hit, from the front
+    o = oracle_lib.Oracle()
+    mixed.upload(o)
+    rf = rf_of(mixed.settings)
+    owner = np.stack([inst[q[covered, 1], q[covered, 0]], prim[q[covered, 1], q[covered, 0]].astype(np.int64)], axis=1)
+    for name, h in (("oracle", o.intersect_many(rays[covered], ray_hook.dxr_flags(rf))), ("product", ray_hook.gpu_intersect(c.r, rays[covered], rf))):
+        assert (h[:, 0] > 0).all(), name
+        assert np.array_equal(h[:, 4:6].astype(np.int64), owner), name
+        assert (h[:, 6] == 1).all(), name
+        assert (np.abs(h[:, 1] - OFFSET) <= 1e-5).all(), name
+    o.close()
+
+
+# ---- 3. pt_trace traces exactly the hook's rays ----------------------------------------------------------------------------------------
+def test_trace_traces_exactly_the_hooks_rays(mixed, mixed_rays):
+    W, H = 32, 32
+    hook, q, rays, cov = mixed_rays
+    covered = cov[0] >= 0
+    c = Ctx(mixed, aov=True)
+    c.use(W, H)
+    st = once(mixed.settings)
+    c.r.reset_stats()
+    for f in range(N):
+        c.trace(st, f)
+        _, alb, nd = c.read()
+        sel = q[:, 2] == f
+        assert np.array_equal(q[sel, 0].reshape(H, W)[0], np.arange(W))                 # the queries of a seed are in image order
+        hit = ray_hook.gpu_intersect(hook.r, rays[sel][covered.ravel()], rf_of(st))
+        assert (hit[:, 0] > 0).all()
+        assert same(nd[..., 3][covered], hit[:, 1]), f
+        assert np.array_equal(alb[..., 3], covered.astype(f32)), f
+        assert (nd[~covered] == 0).all() and (alb[~covered] == 0).all()
+    assert c.r.stats().rays_primary == N * int(covered.sum())
+    c.close()
+
+
+# ---- 4. a debug output's first vertex is the texel's surface point ---------------------------------------------------------------------
+@pytest.mark.parametrize("tc", [0, 1])
+def test_texcoord_debug_output_is_the_samples_own_atlas_position(mixed, mixed_tris, rnd, tc):
+    """PT_DEBUG_OUTPUT_TEXCOORD_k under a bake of set k: the interpolated UV of the first hit against the sample's clamped atlas position.
+    Tolerance: the shrink moves a point by 2^-10 (centroid - point), at most 2^-10 * 2 / 3 of the chart's largest UV edge extent (the issue's
+    2^-10 * extent is used), plus 64 roundings (the restatement's 18, the intersection's barycentrics, the interpolation) at the chart's
+    condition K and the largest UV magnitude."""
+    W, H = 32, 32
+    c = Ctx(mixed, bake=(OFFSET, tc, -1))
+    c.use(W, H)
+    st = once(mixed.settings)
+    st.debug_output = abi.DEBUG_OUTPUT_TEXCOORD_0 + tc
+    inst, prim, which = br.coverage(mixed_tris, W, H, tc)
+    checked = 0
+    for f in range(2):
+        c.trace(st, f)
+        img = c.read()[0]
+        for py, px in zip(*np.nonzero(which >= 0)):
+            t = mixed_tris[which[py, px]]
+            uv, extent = br.sample_uv(t, tc, W, H, int(px), int(py), rnd[f, py, px])
+            K = br.ray(t, tc, W, H, int(px), int(py), rnd[f, py, px], OFFSET)[3] / (br.RAY_ROUNDINGS * 2.0 ** -24)
+            K /= np.abs(t.v0).max() + np.abs(t.e1).max() + np.abs(t.e2).max() + OFFSET
+            tol = 2.0 ** -10 * extent + 64 * 2.0 ** -24 * K * max(1.0, np.abs(t.uv[tc]).max())
+            assert np.abs(img[py, px, 0:2].astype(f64) - uv).max() <= tol, (px, py, f, img[py, px], uv, tol)
+            checked += 1
+        assert (img[which < 0] == np.array([0, 0, 0, 1], f32)).all()
+    assert checked > 200
+    c.close()
+
+
+# ---- 5. radiance against the oracle ----------------------------------------------------------------------------------------------------
+def test_baked_radiance_equals_the_oracles_orthographic_view(oracle_lib):
+    """The oracle's orthographic camera looks along -Ng at the quad, its pixel grid the texel grid, its near plane OFFSET above the quad: same
+    pixel, same seed, same draws, the ray origins differ by their rounding.  64 samples at 32 x 32.
+    Measured on an MI355X: 9.608e-4."""
+    import oracle.pyoracle as po
+    W = H = 32
+    s = lit_scene()
+    c = Ctx(s)
+    c.use(W, H)
+    c.r.set_samples_per_trace(8)
+    st = copy_settings(s.settings); st.reset = 1
+    for f in range(0, 64, 8):
+        c.trace(st, f); st.reset = 0
+    assert c.r.stats().accumulated_frames == 64
+    o = oracle_lib.Oracle()
+    s.upload(o)
+    ref = np.zeros((H, W, 4), f32)
+    st = copy_settings(s.settings); st.reset = 1
+    for f in range(64):
+        o.trace(st, c.params(f), ref); st.reset = 0
+    got = c.r.tonemap(c.out)
+    r = rel_l2(got, po.tonemap(ref))
+    print("tone-mapped relative L2 of the bake against the oracle's orthographic view: %.3e" % r)
+    cov = c.r.bake_coverage(W, H)[0]
+    assert (cov == 0).all()                                          # the chart is the whole atlas
+    o.close(); c.close()
+    # control: without the occluder the bake changes
+    s2 = lit_scene(occluder=False)
+    c2 = Ctx(s2)
+    c2.use(W, H)
+    c2.r.set_samples_per_trace(8)
+    st = copy_settings(s2.settings); st.reset = 1
+    for f in range(0, 64, 8):
+        c2.trace(st, f); st.reset = 0
+    r2 = rel_l2(c2.r.tonemap(c2.out), got)
+    c2.close()
+    assert r2 > 1e-2, r2
+    assert r <= 1e-3, r
+
+
+# ---- 6. uncovered texels ---------------------------------------------------------------------------------------------------------------
+def test_uncovered_texels_are_exactly_black_and_their_tiles_retire_at_min_samples():
+    """The quad's chart is the top left 0.3 x 0.3 of a 48 x 20 atlas and the quad's instance alone is baked (the occluder's faces have UVs too):
+    the tiles of columns 16 .. 47 and of rows 16 .. 19 hold no covered texel."""
+    W, H = 48, 20
+    s = lit_scene(chart=0.3)
+    c = Ctx(s, bake=(OFFSET, 0, 0), aov=True)
+    c.use(W, H)
+    st = copy_settings(s.settings); st.reset = 1
+    black = np.array([0, 0, 0, 1], f32)
+    for f in range(8):
+        c.trace(st, f); st.reset = 0
+        if f in (0, 7):
+            cov = c.r.bake_coverage(W, H)[0] >= 0
+            assert cov[:6, :14].all() and not cov[:, 15:].any() and not cov[7:].any()
+            out, alb, nd = c.read()
+            assert same(out[~cov], np.broadcast_to(black, out[~cov].shape)), f
+            assert (bits(alb[~cov]) == 0).all() and (bits(nd[~cov]) == 0).all(), f
+            assert (alb[cov][:, 3] == 1).all() and (out[cov][:, :3] > 0).any()
+    c.close()
+    c = Ctx(s, bake=(OFFSET, 0, 0))
+    c.use(W, H)
+    c.r.set_adaptive(2, 8, 0.0)
+    st = copy_settings(s.settings)
+    for f in range(8):
+        c.trace(st, f)
+    active, samples, error, _ = c.r.adaptive_read(W, H)
+    assert active == 0
+    assert (samples[:, 1:] == 2).all() and (error[:, 1:] == 0).all() and samples[1, 0] == 2, samples     # all-uncovered tiles: E = 0 at min_samples
+    assert samples[0, 0] == 8, samples                                                   # the lit chart never reaches a threshold of 0
+    assert same(c.read()[0][:, 16:], np.broadcast_to(black, (H, W - 16, 4)))
+    c.close()
+
+
+# ---- 7. composition --------------------------------------------------------------------------------------------------------------------
+CW, CH = 48, 20
+
+
+@pytest.fixture(scope="module")
+def lit():
+    return lit_scene(chart=0.8)
+
+
+@pytest.fixture(scope="module")
+def uniform(lit):
+    """The uninterrupted bake, traced frame by frame: snapshots [n - 1] = (output, albedo, normal_depth)."""
+    c = Ctx(lit, aov=True)
+    c.use(CW, CH)
+    st = copy_settings(lit.settings); st.reset = 1
+    snaps = []
+    for f in range(N):
+        c.trace(st, f); st.reset = 0
+        snaps.append(c.read())
+    c.close()
+    assert not same(snaps[0][0], snaps[N - 1][0])
+    return snaps
+
+
+def test_a_batch_of_four_equals_four_calls(lit, uniform):
+    c = Ctx(lit, aov=True)
+    c.use(CW, CH)
+    c.r.set_samples_per_trace(4)
+    st = copy_settings(lit.settings); st.reset = 1
+    for f in (0, 4):
+        c.trace(st, f); st.reset = 0
+        for a, b in zip(c.read(), uniform[f + 3]):
+            assert same(a, b), f
+    c.close()
+
+
+def test_three_tile_shards_pack_to_the_one_rank_image(lit, uniform):
+    ranks = 3
+    root = Ctx(lit)
+    dst = [root.r.create_output(CW, CH) for _ in range(3)]
+    for k in range(ranks):
+        c = Ctx(lit, aov=True)
+        c.use(CW, CH)
+        st = copy_settings(lit.settings); st.reset = 1
+        for f in range(N):
+            c.trace(st, f, tile_rank=k, tile_rank_count=ranks); st.reset = 0
+        assert (c.r.bake_coverage(CW, CH)[0] >= 0).sum() > CW * CH // 2     # the whole atlas's map on every rank
+        for img, into in zip((c.out, c.alb, c.nd), dst):
+            packed = c.r.tiles_pack(img, k, ranks)
+            root.r.tiles_unpack(packed.clone(), into, k, ranks)
+        c.r.readback(c.out)                                          # the pack has run before the context goes
+        c.close()
+    for into, want in zip(dst, uniform[N - 1]):
+        assert same(root.r.readback(into), want)
+    root.close()
+
+
+def test_save_destroy_create_set_bake_load_continue_equals_the_uninterrupted_run(lit, uniform):
+    a = Ctx(lit, aov=True)
+    a.use(CW, CH)
+    st = copy_settings(lit.settings); st.reset = 1
+    for f in range(3):
+        a.trace(st, f); st.reset = 0
+    blob = a.r.accum_save(CW, CH, a.out, a.alb, a.nd, next_frame=3)
+    a.close()
+    b = Ctx(lit, aov=True)                                           # the bake is a setting, not part of the blob: set before the load
+    b.use(CW, CH)
+    info = b.r.accum_load(blob, b.out, b.alb, b.nd)
+    assert info.accumulated_frames == 3 and info.next_frame == 3
+    for f in range(3, N):
+        b.trace(st, f)
+        for x, y in zip(b.read(), uniform[f]):
+            assert same(x, y), f
+    assert b.r.stats().accumulated_frames == N
+    b.close()
+
+
+def test_bake_off_after_bake_on_is_the_camera_image_of_a_context_that_never_baked(lit):
+    def camera_frames(c):
+        st = copy_settings(lit.settings); st.reset = 1
+        c.r.reset_stats()
+        for f in range(4):
+            c.trace(st, f); st.reset = 0
+        t = c.r.stats()
+        return c.read(), (t.rays, t.rays_primary, t.rays_bounce, t.rays_shadow, t.closest_hits)
+
+    never = Ctx(lit, bake=None, aov=True)
+    never.use(CW, CH)
+    want, rays = camera_frames(never)
+    never.close()
+    c = Ctx(lit, aov=True)
+    c.use(CW, CH)
+    baked, _ = camera_frames(c)
+    assert not same(baked[0], want[0])
+    c.r.set_bake(OFFSET, enable=False)
+    got, rays_got = camera_frames(c)
+    for a, b in zip(got, want):
+        assert same(a, b)
+    assert rays_got == rays
+    c.close()
+
+
+# ---- 8. refusals and the restart -------------------------------------------------------------------------------------------------------
+def test_set_bake_refusals_and_the_restart(lit):
+    c = Ctx(lit, aov=True)
+    c.use(CW, CH)
+    L, h = c.r.L, c.r.h
+    st = copy_settings(lit.settings); st.reset = 1
+    for f in range(3):
+        c.trace(st, f); st.reset = 0
+    assert c.r.stats().accumulated_frames == 3
+
+    def set_rc(*cfg):
+        rc = L.pt_set_bake(h, C.byref(abi.PtBakeConfig(*cfg)))
+        return rc, L.pt_last_error(h).decode()
+
+    nan, inf = float("nan"), float("inf")
+    bad = [((1, 2, -1, OFFSET), "tex_coord"), ((1, -1, -1, OFFSET), "tex_coord"), ((1, 0, -2, OFFSET), "instance"), ((1, 0, -1, 0.0), "surface_offset"),
+           ((1, 0, -1, -0.5), "surface_offset"), ((1, 0, -1, nan), "surface_offset"), ((1, 0, -1, inf), "surface_offset")]
+    for cfg, field in bad:
+        rc, msg = set_rc(*cfg)
+        assert rc == -1 and field in msg, (cfg, rc, msg)
+    assert L.pt_set_bake(h, None) == -1 and "config" in L.pt_last_error(h).decode()
+    # the old config stays and no restart is pending
+    blob = c.r.accum_save(CW, CH, c.out, c.alb, c.nd, next_frame=3)
+    c.trace(st, 3)
+    assert c.r.stats().accumulated_frames == 4
+    ref = c.read()
+    # an instance beyond the table is the trace's to report, with nothing written and the restart still pending
+    assert set_rc(1, 0, len(lit.instances), OFFSET)[0] == 0
+    before = c.read()
+    with pytest.raises(MiptError, match="instance"):
+        c.trace(st, 4)
+    assert all(same(a, b) for a, b in zip(c.read(), before))
+    # a good config: nothing to save until the next trace, which starts anew
+    assert set_rc(1, 0, 0, 2 * OFFSET)[0] == 0
+    need = C.c_size_t()
+    img = abi.PtAccumImages(c.out.data_ptr(), c.alb.data_ptr(), c.nd.data_ptr())
+    assert L.pt_accum_save(h, C.byref(img), CW, CH, 0, 1, 0, None, 0, C.byref(need)) == -6
+    c.trace(st, 4)
+    assert c.r.stats().accumulated_frames == 1
+    assert np.allclose(c.read()[2][..., 3].max(), 2 * OFFSET, rtol=1e-4)          # the new offset is the one traced
+    # pt_accum_load clears the pending restart
+    assert set_rc(1, 0, -1, OFFSET)[0] == 0
+    c.r.accum_load(blob, c.out, c.alb, c.nd)
+    c.trace(st, 3)
+    assert c.r.stats().accumulated_frames == 4
+    assert all(same(a, b) for a, b in zip(c.read(), ref))
+    # a config that is not enabled is not checked
+    assert set_rc(0, 9, -7, nan)[0] == 0
+    c.close()
+    # the megakernel refuses a bake and writes nothing
+    m = Ctx(lit, mode=abi.MODE_MEGAKERNEL)
+    m.use(CW, CH)
+    m.out.fill_(7.0)
+    with pytest.raises(MiptError, match="wavefront"):
+        m.trace(st, 0)
+    assert (m.read()[0] == 7.0).all()
+    m.close()
+
+
+# ---- 9. dilation -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("passes", [1, 2, 5])
+def test_dilate_equals_the_restatement_bit_for_bit(mixed, mixed_rays, passes):
+    W, H = 32, 32
+    c, _, _, cov = mixed_rays
+    filled = cov[0] >= 0
+    rng = np.random.default_rng(5)
+    img = (rng.standard_normal((H, W, 4)) * 10.0 ** rng.uniform(-3, 3, (H, W, 1))).astype(f32)
+    holes = np.nonzero(~filled)
+    pick = rng.choice(len(holes[0]), len(holes[0]) // 3, replace=False)
+    img[holes[0][pick], holes[1][pick]] = np.nan                        # garbage where nothing was rendered: it must not spread
+    t = c.r.torch.from_numpy(img).to("cuda:0")
+    c.r.bake_dilate(t, passes)
+    got = c.r.readback(t)
+    want, now = br.dilate(img, filled, passes)
+    assert same(got, want)
+    assert same(got[filled], img[filled])                               # filled texels are untouched
+    assert np.isfinite(got[now]).all() and now.sum() > filled.sum()
+    for bad in (0, 65):
+        with pytest.raises(MiptError, match="passes"):
+            c.r.bake_dilate(t, bad)
+    assert c.r.L.pt_bake_dilate(c.r.h, None, W, H, 1) == -1
+    assert c.r.L.pt_bake_dilate(c.r.h, C.c_void_p(t.data_ptr()), W + 1, H, 1) == -1

@@ -28,6 +28,15 @@ in focus, --focus-pixel X,Y focuses on what that image position sees (pt_lens_fo
 continues with another lens (a --focus-pixel that now hits other geometry included).
   python tools/render_gltf.py scene.glb --spp 256 --aperture 0.05 --focus-pixel 640,400 --blades 6
 
+--bake W H: texture-space baking (pt_set_bake): the frame is a W x H UV atlas instead of a camera image (--size is ignored): the radiance that
+leaves each texel along its surface normal -- for a diffuse surface, the lightmap.  --bake-uv {0,1} picks the UV set that addresses the atlas
+(glTF's TEXCOORD_1 is conventionally the lightmap set), --bake-instance N bakes one row of the instance table (default: every instance with
+that UV set), --surface-offset D starts the rays D world units above the surface (default: 1e-4 of the scene's bounding diagonal) and
+--dilate N fills N texels beyond the charts' borders from their covered neighbours after the last sample (pt_bake_dilate; after --denoise).
+Composes with --aov (albedo.w is the coverage), --denoise, --adaptive and --checkpoint / --resume (the bake is not part of a checkpoint: repeat
+the bake options).  An ambient-occlusion map is a bake with a white diffuse world under a white sky: see INTEGRATION.md.
+  python tools/render_gltf.py scene.glb --bake 1024 1024 --bake-uv 1 --spp 256 --dilate 4 --out lightmap.exr
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -108,7 +117,16 @@ def main():
     focus.add_argument("--focus-pixel", default=None, metavar="X,Y", help="focus on what this image position sees (default: the image centre)")
     ap.add_argument("--blades", type=int, default=0, metavar="N", help="0 = circular aperture, 3..16 = polygon")
     ap.add_argument("--blade-rotation", type=float, default=0.0, metavar="DEG")
+    ap.add_argument("--bake", type=int, nargs=2, default=None, metavar=("W", "H"), help="render into a W x H UV atlas instead of through the camera")
+    ap.add_argument("--bake-uv", type=int, choices=[0, 1], default=0, help="the UV set that addresses the atlas")
+    ap.add_argument("--bake-instance", type=int, default=-1, metavar="N", help="bake one row of the instance table (default: every instance with the UV set)")
+    ap.add_argument("--surface-offset", type=float, default=None, metavar="D", help="the rays start D world units above the surface (default: 1e-4 of the scene's bounding diagonal)")
+    ap.add_argument("--dilate", type=int, default=0, metavar="N", help="with --bake: fill N texels (1..64) beyond the charts' borders")
     a = ap.parse_args()
+    if a.bake is None and (a.dilate or a.surface_offset is not None or a.bake_instance != -1 or a.bake_uv != 0):
+        ap.error("--bake-uv, --bake-instance, --surface-offset and --dilate need --bake W H")
+    if a.bake is not None and a.aperture > 0:
+        ap.error("--aperture does not apply to --bake: a bake has no lens")
 
     import torch
     from gltf_renderer_amd import abi, camera, gltf
@@ -152,7 +170,7 @@ def main():
         st.flags &= ~(abi.FLAG_ENVIRONMENT_MAP | abi.FLAG_ENVIRONMENT_MIS)
         st.environment_color[:] = (0.6, 0.7, 0.9)
     r.set_bounce_limit(max(a.bounces, abi.REFERENCE_MAX_BOUNCES))
-    w, h = a.size
+    w, h = a.bake if a.bake is not None else a.size
     p = abi.PtExecuteParams()
     p.world_to_view[:] = camera.cm(camera.orbit_world_to_view(tuple(centre), 2.2 * radius, a.azimuth, a.inclination))
     p.view_to_clip[:] = camera.cm(camera.view_to_clip(w / h, math.radians(60), 0.01 * radius, 100.0 * radius))
@@ -169,6 +187,10 @@ def main():
                 sys.exit("--focus-pixel %g,%g: nothing to focus on there, give another position or --focus D" % (fx, fy))
             print("focus at pixel %g,%g: depth %.6g" % (fx, fy, focus_distance))
         r.set_lens(a.aperture, focus_distance, a.blades, math.radians(a.blade_rotation))
+    if a.bake is not None:
+        offset = a.surface_offset if a.surface_offset is not None else 1e-4 * 2.0 * radius
+        r.set_bake(offset, a.bake_uv, a.bake_instance)
+        print("bake %d x %d: UV set %d, %s, surface offset %.6g" % (w, h, a.bake_uv, "every instance" if a.bake_instance < 0 else "instance %d" % a.bake_instance, offset))
     out = r.create_output(w, h)
     aov_albedo = aov_nd = None
     if a.aov or a.denoise is not None:
@@ -232,6 +254,11 @@ def main():
         cfg = abi.PtDenoiseConfig.default()
         cfg.iterations = a.denoise
         r.denoise(out, aov_albedo, aov_nd, out=out, config=cfg)          # in place: the AOVs are only read
+    if a.bake is not None:
+        cover = r.bake_coverage(w, h)[0] >= 0
+        print("bake: %d of %d texels covered (%.1f %%)" % (int(cover.sum()), w * h, 100.0 * cover.mean()))
+        if a.dilate:
+            r.bake_dilate(out, a.dilate)
     _, rgba8 = r.tonemap(out, want_rgba8=True)
     if a.out.lower().endswith(".exr"):
         gltf.write_exr(a.out, r.readback(out)[..., :3], half=True)       # linear radiance
