@@ -309,7 +309,10 @@ __global__ __launch_bounds__(256) void k_fit(const SegBox* __restrict__ T, uint3
 }
 
 // Writes one wide node: the children's boxes on the 8-bit grid of the node's own box (pt_types.h Bvh4Node).  Conservative: every
-// lo is rounded down and every hi up, and each is checked against bvh_dequant, the expression the traversal evaluates.
+// lo is rounded down and every hi up, and each is checked twice: against bvh_dequant, the plane in float, and against the exact p + q s
+// (pt_slab.h bvh_plane_exceeds / _short_of), which the float plane may exceed by half an ulp of a world coordinate -- the traversal's slab
+// test works on the exact plane in the ray's frame, and its pad covers errors relative to the node, not that one.  The exact check lowers
+// a ql or raises a qh (or the step) by one in rare nodes.
 __device__ void wide_write(Bvh4Node* dst, const float (*lo)[3], const float (*hi)[3], const int32_t* ref, int cnt) {
     constexpr int W = kBvhWidth, QW = W / 4;               // QW words per bound (byte k & 3 of word k >> 2 = child k)
     uint32_t qlo[3][QW], qhi[3][QW], exps = 0, origin[3];
@@ -320,13 +323,13 @@ __device__ void wide_write(Bvh4Node* dst, const float (*lo)[3], const float (*hi
         // smallest power-of-two step whose 255th plane reaches the far side
         uint32_t e = (__float_as_uint((top - p) * (1.0f / 255.0f)) >> 23) & 0xffu;
         e = e < 1u ? 1u : (e > 254u ? 254u : e);
-        while (e < 254u && !(bvh_dequant(255u, bvh_step(e), p) >= top)) e++;
+        while (e < 254u && (!(bvh_dequant(255u, bvh_step(e), p) >= top) || bvh_plane_short_of(255u, bvh_step(e), p, top))) e++;
         const float step = bvh_step(e), inv_step = bvh_step(254u - e);
         for (int k = 0; k < cnt; k++) {
             int ql = (int)floorf((lo[k][a] - p) * inv_step), qh = (int)ceilf((hi[k][a] - p) * inv_step);
             ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql); qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-            while (ql > 0 && bvh_dequant((uint32_t)ql, step, p) > lo[k][a]) ql--;
-            while (qh < 255 && bvh_dequant((uint32_t)qh, step, p) < hi[k][a]) qh++;
+            while (ql > 0 && (bvh_dequant((uint32_t)ql, step, p) > lo[k][a] || bvh_plane_exceeds((uint32_t)ql, step, p, lo[k][a]))) ql--;
+            while (qh < 255 && (bvh_dequant((uint32_t)qh, step, p) < hi[k][a] || bvh_plane_short_of((uint32_t)qh, step, p, hi[k][a]))) qh++;
             qlo[a][k >> 2] |= (uint32_t)ql << (8 * (k & 3)); qhi[a][k >> 2] |= (uint32_t)qh << (8 * (k & 3));
         }
         origin[a] = __float_as_uint(p);

@@ -2,9 +2,12 @@
 //
 // One lane = one ray.  Traversal of 64-B 4-wide nodes with 8-bit quantised child boxes (3 x dwordx4 + 1 x dwordx2
 // loads per node; each word holds one bound of all four children, the near and the far word of each axis are picked by the sign of the
-// ray's inverse direction, dequantised with v_cvt_f32_ubyte + v_fma, then
-// the slab test of the four boxes is straight VALU on registers.  Measured: an extra dwordx4 load per node step
-// costs 6 % of the frame, 110 extra VALU instructions per node step cost 1 %), children visited near-to-far (4-key sorting network on (entry distance | slot) packed in one uint), 48-B world-space
+// ray's inverse direction).  The slab test of the four boxes is straight VALU on registers, in the NODE's frame: the ray is moved there
+// once per node and axis (seven instructions an axis), and each of the 24 planes is a v_cvt_f32_ubyte and one v_fma instead of four
+// instructions (pt_slab.h: the arithmetic, its pad, and the proof that no box is culled whose triangle the candidate gate lets stand).
+// The stage is short of vector-issue slots, not of node data: about 5.5 waves per SIMD are resident, the VALU pipe is 57 % busy before
+// counting its multi-cycle instructions, a wave waits on a memory counter for 22 % of its life (profiles/r03e_instruction_mix.txt), and
+// the changes that paid here removed vector instructions from the step (profiles/EXPERIMENTS.md).  Children are visited near-to-far, 48-B world-space
 // triangle packets (3 x dwordx4), a per-lane stack held in LDS ([depth][lane] layout: conflict-free
 // ds_read/ds_write_b32) with a scratch spill for the rare deep path.
 //
@@ -28,14 +31,13 @@ namespace pt {
 #ifndef PT_STACK_LDS
 #define PT_STACK_LDS 24
 #endif
-// Distance to a box plane: (plane - origin) * inv, the subtraction first: its rounding error is RELATIVE to the distance, which
-// the 1.0000004 on the exit distance covers, so a box that the ray enters is never culled.  plane * inv - origin * inv as one fused
-// multiply-add (six VALU instructions fewer per child) has an ABSOLUTE error, half an ulp of |origin * inv|, and for a short ray that starts
-// far from the coordinate origin that is more than the padding -- measured at 1920x1080 on the Sponza-class scene, about one ray in ten
+// Distance to a box plane: (plane - origin) * inv, the subtraction first: its rounding error is RELATIVE to the distance.  plane * inv -
+// origin * inv as one fused multiply-add has an ABSOLUTE error, half an ulp of |origin * inv|, and for a short ray that starts
+// far from the coordinate origin that is more than any padding -- measured at 1920x1080 on the Sponza-class scene, about one ray in ten
 // million then missed a box whose triangle it hits (a wall's box has no thickness), left the scene through the wall and came back as a
 // firefly: 43 pixels of a 64-sample frame beyond 1e-2 of the CPU oracle's, image metric 7.9e-4 of the 1e-3 allowed; subtracting first: 2 pixels,
-// 4.0e-5, and the frame time is the same (22.7 against 22.8 ms: the traversal waits on its node loads, not on these instructions).
-#define PT_SLAB_T(P, A) (((P) - t.o.A) * t.inv.A)
+// 4.0e-5.  The node step keeps the subtraction first where it matters, (node origin - ray origin) * inv once per node, and adds
+// the plane's offset in the node, q * step * inv, to that: errors relative to the node and the ray, covered by an explicit pad (pt_slab.h).
 constexpr int kStackLds = PT_STACK_LDS;       // entries per lane in LDS  (24 * 4 B * 256 lanes = 24 KiB per workgroup)
 constexpr int kStackSpill = 40;     // further entries in scratch
 constexpr int kBlock = 256;
@@ -74,11 +76,11 @@ struct Trav {
 
 PT_DEV void trav_init(Trav& t, const SceneRec& sc, const Ray& r, uint32_t rf, uint32_t mask, int mode, float transmission0) {
     t.o = r.o; t.d = r.d; t.tmin = r.tmin; t.tmax = r.tmax;
-    // 1 / direction by the compiler's full division (a subnormal component must not give NaN), then CLAMPED to +-1e30: the slab test below is
-    // plane * inv - origin * inv, and with inv = inf (a direction component that is exactly zero: an orthographic camera looking along a
-    // world axis, a mirror bounce off an axis-aligned wall) both products are infinities whose difference is NaN -- the ray then missed every
-    // box whose slab it was INSIDE of, i.e. the whole scene.  A huge finite inv keeps the products finite: (plane - origin) * 1e30 is far
-    // beyond any ray interval with the sign it should have, for every plane farther than |origin| * 2^-24 from the origin's coordinate.
+    // 1 / direction by the compiler's full division (a subnormal component must not give NaN), then CLAMPED to +-1e30: with inv = inf (a
+    // direction component that is exactly zero: an orthographic camera looking along a world axis, a mirror bounce off an axis-aligned
+    // wall) a slab test made of products with inv meets inf - inf and 0 * inf, both NaN -- the ray then missed every box whose slab it was
+    // INSIDE of, i.e. the whole scene.  A huge finite inv keeps them finite: (plane - origin) * 1e30 is far beyond any ray interval with
+    // the sign it should have, for every plane farther than |origin| * 2^-24 from the origin's coordinate (what still overflows: pt_slab.h).
     const float kInvMax = 1.0e30f;
     t.inv = v3(clampf(1.0f / r.d.x, -kInvMax, kInvMax), clampf(1.0f / r.d.y, -kInvMax, kInvMax), clampf(1.0f / r.d.z, -kInvMax, kInvMax));
     t.rf = rf; t.mask = mask; t.mode = mode;
@@ -116,7 +118,7 @@ PT_DEV void trav_pop(Trav& t, const SceneRec& sc, const int* lds_stack, const in
     t.cur = v;
 }
 
-#define PT_CSWAP(a, b) { uint32_t _lo = min(a, b), _hi = max(a, b); a = _lo; b = _hi; }
+#define PT_CSWAP(a, b) { const bool _s = b < a; const uint64_t _lo = _s ? b : a, _hi = _s ? a : b; a = _lo; b = _hi; }
 
 // One inner-node step: t.cur >= 0 on entry; on exit t.cur is the nearest hit child, or the popped entry, or kTravDone.
 template <bool COUNT, bool ORDERED = true>
@@ -135,63 +137,66 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
 #endif
     const float limit = t.all_candidates ? t.tmax : t.best.t;
     const int c0 = __float_as_int(chf.x), c1 = __float_as_int(chf.y), c2 = __float_as_int(chf.z), c3 = __float_as_int(chf.w);
-    // dequantise the four boxes (pt_types.h Bvh4Node): plane = origin + q * 2^(exp - 127), byte k of each word = child k
+    // the four boxes (pt_types.h Bvh4Node): plane = origin + q * 2^(exp - 127), byte k of each word = child k
     const uint32_t ex = __float_as_uint(hd.w);
     const float sx = bvh_step(ex & 0xffu), sy = bvh_step((ex >> 8) & 0xffu), sz = bvh_step((ex >> 16) & 0xffu);
     const uint32_t wlx = __float_as_uint(qxy.x), whx = __float_as_uint(qxy.y), wly = __float_as_uint(qxy.z), why = __float_as_uint(qxy.w);
     const uint32_t wlz = __float_as_uint(qz.x), whz = __float_as_uint(qz.y);
-#define PT_DQ4(W, S, O) make_float4(bvh_dequant((W) & 0xffu, S, O), bvh_dequant(((W) >> 8) & 0xffu, S, O), bvh_dequant(((W) >> 16) & 0xffu, S, O), bvh_dequant((W) >> 24, S, O))
-    // lo? / hi? hold the planes the ray meets first / last on each axis (hi / lo swapped where it runs towards minus): the near and the far
-    // plane word of all four children are picked by the sign of the ray's inv BEFORE they are dequantised (two selects per axis), and the slab
-    // test uses them directly instead of fminf / fmaxf of every pair of plane distances: 15 vector instructions fewer in every copy of the
-    // step (tools/kernel_sizes.sh).  The values are the same: lo <= hi per child (the builder's quantisation keeps the order) and inv is
-    // finite and not NaN for every finite direction (trav_init clamps it to +-1e30), so (near - o) * inv <= (far - o) * inv and no 0 * inf
-    // occurs; only the sign of a zero distance can differ, which can change a visiting order but never a hit (candidate_stands).
-    // Measured: EXPERIMENTS.md.
+    // The ray in the node's frame, once per node and axis (pt_slab.h): a plane's distance is then fma((float)q, S, An or Af), a byte conversion
+    // and one fused multiply-add instead of dequantise, subtract, multiply.
+    const SlabAxis ax = slab_axis(sx, hd.x, t.o.x, t.inv.x), ay = slab_axis(sy, hd.y, t.o.y, t.inv.y), az = slab_axis(sz, hd.z, t.o.z, t.inv.z);
+    // The near and the far plane word of all four children are picked by the sign of the ray's inv BEFORE their bytes are converted (two selects
+    // per axis), and the slab test uses them directly instead of fminf / fmaxf of every pair of plane distances: 15 vector instructions fewer
+    // in every copy of the step (tools/kernel_sizes.sh).  The choice is right: lo <= hi per child (the builder's quantisation keeps the
+    // order) and inv is finite and not NaN for every finite direction (trav_init clamps it to +-1e30).  Measured: EXPERIMENTS.md.
     const bool nx = t.inv.x < 0.0f, ny = t.inv.y < 0.0f, nz = t.inv.z < 0.0f;
-    const float4 lox = PT_DQ4(nx ? whx : wlx, sx, hd.x), hix = PT_DQ4(nx ? wlx : whx, sx, hd.x), loy = PT_DQ4(ny ? why : wly, sy, hd.y), hiy = PT_DQ4(ny ? wly : why, sy, hd.y);
-    const float4 loz = PT_DQ4(nz ? whz : wlz, sz, hd.z), hiz = PT_DQ4(nz ? wlz : whz, sz, hd.z);
-#undef PT_DQ4
-    uint32_t key[4];
-#define PT_SLAB(K, CH, LX, LY, LZ, HX, HY, HZ)                                                                            \
+    const uint32_t wnx = nx ? whx : wlx, wfx = nx ? wlx : whx, wny = ny ? why : wly, wfy = ny ? wly : why, wnz = nz ? whz : wlz, wfz = nz ? wlz : whz;
+    bool enters[4];
+    float entry[4];
+#define PT_Q(W, K) ((float)(((W) >> (8 * (K))) & 0xffu))
+#define PT_SLAB(K, CH)                                                                                                    \
     {                                                                                                                     \
-        float a0 = PT_SLAB_T(LX, x), b0 = PT_SLAB_T(HX, x), a1 = PT_SLAB_T(LY, y), b1 = PT_SLAB_T(HY, y);                   \
-        float a2 = PT_SLAB_T(LZ, z), b2 = PT_SLAB_T(HZ, z);                                                                \
+        float a0 = slab_near(PT_Q(wnx, K), ax), b0 = slab_far(PT_Q(wfx, K), ax), a1 = slab_near(PT_Q(wny, K), ay);          \
+        float b1 = slab_far(PT_Q(wfy, K), ay), a2 = slab_near(PT_Q(wnz, K), az), b2 = slab_far(PT_Q(wfz, K), az);           \
         float tn = fmaxf(fmaxf(a0, a1), fmaxf(a2, t.tmin));                                                                \
         float tx = fminf(fminf(b0, b1), fminf(b2, limit)) * 1.0000004f;                                                    \
-        key[K] = (tn <= tx && CH != kEmptyChild) ? ((__float_as_uint(tn) & ~3u) | (uint32_t)K) : 0xffffffffu;              \
+        enters[K] = tn <= tx && CH != kEmptyChild; entry[K] = tn;                                                          \
     }
-    PT_SLAB(0, c0, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x)
-    PT_SLAB(1, c1, lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y)
-    PT_SLAB(2, c2, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z)
-    PT_SLAB(3, c3, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w)
+    PT_SLAB(0, c0) PT_SLAB(1, c1) PT_SLAB(2, c2) PT_SLAB(3, c3)
 #undef PT_SLAB
+#undef PT_Q
     // a step pushes at most three entries: if no active lane is within three of the LDS part's end, every push is a plain ds_write
     const bool shallow = __ballot(t.sp + 3 > kStackLds) == 0;
     if (!ORDERED) {
         // occlusion rays accept any hit: visiting order is irrelevant, skip the sort
         int next = kTravDone;
-        if (key[0] != 0xffffffffu) next = c0;
+        if (enters[0]) next = c0;
 #define PT_PUSH_UNORDERED(F)                                                                                                        \
-        if (key[1] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c1, st); else next = c1; }           \
-        if (key[2] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c2, st); else next = c2; }           \
-        if (key[3] != 0xffffffffu) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c3, st); else next = c3; }
+        if (enters[1]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c1, st); else next = c1; }           \
+        if (enters[2]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c2, st); else next = c2; }           \
+        if (enters[3]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c3, st); else next = c3; }
         if (shallow) { PT_PUSH_UNORDERED(true) } else { PT_PUSH_UNORDERED(false) }
 #undef PT_PUSH_UNORDERED
         if (next != kTravDone) t.cur = next; else trav_pop(t, sc, lds_stack, spill);
         return;
     }
-    // sort the 4 keys ascending (tn >= 0, so its bit pattern orders like the float); misses sink to the end
+    // sort the 4 children as 64-bit (bits of the entry distance, reference) pairs, ascending (tn >= 0, so its bit pattern orders like the
+    // float); a miss is all ones and sinks to the end, equal distances go by reference.  The sorted key carries its child: no slot to look
+    // up afterwards, and the distance keeps all its bits.
+    constexpr uint64_t kMiss = ~0ull;
+    uint64_t key[4];
+#define PT_KEY(K, CH) key[K] = enters[K] ? ((uint64_t)__float_as_uint(entry[K]) << 32 | (uint32_t)CH) : kMiss;
+    PT_KEY(0, c0) PT_KEY(1, c1) PT_KEY(2, c2) PT_KEY(3, c3)
+#undef PT_KEY
     PT_CSWAP(key[0], key[1]) PT_CSWAP(key[2], key[3]) PT_CSWAP(key[0], key[2]) PT_CSWAP(key[1], key[3]) PT_CSWAP(key[1], key[2])
-    auto child_of = [&](uint32_t k) { uint32_t s = k & 3u; return s == 0 ? c0 : (s == 1 ? c1 : (s == 2 ? c2 : c3)); };
-    if (key[0] != 0xffffffffu) {
+    if (key[0] != kMiss) {
 #define PT_PUSH_ORDERED(F)                                                                                                          \
-        if (key[3] != 0xffffffffu) trav_push<F>(t, sc, lds_stack, spill, child_of(key[3]), st);                                         \
-        if (key[2] != 0xffffffffu) trav_push<F>(t, sc, lds_stack, spill, child_of(key[2]), st);                                         \
-        if (key[1] != 0xffffffffu) trav_push<F>(t, sc, lds_stack, spill, child_of(key[1]), st);
+        if (key[3] != kMiss) trav_push<F>(t, sc, lds_stack, spill, (int)(uint32_t)key[3], st);                                          \
+        if (key[2] != kMiss) trav_push<F>(t, sc, lds_stack, spill, (int)(uint32_t)key[2], st);                                          \
+        if (key[1] != kMiss) trav_push<F>(t, sc, lds_stack, spill, (int)(uint32_t)key[1], st);
         if (shallow) { PT_PUSH_ORDERED(true) } else { PT_PUSH_ORDERED(false) }
 #undef PT_PUSH_ORDERED
-        t.cur = child_of(key[0]);
+        t.cur = (int)(uint32_t)key[0];
     } else trav_pop(t, sc, lds_stack, spill);
 }
 
@@ -201,7 +206,8 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
 //      before the triangle is asked depends on the tree -- two trees (this one, the CPU oracle's binary one) then disagree on about one ray
 //      in 10^8, each a different path: fireflies.  So a candidate also has to pass the box test of ITS OWN box, in the node test's
 //      arithmetic, and its distance has to be consistent with that box.  Every ancestor's box contains the triangle's (the builder checks
-//      the dequantised planes against it), each operation of the box test is monotone in the plane under float rounding, so an ancestor
+//      the exact planes p + q s against it), and the node step's distances, taken in the node's frame with an explicit pad, are never on the
+//      wrong side of the distances computed here (pt_slab.h: the inequality and its proof; tests/host/slab_check.cpp), so an ancestor
 //      passes whenever the triangle's own box does: no tree culls a candidate that stands, and none is asked about one that does not.
 //  (2) The tie rule.  Two triangles at EXACTLY the same distance (coplanar, overlapping surfaces): DXR leaves the winner to the order of the
 //      walk; here the lower (instance, primitive) wins.
@@ -210,8 +216,8 @@ PT_DEV bool candidate_stands(const Trav& t, const SceneRec& sc, vec3 v0, vec3 e1
     // (1) the box gate
     const vec3 v1 = v0 + e1, v2 = v0 + e2;                                          // the builder's expression for the box (accel.hip k_seg_pass)
     const vec3 lo = hmin(hmin(v0, v1), v2), hi = hmax(hmax(v0, v1), v2);
-    const float a0 = (lo.x - t.o.x) * t.inv.x, b0 = (hi.x - t.o.x) * t.inv.x, a1 = (lo.y - t.o.y) * t.inv.y, b1 = (hi.y - t.o.y) * t.inv.y;
-    const float a2 = (lo.z - t.o.z) * t.inv.z, b2 = (hi.z - t.o.z) * t.inv.z;
+    const float a0 = own_box_t(lo.x, t.o.x, t.inv.x), b0 = own_box_t(hi.x, t.o.x, t.inv.x), a1 = own_box_t(lo.y, t.o.y, t.inv.y), b1 = own_box_t(hi.y, t.o.y, t.inv.y);
+    const float a2 = own_box_t(lo.z, t.o.z, t.inv.z), b2 = own_box_t(hi.z, t.o.z, t.inv.z);
     const float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));
     const float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fmaxf(a2, b2));
     if (!(tn <= tx * 1.0000004f && tn <= tt * 1.0000004f)) return false;

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/mipt.h"
+#include "pt_slab.h"
 
 namespace pt {
 
@@ -90,10 +91,10 @@ struct __attribute__((aligned(64))) BvhNode {
 static_assert(sizeof(BvhNode) == 64, "BvhNode");
 
 // 64-B 4-wide node, the children's boxes quantised to 8 bits per plane on the grid origin + q * 2^(exp - 127) spanned by the
-// node's own box (three dwordx4 + one dwordx2 load per node step instead of seven dwordx4: the traversal stages are bound by
-// vector-memory instruction issue, not by VALU, so the dequantisation is free and the loads saved are time saved).
-// Quantisation is conservative (lo rounded down, hi rounded up, checked with the very fma the traversal uses), so a ray enters a
-// superset of the children it would enter with exact boxes and finds the same hits.
+// node's own box (three dwordx4 + one dwordx2 load per node step instead of seven dwordx4).  The traversal never forms a plane in
+// world coordinates: it tests the bytes in the node's frame (pt_slab.h), a conversion and a fused multiply-add per plane.
+// Quantisation is conservative (lo rounded down, hi rounded up, checked against the plane in float AND against the exact p + q s,
+// which the traversal's arithmetic stands on), so a ray enters a superset of the children it would enter with exact boxes and finds the same hits.
 // child >= 0: wide node index; child < 0: leaf reference (below); kEmptyChild: unused slot (never entered).
 // The node uses 56 of its 64 bytes and the fourth load brings 8 of them.  A 48-B payload in the same 64-B line and stride (origin as
 // 16-bit cell indices on a per-tree grid, 5-bit step exponents below the root's: three dwordx4 loads, explicit child references kept) was
@@ -114,11 +115,7 @@ constexpr int kNodeFloat4 = (int)(sizeof(Bvh4Node) / 16);
 // Written by the collapse, read by the refit: a child's box is a range query over the triangles' boxes.
 struct __attribute__((aligned(16))) WideRanges { uint32_t first[kBvhWidth], count[kBvhWidth]; };
 constexpr int32_t kEmptyChild = 0x7fffffff;
-// the plane a quantised coordinate stands for; build and traversal must use this one expression
-__host__ __device__ __forceinline__ float bvh_dequant(uint32_t q, float step, float origin) { return __builtin_fmaf((float)q, step, origin); }
-__host__ __device__ __forceinline__ float bvh_step(uint32_t biased_exp) {
-    union { uint32_t u; float f; } c; c.u = biased_exp << 23; return c.f;
-}
+// (bvh_step and bvh_dequant, the grid step and the plane a quantised coordinate stands for: pt_slab.h)
 // Leaf reference: ~(first | (count - 1) << 28): `count` (1..kLeafMax) triangle packets starting at `first`, contiguous because
 // an LBVH subtree covers a contiguous range of the Morton-sorted triangles.  first < 2^28.
 #ifndef PT_LEAF_MAX
