@@ -273,6 +273,12 @@ class PtBakeConfig(C.Structure):
     _fields_ = [("enable", C.c_int32), ("tex_coord", C.c_int32), ("instance", C.c_int32), ("surface_offset", C.c_float)]
 
 
+class PtProbeConfig(C.Structure):
+    """pt_probe_config: light-probe baking (pt_set_probes; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("resolution", C.c_int32), ("count", C.c_int32), ("columns", C.c_int32), ("max_distance", C.c_float)]
+
+
+PROBE_SH_RADIANCE, PROBE_SH_IRRADIANCE = 0, 1
 ACCUM_OUTPUT, ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE = 1, 2, 4, 8
 ACCUM_HEADER_BYTES = 160
 
@@ -311,5 +317,7 @@ assert C.sizeof(PtLensConfig) == 20
 assert [getattr(PtLensConfig, f).offset for f, _ in PtLensConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtBakeConfig) == 16
 assert [getattr(PtBakeConfig, f).offset for f, _ in PtBakeConfig._fields_] == [0, 4, 8, 12]
+assert C.sizeof(PtProbeConfig) == 20
+assert [getattr(PtProbeConfig, f).offset for f, _ in PtProbeConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

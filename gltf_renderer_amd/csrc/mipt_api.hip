@@ -279,7 +279,17 @@ public:
         if (bake && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "a bake runs in the wavefront mode only");
         if (bake && ctx->bake.instance >= (int)ctx->instances.size())
             return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance " + std::to_string(ctx->bake.instance) + " of " + std::to_string(ctx->instances.size()));
+        // Light-probe baking (pt_set_probes): likewise, the paths start at the probes' positions and width x height is the probes' atlas.
+        const bool probes = ctx->probes.enable != 0;
+        if (probes && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes are traced in the wavefront mode only");
+        if (probes) {
+            uint64_t pw, ph;
+            probe_atlas_size(ctx->probes, pw, ph);
+            if (ep->width != pw || ep->height != ph)
+                return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the atlas is " + std::to_string(pw) + " x " + std::to_string(ph) + ", not " + std::to_string(ep->width) + " x " + std::to_string(ep->height));
+        }
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (ctx->probe_restart) { reset = true; ctx->probe_restart = false; }
         if (ctx->bake_restart) { reset = true; ctx->bake_restart = false; }
         if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
         if (ctx->lens_restart) { reset = true; ctx->lens_restart = false; }
@@ -381,8 +391,10 @@ public:
                     ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
                 }
                 const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
+                const ProbeArgs pa = probe_args(ctx);
                 HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
-                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr));
+                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr,
+                                       probes ? &pa : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
@@ -1019,6 +1031,7 @@ int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config) {
         if (config->tex_coord != 0 && config->tex_coord != 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: tex_coord must be 0 or 1");
         if (config->instance < -1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance must be -1 or a row of the instance table");
         if (!std::isfinite(config->surface_offset) || !(config->surface_offset > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: surface_offset must be finite and > 0");
+        if (ctx->probes.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: probes are enabled (pt_set_probes): a trace renders one atlas or the other");
     }
     ctx->bake = *config;
     ctx->bake_restart = true;
@@ -1054,6 +1067,70 @@ int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, in
     if (const hipError_t e = ctx->d_bake_dilate.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "bake_dilate scratch: " + std::to_string(need) + " bytes");
     HIPOK(launch_bake_dilate((float4*)image, ctx->d_bake_owner.as<uint32_t>(), width, height, passes, ctx->d_bake_dilate.as<float4>(),
                              ctx->d_bake_dilate.as<uint8_t>() + n * 16, ctx->stream));
+    return PT_OK;
+}
+
+int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* positions_xyz) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: config is NULL");
+    if (!config->enable) {                        // nothing else of a disabled config is looked at; the layout and the positions go
+        ctx->probes.enable = 0;
+        ctx->probe_restart = true;
+        return PT_OK;
+    }
+    if (!positions_xyz) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: positions_xyz is NULL");
+    if (config->resolution < 16 || config->resolution > 1024 || config->resolution % 16 != 0)
+        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: resolution must be a multiple of 16 in 16..1024");
+    if (config->count < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: count must be >= 1");
+    if (config->columns < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns must be >= 1");
+    if (!std::isfinite(config->max_distance) || !(config->max_distance > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: max_distance must be finite and > 0");
+    uint64_t w, h;
+    probe_atlas_size(*config, w, h);
+    if (w > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns * resolution = " + std::to_string(w) + " exceeds 2^30");
+    if (h > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: rows * resolution = " + std::to_string(h) + " (count / columns rows) exceeds 2^30");
+    for (int64_t i = 0; i < (int64_t)config->count * 3; i++)
+        if (!std::isfinite(positions_xyz[i])) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the position of probe " + std::to_string(i / 3) + " is not finite");
+    if (ctx->bake.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: a bake is enabled (pt_set_bake): a trace renders one atlas or the other");
+    ENTER(ctx);
+    const size_t bytes = (size_t)config->count * 12;
+    // a trace in flight may still read the old positions: the copy goes behind it on the stream, a larger array drains it first (DevBuf)
+    if (const hipError_t e = ctx->d_probe_pos.reserve(ctx->stream, bytes, bytes)) {
+        if (ctx->d_probe_pos.ptr == nullptr) { ctx->probes.enable = 0; ctx->probe_restart = true; }     // the old array went with the failed growth
+        return grow_failed(ctx, e, "probe positions: " + std::to_string(bytes) + " bytes");
+    }
+    if (const hipError_t e = staged_upload(ctx, ctx->d_probe_pos.ptr, positions_xyz, bytes)) {
+        ctx->probes.enable = 0; ctx->probe_restart = true;               // the array may hold part of either set: back to the camera
+        return ctx->fail(PT_ERR_DEVICE, std::string("probe positions: ") + hipGetErrorString(e));
+    }
+    ctx->probes = *config;
+    ctx->probe_restart = true;
+    return PT_OK;
+}
+
+int pt_probe_project(pt_ctx* ctx, const void* atlas_device, uint32_t width, uint32_t height, int kind, float* sh_host) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!atlas_device || !sh_host) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: NULL argument");
+    if (kind != PT_PROBE_SH_RADIANCE && kind != PT_PROBE_SH_IRRADIANCE) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: kind must be PT_PROBE_SH_RADIANCE or PT_PROBE_SH_IRRADIANCE");
+    if (!ctx->probes.enable) return ctx->fail(PT_ERR_NOT_READY, "probe_project: no probes are set");
+    uint64_t w, h;
+    probe_atlas_size(ctx->probes, w, h);
+    if (width != w || height != h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: the atlas is " + std::to_string(w) + " x " + std::to_string(h));
+    ENTER(ctx);
+    const uint32_t n = (uint32_t)ctx->probes.resolution, count = (uint32_t)ctx->probes.count;
+    if (ctx->probe_dirs_n != n) {
+        const size_t bytes = (size_t)n * n * 16;
+        ctx->probe_dirs_n = 0;
+        if (const hipError_t e = ctx->d_probe_dirs.reserve(ctx->stream, bytes, bytes)) return grow_failed(ctx, e, "probe direction table: " + std::to_string(bytes) + " bytes");
+        launch_probe_dirs(ctx->d_probe_dirs.as<float4>(), n, ctx->stream);
+        HIPOK(hipGetLastError());
+        ctx->probe_dirs_n = n;
+    }
+    const size_t out_bytes = (size_t)count * 27 * 4;
+    if (const hipError_t e = ctx->d_probe_sh.reserve(ctx->stream, out_bytes, out_bytes)) return grow_failed(ctx, e, "probe coefficients: " + std::to_string(out_bytes) + " bytes");
+    launch_probe_project((const float4*)atlas_device, ctx->d_probe_dirs.as<float4>(), n, count, (uint32_t)ctx->probes.columns, kind, ctx->d_probe_sh.as<float>(), ctx->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(sh_host, ctx->d_probe_sh.ptr, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPOK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
 
@@ -1243,7 +1320,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake since the last trace: the next trace starts anew");
+    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1338,7 +1415,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false;
+    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false;
     return PT_OK;
 }
 

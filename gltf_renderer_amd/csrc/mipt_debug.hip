@@ -66,6 +66,31 @@ extern "C" int pt_debug_bake_rays(pt_ctx* ctx, const pt_settings* settings, cons
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_bake_rays: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the rays pt_trace would start for the queries {px, py, seed} under the context's probes (pt_set_probes,
+// which must be on) on their atlas, which params->width x height must be -- probe_ray itself, the generate kernel's ray function, one query
+// per lane (pt_wavefront.hip k_debug_probe_rays).  queries: 3 uint32 each, out: 8 floats each (origin, tmin, direction, tmax; zeros with
+// tmax = -1 for a cell without a probe), host arrays.  Leaves the accumulation and a pending restart as they are.
+extern "C" int pt_debug_probe_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
+    if (!ctx || !settings || !params || (n && (!queries || !out))) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->probes.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_probe_rays: no probes are set");
+    uint64_t w, h;
+    probe_atlas_size(ctx->probes, w, h);
+    if (params->width != w || params->height != h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_probe_rays: the atlas is " + std::to_string(w) + " x " + std::to_string(h));
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    FrameConstants fc;
+    memset(&fc, 0, sizeof(fc));
+    fc.res_x = params->width; fc.res_y = params->height;
+    const ProbeArgs pa = probe_args(ctx);
+    TempBuf d_q, d_out;
+    if (d_q.alloc((size_t)n * 12) != hipSuccess || d_out.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_probe_rays: buffers"); }
+    hipError_t e = hipMemcpyAsync(d_q.ptr, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) { launch_debug_probe_rays(fc, pa, d_q.as<uint32_t>(), n, d_out.as<float>(), ctx->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_probe_rays: ") + hipGetErrorString(e));
+}
+
 // test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
 // 8 floats per ray out, pt_kernel.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
 extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, uint32_t ray_flags, int mode, float* out) {

@@ -107,6 +107,12 @@ struct pt_ctx {
     uint32_t bake_w = 0, bake_h = 0;
     pt_bake_config bake_built = {0, 0, -1, 0.0f};
     uint64_t bake_accel = 0;                      // accel_builds + accel_refits when the map was built: the packets it was rasterised from
+    // ---- light-probe baking (pt_set_probes): the config, the probes' positions, and pt_probe_project's direction table and result
+    pt_probe_config probes = {0, 16, 1, 1, 1000.0f};
+    bool probe_restart = false;                   // pt_set_probes: the next pt_trace starts a new accumulation
+    pt::DevBuf d_probe_pos;                       // float[3] per probe (ProbeArgs::positions): probes.count of them while probes.enable != 0
+    pt::DevBuf d_probe_dirs; uint32_t probe_dirs_n = 0;   // the texel-centre directions of a probe_dirs_n^2 map, built by the first pt_probe_project of a resolution
+    pt::DevBuf d_probe_sh;                        // pt_probe_project's 27 floats per probe
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
 
@@ -147,6 +153,19 @@ void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, Frame
 // state of the tree -- and what k_wf_generate_bake takes.  After ensure_accel.  pt_trace and the hook pt_debug_bake_rays both come through
 // here.  (mipt_api.hip)
 int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake);
+
+// The probes of a call (pt_set_probes) as k_wf_generate_probe takes them, and the atlas they make (mipt_api.hip)
+inline void probe_atlas_size(const pt_probe_config& c, uint64_t& w, uint64_t& h) {
+    w = (uint64_t)c.columns * (uint64_t)c.resolution;
+    h = (((uint64_t)c.count + (uint64_t)c.columns - 1) / (uint64_t)c.columns) * (uint64_t)c.resolution;
+}
+inline ProbeArgs probe_args(const pt_ctx* ctx) {
+    ProbeArgs pa;
+    pa.positions = ctx->d_probe_pos.as<float>();
+    pa.n = (uint32_t)ctx->probes.resolution; pa.count = (uint32_t)ctx->probes.count; pa.columns = (uint32_t)ctx->probes.columns;
+    pa.div_n = FastDiv::make(pa.n); pa.max_distance = ctx->probes.max_distance;
+    return pa;
+}
 
 // Pathtracer::BuildAccel (mipt_api.hip) if the tree does not stand for the current tables, as every call that traces rays begins
 int ensure_accel(pt_ctx* ctx);

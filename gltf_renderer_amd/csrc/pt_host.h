@@ -166,16 +166,33 @@ struct BakeArgs {
     float surface_offset;
     int32_t tex_coord;
 };
+// Light-probe baking (pt_set_probes): what k_wf_generate_probe takes as its own argument.
+struct ProbeArgs {
+    const float* positions;   // count * 3, world space (owned by the context)
+    uint32_t n, count, columns;   // each probe is an n x n octahedral map; probe k sits at atlas cell (k % columns, k / columns)
+    FastDiv div_n;
+    float max_distance;       // the probe ray's tmax
+};
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
 // bake: nullptr = camera rays (k_wf_generate); else k_wf_generate_bake starts the paths on the atlas's texels and `lens` is not looked at
+// probes: nullptr likewise; else k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 // aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
-                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr);
+                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr, const ProbeArgs* probes = nullptr);
 // pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+
+// pt_debug_probe_rays: d_out = 8 floats per query {px, py, seed}, probe_ray's ray; zeros with tmax = -1 for an absent probe or a texel off the atlas
+void launch_debug_probe_rays(const FrameConstants& fc, const ProbeArgs& probes, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+
+// ---- probe.hip: pt_probe_project's reduction of an octahedral atlas to spherical harmonics --------------------------------------
+// dirs: n * n float4, the texel-centre directions of an n x n octahedral map (w unused), row-major.  Asynchronous.
+void launch_probe_dirs(float4* dirs, uint32_t n, hipStream_t stream);
+// sh: count * 27 floats on the device, [probe][coefficient][rgb]; atlas: the (columns * n) wide float4 image.  kind: PT_PROBE_SH_*.  Asynchronous.
+void launch_probe_project(const float4* atlas, const float4* dirs, uint32_t n, uint32_t count, uint32_t columns, int kind, float* sh, hipStream_t stream);
 
 // ---- bake.hip: the coverage map of pt_set_bake and pt_bake_dilate's passes ---------------------------------------------------
 // The UV rasteriser over the built tree's packets.  keys: w * h (instance << 32 | primitive of the owner, all ones where none covers);

@@ -24,6 +24,7 @@
 #include "pt_vertex.h"
 #include "pt_host.h"
 #include "pt_bake.h"
+#include "pt_probe.h"
 
 #ifdef PT_TIMING                 // diagnostic build only (tools/shade_sections.py); not part of the C-ABI
 namespace pt { __device__ unsigned long long pt_timing[12]; }
@@ -233,6 +234,58 @@ __global__ __launch_bounds__(kBlock) void k_debug_bake_rays(FrameConstants fc, B
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_bake_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, bake, d_queries, n, d_out);
+}
+
+// Light-probe baking (pt_set_probes): the generate stage of an atlas whose "camera" is a set of points -- k_wf_generate_bake with another ray.
+// Slots, tiles, shards and the queue are k_wf_generate's; the ray of a (texel, sample) is probe_ray's (pt_probe.h).  The resolution is a
+// multiple of PT_TILE, so a workgroup-round (one tile of one sample) lies in one probe's map: the probe index is wave-uniform and the position
+// is read once per wave.  A cell without a probe pushes no ray and counts none; its records are written here, as an uncovered bake texel's.
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock, 7) void k_wf_generate_probe(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, ProbeArgs pa, AovArgs av) {
+    const ShardView sv = shard_view(wf);
+    unsigned n_primary = 0;
+    for (uint32_t rnd = 0; rnd < wf.gen_rounds; rnd++) {
+        const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+        const uint32_t sample = slot_sample(fc, slot);
+        uint32_t px = 0, py = 0;
+        bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
+        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
+        int rc = 0;
+        Ray ray;
+        ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
+        bool present = false;
+        if (valid) present = probe_ray<true>(fc, pa, sample_seed(fc, sample), px, py, rc, ray);
+        const uint32_t idx = queue_push(wf.cnt[0] + sv.shard * kCounterStride, present);
+        if (present) {
+            const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
+            QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
+            QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
+            n_primary++;
+        } else if (valid) {
+            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            wf.L[slot] = zero;
+            if (av.albedo) QST(av.rec_albedo[slot], zero);
+            if (av.normal_depth) QST(av.rec_normal[slot], zero);
+        }
+    }
+    LaneStats st = {0, 0, 0, 0};
+    flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+}
+// Test hook (pt_debug_probe_rays, mipt_debug.hip): probe_ray itself, one query {px, py, seed} per lane (the cells differ from lane to lane)
+__global__ __launch_bounds__(kBlock) void k_debug_probe_rays(FrameConstants fc, ProbeArgs pa, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t px = queries[3 * (size_t)i], py = queries[3 * (size_t)i + 1];
+    int rc = 0;
+    Ray r;
+    r.o = v3(0); r.d = v3(0); r.tmin = 0; r.tmax = -1.0f;
+    if (px < fc.res_x && py < fc.res_y) probe_ray<false>(fc, pa, queries[3 * (size_t)i + 2], px, py, rc, r);
+    float* o = out + (size_t)i * 8;
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
+}
+void launch_debug_probe_rays(const FrameConstants& fc, const ProbeArgs& probes, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_probe_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, probes, d_queries, n, d_out);
 }
 
 // Wave-persistent "while-while" traversal of one shard segment with dynamic ray fetch (pt_traverse.h).
@@ -912,7 +965,8 @@ static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const Sc
 }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake,
+                            const ProbeArgs* probes) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -945,7 +999,9 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     }
     AdaptiveArgs ad = {};
     if (adaptive) ad = *adaptive;
-    if (bake) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_bake<true>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av);
+    if (probes) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_probe<true>), stage, block, 0, stream, fc, wf, counters, ad, *probes, av);
+                  else hipLaunchKernelGGL((k_wf_generate_probe<false>), stage, block, 0, stream, fc, wf, counters, ad, *probes, av); }
+    else if (bake) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_bake<true>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av);
                 else hipLaunchKernelGGL((k_wf_generate_bake<false>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av); }
     else if (adaptive) { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<true, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
                     else hipLaunchKernelGGL((k_wf_generate<true, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }

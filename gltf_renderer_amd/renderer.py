@@ -35,7 +35,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # thin-lens depth of field (additive likewise)
            "pt_set_lens", "pt_lens_focus_at",
            # texture-space baking (additive likewise)
-           "pt_set_bake", "pt_bake_coverage", "pt_bake_dilate"]
+           "pt_set_bake", "pt_bake_coverage", "pt_bake_dilate",
+           # light-probe baking (additive likewise)
+           "pt_set_probes", "pt_probe_project"]
 
 
 class MiptError(RuntimeError):
@@ -119,6 +121,8 @@ def load_library():
     L.pt_set_bake.argtypes = [vp, vp]
     L.pt_bake_coverage.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
     L.pt_bake_dilate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci]
+    L.pt_set_probes.argtypes = [vp, vp, vp]
+    L.pt_probe_project.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci, vp]
     _LIB = L
     return L
 
@@ -357,6 +361,34 @@ class Renderer:
         """pt_bake_dilate: fills the uncovered texels of a device image (create_output) from their covered neighbours, `passes` texels
         deep, in place; for the atlas size of the last bake trace()."""
         self._check(self.L.pt_bake_dilate(self.h, image.data_ptr(), image.shape[1], image.shape[0], int(passes)))
+
+    def set_probes(self, positions, resolution, columns=None, max_distance=1000.0, enable=True):
+        """Light-probe baking (include/mipt.h pt_set_probes): trace() renders an atlas of octahedral maps, resolution x resolution texels
+        for each of the K world-space `positions` (K, 3), `columns` probes to an atlas row (default: about a square).  Returns the atlas
+        size (W, H) trace() then expects.  The next trace() starts a new accumulation.  Wavefront mode only; not together with set_bake().
+        Probes are not part of an accum_save() blob: set the same probes before accum_load().  enable=False returns to the camera."""
+        if not enable:
+            self._check(self.L.pt_set_probes(self.h, C.byref(abi.PtProbeConfig(0, 0, 0, 0, 0.0)), None))
+            return None
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        k = len(pos)
+        if columns is None:
+            columns = max(1, int(np.ceil(np.sqrt(k))))
+        cfg = abi.PtProbeConfig(1, int(resolution), k, int(columns), float(max_distance))
+        self._check(self.L.pt_set_probes(self.h, C.byref(cfg), _p(pos)))
+        return int(columns) * int(resolution), -(-k // int(columns)) * int(resolution)
+
+    def probe_project(self, atlas, kind=0):
+        """pt_probe_project: the nine real spherical-harmonic coefficients (bands 0..2) per channel of every probe of a device atlas
+        (create_output of the size set_probes() returned): float32 (K, 9, 3).  kind: abi.PROBE_SH_RADIANCE, or abi.PROBE_SH_IRRADIANCE
+        for coefficients whose sum over Y_lm(n) is the irradiance on a surface with normal n."""
+        # The library writes 27 floats for each probe of ITS layout, which it holds the atlas size to.  A map is at least 16 x 16, so
+        # an atlas has at most (W / 16) * (H / 16) cells: room for any layout of this size, however the probes were set.
+        cells = max(1, (atlas.shape[1] // 16) * (atlas.shape[0] // 16))
+        sh = np.full((cells, 9, 3), np.nan, np.float32)
+        self._check(self.L.pt_probe_project(self.h, C.c_void_p(atlas.data_ptr()), atlas.shape[1], atlas.shape[0], int(kind), _p(sh)))
+        written = ~np.isnan(sh).all(axis=(1, 2))                       # the rows the library wrote: its probe count (non-finite texels count as 0)
+        return np.ascontiguousarray(sh[:int(np.nonzero(written)[0].max()) + 1 if written.any() else 0])
 
     def focus_at(self, settings, params, px, py):
         """Autofocus (include/mipt.h pt_lens_focus_at): the view-space depth of what the pinhole ray through image position (px, py) sees

@@ -678,6 +678,65 @@ int pt_bake_coverage(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* inst
  * PT_ERR_INVALID_ARGUMENT, with nothing written: a NULL ctx (answered before any device call), a NULL image, a zero width or height, passes
  * outside 1..64, a size other than the map's.  PT_ERR_NOT_READY before the first bake trace. */
 int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, int passes);
+/* Light-probe baking (absent upstream).  A lightmap (pt_set_bake) lights static, UV-mapped surfaces; what moves, and a raster pass, is lit
+ * from light probes: the radiance that arrives at a point from every direction.  With probes on, pt_trace renders an atlas of octahedral
+ * maps instead of a camera image -- one n x n map per probe position -- and pt_probe_project reduces such an atlas to nine
+ * spherical-harmonic (SH) coefficients per probe and channel.  As under a bake only the first ray differs: from its first closest hit on, a
+ * path is the path of a camera frame, so sample batches, tile shards, adaptive sampling, AOVs, pt_accum_save / load and pt_exchange_frame
+ * apply to the atlas as to any W x H image, bit for bit.  With probes off (the default) every image, ray count and stat is what it is without
+ * this section.
+ *   The atlas.  rows = ceil(count / columns), W = columns * n, H = rows * n.  Pixel (px, py) lies in cell cx = px / n, cy = py / n (integer
+ * division) of probe k = cy * columns + cx, at the map texel lx = px - cx * n, ly = py - cy * n.  n is a multiple of 16, so every 16 x 16
+ * tile belongs to one probe: adaptive sampling retires tiles probe by probe.  A cell with k >= count holds no probe (the last row's tail).
+ *   The sample of (px, py) with seed s, float32 throughout, every operation in the order written, products and sums not fused:
+ *     r = the draw the camera ray would make: next_random(px, py, s, 0).  It is the sample's only draw here too, so every later vertex sees
+ *         the random sequence it sees in a camera frame.
+ *     u = fdiv(((float)lx + 0.5) + (r.x - 0.5), (float)n),  v likewise from ly and r.y          (r.x may be exactly 1: u = 1 on the last column)
+ *     d = SquareToSphere(UvToSquare({u, v}))     the reference's equal-area octahedral map (Transforms.hlsli), that of the environment
+ *         importance map; not renormalised, as the environment sample's direction is not; in world axes: the map's +z is world +z
+ *     o = positions[k],  tmin = 0,  tmax = max_distance
+ *     a cell without a probe: no ray, no primary ray counted; the sample is radiance (0, 0, 0) and, with pt_set_aov, zero AOV records: the
+ *         output holds exactly (0, 0, 0, 1) and the AOV targets zeros, after any number of samples (what an uncovered bake texel gets).
+ *   pt_trace under probes: params->width x height must be W x H, else PT_ERR_INVALID_ARGUMENT with nothing written.  Wavefront mode only: a
+ * call in PT_MODE_MEGAKERNEL fails with PT_ERR_INVALID_ARGUMENT and writes nothing.  world_to_view / view_to_clip generate no rays but must
+ * still be valid (identity will do) and still drive the reset comparison; the lens (pt_set_lens) does not apply; debug outputs work, the first
+ * vertex being the probe ray's hit.  With pt_set_aov, normal_depth.w is the mean hit distance from the probe -- its distance map -- and
+ * albedo.w the fraction of rays that hit.  Probes and a bake exclude each other: whichever is enabled second is refused.
+ * Probes are a setting, like the lens and the bake: NOT part of the blob of pt_accum_save, whose format is unchanged -- a caller who resumes
+ * calls pt_set_probes with the same config and positions before pt_accum_load. */
+typedef struct pt_probe_config {
+    int32_t enable;           /* 0 = camera (default) */
+    int32_t resolution;       /* n: each probe is an n x n octahedral map; a multiple of 16 in 16..1024 */
+    int32_t count;            /* K >= 1 probes */
+    int32_t columns;          /* C >= 1 probes per atlas row */
+    float   max_distance;     /* finite, > 0: tmax of the probe's ray */
+} pt_probe_config;            /* 20 bytes */
+/* positions_xyz: host array of count * 3 floats, world space; copied into an array the context owns.  PT_ERR_INVALID_ARGUMENT (the message
+ * names the field or the probe index) for a NULL pointer, a bad field, a non-finite position, W or H above 2^30, or enabling probes while a
+ * bake is enabled (pt_set_bake likewise refuses to enable a bake while probes are on).  All of these are checked only when enable != 0;
+ * with enable == 0 nothing else of the config is looked at and positions_xyz may be NULL.  After such a refusal the old config and the old
+ * positions stay and no restart is pending.  (A device error while the positions are stored -- PT_ERR_OUT_OF_MEMORY, PT_ERR_DEVICE --
+ * may have cost the old positions: it leaves probes off and a restart pending.)  A good config forces a new accumulation on the next
+ * pt_trace, as pt_set_bake does: until that trace pt_accum_save answers PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* positions_xyz);
+/* Projects every probe of a W x H float4 device atlas (width, height must be the W, H of the context's current probe layout) onto the real
+ * spherical harmonics of bands 0..2: sh_host receives count * 9 * 3 floats, [probe][coefficient][rgb].  A pure function of the atlas and
+ * the layout; the atlas's w channel is not read.  Synchronises the stream.  For probe k, with the texel-centre direction
+ *     w(i, j) = SquareToSphere(UvToSquare({fdiv(i + 0.5, n), fdiv(j + 0.5, n)}))
+ *     c[lm][ch] = (4 pi / n^2) * sum over i, j of L(i, j)[ch] * Y_lm(w(i, j))                (float32; the order of the sum is not defined)
+ * Y in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), each constant rounded once to float:
+ *     0.282094792    0.488602512 y    0.488602512 z    0.488602512 x    1.092548431 xy    1.092548431 yz    0.315391565 (3 z^2 - 1)
+ *     1.092548431 xz    0.546274215 (x^2 - y^2)
+ * A texel with a non-finite r, g or b counts as (0, 0, 0).  PT_PROBE_SH_RADIANCE gives c as written: L(w) ~ sum c_lm Y_lm(w).
+ * PT_PROBE_SH_IRRADIANCE multiplies band l by pi, 2 pi / 3, pi / 4 (the clamped-cosine kernel), so that E(n) = sum c_lm Y_lm(n) is the
+ * irradiance on a surface with normal n; a diffuse surface of albedo a then leaves a / pi * E(n).
+ * The texel-centre quadrature is a midpoint rule: its Gram matrix sum Y Y' 4 pi / n^2 differs from the identity by at most (the largest
+ * entry of |G - I|, to two digits) 9.6e-3 at n = 16, 2.4e-3 at n = 32 and 6.1e-4 at n = 64, computed on the CPU in float64 for this
+ * mapping; the error is O(1 / n^2).  Callers who want SH to a part in a thousand bake at n >= 64.
+ * PT_ERR_NOT_READY if no probes are set; PT_ERR_INVALID_ARGUMENT for a NULL ctx (answered before any device call), a NULL pointer, a size
+ * other than W x H, a bad kind. */
+enum { PT_PROBE_SH_RADIANCE = 0, PT_PROBE_SH_IRRADIANCE = 1 };
+int pt_probe_project(pt_ctx* ctx, const void* atlas_device, uint32_t width, uint32_t height, int kind, float* sh_host);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

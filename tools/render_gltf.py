@@ -37,6 +37,14 @@ Composes with --aov (albedo.w is the coverage), --denoise, --adaptive and --chec
 the bake options).  An ambient-occlusion map is a bake with a white diffuse world under a white sky: see INTEGRATION.md.
   python tools/render_gltf.py scene.glb --bake 1024 1024 --bake-uv 1 --spp 256 --dilate 4 --out lightmap.exr
 
+--probes "x,y,z;x,y,z;...": light-probe baking (pt_set_probes): the frame is an atlas of octahedral maps, one --probe-res N x N map (a multiple of
+16, default 32) per world-space position, instead of a camera image (--size is ignored): the radiance that arrives at each position from every
+direction; it goes to --out.  --probe-sh OUT.npy writes the nine spherical-harmonic coefficients per channel of every probe (pt_probe_project,
+a float32 array [probes, 9, 3]); with --irradiance they are scaled so that their sum over Y_lm(n) is the irradiance on a surface with normal n
+(INTEGRATION.md has the shader side).  Composes with --aov (normal_depth.w is the probe's distance map), --adaptive and --checkpoint /
+--resume (the probes are not part of a checkpoint: repeat the probe options).  Not together with --bake or --aperture.
+  python tools/render_gltf.py scene.glb --probes "0,0,1;2,0,1;4,0,1" --probe-res 64 --spp 256 --probe-sh probes.npy --irradiance --out probes.exr
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -122,11 +130,29 @@ def main():
     ap.add_argument("--bake-instance", type=int, default=-1, metavar="N", help="bake one row of the instance table (default: every instance with the UV set)")
     ap.add_argument("--surface-offset", type=float, default=None, metavar="D", help="the rays start D world units above the surface (default: 1e-4 of the scene's bounding diagonal)")
     ap.add_argument("--dilate", type=int, default=0, metavar="N", help="with --bake: fill N texels (1..64) beyond the charts' borders")
+    ap.add_argument("--probes", default=None, metavar="X,Y,Z;...", help="render an atlas of octahedral light probes at these world-space positions instead of through the camera")
+    ap.add_argument("--probe-res", type=int, default=32, metavar="N", help="each probe is an N x N map (a multiple of 16 in 16..1024)")
+    ap.add_argument("--probe-sh", default="", metavar="OUT.npy", help="with --probes: write the probes' spherical-harmonic coefficients [probes, 9, 3]")
+    ap.add_argument("--irradiance", action="store_true", help="with --probe-sh: irradiance coefficients (bands scaled by pi, 2 pi / 3, pi / 4) instead of radiance")
     a = ap.parse_args()
     if a.bake is None and (a.dilate or a.surface_offset is not None or a.bake_instance != -1 or a.bake_uv != 0):
         ap.error("--bake-uv, --bake-instance, --surface-offset and --dilate need --bake W H")
     if a.bake is not None and a.aperture > 0:
         ap.error("--aperture does not apply to --bake: a bake has no lens")
+
+    probe_positions = None
+    if a.probes is not None:
+        if a.bake is not None or a.aperture > 0:
+            ap.error("--probes goes with neither --bake nor --aperture")
+        try:
+            probe_positions = np.array([[float(v) for v in item.split(",")] for item in a.probes.split(";") if item.strip()], np.float32)
+            assert probe_positions.ndim == 2 and probe_positions.shape[1] == 3 and len(probe_positions) >= 1
+        except (ValueError, AssertionError):
+            ap.error("--probes takes positions as \"x,y,z;x,y,z;...\"")
+    elif a.probe_sh or a.irradiance or a.probe_res != 32:
+        ap.error("--probe-res, --probe-sh and --irradiance need --probes")
+    if a.irradiance and not a.probe_sh:
+        ap.error("--irradiance needs --probe-sh OUT.npy")
 
     import torch
     from gltf_renderer_amd import abi, camera, gltf
@@ -171,6 +197,9 @@ def main():
         st.environment_color[:] = (0.6, 0.7, 0.9)
     r.set_bounce_limit(max(a.bounces, abi.REFERENCE_MAX_BOUNCES))
     w, h = a.bake if a.bake is not None else a.size
+    if probe_positions is not None:
+        w, h = r.set_probes(probe_positions, a.probe_res, max_distance=max(1000.0, 4.0 * radius))
+        print("probes: %d of %d x %d texels, atlas %d x %d" % (len(probe_positions), a.probe_res, a.probe_res, w, h))
     p = abi.PtExecuteParams()
     p.world_to_view[:] = camera.cm(camera.orbit_world_to_view(tuple(centre), 2.2 * radius, a.azimuth, a.inclination))
     p.view_to_clip[:] = camera.cm(camera.view_to_clip(w / h, math.radians(60), 0.01 * radius, 100.0 * radius))
@@ -259,6 +288,9 @@ def main():
         print("bake: %d of %d texels covered (%.1f %%)" % (int(cover.sum()), w * h, 100.0 * cover.mean()))
         if a.dilate:
             r.bake_dilate(out, a.dilate)
+    if a.probe_sh:
+        np.save(a.probe_sh, r.probe_project(out, abi.PROBE_SH_IRRADIANCE if a.irradiance else abi.PROBE_SH_RADIANCE))
+        print("probe SH (%s): %s" % ("irradiance" if a.irradiance else "radiance", a.probe_sh))
     _, rgba8 = r.tonemap(out, want_rgba8=True)
     if a.out.lower().endswith(".exr"):
         gltf.write_exr(a.out, r.readback(out)[..., :3], half=True)       # linear radiance
