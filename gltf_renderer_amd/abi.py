@@ -278,6 +278,13 @@ class PtProbeConfig(C.Structure):
     _fields_ = [("enable", C.c_int32), ("resolution", C.c_int32), ("count", C.c_int32), ("columns", C.c_int32), ("max_distance", C.c_float)]
 
 
+class PtMatteConfig(C.Structure):
+    """pt_matte_config: ID mattes (pt_set_matte; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("kind", C.c_int32), ("ranks", C.c_int32), ("id_count", C.c_int32), ("layers", C.c_void_p * 4)]
+
+
+MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
+MATTE_MAX_RANKS = 8
 PROBE_SH_RADIANCE, PROBE_SH_IRRADIANCE = 0, 1
 ACCUM_OUTPUT, ACCUM_ALBEDO, ACCUM_NORMAL_DEPTH, ACCUM_ADAPTIVE = 1, 2, 4, 8
 ACCUM_HEADER_BYTES = 160
@@ -319,5 +326,7 @@ assert C.sizeof(PtBakeConfig) == 16
 assert [getattr(PtBakeConfig, f).offset for f, _ in PtBakeConfig._fields_] == [0, 4, 8, 12]
 assert C.sizeof(PtProbeConfig) == 20
 assert [getattr(PtProbeConfig, f).offset for f, _ in PtProbeConfig._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtMatteConfig) == 48
+assert [getattr(PtMatteConfig, f).offset for f, _ in PtMatteConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

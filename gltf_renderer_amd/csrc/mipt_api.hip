@@ -288,7 +288,11 @@ public:
             if (ep->width != pw || ep->height != ph)
                 return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the atlas is " + std::to_string(pw) + " x " + std::to_string(ph) + ", not " + std::to_string(ep->width) + " x " + std::to_string(ep->height));
         }
+        // ID mattes (pt_set_matte) are written, like the AOVs, by every call without a debug output, under the output's counts and resets.
+        const bool matte = ctx->matte.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
+        if (matte && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "mattes are written in the wavefront mode only");
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (ctx->matte_restart) { reset = true; ctx->matte_restart = false; }
         if (ctx->probe_restart) { reset = true; ctx->probe_restart = false; }
         if (ctx->bake_restart) { reset = true; ctx->bake_restart = false; }
         if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
@@ -307,6 +311,8 @@ public:
             if (int r = ensure_accel(ctx)) return r;
             BakeArgs bk = {};
             if (bake) { if (int r = bake_setup(ctx, ep->width, ep->height, bk)) return r; }
+            MatteArgs mt = {};
+            if (matte) { if (int r = matte_setup(ctx, mt)) return r; }
 
             SceneRec sc = scene_fill(ctx);
             if (ep->environment_map >= 0) scene_set_env(sc, *ctx->envs[ep->environment_map]);
@@ -372,7 +378,7 @@ public:
                 fc.spp = (uint32_t)batch;
                 if ((unsigned long long)fc.pixel_slots * fc.spp > 0x7fffffffull) return ctx->fail(PT_ERR_CAPACITY, "sample batch too large for this resolution");
                 const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * fc.spp);
-                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov);
+                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov, matte);
                 HIPOK(ctx->d_workspace.reserve(ctx->stream, need, need));
                 AdaptiveArgs ad = {};
                 if (adaptive) {
@@ -394,7 +400,7 @@ public:
                 const ProbeArgs pa = probe_args(ctx);
                 HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
                                        ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr,
-                                       probes ? &pa : nullptr));
+                                       probes ? &pa : nullptr, matte ? &mt : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
@@ -513,6 +519,29 @@ int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake) {
     }
     bake.owner = ctx->d_bake_owner.as<uint32_t>(); bake.tris = ctx->d_tris.as<TriPacket>(); bake.shade = ctx->d_shade.as<ShadePacket>();
     bake.surface_offset = ctx->bake.surface_offset; bake.tex_coord = ctx->bake.tex_coord;
+    return PT_OK;
+}
+int matte_setup(pt_ctx* ctx, MatteArgs& matte) {
+    const int kind = ctx->matte.kind;
+    const size_t rows = kind == PT_MATTE_MATERIAL ? (size_t)ctx->n_materials : ctx->instances.size();
+    if (ctx->matte_table_kind != kind || ctx->matte_table_rows != rows) {
+        // row i: the caller's id if it gave one, else the id of the default name "instance_<i>" / "material_<i>"
+        ctx->matte_table_kind = -1;
+        std::vector<uint32_t> table(rows ? rows : 1, 0u);
+        for (size_t i = 0; i < rows; i++) {
+            if (i < ctx->matte_user_ids.size()) { table[i] = ctx->matte_user_ids[i]; continue; }
+            const std::string name = (kind == PT_MATTE_MATERIAL ? "material_" : "instance_") + std::to_string(i);
+            table[i] = pt_matte_id(name.data(), name.size());
+        }
+        // a trace in flight may still read the old table: the copy goes behind it on the stream, a larger table drains it first (DevBuf)
+        const size_t bytes = table.size() * 4;
+        if (const hipError_t e = ctx->d_matte_ids.reserve(ctx->stream, bytes, bytes + bytes / 2)) return grow_failed(ctx, e, "matte id table: " + std::to_string(bytes) + " bytes");
+        if (const hipError_t e = staged_upload(ctx, ctx->d_matte_ids.ptr, table.data(), bytes)) return ctx->fail(PT_ERR_DEVICE, std::string("matte id table: ") + hipGetErrorString(e));
+        ctx->matte_table_kind = kind; ctx->matte_table_rows = rows;
+    }
+    matte.rec = nullptr; matte.ids = ctx->d_matte_ids.as<uint32_t>(); matte.n_ids = (uint32_t)rows;
+    matte.kind = kind; matte.ranks = ctx->matte.ranks;
+    for (int j = 0; j < 4; j++) matte.layers[j] = j < ctx->matte.ranks / 2 ? (float4*)ctx->matte.layers[j] : nullptr;
     return PT_OK;
 }
 int ensure_accel(pt_ctx* ctx) {
@@ -1320,7 +1349,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes since the last trace: the next trace starts anew");
+    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart || ctx->matte_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1415,7 +1444,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false;
+    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false; ctx->matte_restart = false;
     return PT_OK;
 }
 

@@ -113,6 +113,12 @@ struct pt_ctx {
     pt::DevBuf d_probe_pos;                       // float[3] per probe (ProbeArgs::positions): probes.count of them while probes.enable != 0
     pt::DevBuf d_probe_dirs; uint32_t probe_dirs_n = 0;   // the texel-centre directions of a probe_dirs_n^2 map, built by the first pt_probe_project of a resolution
     pt::DevBuf d_probe_sh;                        // pt_probe_project's 27 floats per probe
+    // ---- ID mattes (pt_set_matte): the config with the caller's layers, the caller's ids, and the device table of one id per table row
+    pt_matte_config matte = {0, PT_MATTE_INSTANCE, 2, 0, {nullptr, nullptr, nullptr, nullptr}};
+    bool matte_restart = false;                   // pt_set_matte: the next pt_trace starts a new accumulation
+    std::vector<uint32_t> matte_user_ids;         // fix(ids[i]) of pt_set_matte; rows beyond it get the ids of their default names
+    pt::DevBuf d_matte_ids;                       // uint32 per row (MatteArgs::ids), made by pt_trace for ...
+    int matte_table_kind = -1; size_t matte_table_rows = 0;   // ... this kind (-1: stale) and this many rows of the instance / material table
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
 
@@ -166,6 +172,10 @@ inline ProbeArgs probe_args(const pt_ctx* ctx) {
     pa.div_n = FastDiv::make(pa.n); pa.max_distance = ctx->probes.max_distance;
     return pa;
 }
+
+// The mattes of a call (pt_set_matte): the device table of ids -- made now unless it stands for this kind and this many rows -- and what
+// k_wf_matte / k_wf_matte_resolve take.  (mipt_api.hip)
+int matte_setup(pt_ctx* ctx, MatteArgs& matte);
 
 // Pathtracer::BuildAccel (mipt_api.hip) if the tree does not stand for the current tables, as every call that traces rays begins
 int ensure_accel(pt_ctx* ctx);

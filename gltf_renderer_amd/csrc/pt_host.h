@@ -132,7 +132,8 @@ struct DebugQueues {
     float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
 };
 hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false);   // aov: with the two AOV record arrays behind the rest
+// aov: with the two AOV record arrays behind the rest; matte: with the matte record array behind those (whether or not they are used)
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false, bool matte = false);
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
 struct AdaptiveTile {
@@ -173,20 +174,38 @@ struct ProbeArgs {
     FastDiv div_n;
     float max_distance;       // the probe ray's tmax
 };
+// ID mattes (pt_set_matte): what k_wf_matte and k_wf_matte_resolve take as their own argument.  One id per slot, written by k_wf_matte
+// between the primary traversal and the first shade stage (beside k_wf_aov), folded into the caller's layers by k_wf_matte_resolve.
+struct MatteArgs {
+    uint32_t* rec;            // per slot: the id of the first ray's closest hit, 0 for a miss or a slot without a ray (workspace, set by launch_wavefront)
+    const uint32_t* ids;      // the id of every row of the instance table (PT_MATTE_INSTANCE) or the material table (owned by the context)
+    uint32_t n_ids;
+    int32_t kind, ranks;      // PT_MATTE_*; K = 2, 4, 6 or 8
+    float4* layers[4];        // the caller's layers, res_x * res_y each: the first K / 2
+};
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
 // bake: nullptr = camera rays (k_wf_generate); else k_wf_generate_bake starts the paths on the atlas's texels and `lens` is not looked at
 // probes: nullptr likewise; else k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
 // adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
 // aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
+// matte: nullptr = no mattes (no k_wf_matte / k_wf_matte_resolve launch); else the id table and the caller's layers (the record pointer is
+//      ignored) and a workspace of wavefront_workspace_bytes(fc, stage_blocks, aov, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
-                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr, const ProbeArgs* probes = nullptr);
+                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr, const ProbeArgs* probes = nullptr,
+                            const MatteArgs* matte = nullptr);
 // pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
 
 // pt_debug_probe_rays: d_out = 8 floats per query {px, py, seed}, probe_ray's ray; zeros with tmax = -1 for an absent probe or a texel off the atlas
 void launch_debug_probe_rays(const FrameConstants& fc, const ProbeArgs& probes, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+
+// ---- matte.hip: pt_matte_extract's mask of a set of ids ----------------------------------------------------------------------------
+constexpr int kMatteExtractMaxIds = 64;
+struct MatteExtractIds { uint32_t id[kMatteExtractMaxIds]; };     // after the exponent fix; by value in the kernel's arguments
+// mask[p] = the sequential float32 sum over ranks 0 .. ranks - 1 of the coverages whose id is among ids.id[0 .. count - 1].  Asynchronous.
+void launch_matte_extract(const float4* const layers[4], int ranks, uint32_t pixels, const MatteExtractIds& ids, int count, float* mask, hipStream_t stream);
 
 // ---- probe.hip: pt_probe_project's reduction of an octahedral atlas to spherical harmonics --------------------------------------
 // dirs: n * n float4, the texel-centre directions of an n x n octahedral map (w unused), row-major.  Asynchronous.

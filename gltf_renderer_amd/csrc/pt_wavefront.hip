@@ -20,11 +20,13 @@
 #define PT_LUT_LDS 1          // every stage kernel of this file stages the sRGB table into LDS (pt_shading.h stage_luts)
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "pt_vertex.h"
 #include "pt_host.h"
 #include "pt_bake.h"
 #include "pt_probe.h"
+#include "pt_matte.h"
 
 #ifdef PT_TIMING                 // diagnostic build only (tools/shade_sections.py); not part of the C-ABI
 namespace pt { __device__ unsigned long long pt_timing[12]; }
@@ -865,6 +867,51 @@ __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuff
     if (AOV) resolve_aov(fc, wf, av, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
 }
 
+// ID mattes (pt_set_matte): which object or material each sample's first ray sees, one 32-bit id per slot.  A stage of its own in k_wf_aov's
+// window -- queue 0's entries and wf.hit are intact between the primary traversal and the first shade stage -- and far lighter: per entry
+// the slot word of the ray, the hit word, the instance word of the hit's shading packet, for the material kind the row's material_id, the
+// id of that row, and one store.  None of the shade stage's LDS tables is needed and none is staged.  The records were cleared before the
+// generate stage, so a slot that never had a ray (an uncovered bake texel, a cell without a probe) reads 0 like a miss.
+__global__ __launch_bounds__(kBlock) void k_wf_matte(SceneRec sc, WfBuffers wf, MatteArgs ma) {
+    const ShardView sv = shard_view(wf);
+    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
+    const size_t base = (size_t)sv.shard * wf.seg_cap;
+    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
+        const uint32_t slot = QLD(((const uint32_t*)(wf.ray_d[0] + base + i))[3]), hb = QLD(((const uint32_t*)(wf.hit + base + i))[3]);
+        uint32_t id = 0u;
+        if (hb != kMissTri) {
+            uint32_t row = sc.shade[hb & 0x7fffffffu].inst;
+            if (ma.kind == PT_MATTE_MATERIAL) row = sc.instances[row].gpu.material_id;
+            if (row < ma.n_ids) id = ma.ids[row];
+        }
+        if (slot < wf.capacity) QST(ma.rec[slot], id);
+    }
+}
+// The matte part of a resolve, a kernel of its own launched right before k_wf_resolve (whose adaptive instantiations update the tiles'
+// `active` flags this one reads) on the resolve's grid: one block per rank-local tile, one thread per pixel slot.  A thread reads its
+// pixel's K / 2 float4 once, folds the batch's records in sample order with the output's counts (pt_matte.h), sorts and writes once; the K
+// ranks stay in registers (RANKS is a template constant: every index is static).  A tile retired by adaptive sampling is not written.
+template <int RANKS, bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_matte_resolve(FrameConstants fc, AdaptiveArgs ad, MatteArgs ma) {
+    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
+    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t px, py;
+    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
+    const size_t at = (size_t)py * fc.res_x + px;
+    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
+    const int first = accumulate ? fc.accumulated_frames : -1;          // samples already in the layers; < 0: every sample is the first
+    MatteRanks<RANKS> m;
+#pragma unroll
+    for (int j = 0; j < RANKS / 2; j++) matte_unpack(m, j, first > 0 ? ma.layers[j][at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t k = 0; k < fc.spp; k++) {
+        const uint32_t h = QLD(ma.rec[k * fc.pixel_slots + pslot]);
+        matte_fold_sample(m, h, first < 0 ? 0 : first + (int)k);
+    }
+    matte_sort(m);
+#pragma unroll
+    for (int j = 0; j < RANKS / 2; j++) ma.layers[j][at] = matte_pack(m, j);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 static uint32_t blocks_per_shard_for(int stage_blocks) {
     uint32_t b = (uint32_t)(stage_blocks > 0 ? stage_blocks : 1536) / kShards;
@@ -888,9 +935,12 @@ static size_t state_slots_for(size_t slots) { return (size_t)chunks_per_shard_fo
 
 // the AOV records (AovArgs::rec_albedo, rec_normal) lie behind everything carve() hands out: a workspace without them is laid out as ever
 static size_t aov_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, false) + 255) & ~(size_t)255; }
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov) {
+// ... and the matte records (MatteArgs::rec) behind those, at the same place with AOVs on or off
+static size_t matte_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, true) + 255) & ~(size_t)255; }
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov, bool matte) {
     const uint32_t bps = blocks_per_shard_for(stage_blocks);
     const size_t slots = state_slots_for((size_t)fc.my_tiles * kBlock * fc.spp);
+    if (matte) return matte_records_offset(fc, stage_blocks) + slots * 4;
     if (aov) return aov_records_offset(fc, stage_blocks) + slots * (2 * 16);
     const size_t q = (size_t)kShards * seg_cap_for(fc, bps);
     return slots * (5 * 16) + q * (4 * 16 + 4 * 16 + 16 + 2 * 16 + 2 * 2 * 16) + kCounterArrays * kShards * kCounterStride * 4 + 52 * 256;
@@ -966,7 +1016,7 @@ static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const Sc
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake,
-                            const ProbeArgs* probes) {
+                            const ProbeArgs* probes, const MatteArgs* matte) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -996,6 +1046,12 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         av = *aov;
         av.rec_albedo = (float4*)((char*)workspace + aov_records_offset(fc, stage_blocks));
         av.rec_normal = av.rec_albedo + state_slots_for(slots);
+    }
+    MatteArgs mt = {};
+    if (matte) {                                                        // the records start as misses: no generate kernel knows of them
+        mt = *matte;
+        mt.rec = (uint32_t*)((char*)workspace + matte_records_offset(fc, stage_blocks));
+        if ((e = hipMemsetAsync(mt.rec, 0, (size_t)slots * 4, stream)) != hipSuccess) return e;
     }
     AdaptiveArgs ad = {};
     if (adaptive) ad = *adaptive;
@@ -1053,6 +1109,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         mark(STAGE_TRACE);
     }
     if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
+    if (matte) { hipLaunchKernelGGL(k_wf_matte, stage, block, 0, stream, sc, wf, mt); mark(STAGE_SHADE); }         // likewise
     for (int b = 0; b < iterations; b++) {
         const int cur = b & 1;
         const dim3 gs = cap(grid_of(b), env_shade_bps), gt = cap(grid_of(b), env_trace_bps);
@@ -1067,6 +1124,20 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
             launch_shadow(gt, wt, b);
         }
         mark(STAGE_SHADOW);
+    }
+    if (matte) {                                                        // before the resolve retires tiles: both see the call's `active` flags
+        auto launch_matte = [&](auto ranks) {
+            constexpr int R = decltype(ranks)::value;
+            if (adaptive) hipLaunchKernelGGL((k_wf_matte_resolve<R, true>), full, block, 0, stream, fc, ad, mt);
+            else hipLaunchKernelGGL((k_wf_matte_resolve<R, false>), full, block, 0, stream, fc, ad, mt);
+        };
+        switch (mt.ranks) {
+            case 2: launch_matte(std::integral_constant<int, 2>()); break;
+            case 4: launch_matte(std::integral_constant<int, 4>()); break;
+            case 6: launch_matte(std::integral_constant<int, 6>()); break;
+            default: launch_matte(std::integral_constant<int, 8>()); break;
+        }
+        mark(STAGE_RESOLVE);
     }
     if (aov) { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, true>), full, block, 0, stream, fc, wf, output, ad, av);
                else hipLaunchKernelGGL((k_wf_resolve<false, true>), full, block, 0, stream, fc, wf, output, ad, av); }

@@ -37,7 +37,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # texture-space baking (additive likewise)
            "pt_set_bake", "pt_bake_coverage", "pt_bake_dilate",
            # light-probe baking (additive likewise)
-           "pt_set_probes", "pt_probe_project"]
+           "pt_set_probes", "pt_probe_project",
+           # ID mattes (additive likewise)
+           "pt_set_matte", "pt_matte_id", "pt_matte_extract"]
 
 
 class MiptError(RuntimeError):
@@ -123,6 +125,10 @@ def load_library():
     L.pt_bake_dilate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci]
     L.pt_set_probes.argtypes = [vp, vp, vp]
     L.pt_probe_project.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci, vp]
+    L.pt_set_matte.argtypes = [vp, vp, vp]
+    L.pt_matte_id.argtypes = [C.c_char_p, C.c_size_t]
+    L.pt_matte_id.restype = C.c_uint32
+    L.pt_matte_extract.argtypes = [vp, vp, ci, C.c_uint32, C.c_uint32, vp, ci, vp]
     _LIB = L
     return L
 
@@ -389,6 +395,45 @@ class Renderer:
         self._check(self.L.pt_probe_project(self.h, C.c_void_p(atlas.data_ptr()), atlas.shape[1], atlas.shape[0], int(kind), _p(sh)))
         written = ~np.isnan(sh).all(axis=(1, 2))                       # the rows the library wrote: its probe count (non-finite texels count as 0)
         return np.ascontiguousarray(sh[:int(np.nonzero(written)[0].max()) + 1 if written.any() else 0])
+
+    def set_matte(self, kind, layers, ids=None):
+        """ID mattes (include/mipt.h pt_set_matte): trace() accumulates, beside the output, a ranked list of (id, coverage) pairs per pixel
+        in Cryptomatte's layout.  kind: abi.MATTE_INSTANCE or abi.MATTE_MATERIAL; layers: 1 to 4 float32 CUDA tensors (H, W, 4) like the
+        output, caller-owned, layer j holding ranks 2j and 2j + 1 (so K = 2 * len(layers)); ids: optional uint32 ids for the first
+        len(ids) table rows (the rest get matte_id("instance_<i>") / matte_id("material_<i>")).  layers=None turns mattes off.  The next
+        trace() starts a new accumulation.  Wavefront mode only.  The layers are not part of an accum_save() blob: keep them and call
+        set_matte() before accum_load().  View a layer's ids with readback(layer).view(np.uint32)[..., 0::2]."""
+        if not layers:
+            self._check(self.L.pt_set_matte(self.h, C.byref(abi.PtMatteConfig(0, 0, 0, 0)), None))
+            self._matte = None
+            return
+        for t in layers:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4
+        idv = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+        cfg = abi.PtMatteConfig(1, int(kind), 2 * len(layers), 0 if idv is None else len(idv))
+        for j, t in enumerate(layers[:4]):
+            cfg.layers[j] = t.data_ptr()
+        self._check(self.L.pt_set_matte(self.h, C.byref(cfg), _p(idv) if idv is not None and len(idv) else None))
+        self._matte = list(layers)                    # the library keeps the pointers: keep the tensors alive with the renderer
+
+    def matte_extract(self, layers, ids, out=None):
+        """pt_matte_extract: the anti-aliased mask (H, W) float32 CUDA tensor of a set of 1..64 ids over matte layers (of set_matte(), or
+        any tensors of that layout): per pixel the sum of the coverages of the ranks whose id is in the set.  Asynchronous."""
+        t = self.torch
+        h, w = layers[0].shape[:2]
+        if out is None:
+            out = t.empty((h, w), dtype=t.float32, device=layers[0].device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == t.float32 and tuple(out.shape) == (h, w)
+        ptrs = (C.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
+        idv = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._check(self.L.pt_matte_extract(self.h, ptrs, 2 * len(layers), w, h, _p(idv), len(idv), C.c_void_p(out.data_ptr())))
+        return out
+
+    @staticmethod
+    def matte_id(name):
+        """pt_matte_id: Cryptomatte's 32-bit id of a name (str or bytes).  No GPU call."""
+        b = name.encode() if isinstance(name, str) else bytes(name)
+        return int(load_library().pt_matte_id(b, len(b)))
 
     def focus_at(self, settings, params, px, py):
         """Autofocus (include/mipt.h pt_lens_focus_at): the view-space depth of what the pinhole ray through image position (px, py) sees

@@ -737,6 +737,65 @@ int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* posit
  * other than W x H, a bad kind. */
 enum { PT_PROBE_SH_RADIANCE = 0, PT_PROBE_SH_IRRADIANCE = 1 };
 int pt_probe_project(pt_ctx* ctx, const void* atlas_device, uint32_t width, uint32_t height, int kind, float* sh_host);
+/* ID mattes (absent upstream): which object or material every pixel sees, and with how much coverage -- per pixel a ranked list of
+ * (id, coverage) pairs in Cryptomatte's layout, accumulated beside the output for compositors, annotation and lightmap editors.  Off by
+ * default; with it off every image, ray count and stat is what it is without this section, and with it on the output, the AOV targets, the
+ * ray counts and accumulated_frames are bit for bit what they are without it.
+ *   Ids.  pt_matte_id(name, length) = fix(MurmurHash3_x86_32(name bytes, seed 0)), with Cryptomatte's exponent fix
+ *     fix(h):  if ((h >> 23) & 0xff) is 0 or 255:  h ^= 1 << 23
+ * after which an id read as a float is finite and normal, and never 0.  The id of table row i -- a row of the instance table
+ * (PT_MATTE_INSTANCE) or of the material table (PT_MATTE_MATERIAL) -- is fix(ids[i]) for i < id_count, else pt_matte_id of the ASCII name
+ * "instance_<i>" / "material_<i>", i in decimal without padding.  The context keeps its own device copy of the ids, which pt_trace
+ * materialises for the current instance or material table (a table that grew gets the default ids for its new rows).  Bit pattern 0 means
+ * "empty rank" in a layer and "miss" in a sample's record.
+ *   Layout.  Layer j holds ranks 2j and 2j + 1 of each pixel as (id_2j bits, cov_2j, id_2j+1 bits, cov_2j+1): Cryptomatte's RGBA layout,
+ * W * H float4, caller-owned like pt_execute_params.output.  Ids are moved and compared as 32-bit integers, never as floats; a caller
+ * reinterprets the x and z channels' bits.  An empty rank is (0, +0).
+ *   One sample.  For pixel p, the record h of a sample is the id of the first closest hit of the sample's first ray -- the camera ray, the
+ * lens ray, the bake texel's ray or the probe's ray: the hit the AOVs describe, after the any-hit alpha test, under the call's cull flag --
+ * where the hit's row is the hit triangle's instance-table row or, for PT_MATTE_MATERIAL, that row's material_id.  A miss gives h = 0; so
+ * does a pixel that starts no ray (an uncovered bake texel, a probe cell without a probe).
+ *   The fold.  n = the samples already in the layers, which follows the output's count (accumulated_frames + the sample's index in the
+ * batch); in a call without FLAG_ACCUMULATE every sample is the first (n = 0).  float32 throughout, in the order written, not fused:
+ *     n == 0:  all ranks become empty; if h != 0, rank 0 = (h, 1.0f)
+ *     n  > 0:  b = fdiv(1.0f, (float)n + 1.0f)
+ *              every non-empty rank:  c = c + b * (x - c),  x = 1.0f if its id == h (and h != 0), else 0.0f       (the AOVs' running mean)
+ *              if h != 0 and no rank holds h:  an empty rank becomes (h, b); if NO RANK IS EMPTY THE SAMPLE'S ID IS DROPPED
+ * After a call's last sample the ranks are sorted: non-empty before empty, then coverage descending, then id ascending as unsigned.  The
+ * order is total, so the state after a call depends only on the multiset of pairs and a batch of S samples equals S calls one by one, bit
+ * for bit.  A pixel that met more than K ids has dropped samples: its coverages then sum to LESS than its hit fraction (albedo.w of
+ * pt_set_aov); a caller who sees that raises `ranks`.  Which id is dropped depends on the order of the samples, never on the batch size.
+ *   Composition, as for pt_set_aov: a tile shard writes only the rank's tiles; a tile retired by adaptive sampling is not written (it
+ * equals the uniform matte after its own count); a call with a debug output, or one past max_accumulated_frames, leaves the layers
+ * untouched.  Wavefront mode only: a matte call in PT_MODE_MEGAKERNEL fails with PT_ERR_INVALID_ARGUMENT and writes nothing.
+ *   The layers are NOT part of the blob of pt_accum_save, whose format is unchanged: they are caller-owned and, with the count, the whole
+ * matte state.  A caller who resumes keeps (or restores) them and calls pt_set_matte before pt_accum_load.
+ *   pt_tiles_pack, pt_tiles_unpack and pt_exchange_frame in PT_EXCHANGE_GATHER mode take a layer as any float4 image (they copy bits).
+ * PT_EXCHANGE_REDUCE must not be used on a layer: it would add ids as floats. */
+enum { PT_MATTE_INSTANCE = 0, PT_MATTE_MATERIAL = 1 };
+#define PT_MATTE_MAX_RANKS 8
+typedef struct pt_matte_config {
+    int32_t enable;      /* 0 = off (default) */
+    int32_t kind;        /* PT_MATTE_INSTANCE: the hit's row of the instance table; PT_MATTE_MATERIAL: that row's material_id */
+    int32_t ranks;       /* K = 2, 4, 6 or 8 (id, coverage) pairs per pixel */
+    int32_t id_count;    /* entries of `ids`; 0 = default ids only */
+    void*   layers[4];   /* device, W*H float4 each, caller-owned like pt_execute_params.output; the first K/2 non-NULL */
+} pt_matte_config;       /* 48 bytes */
+/* ids: host array of id_count entries, copied (after fix); may be NULL with id_count == 0.  PT_ERR_INVALID_ARGUMENT (the message names the
+ * field) for a NULL config and, checked only when enable != 0: a bad kind or ranks, a NULL layer among the first K/2, id_count < 0,
+ * id_count > 0 with ids NULL.  After such a refusal the old config stays and no restart is pending.  A good config forces a new
+ * accumulation on the next pt_trace, so that the layers and the output always hold the same samples: until that trace pt_accum_save
+ * answers PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int      pt_set_matte(pt_ctx* ctx, const pt_matte_config* config, const uint32_t* ids);
+/* Cryptomatte's id of a name (see above).  Pure: no context, no device. */
+uint32_t pt_matte_id(const char* name, size_t length);
+/* The anti-aliased mask of a set of ids: per pixel, mask = the sequential float32 sum, over ranks 0 .. K - 1 in this order and starting from
+ * 0.0f, of cov_r where id_r is among fix(ids[0 .. id_count - 1]).  layers: host array of the K/2 device layers; mask: device, W * H float.
+ * A pure function of the layers (no pt_trace state: it takes layers after an exchange or from a file alike), enqueued on the context's
+ * stream.  PT_ERR_INVALID_ARGUMENT, with nothing written, for a NULL ctx (answered before any device call), a NULL pointer, a zero size,
+ * ranks other than 2, 4, 6, 8, id_count outside 1..64. */
+int      pt_matte_extract(pt_ctx* ctx, const void* const* layers, int ranks, uint32_t width, uint32_t height,
+                          const uint32_t* ids, int id_count, void* mask);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -45,11 +45,20 @@ a float32 array [probes, 9, 3]); with --irradiance they are scaled so that their
 --resume (the probes are not part of a checkpoint: repeat the probe options).  Not together with --bake or --aperture.
   python tools/render_gltf.py scene.glb --probes "0,0,1;2,0,1;4,0,1" --probe-res 64 --spp 256 --probe-sh probes.npy --irradiance --out probes.exr
 
+--matte instance|material: ID mattes (pt_set_matte): per pixel a ranked list of (id, coverage) pairs in Cryptomatte's layout -- which object
+(row of the instance table) or material each pixel sees, anti-aliased -- accumulated with the frame.  --matte-ranks K (2, 4, 6 or 8, default 6)
+pairs per pixel; --matte-out PREFIX writes one uncompressed 32-bit float RGBA EXR per layer, PREFIX_00.exr ... (R, B = the ids' bits, G, A =
+their coverages; ranks 2j and 2j + 1 in layer j), and PREFIX.json, the manifest {"instance_<i>" | "material_<i>": id as 8 hex digits}.
+Composes with --aov, --adaptive, --bake and --probes; the layers are not part of a checkpoint, so not with --checkpoint / --resume here.
+  python tools/render_gltf.py scene.glb --spp 64 --matte instance --matte-ranks 6 --matte-out crypto --out frame.png
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
+import json
 import math
 import os
+import struct
 import sys
 
 import numpy as np
@@ -99,6 +108,31 @@ def resume_mismatch(info, size, aov, adaptive, accum_flags):
     return None
 
 
+def write_exr_rgba32f(path, rgba):
+    """An uncompressed scanline OpenEXR file with the four FLOAT channels A, B, G, R of an (H, W, 4) float32 image, bit for bit: the ids of a
+    matte layer are 32-bit patterns, which neither a half-float nor a tone-mapped file keeps."""
+    a = np.ascontiguousarray(rgba, np.float32)
+    h, w = a.shape[:2]
+
+    def attr(name, kind, data):
+        return name.encode() + b"\0" + kind.encode() + b"\0" + struct.pack("<i", len(data)) + data
+
+    chlist = b"".join(c.encode() + b"\0" + struct.pack("<iBBBBii", 2, 0, 0, 0, 0, 1, 1) for c in "ABGR") + b"\0"      # pixel type 2 = FLOAT
+    box = struct.pack("<iiii", 0, 0, w - 1, h - 1)
+    head = (struct.pack("<ii", 20000630, 2) + attr("channels", "chlist", chlist) + attr("compression", "compression", b"\0") + attr("dataWindow", "box2i", box) +
+            attr("displayWindow", "box2i", box) + attr("lineOrder", "lineOrder", b"\0") + attr("pixelAspectRatio", "float", struct.pack("<f", 1.0)) +
+            attr("screenWindowCenter", "v2f", struct.pack("<ff", 0.0, 0.0)) + attr("screenWindowWidth", "float", struct.pack("<f", 1.0)) + b"\0")
+    line = 8 + 16 * w
+    first = len(head) + 8 * h
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(struct.pack("<%dQ" % h, *[first + y * line for y in range(h)]))
+        for y in range(h):
+            f.write(struct.pack("<ii", y, 16 * w))
+            for ch in (3, 2, 1, 0):                                          # a scanline holds its channels in alphabetical order
+                f.write(a[y, :, ch].tobytes())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("path")
@@ -134,7 +168,16 @@ def main():
     ap.add_argument("--probe-res", type=int, default=32, metavar="N", help="each probe is an N x N map (a multiple of 16 in 16..1024)")
     ap.add_argument("--probe-sh", default="", metavar="OUT.npy", help="with --probes: write the probes' spherical-harmonic coefficients [probes, 9, 3]")
     ap.add_argument("--irradiance", action="store_true", help="with --probe-sh: irradiance coefficients (bands scaled by pi, 2 pi / 3, pi / 4) instead of radiance")
+    ap.add_argument("--matte", default=None, choices=["instance", "material"], help="accumulate ID mattes of the instances or of the materials")
+    ap.add_argument("--matte-ranks", type=int, default=6, choices=[2, 4, 6, 8], metavar="K", help="(id, coverage) pairs per pixel: 2, 4, 6 or 8")
+    ap.add_argument("--matte-out", default="", metavar="PREFIX", help="with --matte: PREFIX_00.exr ... (one per layer) and the manifest PREFIX.json")
     a = ap.parse_args()
+    if a.matte is None and (a.matte_out or a.matte_ranks != 6):
+        ap.error("--matte-ranks and --matte-out need --matte instance|material")
+    if a.matte is not None and not a.matte_out:
+        ap.error("--matte needs --matte-out PREFIX")
+    if a.matte is not None and (a.checkpoint or a.resume):
+        ap.error("--matte goes with neither --checkpoint nor --resume: the layers are not part of a checkpoint")
     if a.bake is None and (a.dilate or a.surface_offset is not None or a.bake_instance != -1 or a.bake_uv != 0):
         ap.error("--bake-uv, --bake-instance, --surface-offset and --dilate need --bake W H")
     if a.bake is not None and a.aperture > 0:
@@ -225,6 +268,10 @@ def main():
     if a.aov or a.denoise is not None:
         aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
         r.set_aov(aov_albedo, aov_nd)
+    matte_layers = None
+    if a.matte is not None:
+        matte_layers = [r.create_output(w, h) for _ in range(a.matte_ranks // 2)]
+        r.set_matte(abi.MATTE_MATERIAL if a.matte == "material" else abi.MATTE_INSTANCE, matte_layers)
     adaptive_cfg = None if a.adaptive is None else (min(a.min_spp, a.spp), a.spp, a.adaptive)
     if adaptive_cfg is not None:
         r.set_samples_per_trace(min(a.batch, 64))
@@ -298,6 +345,22 @@ def main():
         gltf.write_pfm(a.out, r.readback(out)[..., :3])
     else:
         gltf.write_png(a.out, rgba8, 3)                                  # tone-mapped (AgX + sRGB), ToneMapper.ps.hlsl
+    if matte_layers is not None:
+        seen = set()
+        for j, layer in enumerate(matte_layers):
+            img = r.readback(layer)
+            write_exr_rgba32f("%s_%02d.exr" % (a.matte_out, j), img)
+            seen |= set(np.unique(img.view(np.uint32)[..., 0::2]).tolist()) - {0}
+        # the default names of the table's rows, up to the last row a pixel shows (the scene header carries no names)
+        manifest, rows = {}, 0
+        while seen and rows < (1 << 20):
+            name = "%s_%d" % (a.matte, rows)
+            manifest[name] = "%08x" % Renderer.matte_id(name)
+            seen.discard(int(manifest[name], 16))
+            rows += 1
+        with open(a.matte_out + ".json", "w") as f:
+            json.dump(manifest, f, indent=1)
+        print("matte (%s, %d ranks): %s_00.exr .. %s_%02d.exr, manifest %s.json (%d names)" % (a.matte, a.matte_ranks, a.matte_out, a.matte_out, len(matte_layers) - 1, a.matte_out, rows))
     if a.aov:
         opaque = np.full((h, w, 1), 255, np.uint8)
         alb8, nrm8, depth = aov_images(r.readback(aov_albedo), r.readback(aov_nd))
