@@ -434,8 +434,8 @@ __device__ void collapse_one(const BvhNode* __restrict__ nodes2, uint32_t binary
             slot++;
         }
     }
-    // Children in decreasing surface area: occlusion rays enter the children in slot order
-    // (any hit ends them, so they skip the distance sort) and the biggest child is the likeliest to hold an occluder.  Closest-hit
+    // Children in decreasing surface area: occlusion rays (any hit ends them, so they skip the distance sort) take the child they enter
+    // farthest along the ray, the lowest slot among equals, and push the others in slot order; alpha-shadow rays walk in slot order.  Closest-hit
     // rays sort by distance anyway.  A 4-element sorting network on static indices (dynamic indexing would put the arrays in scratch).
     {
         float key[kBvhWidth];

@@ -168,13 +168,23 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     // a step pushes at most three entries: if no active lane is within three of the LDS part's end, every push is a plain ds_write
     const bool shallow = __ballot(t.sp + 3 > kStackLds) == 0;
     if (!ORDERED) {
-        // occlusion rays accept any hit: visiting order is irrelevant, skip the sort
-        int next = kTravDone;
-        if (enters[0]) next = c0;
+        // An accept-first occlusion ray ends at any hit, so its visiting order is free: it goes on with the entering child it enters FARTHEST
+        // along the ray.  It starts on a surface, inside the boxes around that surface, which rarely hold its occluder; in an enclosed scene
+        // the occluder is the shell at the ray's far end (profiles/EXPERIMENTS.md).  A max over four float keys (a miss is -1, tn >= 0) and
+        // first-match selects, no sort; equal keys go to the lowest slot, the child of the largest area.  The other entering children are
+        // pushed in ascending slot order.  Alpha-shadow rays multiply transmissions in visiting order: their keys all tie, which is the slot
+        // order they always had, bit for bit (a constant in the DEFAULTS copies, which have no such rays).
+#define PT_PICK_KEY(K) (enters[K] ? (t.all_candidates ? 0.0f : entry[K]) : -1.0f)
+        const float k0 = PT_PICK_KEY(0), k1 = PT_PICK_KEY(1), k2 = PT_PICK_KEY(2), k3 = PT_PICK_KEY(3);
+#undef PT_PICK_KEY
+        const float far = fmaxf(fmaxf(k0, k1), fmaxf(k2, k3));
+        const bool p0 = k0 == far, p1 = !p0 && k1 == far, p2 = !(p0 || p1) && k2 == far, p3 = !(p0 || p1 || p2);
+        const int next = far < 0.0f ? kTravDone : (p0 ? c0 : (p1 ? c1 : (p2 ? c2 : c3)));
 #define PT_PUSH_UNORDERED(F)                                                                                                        \
-        if (enters[1]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c1, st); else next = c1; }           \
-        if (enters[2]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c2, st); else next = c2; }           \
-        if (enters[3]) { if (next != kTravDone) trav_push<F>(t, sc, lds_stack, spill, c3, st); else next = c3; }
+        if (enters[0] && !p0) trav_push<F>(t, sc, lds_stack, spill, c0, st);                                                       \
+        if (enters[1] && !p1) trav_push<F>(t, sc, lds_stack, spill, c1, st);                                                       \
+        if (enters[2] && !p2) trav_push<F>(t, sc, lds_stack, spill, c2, st);                                                       \
+        if (enters[3] && !p3) trav_push<F>(t, sc, lds_stack, spill, c3, st);
         if (shallow) { PT_PUSH_UNORDERED(true) } else { PT_PUSH_UNORDERED(false) }
 #undef PT_PUSH_UNORDERED
         if (next != kTravDone) t.cur = next; else trav_pop(t, sc, lds_stack, spill);
