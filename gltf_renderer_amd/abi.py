@@ -283,6 +283,22 @@ class PtMatteConfig(C.Structure):
     _fields_ = [("enable", C.c_int32), ("kind", C.c_int32), ("ranks", C.c_int32), ("id_count", C.c_int32), ("layers", C.c_void_p * 4)]
 
 
+class PtMotionConfig(C.Structure):
+    """pt_motion_config: motion vectors (pt_set_motion; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("_pad", C.c_int32), ("motion", C.c_void_p), ("prev_world_to_view", C.c_float * 16),
+                ("prev_view_to_clip", C.c_float * 16)]
+
+
+class PtReprojectConfig(C.Structure):
+    """pt_reproject_config (pt_reproject)."""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("depth_tolerance", C.c_float)]
+
+    @classmethod
+    def defaults(cls):
+        return cls(0.1, 32.0, 0.02)
+
+
+MOTION_SNAPSHOT_NONE, MOTION_SNAPSHOT_VALID, MOTION_SNAPSHOT_STALE = 0, 1, 2
 MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
 MATTE_MAX_RANKS = 8
 PROBE_SH_RADIANCE, PROBE_SH_IRRADIANCE = 0, 1
@@ -328,5 +344,8 @@ assert C.sizeof(PtProbeConfig) == 20
 assert [getattr(PtProbeConfig, f).offset for f, _ in PtProbeConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtMatteConfig) == 48
 assert [getattr(PtMatteConfig, f).offset for f, _ in PtMatteConfig._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtMotionConfig) == 144
+assert [getattr(PtMotionConfig, f).offset for f, _ in PtMotionConfig._fields_] == [0, 4, 8, 16, 80]
+assert C.sizeof(PtReprojectConfig) == 12
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

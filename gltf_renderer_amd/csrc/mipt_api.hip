@@ -157,6 +157,7 @@ void mark_buffer_users(pt_ctx* ctx, int handle) {
 }  // namespace
 
 // (pt_ctx.h)
+void pt::world_to_clip_of(const float* view_to_clip, const float* world_to_view, float* out) { mat4_mul(view_to_clip, world_to_view, out); }
 bool pt::camera_setup(const pt_execute_params* ep, const pt_lens_config& cfg, CameraSetup& cam) {
     mat4_mul(ep->view_to_clip, ep->world_to_view, cam.world_to_clip);               // Pathtracer.cpp:262
     double v2w[16];
@@ -291,7 +292,12 @@ public:
         // ID mattes (pt_set_matte) are written, like the AOVs, by every call without a debug output, under the output's counts and resets.
         const bool matte = ctx->matte.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
         if (matte && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "mattes are written in the wavefront mode only");
+        // Motion vectors (pt_set_motion) likewise; they describe camera rays, so not under a bake or probes.
+        const bool motion = ctx->motion.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
+        if (motion && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors are written in the wavefront mode only");
+        if (motion && (bake || probes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors describe camera rays: not under a bake or probes");
         if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
+        if (ctx->motion_restart) { reset = true; ctx->motion_restart = false; }
         if (ctx->matte_restart) { reset = true; ctx->matte_restart = false; }
         if (ctx->probe_restart) { reset = true; ctx->probe_restart = false; }
         if (ctx->bake_restart) { reset = true; ctx->bake_restart = false; }
@@ -378,7 +384,7 @@ public:
                 fc.spp = (uint32_t)batch;
                 if ((unsigned long long)fc.pixel_slots * fc.spp > 0x7fffffffull) return ctx->fail(PT_ERR_CAPACITY, "sample batch too large for this resolution");
                 const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * fc.spp);
-                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov, matte);
+                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov, matte, motion);
                 HIPOK(ctx->d_workspace.reserve(ctx->stream, need, need));
                 AdaptiveArgs ad = {};
                 if (adaptive) {
@@ -398,9 +404,11 @@ public:
                 }
                 const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
                 const ProbeArgs pa = probe_args(ctx);
+                MotionArgs mo = {};
+                if (motion) motion_setup(ctx, world_to_clip, ep, mo);
                 HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
                                        ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr,
-                                       probes ? &pa : nullptr, matte ? &mt : nullptr));
+                                       probes ? &pa : nullptr, matte ? &mt : nullptr, motion ? &mo : nullptr));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
@@ -1349,7 +1357,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart || ctx->matte_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte since the last trace: the next trace starts anew");
+    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart || ctx->matte_restart || ctx->motion_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte / pt_set_motion since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1444,7 +1452,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false; ctx->matte_restart = false;
+    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false; ctx->matte_restart = false; ctx->motion_restart = false;
     return PT_OK;
 }
 

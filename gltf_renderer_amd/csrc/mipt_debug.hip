@@ -123,6 +123,38 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the motion records (pt_set_motion) pt_trace would write for caller-supplied first rays under `settings`
+// (its cull flag), `params` (the current camera, the image size) and the context's motion config (the previous camera) and snapshot --
+// k_debug_intersect's closest hit, then k_wf_motion's own record function (motion.hip k_debug_motion).  rays: 8 floats each as
+// pt_debug_intersect takes them; out: 8 floats each (record.xyzw, instance, primitive, u, v; zeros with instance = primitive = -1 for a miss),
+// host arrays.  The config's enable and target are not looked at.  Leaves the accumulation and a pending restart as they are.
+extern "C" int pt_debug_motion(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const float* rays, uint32_t n, float* out) {
+    if (!ctx || !settings || !params || (n && (!rays || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
+    CameraSetup cam;
+    if (!camera_setup(params, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    if (n == 0) return PT_OK;
+    SceneRec sc = scene_fill(ctx);
+    MotionArgs mo;
+    motion_setup(ctx, cam.world_to_clip, params, mo);
+    const uint32_t lanes = (n + 255u) & ~255u;
+    TempBuf rays_buf, out_buf, deep_buf;
+    if (rays_buf.alloc((size_t)n * 32) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_motion: ray buffers"); }
+    if (const uint32_t entries = deep_stack_entries(ctx)) {
+        if (deep_buf.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_motion: deep stack"); }
+        sc.deep_stack = deep_buf.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = lanes;
+    }
+    hipError_t e = hipMemcpyAsync(rays_buf.ptr, rays, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        launch_debug_motion(sc, mo, rays_buf.as<float>(), n, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, out_buf.as<float>(), ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, out_buf.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_motion: ") + hipGetErrorString(e));
+}
+
 // test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
 // 2: the fused k_wf_traverse -- on queues the caller fills (pt_wavefront.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
 // (origin, tmin = 0: the queue format has none, direction, tmax) with the shard 0..255 each is queued in (the caller's order within a shard is

@@ -119,6 +119,12 @@ struct pt_ctx {
     std::vector<uint32_t> matte_user_ids;         // fix(ids[i]) of pt_set_matte; rows beyond it get the ids of their default names
     pt::DevBuf d_matte_ids;                       // uint32 per row (MatteArgs::ids), made by pt_trace for ...
     int matte_table_kind = -1; size_t matte_table_rows = 0;   // ... this kind (-1: stale) and this many rows of the instance / material table
+    // ---- motion vectors (pt_set_motion): the config with the caller's target, and the previous pose (pt_motion_snapshot)
+    pt_motion_config motion = {};
+    bool motion_restart = false;                  // pt_set_motion: the next pt_trace starts a new accumulation
+    pt::DevBuf d_motion_snap;                     // 3 float4 per triangle of the instance table, at InstanceRec::tri_offset + prim (MotionArgs::snap)
+    bool motion_snap_taken = false;               // a snapshot exists; it stands for a table of ...
+    std::vector<uint32_t> motion_snap_counts;     // ... these tri_count, row by row
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
 
@@ -176,6 +182,13 @@ inline ProbeArgs probe_args(const pt_ctx* ctx) {
 // The mattes of a call (pt_set_matte): the device table of ids -- made now unless it stands for this kind and this many rows -- and what
 // k_wf_matte / k_wf_matte_resolve take.  (mipt_api.hip)
 int matte_setup(pt_ctx* ctx, MatteArgs& matte);
+
+// The motion vectors of a call (pt_set_motion): the two cameras, the snapshot if it is valid for the current instance table, the caller's
+// target.  mc = the call's world_to_clip (CameraSetup).  motion_snapshot_state: PT_MOTION_SNAPSHOT_*.  (motion.hip)
+int motion_snapshot_state(const pt_ctx* ctx);
+void motion_setup(const pt_ctx* ctx, const float* world_to_clip, const pt_execute_params* ep, MotionArgs& motion);
+// world_to_clip = view_to_clip * world_to_view by the routine camera_setup forms a call's with (mipt_api.hip)
+void world_to_clip_of(const float* view_to_clip, const float* world_to_view, float* out);
 
 // Pathtracer::BuildAccel (mipt_api.hip) if the tree does not stand for the current tables, as every call that traces rays begins
 int ensure_accel(pt_ctx* ctx);

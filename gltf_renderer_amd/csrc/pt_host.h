@@ -132,8 +132,9 @@ struct DebugQueues {
     float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
 };
 hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
-// aov: with the two AOV record arrays behind the rest; matte: with the matte record array behind those (whether or not they are used)
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false, bool matte = false);
+// aov: with the two AOV record arrays behind the rest; matte: with the matte record array behind those (whether or not they are used);
+// motion: with the motion record array behind those likewise
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false, bool matte = false, bool motion = false);
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
 struct AdaptiveTile {
@@ -183,6 +184,18 @@ struct MatteArgs {
     int32_t kind, ranks;      // PT_MATTE_*; K = 2, 4, 6 or 8
     float4* layers[4];        // the caller's layers, res_x * res_y each: the first K / 2
 };
+// Motion vectors (pt_set_motion): what k_wf_motion and k_wf_motion_resolve take as their own argument.  One record per slot, written by
+// k_wf_motion between the primary traversal and the first shade stage (beside k_wf_aov), blended into the caller's target by
+// k_wf_motion_resolve.  The matrices are wave-uniform kernel arguments (scalar registers).
+struct MotionArgs {
+    float4* rec;              // per slot: the sample's record, zeros for a miss or a non-finite record (workspace, set by launch_wavefront)
+    const float4* snap;       // the previous pose: 3 float4 (v0, e1, e2) per triangle at InstanceRec::tri_offset + prim; nullptr = the current packets
+    uint32_t n_snap;          // entries of snap
+    uint32_t width, height;
+    float4* target;           // the caller's target, res_x * res_y
+    float mc[16], mp[16];     // world_to_clip of this call and of the previous frame
+    float vc[16], vp[16];     // world_to_view likewise
+};
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
 // bake: nullptr = camera rays (k_wf_generate); else k_wf_generate_bake starts the paths on the atlas's texels and `lens` is not looked at
 // probes: nullptr likewise; else k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
@@ -191,10 +204,12 @@ struct MatteArgs {
 //      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
 // matte: nullptr = no mattes (no k_wf_matte / k_wf_matte_resolve launch); else the id table and the caller's layers (the record pointer is
 //      ignored) and a workspace of wavefront_workspace_bytes(fc, stage_blocks, aov, true)
+// motion: nullptr = no motion vectors (no k_wf_motion / k_wf_motion_resolve launch); else the cameras, the snapshot and the caller's target
+//      (the record pointer is ignored) and a workspace of wavefront_workspace_bytes(fc, stage_blocks, aov, matte, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
                             const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr, const ProbeArgs* probes = nullptr,
-                            const MatteArgs* matte = nullptr);
+                            const MatteArgs* matte = nullptr, const MotionArgs* motion = nullptr);
 // pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
 
@@ -206,6 +221,22 @@ constexpr int kMatteExtractMaxIds = 64;
 struct MatteExtractIds { uint32_t id[kMatteExtractMaxIds]; };     // after the exponent fix; by value in the kernel's arguments
 // mask[p] = the sequential float32 sum over ranks 0 .. ranks - 1 of the coverages whose id is among ids.id[0 .. count - 1].  Asynchronous.
 void launch_matte_extract(const float4* const layers[4], int ranks, uint32_t pixels, const MatteExtractIds& ids, int count, float* mask, hipStream_t stream);
+
+// ---- motion.hip: the previous pose, the hook's records and pt_reproject ---------------------------------------------------------------
+// snap[instances[T.inst].tri_offset + T.prim] = (T.v0, T.e1, T.e2) with w lanes 0, for every packet T of the built tree.  Asynchronous.
+void launch_motion_snapshot(const TriPacket* tris, uint32_t n_tris, const InstanceRec* instances, uint32_t n_instances, float4* snap, uint32_t n_snap, hipStream_t stream);
+// pt_debug_motion: d_rays = 8 floats per ray as pt_debug_intersect takes them; d_out = 8 floats per ray (record.xyzw, instance, primitive, u, v),
+// zeros with instance = primitive = -1 for a miss.  The closest hit is k_debug_intersect's, the record k_wf_motion's own function.
+void launch_debug_motion(const SceneRec& sc, const MotionArgs& ma, const float* d_rays, uint32_t n, uint32_t rf, float* d_out, hipStream_t stream);
+struct ReprojectArgs {
+    const float4 *color, *motion, *prev_color, *prev_motion;
+    const float* prev_length;     // nullptr = 1 everywhere
+    float4* out_color;
+    float* out_length;
+    uint32_t w, h;
+    float alpha_min, max_history, depth_tolerance;
+};
+void launch_reproject(const ReprojectArgs& a, hipStream_t stream);
 
 // ---- probe.hip: pt_probe_project's reduction of an octahedral atlas to spherical harmonics --------------------------------------
 // dirs: n * n float4, the texel-centre directions of an n x n octahedral map (w unused), row-major.  Asynchronous.

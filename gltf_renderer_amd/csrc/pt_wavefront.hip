@@ -27,6 +27,7 @@
 #include "pt_bake.h"
 #include "pt_probe.h"
 #include "pt_matte.h"
+#include "pt_motion.h"
 
 #ifdef PT_TIMING                 // diagnostic build only (tools/shade_sections.py); not part of the C-ABI
 namespace pt { __device__ unsigned long long pt_timing[12]; }
@@ -912,6 +913,36 @@ __global__ __launch_bounds__(kBlock) void k_wf_matte_resolve(FrameConstants fc, 
     for (int j = 0; j < RANKS / 2; j++) ma.layers[j][at] = matte_pack(m, j);
 }
 
+// Motion vectors (pt_set_motion): where the surface each sample's first ray sees was in the previous frame, one float4 per slot.  A stage of
+// its own in k_wf_aov's window, as light as k_wf_matte: per entry the slot word of the ray, the hit, the hit's TriPacket (one 64-byte line),
+// the instance row's tri_offset and the 48-byte snapshot entry, then one non-temporal store.  The four matrices are kernel arguments, hence
+// wave-uniform scalars; none of the shade stage's LDS tables is staged.  The records were cleared before the generate stage.
+__global__ __launch_bounds__(kBlock) void k_wf_motion(SceneRec sc, WfBuffers wf, MotionArgs ma) {
+    const ShardView sv = shard_view(wf);
+    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
+    const size_t base = (size_t)sv.shard * wf.seg_cap;
+    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
+        const uint32_t slot = QLD(((const uint32_t*)(wf.ray_d[0] + base + i))[3]);
+        const float4 h = QLD(wf.hit[base + i]);
+        const uint32_t hb = __float_as_uint(h.w), tri = hb & 0x7fffffffu;
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hb != kMissTri && tri < sc.num_tris) r = motion_record(sc, ma, tri, h.y, h.z);
+        if (slot < wf.capacity) QST(ma.rec[slot], r);
+    }
+}
+// The motion part of a resolve, a kernel of its own launched right before k_wf_resolve (whose adaptive instantiations update the tiles'
+// `active` flags this one reads) on the resolve's grid: the target is the running mean of the records with the output's counts, by
+// resolve_aov_target.  A tile retired by adaptive sampling is not written.
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_motion_resolve(FrameConstants fc, WfBuffers wf, AdaptiveArgs ad, MotionArgs ma) {
+    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
+    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t px, py;
+    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
+    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
+    resolve_aov_target(fc, wf, ma.rec, ma.target, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 static uint32_t blocks_per_shard_for(int stage_blocks) {
     uint32_t b = (uint32_t)(stage_blocks > 0 ? stage_blocks : 1536) / kShards;
@@ -937,9 +968,12 @@ static size_t state_slots_for(size_t slots) { return (size_t)chunks_per_shard_fo
 static size_t aov_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, false) + 255) & ~(size_t)255; }
 // ... and the matte records (MatteArgs::rec) behind those, at the same place with AOVs on or off
 static size_t matte_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, true) + 255) & ~(size_t)255; }
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov, bool matte) {
+// ... and the motion records (MotionArgs::rec) behind those, likewise
+static size_t motion_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, true, true) + 255) & ~(size_t)255; }
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov, bool matte, bool motion) {
     const uint32_t bps = blocks_per_shard_for(stage_blocks);
     const size_t slots = state_slots_for((size_t)fc.my_tiles * kBlock * fc.spp);
+    if (motion) return motion_records_offset(fc, stage_blocks) + slots * 16;
     if (matte) return matte_records_offset(fc, stage_blocks) + slots * 4;
     if (aov) return aov_records_offset(fc, stage_blocks) + slots * (2 * 16);
     const size_t q = (size_t)kShards * seg_cap_for(fc, bps);
@@ -1016,7 +1050,7 @@ static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const Sc
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake,
-                            const ProbeArgs* probes, const MatteArgs* matte) {
+                            const ProbeArgs* probes, const MatteArgs* matte, const MotionArgs* motion) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -1052,6 +1086,12 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         mt = *matte;
         mt.rec = (uint32_t*)((char*)workspace + matte_records_offset(fc, stage_blocks));
         if ((e = hipMemsetAsync(mt.rec, 0, (size_t)slots * 4, stream)) != hipSuccess) return e;
+    }
+    MotionArgs mo = {};
+    if (motion) {                                                       // likewise
+        mo = *motion;
+        mo.rec = (float4*)((char*)workspace + motion_records_offset(fc, stage_blocks));
+        if ((e = hipMemsetAsync(mo.rec, 0, (size_t)slots * 16, stream)) != hipSuccess) return e;
     }
     AdaptiveArgs ad = {};
     if (adaptive) ad = *adaptive;
@@ -1110,6 +1150,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     }
     if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
     if (matte) { hipLaunchKernelGGL(k_wf_matte, stage, block, 0, stream, sc, wf, mt); mark(STAGE_SHADE); }         // likewise
+    if (motion) { hipLaunchKernelGGL(k_wf_motion, stage, block, 0, stream, sc, wf, mo); mark(STAGE_SHADE); }        // likewise
     for (int b = 0; b < iterations; b++) {
         const int cur = b & 1;
         const dim3 gs = cap(grid_of(b), env_shade_bps), gt = cap(grid_of(b), env_trace_bps);
@@ -1137,6 +1178,11 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
             case 6: launch_matte(std::integral_constant<int, 6>()); break;
             default: launch_matte(std::integral_constant<int, 8>()); break;
         }
+        mark(STAGE_RESOLVE);
+    }
+    if (motion) {                                                       // likewise
+        if (adaptive) hipLaunchKernelGGL((k_wf_motion_resolve<true>), full, block, 0, stream, fc, wf, ad, mo);
+        else hipLaunchKernelGGL((k_wf_motion_resolve<false>), full, block, 0, stream, fc, wf, ad, mo);
         mark(STAGE_RESOLVE);
     }
     if (aov) { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, true>), full, block, 0, stream, fc, wf, output, ad, av);

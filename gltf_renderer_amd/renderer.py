@@ -39,7 +39,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # light-probe baking (additive likewise)
            "pt_set_probes", "pt_probe_project",
            # ID mattes (additive likewise)
-           "pt_set_matte", "pt_matte_id", "pt_matte_extract"]
+           "pt_set_matte", "pt_matte_id", "pt_matte_extract",
+           # motion vectors and temporal reprojection (additive likewise)
+           "pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject"]
 
 
 class MiptError(RuntimeError):
@@ -129,6 +131,10 @@ def load_library():
     L.pt_matte_id.argtypes = [C.c_char_p, C.c_size_t]
     L.pt_matte_id.restype = C.c_uint32
     L.pt_matte_extract.argtypes = [vp, vp, ci, C.c_uint32, C.c_uint32, vp, ci, vp]
+    L.pt_motion_snapshot.argtypes = [vp, ci]
+    L.pt_motion_snapshot_state.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.pt_set_motion.argtypes = [vp, vp]
+    L.pt_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     _LIB = L
     return L
 
@@ -415,6 +421,57 @@ class Renderer:
             cfg.layers[j] = t.data_ptr()
         self._check(self.L.pt_set_matte(self.h, C.byref(cfg), _p(idv) if idv is not None and len(idv) else None))
         self._matte = list(layers)                    # the library keeps the pointers: keep the tensors alive with the renderer
+
+    def motion_snapshot(self, take=True):
+        """pt_motion_snapshot: keeps the current pose of every triangle as the previous pose of the frames traced next (builds or refits
+        the tree first if it is dirty); take=False frees it.  Pose frame f - 1, call this, pose frame f, trace()."""
+        self._check(self.L.pt_motion_snapshot(self.h, int(bool(take))))
+
+    def motion_snapshot_state(self):
+        """pt_motion_snapshot_state: abi.MOTION_SNAPSHOT_NONE, _VALID (same rows and triangle counts as when it was taken) or _STALE."""
+        out = C.c_int32(-1)
+        self._check(self.L.pt_motion_snapshot_state(self.h, C.byref(out)))
+        return out.value
+
+    def set_motion(self, motion, prev_world_to_view=None, prev_view_to_clip=None):
+        """Motion vectors (include/mipt.h pt_set_motion): trace() accumulates, beside the output, per pixel (previous minus current
+        screen position in pixels, previous view depth, current view depth) into `motion`, a float32 CUDA tensor (H, W, 4) like the
+        output, caller-owned.  prev_*: the previous frame's camera as 16 floats, glm column-major like PtExecuteParams' (abi.mat4_to_c of
+        the camera module's row-major matrices).  motion=None turns the pass off.  The next trace() starts a new accumulation.
+        Wavefront mode only, not under a bake or probes.  Neither the target nor the snapshot is part of an accum_save() blob."""
+        if motion is None:
+            self._check(self.L.pt_set_motion(self.h, C.byref(abi.PtMotionConfig())))
+            self._motion = None
+            return
+        assert motion.is_cuda and motion.is_contiguous() and motion.dtype == self.torch.float32 and motion.dim() == 3 and motion.shape[2] == 4
+        cfg = abi.PtMotionConfig()
+        cfg.enable = 1
+        cfg.motion = motion.data_ptr()
+        cfg.prev_world_to_view[:] = [float(v) for v in np.asarray(prev_world_to_view, np.float32).reshape(-1)]
+        cfg.prev_view_to_clip[:] = [float(v) for v in np.asarray(prev_view_to_clip, np.float32).reshape(-1)]
+        self._check(self.L.pt_set_motion(self.h, C.byref(cfg)))
+        self._motion = motion                         # the library keeps the pointer: keep the tensor alive with the renderer
+
+    def reproject(self, color, motion, prev_color, prev_motion, prev_length=None, out_color=None, out_length=None, config=None):
+        """The temporal filter (include/mipt.h pt_reproject): blends `color` with the previous frame's result `prev_color` read at the
+        motion vector, where the previous frame's depth (prev_motion.w) agrees.  color / motion / prev_color / prev_motion: float32 CUDA
+        tensors (H, W, 4); prev_length: (H, W) float32 history lengths or None (1 everywhere).  out_color: None = a new tensor, `color`
+        itself = in place.  config: abi.PtReprojectConfig (None = the defaults).  Asynchronous.  Returns (out_color, out_length)."""
+        t = self.torch
+        h, w = color.shape[:2]
+        if out_color is None:
+            out_color = t.empty_like(color)
+        if out_length is None:
+            out_length = t.empty((h, w), dtype=t.float32, device=color.device)
+        for x in (color, motion, prev_color, prev_motion, out_color):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+        for x in (prev_length, out_length):
+            assert x is None or (x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and tuple(x.shape) == (h, w))
+        self._check(self.L.pt_reproject(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
+                                        C.c_void_p(motion.data_ptr()), C.c_void_p(prev_color.data_ptr()), C.c_void_p(prev_motion.data_ptr()),
+                                        C.c_void_p(prev_length.data_ptr()) if prev_length is not None else None, w, h,
+                                        C.c_void_p(out_color.data_ptr()), C.c_void_p(out_length.data_ptr())))
+        return out_color, out_length
 
     def matte_extract(self, layers, ids, out=None):
         """pt_matte_extract: the anti-aliased mask (H, W) float32 CUDA tensor of a set of 1..64 ids over matte layers (of set_matte(), or

@@ -796,6 +796,87 @@ uint32_t pt_matte_id(const char* name, size_t length);
  * ranks other than 2, 4, 6, 8, id_count outside 1..64. */
 int      pt_matte_extract(pt_ctx* ctx, const void* const* layers, int ranks, uint32_t width, uint32_t height,
                           const uint32_t* ids, int id_count, void* mask);
+/* Motion vectors and temporal reprojection (absent upstream): for each pixel, where the surface it sees was in the previous frame of an
+ * animation -- the motion AOV a compositor blurs with, and the history read of a temporal filter.  Off by default; with it off every image,
+ * ray count and stat is what it is without this section, and with it on the output, the AOV targets, the matte layers, every ray count and
+ * accumulated_frames are bit for bit what they are without it.  Everything below is float32 in the order written, products and sums not
+ * fused; fdiv is the correctly rounded division; matrices are glm column-major, M[4 * c + r].
+ *   The previous pose.  pt_motion_snapshot(ctx, take != 0) builds or refits the acceleration structure if it is dirty (as pt_lens_focus_at
+ * does) and copies, for every triangle packet T of the tree, (T.v0, T.e1, T.e2) -- world space, 3 float4 with w = 0, 48 bytes -- to
+ *     snap[instances[T.inst].tri_offset + T.prim]
+ * an instance-major address that no rebuild or reordering of the tree changes.  The array belongs to the context, has one entry per
+ * triangle of the instance table, is regrown when the table grows and freed by pt_destroy or by take == 0.  The context records the
+ * table's row count and every row's triangle count.  A snapshot is VALID for a trace iff the current instance table has the same row
+ * count and the same per-row triangle counts: it survives refits (moved instances, pt_buffer_update, pt_skin_run),
+ * pt_accel_request_rebuild and a change of builder, and goes STALE when the triangle set changes.  With no valid snapshot the previous
+ * geometry is the current geometry: right for a camera moving through a static scene, and for the first frame of a sequence.  It covers
+ * rigid, skinned and morphed meshes alike.  A caller poses frame f - 1, takes the snapshot, poses frame f and traces. */
+enum { PT_MOTION_SNAPSHOT_NONE = 0, PT_MOTION_SNAPSHOT_VALID = 1, PT_MOTION_SNAPSHOT_STALE = 2 };
+int pt_motion_snapshot(pt_ctx* ctx, int take);
+int pt_motion_snapshot_state(pt_ctx* ctx, int32_t* state_out);
+/*   One sample.  A sample's first ray is the camera ray or the lens ray; its first closest hit -- the hit the AOVs describe, after the
+ * any-hit alpha test, under the call's cull flag -- lies on packet T with barycentrics (u, v):
+ *     Pc = (T.v0 + u * T.e1) + v * T.e2                                      componentwise
+ *     S  = snap[instances[T.inst].tri_offset + T.prim] if the snapshot is valid, else T
+ *     Pp = (S.v0 + u * S.e1) + v * S.e2
+ *     Mc = the world_to_clip this pt_trace forms for its reset comparison;  Mp = the same routine applied to the two prev_ matrices
+ *     Vc = params->world_to_view;  Vp = prev_world_to_view
+ *     clip_k(M, P) = ((M[k] P.x + M[4+k] P.y) + M[8+k] P.z) + M[12+k]        k = 0, 1, 3
+ *     sx(M, P) = ((fdiv(clip_0, clip_3) + 1.0f) * 0.5f) * (float)W
+ *     sy(M, P) = ((1.0f - fdiv(clip_1, clip_3)) * 0.5f) * (float)H           the inverse of the pinhole ray's pixel-to-clip map
+ *     z(V, P)  = -(((V[2] P.x + V[6] P.y) + V[10] P.z) + V[14])              view depth, positive in front
+ *     record   = (sx(Mp, Pp) - sx(Mc, Pc),  sy(Mp, Pp) - sy(Mc, Pc),  z(Vp, Pp),  z(Vc, Pc))
+ * xy is "where the point was minus where it is", in pixels: the offset at which a history image is read.  A triangle that did not move,
+ * under an unchanged camera, runs the same operations on the same inputs: its record is exactly (0, 0, z, z).  Both projections go through
+ * the matrices, not the pixel centre, so the jitter cancels; under a lens the point is projected through the pinhole.  record.z <= 0: the
+ * point was behind the previous camera and xy is meaningless.  A miss gives zeros; so does a record with a non-finite component.
+ *   The target is the running mean of its samples with the output's weights, in sample order, under the output's counts and resets (the
+ * AOVs' arithmetic): a batch equals the calls one by one; a call without FLAG_ACCUMULATE leaves the one sample; a tile shard writes only
+ * the rank's tiles; a tile retired by adaptive sampling is not written; a call with a debug output, or one past max_accumulated_frames,
+ * leaves the target untouched.  Wavefront mode only: a motion call in PT_MODE_MEGAKERNEL, or under a bake or probes, fails with
+ * PT_ERR_INVALID_ARGUMENT and writes nothing.
+ *   Neither the target nor the snapshot is part of the blob of pt_accum_save, whose format is unchanged.  A caller who resumes keeps the
+ * target, poses frame f - 1, takes the snapshot again and calls pt_set_motion before pt_accum_load. */
+typedef struct pt_motion_config {
+    int32_t enable;                 /* 0 = off (default) */
+    int32_t _pad;
+    void*   motion;                 /* device, W*H float4, caller-owned like pt_execute_params.output */
+    float   prev_world_to_view[16];
+    float   prev_view_to_clip[16];
+} pt_motion_config;                 /* 144 bytes */
+/* PT_ERR_INVALID_ARGUMENT for a NULL config and, when enabled, a NULL target or a non-finite matrix entry; after a refusal the old config
+ * stays and no restart is pending.  A good config forces a new accumulation on the next pt_trace, as pt_set_aov does: until that trace
+ * pt_accum_save answers PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int pt_set_motion(pt_ctx* ctx, const pt_motion_config* config);
+/* The temporal filter: blends a frame with the previous frame's result read at the motion vector.  A pure function of its images, like
+ * pt_denoise: it reads no pt_trace state and is enqueued on the context's stream.  color, prev_color, out_color: W*H float4; motion,
+ * prev_motion: W*H float4 in the layout above (prev_motion.w is the previous frame's own view depth, so the two motion images are all the
+ * geometry it needs); prev_length, out_length: W*H float, the history length (prev_length NULL = 1 everywhere).  Pixel (x, y), c = color,
+ * m = motion:
+ *     USABLE iff every component of m is finite, m.w > 0, m.z > 0, and s = ((float)x + m.x, (float)y + m.y) has -1 < s.x < W, -1 < s.y < H
+ *     otherwise out_color = c, all four channels bit for bit, and out_length = 1
+ *     x0 = floorf(s.x), fx = s.x - x0; y likewise.  Taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner,
+ *     b = (i ? fx : 1 - fx) * (j ? fy : 1 - fy)
+ *     a tap COUNTS iff q is in the image, prev_motion[q] is finite with .w > 0, fabsf(prev_motion[q].w - m.z) <= depth_tolerance * m.z,
+ *         prev_color[q].rgb is finite, and prev_length[q] is finite and >= 1        (exclusion is a select: a NaN cannot leak)
+ *     ws, hist.rgb, hl = the sequential sums of b, b * prev_color[q].rgb, b * prev_length[q] over the taps that count
+ *     ws <= 0: the pixel is treated as not usable.  Otherwise
+ *     hist = hist / ws;  hl = hl / ws;  n = fminf(hl + 1.0f, max_history);  a = fmaxf(fdiv(1.0f, n), alpha_min)
+ *     out.rgb = hist + a * (c.rgb - hist);  out.w = c.w;  out_length = n
+ * A silhouette pixel whose samples partly miss has a mean depth that matches nothing: it simply keeps its current colour -- the filter is
+ * conservative there by construction.  There is no neighbourhood colour clamp, no normal test and no variance estimate.
+ * PT_ERR_INVALID_ARGUMENT with nothing written for a NULL ctx (answered before any device call), a NULL required image, a zero size or one
+ * above 2^30 (or W * H above 2^31 - 1), a config value out of range, out_color overlapping anything but color (which it may BE: in place),
+ * out_length overlapping any input. */
+typedef struct pt_reproject_config {
+    float alpha_min;        /* 0..1: least weight of the current frame.  default 0.1 */
+    float max_history;      /* finite, >= 1: cap of the history length.   default 32 */
+    float depth_tolerance;  /* finite, > 0, relative.                      default 0.02 */
+} pt_reproject_config;      /* 12 bytes */
+int pt_reproject(pt_ctx* ctx, const pt_reproject_config* config /* NULL = defaults */,
+                 const void* color, const void* motion,
+                 const void* prev_color, const void* prev_motion, const void* prev_length /* W*H float; NULL = 1 everywhere */,
+                 uint32_t width, uint32_t height, void* out_color, void* out_length /* W*H float */);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

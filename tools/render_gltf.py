@@ -52,6 +52,17 @@ their coverages; ranks 2j and 2j + 1 in layer j), and PREFIX.json, the manifest 
 Composes with --aov, --adaptive, --bake and --probes; the layers are not part of a checkpoint, so not with --checkpoint / --resume here.
   python tools/render_gltf.py scene.glb --spp 64 --matte instance --matte-ranks 6 --matte-out crypto --out frame.png
 
+--motion-out FILE --prev-time T: the motion-vector pass (pt_set_motion) of an animated scene: poses --animation at time T, takes the snapshot of
+that pose (pt_motion_snapshot), poses --time and accumulates, beside the frame, per pixel (previous minus current screen position in pixels,
+previous view depth, current view depth); FILE is an uncompressed 32-bit float RGBA EXR (or a float32 .npy, H x W x 4).  The camera stands still.
+  python tools/render_gltf.py figure.glb --animation 0 --prev-time 0.46 --time 0.5 --spp 16 --motion-out motion.exr
+
+--sequence T0:T1:FPS: renders the frames of --animation at T0, T0 + 1 / FPS, ... <= T1, --spp samples each, to <out>_0000.<ext>, <out>_0001.<ext>,
+...; every frame after the first carries the motion vectors against the frame before it.  With --temporal each frame is denoised (pt_denoise,
+--denoise ITERATIONS or 5) and then blended with the previous filtered frame read at its motion vector (pt_reproject): the flicker of a
+low-sample sequence denoised frame by frame goes.  Camera renders only: not with --bake, --probes, --adaptive, --matte, --checkpoint, --resume.
+  python tools/render_gltf.py figure.glb --animation 0 --sequence 0:2:24 --temporal --spp 16 --out shot.png
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -106,6 +117,23 @@ def resume_mismatch(info, size, aov, adaptive, accum_flags):
         if have != want:
             return "it was rendered with --min-spp %d --spp %d --adaptive %.9g, not %d / %d / %.9g" % (have + want)
     return None
+
+
+def sequence_frames(spec):
+    """"T0:T1:FPS" -> the frame times T0 + i / FPS <= T1 (a tolerance of a millionth of a frame); ValueError for anything else."""
+    parts = spec.split(":")
+    if len(parts) != 3:
+        raise ValueError(spec)
+    t0, t1, fps = (float(v) for v in parts)
+    if not (math.isfinite(t0) and math.isfinite(t1) and math.isfinite(fps)) or fps <= 0 or t1 < t0:
+        raise ValueError(spec)
+    n = int(math.floor((t1 - t0) * fps + 1e-6)) + 1
+    return [t0 + i / fps for i in range(n)]
+
+
+def numbered_path(out, i):
+    stem, ext = os.path.splitext(out)
+    return "%s_%04d%s" % (stem, i, ext)
 
 
 def write_exr_rgba32f(path, rgba):
@@ -171,7 +199,27 @@ def main():
     ap.add_argument("--matte", default=None, choices=["instance", "material"], help="accumulate ID mattes of the instances or of the materials")
     ap.add_argument("--matte-ranks", type=int, default=6, choices=[2, 4, 6, 8], metavar="K", help="(id, coverage) pairs per pixel: 2, 4, 6 or 8")
     ap.add_argument("--matte-out", default="", metavar="PREFIX", help="with --matte: PREFIX_00.exr ... (one per layer) and the manifest PREFIX.json")
+    ap.add_argument("--motion-out", default="", metavar="FILE", help="write the motion-vector pass (.exr: 32-bit float RGBA; .npy); needs --prev-time")
+    ap.add_argument("--prev-time", type=float, default=None, metavar="T", help="with --motion-out: the animation time of the previous frame")
+    ap.add_argument("--sequence", default=None, metavar="T0:T1:FPS", help="render numbered frames of --animation from T0 to T1")
+    ap.add_argument("--temporal", action="store_true", help="with --sequence: pt_denoise, then pt_reproject onto the previous frame")
     a = ap.parse_args()
+    if bool(a.motion_out) != (a.prev_time is not None):
+        ap.error("--motion-out FILE and --prev-time T go together")
+    if a.temporal and a.sequence is None:
+        ap.error("--temporal needs --sequence T0:T1:FPS")
+    sequence_times = None
+    if a.sequence is not None:
+        try:
+            sequence_times = sequence_frames(a.sequence)
+        except ValueError:
+            ap.error("--sequence takes T0:T1:FPS with T1 >= T0 and FPS > 0")
+    if (a.motion_out or sequence_times is not None) and (a.bake is not None or a.probes is not None):
+        ap.error("motion vectors describe camera rays: --motion-out and --sequence go with neither --bake nor --probes")
+    if sequence_times is not None and (a.adaptive is not None or a.matte is not None or a.checkpoint or a.resume or a.motion_out):
+        ap.error("--sequence goes with none of --adaptive, --matte, --checkpoint, --resume, --motion-out")
+    if a.motion_out and (a.checkpoint or a.resume):
+        ap.error("--motion-out goes with neither --checkpoint nor --resume: the pass is not part of a checkpoint")
     if a.matte is None and (a.matte_out or a.matte_ranks != 6):
         ap.error("--matte-ranks and --matte-out need --matte instance|material")
     if a.matte is not None and not a.matte_out:
@@ -204,10 +252,18 @@ def main():
     r = Renderer(0)
     sc = gltf.GltfScene(a.path)
     sc.upload(r)
-    if a.animation >= 0:
-        sc.animate(a.animation, a.time)
-    sc.calculate_global_transforms(0)
-    lights = sc.frame(r, 0)
+
+    def pose(t):
+        """The scene at animation time t in the context: node transforms, skinning, the instance table.  Returns the light count."""
+        if a.animation >= 0:
+            sc.animate(a.animation, t)
+        sc.calculate_global_transforms(0)
+        return sc.frame(r, 0)
+
+    if a.motion_out:                                                     # the previous frame's pose first: its triangles are the snapshot
+        pose(a.prev_time)
+        r.motion_snapshot()
+    lights = pose(sequence_times[0] if sequence_times is not None else a.time)
     # bounds from the loaded streams and node transforms
     lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
     c = sc.counts()
@@ -265,13 +321,56 @@ def main():
         print("bake %d x %d: UV set %d, %s, surface offset %.6g" % (w, h, a.bake_uv, "every instance" if a.bake_instance < 0 else "instance %d" % a.bake_instance, offset))
     out = r.create_output(w, h)
     aov_albedo = aov_nd = None
-    if a.aov or a.denoise is not None:
+    if a.aov or a.denoise is not None or a.temporal:
         aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
         r.set_aov(aov_albedo, aov_nd)
     matte_layers = None
     if a.matte is not None:
         matte_layers = [r.create_output(w, h) for _ in range(a.matte_ranks // 2)]
         r.set_matte(abi.MATTE_MATERIAL if a.matte == "material" else abi.MATTE_INSTANCE, matte_layers)
+    motion = None
+    if a.motion_out or sequence_times is not None:                       # the camera stands still: the previous matrices are this frame's
+        motion = r.create_output(w, h)
+        r.set_motion(motion, p.world_to_view[:], p.view_to_clip[:])
+
+    def write_frame(path, image):
+        if path.lower().endswith(".exr"):
+            gltf.write_exr(path, r.readback(image)[..., :3], half=True)  # linear radiance
+        elif path.lower().endswith(".pfm"):
+            gltf.write_pfm(path, r.readback(image)[..., :3])
+        else:
+            gltf.write_png(path, r.tonemap(image, want_rgba8=True)[1], 3)   # tone-mapped (AgX + sRGB), ToneMapper.ps.hlsl
+
+    if sequence_times is not None:
+        # per frame: snapshot of the pose just rendered, the next pose, --spp samples of a new accumulation with the motion pass beside it,
+        # then (--temporal) pt_denoise and pt_reproject onto the previous filtered frame
+        prev_color = prev_motion = prev_length = None
+        dn = abi.PtDenoiseConfig.default()
+        if a.denoise is not None:
+            dn.iterations = a.denoise
+        for i, t in enumerate(sequence_times):
+            if i > 0:
+                r.motion_snapshot()
+                p.light_count = pose(t)
+            st.reset = 1
+            for k in range(a.spp):
+                p.frame = i * a.spp + k
+                r.trace(st, p, out)
+                st.reset = 0
+            shown = out
+            if a.temporal:
+                shown = r.denoise(out, aov_albedo, aov_nd, config=dn)
+                if prev_color is not None:
+                    shown, prev_length = r.reproject(shown, motion, prev_color, prev_motion, prev_length)
+                prev_color, prev_motion = shown, motion.clone()
+            elif a.denoise is not None:
+                shown = r.denoise(out, aov_albedo, aov_nd, config=dn)
+            write_frame(numbered_path(a.out, i), shown)
+        torch.cuda.synchronize()
+        s = r.stats()
+        print("%s: %d frames %s .. %s, t = %.4g .. %.4g, %d spp each%s, last trace %.2f ms" % (a.path, len(sequence_times), numbered_path(a.out, 0),
+              numbered_path(a.out, len(sequence_times) - 1), sequence_times[0], sequence_times[-1], a.spp, ", denoised and reprojected" if a.temporal else "", s.trace_ms))
+        return
     adaptive_cfg = None if a.adaptive is None else (min(a.min_spp, a.spp), a.spp, a.adaptive)
     if adaptive_cfg is not None:
         r.set_samples_per_trace(min(a.batch, 64))
@@ -345,6 +444,15 @@ def main():
         gltf.write_pfm(a.out, r.readback(out)[..., :3])
     else:
         gltf.write_png(a.out, rgba8, 3)                                  # tone-mapped (AgX + sRGB), ToneMapper.ps.hlsl
+    if a.motion_out:
+        mv = r.readback(motion)
+        if a.motion_out.lower().endswith(".npy"):
+            np.save(a.motion_out, mv)
+        else:
+            write_exr_rgba32f(a.motion_out, mv)
+        moving = mv[..., 3] > 0
+        print("motion (t = %.4g -> %.4g): %s, %d of %d pixels covered, largest vector %.2f px" % (a.prev_time, a.time, a.motion_out, int(moving.sum()), w * h,
+              float(np.hypot(mv[..., 0], mv[..., 1])[moving].max()) if moving.any() else 0.0))
     if matte_layers is not None:
         seen = set()
         for j, layer in enumerate(matte_layers):
