@@ -298,6 +298,15 @@ class PtReprojectConfig(C.Structure):
         return cls(0.1, 32.0, 0.02)
 
 
+class PtMotionBlurConfig(C.Structure):
+    """pt_motion_blur_config (pt_motion_blur)."""
+    _fields_ = [("shutter", C.c_float), ("max_radius", C.c_float), ("taps", C.c_int32), ("jitter", C.c_int32), ("depth_softness", C.c_float)]
+
+    @classmethod
+    def defaults(cls):
+        return cls(0.5, 32.0, 16, 1, 0.05)
+
+
 MOTION_SNAPSHOT_NONE, MOTION_SNAPSHOT_VALID, MOTION_SNAPSHOT_STALE = 0, 1, 2
 MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
 MATTE_MAX_RANKS = 8
@@ -347,5 +356,7 @@ assert [getattr(PtMatteConfig, f).offset for f, _ in PtMatteConfig._fields_] == 
 assert C.sizeof(PtMotionConfig) == 144
 assert [getattr(PtMotionConfig, f).offset for f, _ in PtMotionConfig._fields_] == [0, 4, 8, 16, 80]
 assert C.sizeof(PtReprojectConfig) == 12
+assert C.sizeof(PtMotionBlurConfig) == 20
+assert [getattr(PtMotionBlurConfig, f).offset for f, _ in PtMotionBlurConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

@@ -125,6 +125,8 @@ struct pt_ctx {
     pt::DevBuf d_motion_snap;                     // 3 float4 per triangle of the instance table, at InstanceRec::tri_offset + prim (MotionArgs::snap)
     bool motion_snap_taken = false;               // a snapshot exists; it stands for a table of ...
     std::vector<uint32_t> motion_snap_counts;     // ... these tri_count, row by row
+    // ---- pt_motion_blur: the per-pixel streak image V, then the tile maxima T and their neighbourhood maxima N, for one image size
+    pt::DevBuf d_blur;
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
 

@@ -238,6 +238,20 @@ struct ReprojectArgs {
 };
 void launch_reproject(const ReprojectArgs& a, hipStream_t stream);
 
+// ---- blur.hip: pt_motion_blur's three kernels ------------------------------------------------------------------------------------------
+// V: w * h float4 (half streak x, y, its length, depth); T, N: tiles_x * tiles_y float4 each (a tile's longest streak; the longest within
+// `reach` tiles) -- context-owned scratch.  out overlaps neither input.  Asynchronous.
+struct BlurArgs {
+    const float4 *color, *motion;
+    float4 *V, *T, *N, *out;
+    uint32_t w, h, tiles_x, tiles_y;
+    float half_shutter;           // 0.5f * shutter, formed once
+    float max_radius, depth_softness;
+    int taps, jitter;
+    int reach;                    // (int)ceilf(max_radius / 16.0f): 1..4
+};
+hipError_t launch_motion_blur(const BlurArgs& a, hipStream_t stream);
+
 // ---- probe.hip: pt_probe_project's reduction of an octahedral atlas to spherical harmonics --------------------------------------
 // dirs: n * n float4, the texel-centre directions of an n x n octahedral map (w unused), row-major.  Asynchronous.
 void launch_probe_dirs(float4* dirs, uint32_t n, hipStream_t stream);

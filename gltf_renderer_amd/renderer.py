@@ -41,7 +41,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # ID mattes (additive likewise)
            "pt_set_matte", "pt_matte_id", "pt_matte_extract",
            # motion vectors and temporal reprojection (additive likewise)
-           "pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject"]
+           "pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject",
+           # motion blur along the motion vectors (additive likewise)
+           "pt_motion_blur"]
 
 
 class MiptError(RuntimeError):
@@ -135,6 +137,7 @@ def load_library():
     L.pt_motion_snapshot_state.argtypes = [vp, C.POINTER(C.c_int32)]
     L.pt_set_motion.argtypes = [vp, vp]
     L.pt_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.pt_motion_blur.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     _LIB = L
     return L
 
@@ -472,6 +475,21 @@ class Renderer:
                                         C.c_void_p(prev_length.data_ptr()) if prev_length is not None else None, w, h,
                                         C.c_void_p(out_color.data_ptr()), C.c_void_p(out_length.data_ptr())))
         return out_color, out_length
+
+    def motion_blur(self, color, motion, out=None, config=None):
+        """The shutter-time blur along the motion vectors (include/mipt.h pt_motion_blur): a reconstruction filter over `color` and the
+        `motion` target of set_motion() (or any images of that layout), both float32 CUDA tensors (H, W, 4).  out: where the result goes
+        (None = a new tensor; never an input: there is no in-place mode).  config: abi.PtMotionBlurConfig (None = the defaults).
+        Asynchronous on the context's stream.  Returns the output tensor."""
+        t = self.torch
+        if out is None:
+            out = t.empty_like(color)
+        for x in (color, motion, out):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+        h, w = color.shape[:2]
+        self._check(self.L.pt_motion_blur(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
+                                          C.c_void_p(motion.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
+        return out
 
     def matte_extract(self, layers, ids, out=None):
         """pt_matte_extract: the anti-aliased mask (H, W) float32 CUDA tensor of a set of 1..64 ids over matte layers (of set_matte(), or

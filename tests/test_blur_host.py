@@ -1,0 +1,139 @@
+"""CPU-only checks of pt_motion_blur (include/mipt.h): the symbol and the config mirror against the header, the call that answers without a
+device, and the restatement (tests/blur_ref.py) that tests/test_gpu_blur.py holds the GPU to -- its own properties: no motion returns the
+input's bits, the tile maximum's tie rule and the neighbour maximum's order, how far a streak reaches, and what a bright moving block does
+to the ground behind it."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from gltf_renderer_amd import abi, renderer
+from tests import blur_ref as br
+
+f32, u32 = np.float32, np.uint32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def header():
+    return open(os.path.join(ROOT, "include", "mipt.h")).read()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(u32)
+
+
+def test_the_symbol_is_exported_and_declared():
+    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
+    assert re.search(r"\bint\s+pt_motion_blur\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_motion_blur_config\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*\w*\s*,"
+                     r"\s*const\s+void\s*\*\s*\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*void\s*\*\s*\w*\s*\)\s*;", text)
+    assert text.index("pt_reproject(") < text.index("pt_motion_blur(")           # after pt_reproject
+    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)                   # additive: the version stays
+    assert hasattr(renderer.load_library(), "pt_motion_blur") and "pt_motion_blur" in renderer.EXPORTS
+    assert callable(getattr(renderer.Renderer, "motion_blur"))
+
+
+def test_the_config_mirror_matches_the_header():
+    m = re.search(r"typedef struct pt_motion_blur_config \{(.*?)\} pt_motion_blur_config;", header(), re.S)
+    assert m, "include/mipt.h lacks pt_motion_blur_config"
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    fields = re.findall(r"(float|int32_t)\s+([a-z_]+)\s*;", body)
+    assert fields == [("float", "shutter"), ("float", "max_radius"), ("int32_t", "taps"), ("int32_t", "jitter"), ("float", "depth_softness")]
+    A = abi.PtMotionBlurConfig
+    assert [n for n, _ in A._fields_] == [n for _, n in fields]
+    assert [t for _, t in A._fields_] == [C.c_float if t == "float" else C.c_int32 for t, _ in fields]
+    assert C.sizeof(A) == 20 and [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12, 16]
+    d = A.defaults()
+    assert (f32(d.shutter), f32(d.max_radius), d.taps, d.jitter, f32(d.depth_softness)) == (f32(0.5), f32(32.0), 16, 1, f32(0.05))
+    assert (d.shutter, d.max_radius, d.taps, d.jitter, f32(d.depth_softness)) == tuple(f32(v) if isinstance(v, float) else v for v in br.DEFAULTS.values())
+    h = header()
+    for words in ("not ray-traced motion blur", "does not blur", "centred on the frame", "linear over the frame", "3.97", "12 %"):
+        assert words in h, words                                  # the limits are stated where a caller reads them
+
+
+def test_a_null_context_answers_minus_one_without_a_device():
+    L = renderer.load_library()
+    img = [np.full((4, 4, 4), 2.0, f32) for _ in range(3)]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert L.pt_motion_blur(None, None, p(img[0]), p(img[1]), 4, 4, p(img[2])) == -1
+    cfg = abi.PtMotionBlurConfig.defaults()
+    assert L.pt_motion_blur(None, C.byref(cfg), p(img[0]), p(img[1]), 4, 4, p(img[2])) == -1
+    assert L.pt_motion_blur(None, None, None, None, 0, 0, None) == -1
+    assert all((a == 2.0).all() for a in img)
+
+
+# ---- the restatement -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [(40, 24), (17, 33)])
+def test_no_motion_and_motion_below_half_a_pixel_return_the_inputs_bits(size):
+    w, h = size
+    rng = np.random.default_rng(11 * w)
+    color, motion = br.random_field(rng, w, h)
+    still = motion.copy(); still[..., :2] = 0
+    out, info = br.blur(color, still)
+    assert np.array_equal(bits(out), bits(color)) and not info["blurred"].any() and not info["counted"].any()
+    # scaled so that the longest half streak stays under half a pixel: every tile copies
+    finite = np.where(np.isfinite(motion[..., :2]), motion[..., :2], 0)
+    longest = np.sqrt((finite.astype(np.float64) ** 2).sum(axis=-1)).max()
+    slow = motion.copy(); slow[..., :2] = (motion[..., :2] * f32(0.49 / (0.25 * longest))).astype(f32)
+    out, info = br.blur(color, slow)
+    assert info["moving"].sum() > w * h // 4 and 0.4 < info["N"][..., 2].max() < 0.5
+    assert np.array_equal(bits(out), bits(color)) and not info["blurred"].any()
+    # the same field unscaled does blur
+    out, info = br.blur(color, motion)
+    assert info["blurred"].sum() > w * h // 2 and not np.array_equal(bits(out), bits(color))
+
+
+def test_tie_rules_of_the_tile_and_neighbour_maxima():
+    w, h = 48, 16
+    color = np.random.default_rng(3).random((h, w, 4)).astype(f32)
+    motion = np.zeros((h, w, 4), f32)
+    motion[..., 2] = motion[..., 3] = 4.0
+    motion[5, 3, :2] = (-10.0, 0.0)
+    motion[9, 2, :2] = (0.0, -10.0)
+    motion[4, 40, :2] = (6.0, 8.0)
+    _, info = br.blur(color, motion, shutter=1.0, max_radius=16.0)
+    T, N = info["T"], info["N"]
+    assert T.shape == (1, 3, 3) and N.shape == (1, 3, 3)
+    # all three streaks are 5 long.  Tile 0: (y 5, x 3) comes before (y 9, x 2) in (y, x) order although its x is larger; (-0) * h = -0
+    # (by value: the middle tile's static pixels have a vector of (-0) * h = -0 too)
+    assert np.array_equal(T[0], np.array([(5.0, -0.0, 5.0), (0.0, 0.0, 0.0), (-3.0, -4.0, 5.0)], f32))
+    assert np.array_equal(bits(T[0, 0]), bits(np.array((5.0, -0.0, 5.0), f32))) and np.array_equal(bits(T[0, 2]), bits(np.array((-3.0, -4.0, 5.0), f32)))
+    # tile 1 sees 5, 0, 5 in dx order: the first is held, the equal third does not replace it; tile 2 sees 0 then its own 5
+    assert np.array_equal(bits(N[0]), bits(np.array([(5.0, -0.0, 5.0), (5.0, -0.0, 5.0), (-3.0, -4.0, 5.0)], f32)))
+
+
+def reach_field():
+    w, h = 160, 16
+    rng = np.random.default_rng(160)
+    color = rng.random((h, w, 4)).astype(f32)
+    motion = np.zeros((h, w, 4), f32)
+    motion[..., 2] = motion[..., 3] = 4.0
+    motion[2:12, 2:12, :2] = rng.uniform(60, 90, (10, 10, 2)).astype(f32) * rng.choice(np.array([-1.0, 1.0], f32), (10, 10, 2))
+    return color, motion
+
+
+def test_a_streak_reaches_r_tiles_and_no_farther():
+    color, motion = reach_field()
+    out, info = br.blur(color, motion, shutter=2.0, max_radius=64.0)
+    assert info["clamped"][2:12, 2:12].all() and (info["V"][..., 2] > 0).sum() == 100
+    assert np.all(info["N"][0, :5, 2] == 64.0) and np.all(info["N"][0, 5:, 2] == 0.0)         # r = 4: tiles 0..4
+    assert np.array_equal(bits(out[:, 80:]), bits(color[:, 80:])) and not info["blurred"][:, 80:].any()
+    assert info["blurred"][:, :80].all() and (bits(out[:, :80, :3]) != bits(color[:, :80, :3])).any(axis=-1).sum() > 100
+
+
+@pytest.mark.parametrize("size", [(40, 24), (17, 33)])
+def test_a_bright_block_spreads_over_the_ground_and_leaves_the_rest_alone(size):
+    w, h = size
+    color, motion, on_block = br.block_field(np.random.default_rng(w), w, h)
+    out, info = br.blur(color, motion, shutter=1.0, max_radius=16.0, taps=16)
+    assert np.array_equal(bits(info["N"][..., 2].max()), bits(f32(6.5)))                       # half of (12, 5): 13 / 2
+    changed = (bits(out[..., :3]) != bits(color[..., :3])).any(axis=-1)
+    off = changed & ~on_block
+    assert off.sum() >= 50, off.sum()
+    assert np.all(out[off][:, :3] >= color[off][:, :3]) and np.all((out[off][:, :3] > color[off][:, :3]).any(axis=-1))
+    static = info["V"][..., 2] == 0
+    assert (static & ~changed).sum() >= 400, (static & ~changed).sum()
+    assert changed[:3].any()                                                                   # the block spreads over the misses above it too
+    assert np.array_equal(bits(out[..., 3]), bits(color[..., 3]))
+    assert (info["counted"] >= 8).sum() >= 40

@@ -63,6 +63,13 @@ previous view depth, current view depth); FILE is an uncompressed 32-bit float R
 low-sample sequence denoised frame by frame goes.  Camera renders only: not with --bake, --probes, --adaptive, --matte, --checkpoint, --resume.
   python tools/render_gltf.py figure.glb --animation 0 --sequence 0:2:24 --temporal --spp 16 --out shot.png
 
+--motion-blur SHUTTER: a shutter-time blur of the finished frame along its motion vectors (pt_motion_blur; SHUTTER in (0, 2] is the open share
+of the frame interval, 0.5 = a 180 degree shutter), applied after --denoise and --temporal and before tone mapping.  --blur-radius R caps the
+half streak (1..64 px, default 32), --blur-taps N sets the taps along it (2..64, default 16).  It needs motion vectors: use it with --sequence,
+or with --prev-time T on a single frame (--motion-out is then optional).  A reconstruction filter, not ray-traced motion blur (include/mipt.h).
+  python tools/render_gltf.py figure.glb --animation 0 --sequence 0:2:24 --temporal --motion-blur 0.5 --spp 16 --out shot.png
+  python tools/render_gltf.py figure.glb --animation 0 --prev-time 0.46 --time 0.5 --motion-blur 0.5 --spp 64 --out frame.png
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -200,12 +207,28 @@ def main():
     ap.add_argument("--matte-ranks", type=int, default=6, choices=[2, 4, 6, 8], metavar="K", help="(id, coverage) pairs per pixel: 2, 4, 6 or 8")
     ap.add_argument("--matte-out", default="", metavar="PREFIX", help="with --matte: PREFIX_00.exr ... (one per layer) and the manifest PREFIX.json")
     ap.add_argument("--motion-out", default="", metavar="FILE", help="write the motion-vector pass (.exr: 32-bit float RGBA; .npy); needs --prev-time")
-    ap.add_argument("--prev-time", type=float, default=None, metavar="T", help="with --motion-out: the animation time of the previous frame")
+    ap.add_argument("--prev-time", type=float, default=None, metavar="T", help="with --motion-out or --motion-blur: the animation time of the previous frame")
     ap.add_argument("--sequence", default=None, metavar="T0:T1:FPS", help="render numbered frames of --animation from T0 to T1")
     ap.add_argument("--temporal", action="store_true", help="with --sequence: pt_denoise, then pt_reproject onto the previous frame")
+    ap.add_argument("--motion-blur", type=float, default=None, metavar="SHUTTER", help="blur the finished frame along its motion vectors; SHUTTER in (0, 2]; needs --sequence or --prev-time")
+    ap.add_argument("--blur-radius", type=float, default=None, metavar="R", help="with --motion-blur: cap of the half streak in pixels (1..64, default 32)")
+    ap.add_argument("--blur-taps", type=int, default=None, metavar="N", help="with --motion-blur: taps along the streak (2..64, default 16)")
     a = ap.parse_args()
-    if bool(a.motion_out) != (a.prev_time is not None):
-        ap.error("--motion-out FILE and --prev-time T go together")
+    if a.motion_out and a.prev_time is None:
+        ap.error("--motion-out FILE needs --prev-time T")
+    if a.prev_time is not None and not (a.motion_out or a.motion_blur is not None):
+        ap.error("--prev-time T goes with --motion-out FILE or --motion-blur SHUTTER")
+    if a.motion_blur is None and (a.blur_radius is not None or a.blur_taps is not None):
+        ap.error("--blur-radius and --blur-taps need --motion-blur SHUTTER")
+    if a.motion_blur is not None:
+        if a.sequence is None and a.prev_time is None:
+            ap.error("--motion-blur needs motion vectors: give --sequence T0:T1:FPS, or --prev-time T for a single frame")
+        if not (0.0 < a.motion_blur <= 2.0):
+            ap.error("--motion-blur takes a shutter in (0, 2]")
+        if a.blur_radius is not None and not (1.0 <= a.blur_radius <= 64.0):
+            ap.error("--blur-radius takes 1..64 pixels")
+        if a.blur_taps is not None and not (2 <= a.blur_taps <= 64):
+            ap.error("--blur-taps takes 2..64")
     if a.temporal and a.sequence is None:
         ap.error("--temporal needs --sequence T0:T1:FPS")
     sequence_times = None
@@ -214,12 +237,12 @@ def main():
             sequence_times = sequence_frames(a.sequence)
         except ValueError:
             ap.error("--sequence takes T0:T1:FPS with T1 >= T0 and FPS > 0")
-    if (a.motion_out or sequence_times is not None) and (a.bake is not None or a.probes is not None):
-        ap.error("motion vectors describe camera rays: --motion-out and --sequence go with neither --bake nor --probes")
+    if (a.prev_time is not None or sequence_times is not None) and (a.bake is not None or a.probes is not None):
+        ap.error("motion vectors describe camera rays: --motion-out, --motion-blur and --sequence go with neither --bake nor --probes")
     if sequence_times is not None and (a.adaptive is not None or a.matte is not None or a.checkpoint or a.resume or a.motion_out):
         ap.error("--sequence goes with none of --adaptive, --matte, --checkpoint, --resume, --motion-out")
-    if a.motion_out and (a.checkpoint or a.resume):
-        ap.error("--motion-out goes with neither --checkpoint nor --resume: the pass is not part of a checkpoint")
+    if a.prev_time is not None and (a.checkpoint or a.resume):
+        ap.error("--motion-out and --motion-blur go with neither --checkpoint nor --resume: the pass is not part of a checkpoint")
     if a.matte is None and (a.matte_out or a.matte_ranks != 6):
         ap.error("--matte-ranks and --matte-out need --matte instance|material")
     if a.matte is not None and not a.matte_out:
@@ -260,7 +283,7 @@ def main():
         sc.calculate_global_transforms(0)
         return sc.frame(r, 0)
 
-    if a.motion_out:                                                     # the previous frame's pose first: its triangles are the snapshot
+    if a.prev_time is not None:                                          # the previous frame's pose first: its triangles are the snapshot
         pose(a.prev_time)
         r.motion_snapshot()
     lights = pose(sequence_times[0] if sequence_times is not None else a.time)
@@ -329,9 +352,17 @@ def main():
         matte_layers = [r.create_output(w, h) for _ in range(a.matte_ranks // 2)]
         r.set_matte(abi.MATTE_MATERIAL if a.matte == "material" else abi.MATTE_INSTANCE, matte_layers)
     motion = None
-    if a.motion_out or sequence_times is not None:                       # the camera stands still: the previous matrices are this frame's
+    if a.prev_time is not None or sequence_times is not None:            # the camera stands still: the previous matrices are this frame's
         motion = r.create_output(w, h)
         r.set_motion(motion, p.world_to_view[:], p.view_to_clip[:])
+    blur = None
+    if a.motion_blur is not None:
+        blur = abi.PtMotionBlurConfig.defaults()
+        blur.shutter = a.motion_blur
+        if a.blur_radius is not None:
+            blur.max_radius = a.blur_radius
+        if a.blur_taps is not None:
+            blur.taps = a.blur_taps
 
     def write_frame(path, image):
         if path.lower().endswith(".exr"):
@@ -365,11 +396,13 @@ def main():
                 prev_color, prev_motion = shown, motion.clone()
             elif a.denoise is not None:
                 shown = r.denoise(out, aov_albedo, aov_nd, config=dn)
+            if blur is not None:                                         # after the filters; the history above stays unblurred
+                shown = r.motion_blur(shown, motion, config=blur)
             write_frame(numbered_path(a.out, i), shown)
         torch.cuda.synchronize()
         s = r.stats()
         print("%s: %d frames %s .. %s, t = %.4g .. %.4g, %d spp each%s, last trace %.2f ms" % (a.path, len(sequence_times), numbered_path(a.out, 0),
-              numbered_path(a.out, len(sequence_times) - 1), sequence_times[0], sequence_times[-1], a.spp, ", denoised and reprojected" if a.temporal else "", s.trace_ms))
+              numbered_path(a.out, len(sequence_times) - 1), sequence_times[0], sequence_times[-1], a.spp, (", denoised and reprojected" if a.temporal else "") + (", motion blur at shutter %g" % a.motion_blur if blur is not None else ""), s.trace_ms))
         return
     adaptive_cfg = None if a.adaptive is None else (min(a.min_spp, a.spp), a.spp, a.adaptive)
     if adaptive_cfg is not None:
@@ -434,6 +467,9 @@ def main():
         print("bake: %d of %d texels covered (%.1f %%)" % (int(cover.sum()), w * h, 100.0 * cover.mean()))
         if a.dilate:
             r.bake_dilate(out, a.dilate)
+    if blur is not None:                                                 # after the denoiser, before tone mapping
+        out = r.motion_blur(out, motion, config=blur)
+        print("motion blur (t = %.4g -> %.4g): shutter %g, half streak <= %g px, %d taps" % (a.prev_time, a.time, blur.shutter, blur.max_radius, blur.taps))
     if a.probe_sh:
         np.save(a.probe_sh, r.probe_project(out, abi.PROBE_SH_IRRADIANCE if a.irradiance else abi.PROBE_SH_RADIANCE))
         print("probe SH (%s): %s" % ("irradiance" if a.irradiance else "radiance", a.probe_sh))
