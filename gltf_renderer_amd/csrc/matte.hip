@@ -77,7 +77,7 @@ int pt_set_matte(pt_ctx* ctx, const pt_matte_config* config, const uint32_t* ids
     if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "matte: config is NULL");
     if (!config->enable) {                         // nothing else of a disabled config is looked at; the layers are no longer written
         ctx->matte.enable = 0;
-        ctx->matte_restart = true;
+        ctx->restart_pending = true;
         return PT_OK;
     }
     if (config->kind != PT_MATTE_INSTANCE && config->kind != PT_MATTE_MATERIAL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "matte: kind must be PT_MATTE_INSTANCE or PT_MATTE_MATERIAL");
@@ -90,7 +90,7 @@ int pt_set_matte(pt_ctx* ctx, const pt_matte_config* config, const uint32_t* ids
     ctx->matte_user_ids.resize((size_t)config->id_count);
     for (int i = 0; i < config->id_count; i++) ctx->matte_user_ids[(size_t)i] = matte_fix(ids[i]);
     ctx->matte_table_kind = -1;                    // the device table is made anew by the next matte pt_trace
-    ctx->matte_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 

@@ -268,57 +268,25 @@ public:
         if (!camera_setup(ep, ctx->lens, cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "singular camera matrix");
         const float* world_to_clip = cam.world_to_clip;                                  // :262
         bool reset = memcmp(world_to_clip, ctx->previous_world_to_clip, 64) != 0 || settings->reset;   // :267-271
-        // Adaptive sampling (pt_set_adaptive) applies to accumulating calls without a debug output.  Its tile state describes the output
-        // only if the last accumulation step was adaptive and of the same size and tile shard: otherwise the call starts a new one.
-        const bool adaptive = ctx->adaptive.enable != 0 && (settings->flags & PT_FLAG_ACCUMULATE) && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
-        if (adaptive && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive sampling runs in the wavefront mode only");
-        // First-hit AOVs (pt_set_aov) are written by every call without a debug output, under the output's counts and resets.
-        const bool aov = ctx->aov.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
-        if (aov && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "AOVs are written in the wavefront mode only");
-        // Texture-space baking (pt_set_bake): the generate stage starts the paths on the atlas's texels; everything else is this function as it is.
-        const bool bake = ctx->bake.enable != 0;
-        if (bake && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "a bake runs in the wavefront mode only");
-        if (bake && ctx->bake.instance >= (int)ctx->instances.size())
-            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance " + std::to_string(ctx->bake.instance) + " of " + std::to_string(ctx->instances.size()));
-        // Light-probe baking (pt_set_probes): likewise, the paths start at the probes' positions and width x height is the probes' atlas.
-        const bool probes = ctx->probes.enable != 0;
-        if (probes && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes are traced in the wavefront mode only");
-        if (probes) {
-            uint64_t pw, ph;
-            probe_atlas_size(ctx->probes, pw, ph);
-            if (ep->width != pw || ep->height != ph)
-                return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the atlas is " + std::to_string(pw) + " x " + std::to_string(ph) + ", not " + std::to_string(ep->width) + " x " + std::to_string(ep->height));
-        }
-        // ID mattes (pt_set_matte) are written, like the AOVs, by every call without a debug output, under the output's counts and resets.
-        const bool matte = ctx->matte.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
-        if (matte && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "mattes are written in the wavefront mode only");
-        // Motion vectors (pt_set_motion) likewise; they describe camera rays, so not under a bake or probes.
-        const bool motion = ctx->motion.enable != 0 && settings->debug_output == PT_DEBUG_OUTPUT_NONE;
-        if (motion && ctx->kernel_mode == PT_MODE_MEGAKERNEL) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors are written in the wavefront mode only");
-        if (motion && (bake || probes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors describe camera rays: not under a bake or probes");
-        if (ctx->adaptive_restart) { reset = true; ctx->adaptive_restart = false; }
-        if (ctx->motion_restart) { reset = true; ctx->motion_restart = false; }
-        if (ctx->matte_restart) { reset = true; ctx->matte_restart = false; }
-        if (ctx->probe_restart) { reset = true; ctx->probe_restart = false; }
-        if (ctx->bake_restart) { reset = true; ctx->bake_restart = false; }
-        if (ctx->aov_restart) { reset = true; ctx->aov_restart = false; }
-        if (ctx->lens_restart) { reset = true; ctx->lens_restart = false; }
-        if (adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
+        WavefrontPasses passes;                                                          // the call's optional passes, or why it cannot run them
+        if (int r = select_passes(ctx, settings, ep, passes)) return r;
+        if (ctx->restart_pending) { reset = true; ctx->restart_pending = false; }        // a pt_set_* since the last trace (pt_ctx.h)
+        // The adaptive tile state describes the output only if the last accumulation step was adaptive and of the same size and tile
+        // shard: otherwise the call starts a new one.
+        if (passes.adaptive && (ep->width != ctx->ad_w || ep->height != ctx->ad_h || ep->tile_rank != ctx->ad_rank ||
                          (ep->tile_rank_count ? ep->tile_rank_count : 1u) != ctx->ad_rank_count || ctx->accumulated_frames != ctx->ad_frames))
             reset = true;
         if (reset) ctx->accumulated_frames = 0;
         // an adaptive accumulation ends where its tiles must stop: min(max_samples, max_accumulated_frames)
-        const int frame_cap = adaptive ? std::min(ctx->adaptive.max_samples, settings->max_accumulated_frames) : settings->max_accumulated_frames;
+        const int frame_cap = passes.adaptive ? std::min(ctx->adaptive.max_samples, settings->max_accumulated_frames) : settings->max_accumulated_frames;
         if (ctx->accumulated_frames < frame_cap) {                                       // :273
             if (ep->light_count > ctx->n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "light_count exceeds uploaded lights");
             if (ep->environment_map >= 0 && !live_env(ctx, ep->environment_map))
                 return ctx->fail(PT_ERR_BAD_HANDLE, "bad environment map handle");
             if (!ep->output) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "output is null");
             if (int r = ensure_accel(ctx)) return r;
-            BakeArgs bk = {};
-            if (bake) { if (int r = bake_setup(ctx, ep->width, ep->height, bk)) return r; }
-            MatteArgs mt = {};
-            if (matte) { if (int r = matte_setup(ctx, mt)) return r; }
+            if (passes.bake) { if (int r = bake_setup(ctx, ep->width, ep->height, passes.bk)) return r; }
+            if (passes.matte) { if (int r = matte_setup(ctx, passes.mt)) return r; }
 
             SceneRec sc = scene_fill(ctx);
             if (ep->environment_map >= 0) scene_set_env(sc, *ctx->envs[ep->environment_map]);
@@ -362,12 +330,12 @@ public:
             fc.div_pixel_slots = FastDiv::make(fc.pixel_slots); fc.div_tiles_x = FastDiv::make(fc.tiles_x);
             fc.seed_step = settings->use_frame_as_seed ? 1u : 0u;
 
+            // workgroups of a wavefront stage launch: the caller's (pt_set_kernel_mode), else by the slots of the batch
+            const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * (size_t)batch);
             // deep traversal stack (trees that need more than the 64 on-chip entries): (need - 64) entries for every lane of the widest
             // traversal launch of this call
             if (const uint32_t entries = deep_stack_entries(ctx)) {
-                size_t lanes;
-                if (ctx->kernel_mode == PT_MODE_MEGAKERNEL) lanes = (size_t)fc.my_tiles * 256;
-                else lanes = (size_t)traversal_grid_lanes(ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * (size_t)batch));
+                const size_t lanes = ctx->kernel_mode == PT_MODE_MEGAKERNEL ? (size_t)fc.my_tiles * 256 : traversal_grid_lanes(stage_blocks);
                 const size_t need = (size_t)entries * lanes * 4;
                 if (const hipError_t e = ctx->d_deep.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "deep traversal stack: " + std::to_string(need) + " bytes");
                 sc.deep_stack = ctx->d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
@@ -383,39 +351,19 @@ public:
             } else {
                 fc.spp = (uint32_t)batch;
                 if ((unsigned long long)fc.pixel_slots * fc.spp > 0x7fffffffull) return ctx->fail(PT_ERR_CAPACITY, "sample batch too large for this resolution");
-                const int stage_blocks = ctx->stage_blocks > 0 ? ctx->stage_blocks : stage_blocks_for((size_t)fc.pixel_slots * fc.spp);
-                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, aov, matte, motion);
+                const size_t need = wavefront_workspace_bytes(fc, stage_blocks, passes);
                 HIPOK(ctx->d_workspace.reserve(ctx->stream, need, need));
-                AdaptiveArgs ad = {};
-                if (adaptive) {
-                    // tile state (rank-local tiles) and half buffer; a new accumulation makes every tile active with 0 samples
-                    const size_t px = (size_t)ep->width * ep->height, tiles = fc.my_tiles ? fc.my_tiles : 1;
-                    if (int r = adaptive_state(ctx, tiles, px)) return r;
-                    if (ctx->accumulated_frames == 0) {
-                        const AdaptiveTile fresh = {1u, 0u, 0.0f, 0u};
-                        const std::vector<AdaptiveTile> init(tiles, fresh);
-                        HIPOK(staged_upload(ctx, ctx->d_ad_tiles.ptr, init.data(), tiles * sizeof(AdaptiveTile)));
-                        HIPOK(hipMemsetAsync(ctx->d_ad_half.ptr, 0, px * 16, ctx->stream));
-                    }
-                    ad.tiles = ctx->d_ad_tiles.as<AdaptiveTile>(); ad.half = ctx->d_ad_half.as<float4>();
-                    ad.min_samples = ctx->adaptive.min_samples; ad.cap = frame_cap; ad.threshold = ctx->adaptive.threshold;
-                    ctx->ad_w = ep->width; ctx->ad_h = ep->height; ctx->ad_rank = fc.tile_rank; ctx->ad_rank_count = fc.tile_rank_count;
-                    ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
-                }
-                const AovArgs av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
-                const ProbeArgs pa = probe_args(ctx);
-                MotionArgs mo = {};
-                if (motion) motion_setup(ctx, world_to_clip, ep, mo);
+                if (passes.adaptive) { if (int r = adaptive_setup(ctx, ep, fc, frame_cap, passes.ad)) return r; }
+                if (passes.motion) motion_setup(ctx, world_to_clip, ep, passes.mo);
                 HIPOK(launch_wavefront(sc, fc, cam.lens, (float4*)ep->output, ctx->d_counters.as<Counters>(), ctx->counters_enabled, ctx->d_workspace.ptr, stage_blocks,
-                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, adaptive ? &ad : nullptr, aov ? &av : nullptr, bake ? &bk : nullptr,
-                                       probes ? &pa : nullptr, matte ? &mt : nullptr, motion ? &mo : nullptr));
+                                       ctx->stage_timing ? &ctx->timers : nullptr, ctx->stream, passes));
             }
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(ctx->ev_trace[1], ctx->stream));
             ctx->have_trace = true;
             if (settings->flags & PT_FLAG_ACCUMULATE) ctx->accumulated_frames += batch;   // :355-359
             else ctx->accumulated_frames = 0;
-            ctx->ad_frames = adaptive ? ctx->accumulated_frames : -1;
+            ctx->ad_frames = passes.adaptive ? ctx->accumulated_frames : -1;
         }
         memcpy(ctx->previous_world_to_clip, world_to_clip, 64);                          // :366
         return PT_OK;
@@ -508,6 +456,55 @@ public:
         return PT_OK;
     }
 };
+int select_passes(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* ep, WavefrontPasses& p) {
+    const bool plain = settings->debug_output == PT_DEBUG_OUTPUT_NONE, megakernel = ctx->kernel_mode == PT_MODE_MEGAKERNEL;
+    // Adaptive sampling (pt_set_adaptive) applies to accumulating calls without a debug output.
+    p.adaptive = ctx->adaptive.enable != 0 && (settings->flags & PT_FLAG_ACCUMULATE) && plain;
+    if (p.adaptive && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive sampling runs in the wavefront mode only");
+    // First-hit AOVs (pt_set_aov) are written by every call without a debug output, under the output's counts and resets.
+    p.aov = ctx->aov.enable != 0 && plain;
+    if (p.aov && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "AOVs are written in the wavefront mode only");
+    // Texture-space baking (pt_set_bake): the generate stage starts the paths on the atlas's texels; everything else is PathtraceScene as it is.
+    p.bake = ctx->bake.enable != 0;
+    if (p.bake && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "a bake runs in the wavefront mode only");
+    if (p.bake && ctx->bake.instance >= (int)ctx->instances.size())
+        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance " + std::to_string(ctx->bake.instance) + " of " + std::to_string(ctx->instances.size()));
+    // Light-probe baking (pt_set_probes): likewise, the paths start at the probes' positions and width x height is the probes' atlas.
+    p.probes = ctx->probes.enable != 0;
+    if (p.probes && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes are traced in the wavefront mode only");
+    if (p.probes) {
+        uint64_t pw, ph;
+        probe_atlas_size(ctx->probes, pw, ph);
+        if (ep->width != pw || ep->height != ph)
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the atlas is " + std::to_string(pw) + " x " + std::to_string(ph) + ", not " + std::to_string(ep->width) + " x " + std::to_string(ep->height));
+    }
+    // ID mattes (pt_set_matte) are written, like the AOVs, by every call without a debug output, under the output's counts and resets.
+    p.matte = ctx->matte.enable != 0 && plain;
+    if (p.matte && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "mattes are written in the wavefront mode only");
+    // Motion vectors (pt_set_motion) likewise; they describe camera rays, so not under a bake or probes.
+    p.motion = ctx->motion.enable != 0 && plain;
+    if (p.motion && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors are written in the wavefront mode only");
+    if (p.motion && (p.bake || p.probes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors describe camera rays: not under a bake or probes");
+    if (p.aov) p.av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
+    if (p.probes) p.pa = probe_args(ctx);
+    return PT_OK;
+}
+int adaptive_setup(pt_ctx* ctx, const pt_execute_params* ep, const FrameConstants& fc, int frame_cap, AdaptiveArgs& ad) {
+    // tile state (rank-local tiles) and half buffer; a new accumulation makes every tile active with 0 samples
+    const size_t px = (size_t)ep->width * ep->height, tiles = fc.my_tiles ? fc.my_tiles : 1;
+    if (int r = adaptive_state(ctx, tiles, px)) return r;
+    if (ctx->accumulated_frames == 0) {
+        const AdaptiveTile fresh = {1u, 0u, 0.0f, 0u};
+        const std::vector<AdaptiveTile> init(tiles, fresh);
+        HIPOK(staged_upload(ctx, ctx->d_ad_tiles.ptr, init.data(), tiles * sizeof(AdaptiveTile)));
+        HIPOK(hipMemsetAsync(ctx->d_ad_half.ptr, 0, px * 16, ctx->stream));
+    }
+    ad.tiles = ctx->d_ad_tiles.as<AdaptiveTile>(); ad.half = ctx->d_ad_half.as<float4>();
+    ad.min_samples = ctx->adaptive.min_samples; ad.cap = frame_cap; ad.threshold = ctx->adaptive.threshold;
+    ctx->ad_w = ep->width; ctx->ad_h = ep->height; ctx->ad_rank = fc.tile_rank; ctx->ad_rank_count = fc.tile_rank_count;
+    ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
+    return PT_OK;
+}
 int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake) {
     const uint64_t accel = (uint64_t)ctx->accel_builds + ctx->accel_refits;
     const size_t texels = (size_t)width * height;
@@ -1035,7 +1032,7 @@ int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_config* config) {
         if (!std::isfinite(config->threshold) || config->threshold < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "adaptive: threshold must be finite and >= 0");
     }
     ctx->adaptive = *config;
-    ctx->adaptive_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 
@@ -1043,7 +1040,7 @@ int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config) {
     if (!ctx || !config) return PT_ERR_INVALID_ARGUMENT;
     if (config->enable && !config->albedo && !config->normal_depth) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "aov: enabled without a target");
     ctx->aov = *config;
-    ctx->aov_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 
@@ -1057,7 +1054,7 @@ int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config) {
         if (!std::isfinite(config->blade_rotation)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: blade_rotation must be finite");
     }
     ctx->lens = *config;
-    ctx->lens_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 
@@ -1071,7 +1068,7 @@ int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config) {
         if (ctx->probes.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: probes are enabled (pt_set_probes): a trace renders one atlas or the other");
     }
     ctx->bake = *config;
-    ctx->bake_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 
@@ -1112,7 +1109,7 @@ int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* posit
     if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: config is NULL");
     if (!config->enable) {                        // nothing else of a disabled config is looked at; the layout and the positions go
         ctx->probes.enable = 0;
-        ctx->probe_restart = true;
+        ctx->restart_pending = true;
         return PT_OK;
     }
     if (!positions_xyz) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: positions_xyz is NULL");
@@ -1132,15 +1129,15 @@ int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* posit
     const size_t bytes = (size_t)config->count * 12;
     // a trace in flight may still read the old positions: the copy goes behind it on the stream, a larger array drains it first (DevBuf)
     if (const hipError_t e = ctx->d_probe_pos.reserve(ctx->stream, bytes, bytes)) {
-        if (ctx->d_probe_pos.ptr == nullptr) { ctx->probes.enable = 0; ctx->probe_restart = true; }     // the old array went with the failed growth
+        if (ctx->d_probe_pos.ptr == nullptr) { ctx->probes.enable = 0; ctx->restart_pending = true; }     // the old array went with the failed growth
         return grow_failed(ctx, e, "probe positions: " + std::to_string(bytes) + " bytes");
     }
     if (const hipError_t e = staged_upload(ctx, ctx->d_probe_pos.ptr, positions_xyz, bytes)) {
-        ctx->probes.enable = 0; ctx->probe_restart = true;               // the array may hold part of either set: back to the camera
+        ctx->probes.enable = 0; ctx->restart_pending = true;               // the array may hold part of either set: back to the camera
         return ctx->fail(PT_ERR_DEVICE, std::string("probe positions: ") + hipGetErrorString(e));
     }
     ctx->probes = *config;
-    ctx->probe_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 
@@ -1357,7 +1354,7 @@ int pt_accum_save(pt_ctx* ctx, const pt_accum_images* images, uint32_t width, ui
     const uint32_t world = tile_rank_count ? tile_rank_count : 1u;
     if (tile_rank >= world) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "accum_save: tile_rank >= tile_rank_count");
     if (ctx->accumulated_frames == 0) return ctx->fail(PT_ERR_NOT_READY, "accum_save: nothing accumulated");
-    if (ctx->adaptive_restart || ctx->aov_restart || ctx->lens_restart || ctx->bake_restart || ctx->probe_restart || ctx->matte_restart || ctx->motion_restart) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte / pt_set_motion since the last trace: the next trace starts anew");
+    if (ctx->restart_pending) return ctx->fail(PT_ERR_NOT_READY, "accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte / pt_set_motion since the last trace: the next trace starts anew");
     // the tile state is part of the accumulation under the condition PathtraceScene continues an adaptive one
     const bool adaptive = ctx->adaptive.enable != 0 && ctx->ad_ready && ctx->ad_w == width && ctx->ad_h == height && ctx->ad_rank == tile_rank &&
                           ctx->ad_rank_count == world && ctx->ad_frames == ctx->accumulated_frames;
@@ -1452,7 +1449,7 @@ int pt_accum_load(pt_ctx* ctx, const void* host_blob, size_t bytes, const pt_acc
         ctx->ad_my_tiles = info.tiles; ctx->ad_ready = true;
     }
     ctx->ad_frames = adaptive ? info.accumulated_frames : -1;
-    ctx->adaptive_restart = false; ctx->aov_restart = false; ctx->lens_restart = false; ctx->bake_restart = false; ctx->probe_restart = false; ctx->matte_restart = false; ctx->motion_restart = false;
+    ctx->restart_pending = false;
     return PT_OK;
 }
 

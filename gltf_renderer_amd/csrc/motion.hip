@@ -186,7 +186,7 @@ int pt_set_motion(pt_ctx* ctx, const pt_motion_config* config) {
     if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: config is NULL");
     if (!config->enable) {                         // nothing else of a disabled config is looked at; the target is no longer written
         ctx->motion.enable = 0;
-        ctx->motion_restart = true;
+        ctx->restart_pending = true;
         return PT_OK;
     }
     if (!config->motion) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: the target is NULL");
@@ -194,7 +194,7 @@ int pt_set_motion(pt_ctx* ctx, const pt_motion_config* config) {
         if (!std::isfinite(config->prev_world_to_view[i]) || !std::isfinite(config->prev_view_to_clip[i]))
             return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: a previous camera matrix has a non-finite entry");
     ctx->motion = *config;
-    ctx->motion_restart = true;
+    ctx->restart_pending = true;
     return PT_OK;
 }
 

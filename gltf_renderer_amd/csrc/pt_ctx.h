@@ -80,11 +80,13 @@ struct pt_ctx {
     bool have_trace = false, have_accel = false, have_skin = false;
     int bounce_limit = PT_REFERENCE_MAX_BOUNCES;
     int samples_per_trace = 1;
+    // pt_set_adaptive / _aov / _lens / _bake / _probes / _matte / _motion since the last trace: the next pt_trace that gets as far as its
+    // reset starts a new accumulation (PathtraceScene consumes it; pt_accum_save refuses while it stands; pt_accum_load clears it)
+    bool restart_pending = false;
     bool cull_null_shadow = false;
     bool counters_enabled = false;
     // ---- adaptive sampling (pt_set_adaptive): per rank-local tile state and the half buffer, for one size and tile shard
     pt_adaptive_config adaptive = {0, 2, 2, 0.0f};
-    bool adaptive_restart = false;                // pt_set_adaptive: the next pt_trace starts a new accumulation
     pt::DevBuf d_ad_tiles, d_ad_half;             // AdaptiveTile per tile, float4 per pixel
     uint32_t ad_w = 0, ad_h = 0, ad_rank = 0, ad_rank_count = 0, ad_my_tiles = 0;
     bool ad_ready = false;                        // an adaptive trace ran for (ad_w, ad_h, ad_rank, ad_rank_count)
@@ -93,13 +95,10 @@ struct pt_ctx {
     pt::DevBuf d_accum;
     // ---- first-hit AOVs (pt_set_aov): the caller's targets
     pt_aov_config aov = {0, nullptr, nullptr};
-    bool aov_restart = false;                     // pt_set_aov: the next pt_trace starts a new accumulation
     // ---- thin lens (pt_set_lens)
     pt_lens_config lens = {0, 0.0f, 1.0f, 0, 0.0f};
-    bool lens_restart = false;                    // pt_set_lens: the next pt_trace starts a new accumulation
     // ---- texture-space baking (pt_set_bake): the config, and the coverage map of one atlas size, config and state of the tree
     pt_bake_config bake = {0, 0, -1, 0.0f};
-    bool bake_restart = false;                    // pt_set_bake: the next pt_trace starts a new accumulation
     pt::DevBuf d_bake_keys, d_bake_owner;         // per texel: the owner's (instance << 32 | primitive); its index into d_tris / d_shade (BakeArgs::owner)
     pt::DevBuf d_bake_scratch;                    // the rasteriser's bin counts and scan (bake.hip)
     pt::DevBuf d_bake_dilate;                     // pt_bake_dilate: one image and two fill masks
@@ -109,19 +108,16 @@ struct pt_ctx {
     uint64_t bake_accel = 0;                      // accel_builds + accel_refits when the map was built: the packets it was rasterised from
     // ---- light-probe baking (pt_set_probes): the config, the probes' positions, and pt_probe_project's direction table and result
     pt_probe_config probes = {0, 16, 1, 1, 1000.0f};
-    bool probe_restart = false;                   // pt_set_probes: the next pt_trace starts a new accumulation
     pt::DevBuf d_probe_pos;                       // float[3] per probe (ProbeArgs::positions): probes.count of them while probes.enable != 0
     pt::DevBuf d_probe_dirs; uint32_t probe_dirs_n = 0;   // the texel-centre directions of a probe_dirs_n^2 map, built by the first pt_probe_project of a resolution
     pt::DevBuf d_probe_sh;                        // pt_probe_project's 27 floats per probe
     // ---- ID mattes (pt_set_matte): the config with the caller's layers, the caller's ids, and the device table of one id per table row
     pt_matte_config matte = {0, PT_MATTE_INSTANCE, 2, 0, {nullptr, nullptr, nullptr, nullptr}};
-    bool matte_restart = false;                   // pt_set_matte: the next pt_trace starts a new accumulation
     std::vector<uint32_t> matte_user_ids;         // fix(ids[i]) of pt_set_matte; rows beyond it get the ids of their default names
     pt::DevBuf d_matte_ids;                       // uint32 per row (MatteArgs::ids), made by pt_trace for ...
     int matte_table_kind = -1; size_t matte_table_rows = 0;   // ... this kind (-1: stale) and this many rows of the instance / material table
     // ---- motion vectors (pt_set_motion): the config with the caller's target, and the previous pose (pt_motion_snapshot)
     pt_motion_config motion = {};
-    bool motion_restart = false;                  // pt_set_motion: the next pt_trace starts a new accumulation
     pt::DevBuf d_motion_snap;                     // 3 float4 per triangle of the instance table, at InstanceRec::tri_offset + prim (MotionArgs::snap)
     bool motion_snap_taken = false;               // a snapshot exists; it stands for a table of ...
     std::vector<uint32_t> motion_snap_counts;     // ... these tri_count, row by row
@@ -180,6 +176,14 @@ inline ProbeArgs probe_args(const pt_ctx* ctx) {
     pa.div_n = FastDiv::make(pa.n); pa.max_distance = ctx->probes.max_distance;
     return pa;
 }
+
+// The optional passes of a call: which are on for these settings, the refusals -- no pass runs in the megakernel mode, a bake's instance,
+// the probes' atlas size, no motion vectors under a bake or probes -- and the blocks that are plain copies of the context (the AOV targets,
+// the probes).  The blocks that need the device are filled by the *_setup functions, each where its failure has its place among the call's
+// other refusals.  adaptive_setup: the tile state and half buffer for this size and shard, fresh if the call starts an accumulation;
+// frame_cap: where that ends.  (mipt_api.hip)
+int select_passes(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* ep, WavefrontPasses& passes);
+int adaptive_setup(pt_ctx* ctx, const pt_execute_params* ep, const FrameConstants& fc, int frame_cap, AdaptiveArgs& adaptive);
 
 // The mattes of a call (pt_set_matte): the device table of ids -- made now unless it stands for this kind and this many rows -- and what
 // k_wf_matte / k_wf_matte_resolve take.  (mipt_api.hip)

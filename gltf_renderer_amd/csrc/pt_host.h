@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "pt_types.h"
+#include "pt_workspace.h"
 
 namespace pt {
 
@@ -132,9 +133,6 @@ struct DebugQueues {
     float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
 };
 hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
-// aov: with the two AOV record arrays behind the rest; matte: with the matte record array behind those (whether or not they are used);
-// motion: with the motion record array behind those likewise
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov = false, bool matte = false, bool motion = false);
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
 struct AdaptiveTile {
@@ -196,20 +194,22 @@ struct MotionArgs {
     float mc[16], mp[16];     // world_to_clip of this call and of the previous frame
     float vc[16], vp[16];     // world_to_view likewise
 };
+// The optional passes of one wavefront trace: which are on, and the argument block of each that is (the block of a pass that is off is
+// not looked at).  PathtraceScene fills it (select_passes and the *_setup functions); launch_wavefront and wavefront_workspace_bytes read it.
+struct WavefrontPasses {
+    bool adaptive = false; AdaptiveArgs ad = {};   // off: every tile of the rank is rendered (the plain kernels); on: the adaptive generate / resolve run
+    bool aov = false; AovArgs av = {};             // off: the plain resolve, no k_wf_aov launch; on: the caller's targets (the workspace holds the records; so below)
+    bool bake = false; BakeArgs bk = {};           // off: camera rays (k_wf_generate); on: k_wf_generate_bake starts the paths on the atlas's texels, `lens` is not looked at
+    bool probes = false; ProbeArgs pa = {};        // off likewise; on: k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
+    bool matte = false; MatteArgs mt = {};         // off: no k_wf_matte / k_wf_matte_resolve launch; on: the id table and the caller's layers
+    bool motion = false; MotionArgs mo = {};       // off: no k_wf_motion / k_wf_motion_resolve launch; on: the cameras, the snapshot and the caller's target
+    WorkspaceRecords records() const { return {aov, matte, motion}; }     // the record arrays the workspace holds for them (pt_workspace.h)
+};
+// bytes of the workspace launch_wavefront needs for these frame constants, stage workgroups and passes (pt_workspace.h: the layout)
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, const WavefrontPasses& passes);
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
-// bake: nullptr = camera rays (k_wf_generate); else k_wf_generate_bake starts the paths on the atlas's texels and `lens` is not looked at
-// probes: nullptr likewise; else k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
-// adaptive: nullptr = every tile of the rank is rendered (the plain kernels); else the adaptive generate / resolve run
-// aov: nullptr = no AOVs (the plain resolve, no k_wf_aov launch); else the caller's targets (the record pointers are ignored) and a
-//      workspace of wavefront_workspace_bytes(fc, stage_blocks, true)
-// matte: nullptr = no mattes (no k_wf_matte / k_wf_matte_resolve launch); else the id table and the caller's layers (the record pointer is
-//      ignored) and a workspace of wavefront_workspace_bytes(fc, stage_blocks, aov, true)
-// motion: nullptr = no motion vectors (no k_wf_motion / k_wf_motion_resolve launch); else the cameras, the snapshot and the caller's target
-//      (the record pointer is ignored) and a workspace of wavefront_workspace_bytes(fc, stage_blocks, aov, matte, true)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive = nullptr,
-                            const AovArgs* aov = nullptr, const BakeArgs* bake = nullptr, const ProbeArgs* probes = nullptr,
-                            const MatteArgs* matte = nullptr, const MotionArgs* motion = nullptr);
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const WavefrontPasses& passes);
 // pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
 

@@ -24,6 +24,7 @@
 
 #include "pt_vertex.h"
 #include "pt_host.h"
+#include "pt_workspace.h"
 #include "pt_bake.h"
 #include "pt_probe.h"
 #include "pt_matte.h"
@@ -52,11 +53,9 @@ extern "C" int pt_debug_read_util(unsigned long long* out16, int reset) {
 #endif
 namespace pt {
 
-constexpr uint32_t kShards = 256;
+// (kShards, kXcds, kCounterStride and kCounterArrays: pt_workspace.h, with the layout they size)
 constexpr uint32_t kMissTri = 0x7fffffffu;
 constexpr uint32_t kNoHint = 0xffffffffu;
-constexpr uint32_t kCounterStride = 16;      // one 64-B line per shard counter
-constexpr int kCounterArrays = 7;
 
 struct WfBuffers {
     // per slot (one path per pixel of this rank)
@@ -139,8 +138,7 @@ PT_DEV ShardView shard_view(const WfBuffers& wf) {
 // stage launch has the same grid, and shard s = blockIdx % kShards is only ever touched by workgroups with blockIdx % 8 == s % 8:
 // a path lives its whole life on ONE XCD.  Tiles are dealt round-robin over all workgroups, so every XCD sees the whole screen: giving
 // each XCD a contiguous band of tiles was slower, because the XCD whose band holds the expensive part of the picture finishes last
-// while the others idle (profiles/EXPERIMENTS.md).
-constexpr uint32_t kXcds = 8;
+// while the others idle (profiles/EXPERIMENTS.md).  (kXcds: pt_workspace.h)
 // Adaptive sampling (pt_set_adaptive): is the tile of a workgroup-round's (tile, sample) pair still active?  `slot0` = the round's first
 // slot (workgroup-uniform), so the state is read once per round; a retired tile pushes no ray and every later stage is unchanged.
 PT_DEV bool adaptive_tile_active(const FrameConstants& fc, const AdaptiveArgs& ad, uint32_t slot0) {
@@ -944,76 +942,28 @@ __global__ __launch_bounds__(kBlock) void k_wf_motion_resolve(FrameConstants fc,
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static uint32_t blocks_per_shard_for(int stage_blocks) {
-    uint32_t b = (uint32_t)(stage_blocks > 0 ? stage_blocks : 1536) / kShards;
-    return b < 1 ? 1 : b;
-}
-// k_wf_generate: workgroup-rounds that cover the (tile, sample) pairs.  Counted per XCD -- an eighth of the tiles, rounded up, against an
-// eighth of the kShards * blocks_per_shard workgroups -- which is what sizes the queue segments and the workspace.
-static uint32_t gen_rounds_for(const FrameConstants& fc, uint32_t blocks_per_shard) {
-    const uint32_t per_xcd = kShards * blocks_per_shard / kXcds;
-    const uint32_t pairs = (fc.my_tiles + kXcds - 1) / kXcds * fc.spp;
-    return (pairs + per_xcd - 1) / per_xcd;
-}
-static uint32_t seg_cap_for(const FrameConstants& fc, uint32_t blocks_per_shard) {
-    // a generate round gives shard s one tile from each of its blocks_per_shard workgroups {s, s + kShards, ...}
-    return gen_rounds_for(fc, blocks_per_shard) * blocks_per_shard * kBlock;
+// The workspace's layout is pt_workspace.h's, for the call's tiles, samples, stage workgroups and record arrays.
+size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, const WavefrontPasses& passes) {
+    return workspace_layout(fc.my_tiles, fc.spp, stage_blocks, passes.records(), kBlock).total;
 }
 
-// entries of each path-state array: whole 256-slot chunks, the same number for every shard
-static uint32_t chunks_per_shard_for(size_t slots) { return (uint32_t)(((slots + kBlock - 1) / kBlock + kShards - 1) / kShards); }
-static size_t state_slots_for(size_t slots) { return (size_t)chunks_per_shard_for(slots) * kShards * kBlock; }
-
-// the AOV records (AovArgs::rec_albedo, rec_normal) lie behind everything carve() hands out: a workspace without them is laid out as ever
-static size_t aov_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, false) + 255) & ~(size_t)255; }
-// ... and the matte records (MatteArgs::rec) behind those, at the same place with AOVs on or off
-static size_t matte_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, true) + 255) & ~(size_t)255; }
-// ... and the motion records (MotionArgs::rec) behind those, likewise
-static size_t motion_records_offset(const FrameConstants& fc, int stage_blocks) { return (wavefront_workspace_bytes(fc, stage_blocks, true, true) + 255) & ~(size_t)255; }
-size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, bool aov, bool matte, bool motion) {
-    const uint32_t bps = blocks_per_shard_for(stage_blocks);
-    const size_t slots = state_slots_for((size_t)fc.my_tiles * kBlock * fc.spp);
-    if (motion) return motion_records_offset(fc, stage_blocks) + slots * 16;
-    if (matte) return matte_records_offset(fc, stage_blocks) + slots * 4;
-    if (aov) return aov_records_offset(fc, stage_blocks) + slots * (2 * 16);
-    const size_t q = (size_t)kShards * seg_cap_for(fc, bps);
-    return slots * (5 * 16) + q * (4 * 16 + 4 * 16 + 16 + 2 * 16 + 2 * 2 * 16) + kCounterArrays * kShards * kCounterStride * 4 + 52 * 256;
-}
-
-static WfBuffers carve(void* base, const FrameConstants& fc, int stage_blocks) {
-    const uint32_t slots = fc.my_tiles * kBlock * fc.spp;
-    const size_t state_slots = state_slots_for(slots);
+static WfBuffers carve(void* workspace, const WorkspaceLayout& l, uint32_t slots) {
+    auto at = [&](size_t offset) { return (float4*)((char*)workspace + offset); };
     WfBuffers wf;
-    wf.chunks_per_shard = chunks_per_shard_for(slots);
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-    wf.blocks_per_shard = blocks_per_shard_for(stage_blocks);
-    wf.seg_cap = seg_cap_for(fc, wf.blocks_per_shard);
-    wf.gen_region_tiles = 0;
-    wf.gen_rounds = gen_rounds_for(fc, wf.blocks_per_shard);
-    const size_t q = (size_t)kShards * wf.seg_cap;
-    for (int k = 0; k < kCounterArrays; k++) wf.cnt[k] = (uint32_t*)take((size_t)kShards * kCounterStride * 4);
-    wf.L = (float4*)take(state_slots * 16);
-    wf.beta_pdf = (float4*)take(state_slots * 16);
-    wf.thr_misc = (float4*)take(state_slots * 16);
-    wf.pend = (float4*)take(state_slots * 32);
-    for (int k = 0; k < 2; k++) { wf.ray_o[k] = (float4*)take(q * 16); wf.ray_d[k] = (float4*)take(q * 16); }
-    for (int k = 0; k < 2; k++) { wf.q_beta[k] = (float4*)take(q * 16); wf.q_thr[k] = (float4*)take(q * 16); }
-    wf.hit = (float4*)take(q * 16);
-    wf.env_a = (float4*)take(q * 16);
-    wf.env_b = (float4*)take(q * 16);
-    wf.sh_o = (float4*)take(q * 2 * 16);
-    wf.sh_d = (float4*)take(q * 2 * 16);
-    wf.sh_c = nullptr;
-    wf.occ_cache = nullptr;
-    wf.capacity = slots;
+    wf.chunks_per_shard = l.chunks_per_shard; wf.blocks_per_shard = l.blocks_per_shard; wf.seg_cap = l.seg_cap;
+    wf.gen_region_tiles = 0; wf.gen_rounds = l.gen_rounds;
+    for (int k = 0; k < kCounterArrays; k++) wf.cnt[k] = (uint32_t*)at(l.cnt[k]);
+    wf.L = at(l.L); wf.beta_pdf = at(l.beta_pdf); wf.thr_misc = at(l.thr_misc); wf.pend = at(l.pend);
+    for (int k = 0; k < 2; k++) { wf.ray_o[k] = at(l.ray_o[k]); wf.ray_d[k] = at(l.ray_d[k]); wf.q_beta[k] = at(l.q_beta[k]); wf.q_thr[k] = at(l.q_thr[k]); }
+    wf.hit = at(l.hit); wf.env_a = at(l.env_a); wf.env_b = at(l.env_b); wf.sh_o = at(l.sh_o); wf.sh_d = at(l.sh_d);
+    wf.sh_c = nullptr; wf.occ_cache = nullptr; wf.capacity = slots;
     return wf;
 }
 
 int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
-// ---- the traversal stages' ray flags, kernel copies and launches: ONE statement of each, used by launch_wavefront and by the test hook
+// ---- the traversal stages' ray flags, kernel copies and launches: ONE statement of each, called by launch_wavefront and by the test hook
 // debug_trace_queues below, so that the hook launches what a frame launches.
 // Ray flags and instance mask of the closest-hit rays of bounce b.
 static void traversal_ray_flags(uint32_t flags, int b, uint32_t& rf, uint32_t& rmask) {
@@ -1026,31 +976,24 @@ static void traversal_ray_flags(uint32_t flags, int b, uint32_t& rf, uint32_t& r
 }
 // the traversal kernels compiled for rays with no flags, if that is what the frame's settings give them
 static bool traversal_defaults(uint32_t flags) { return (flags & kTravFlagMask) == 0; }
+// A run-time bool as a compile-time one: f(std::true_type()) or f(std::false_type()), so that a launch line is written once for both
+// kernel copies.  pick2: two of them.
+template <class F> static void pick(bool a, F&& f) { if (a) f(std::true_type()); else f(std::false_type()); }
+template <class F> static void pick2(bool a, bool b, F&& f) { pick(a, [&](auto A) { pick(b, [&](auto B) { f(A, B); }); }); }
 static void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
                             uint32_t rmask, Counters* counters) {
-    const dim3 block(kBlock);
-    if (traversal_defaults(fc.flags)) { if (count) hipLaunchKernelGGL((k_wf_trace<true, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
-                                        else hipLaunchKernelGGL((k_wf_trace<false, true>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
-    else { if (count) hipLaunchKernelGGL((k_wf_trace<true, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters);
-           else hipLaunchKernelGGL((k_wf_trace<false, false>), grid, block, 0, stream, sc, fc, w, cur, b, rf, rmask, counters); }
+    pick2(count, traversal_defaults(fc.flags), [&](auto COUNT, auto DEFAULTS) { hipLaunchKernelGGL((k_wf_trace<COUNT.value, DEFAULTS.value>), grid, dim3(kBlock), 0, stream, sc, fc, w, cur, b, rf, rmask, counters); });
 }
 static void launch_wf_traverse(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int nxt, int b, uint32_t rf,
                                uint32_t rmask, Counters* counters) {
-    const dim3 block(kBlock);
-    const uint32_t flags = fc.flags;
-    if (traversal_defaults(flags)) { if (count) hipLaunchKernelGGL((k_wf_traverse<true, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
-                                     else hipLaunchKernelGGL((k_wf_traverse<false, true>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
-    else { if (count) hipLaunchKernelGGL((k_wf_traverse<true, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters);
-           else hipLaunchKernelGGL((k_wf_traverse<false, false>), grid, block, 0, stream, sc, fc, w, nxt, b, rf, rmask, flags, counters); }
+    pick2(count, traversal_defaults(fc.flags), [&](auto COUNT, auto DEFAULTS) { hipLaunchKernelGGL((k_wf_traverse<COUNT.value, DEFAULTS.value>), grid, dim3(kBlock), 0, stream, sc, fc, w, nxt, b, rf, rmask, fc.flags, counters); });
 }
 static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const WfBuffers& w, int b, uint32_t flags, float tmax, Counters* counters) {
-    if (count) hipLaunchKernelGGL(k_wf_shadow<true>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters);
-    else hipLaunchKernelGGL(k_wf_shadow<false>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters);
+    pick(count, [&](auto COUNT) { hipLaunchKernelGGL(k_wf_shadow<COUNT.value>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters); });
 }
 
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
-                            int stage_blocks, StageTimers* timers, hipStream_t stream, const AdaptiveArgs* adaptive, const AovArgs* aov, const BakeArgs* bake,
-                            const ProbeArgs* probes, const MatteArgs* matte, const MotionArgs* motion) {
+                            int stage_blocks, StageTimers* timers, hipStream_t stream, const WavefrontPasses& passes) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
     // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
@@ -1070,47 +1013,35 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         timers->used = k + 1;
     };
     const uint32_t slots = fc.my_tiles * kBlock * fc.spp;
-    WfBuffers wf = carve(workspace, fc, stage_blocks);
+    const WorkspaceLayout lay = workspace_layout(fc.my_tiles, fc.spp, stage_blocks, passes.records(), kBlock);
+    WfBuffers wf = carve(workspace, lay, slots);
     hipError_t e = hipMemsetAsync(wf.cnt[0], 0, (size_t)kCounterArrays * kShards * kCounterStride * 4, stream);     // the counter arrays are contiguous
     if (e) return e;
     const dim3 block(kBlock), full(fc.my_tiles), stage(kShards * wf.blocks_per_shard);
     if (timers) { hipEvent_t ev = event_at(0); if (ev) hipEventRecord(ev, stream); else timers = nullptr; }
-    AovArgs av = {};
-    if (aov) {
-        av = *aov;
-        av.rec_albedo = (float4*)((char*)workspace + aov_records_offset(fc, stage_blocks));
-        av.rec_normal = av.rec_albedo + state_slots_for(slots);
-    }
-    MatteArgs mt = {};
+    // the argument blocks as the kernels take them: zeros for a pass that is off, the record pointers from the layout
+    const bool adaptive = passes.adaptive, aov = passes.aov, matte = passes.matte, motion = passes.motion;
+    const AdaptiveArgs ad = adaptive ? passes.ad : AdaptiveArgs{};
+    AovArgs av = aov ? passes.av : AovArgs{};
+    MatteArgs mt = matte ? passes.mt : MatteArgs{};
+    MotionArgs mo = motion ? passes.mo : MotionArgs{};
+    if (aov) { av.rec_albedo = (float4*)((char*)workspace + lay.rec_albedo); av.rec_normal = (float4*)((char*)workspace + lay.rec_normal); }
     if (matte) {                                                        // the records start as misses: no generate kernel knows of them
-        mt = *matte;
-        mt.rec = (uint32_t*)((char*)workspace + matte_records_offset(fc, stage_blocks));
+        mt.rec = (uint32_t*)((char*)workspace + lay.rec_matte);
         if ((e = hipMemsetAsync(mt.rec, 0, (size_t)slots * 4, stream)) != hipSuccess) return e;
     }
-    MotionArgs mo = {};
     if (motion) {                                                       // likewise
-        mo = *motion;
-        mo.rec = (float4*)((char*)workspace + motion_records_offset(fc, stage_blocks));
+        mo.rec = (float4*)((char*)workspace + lay.rec_motion);
         if ((e = hipMemsetAsync(mo.rec, 0, (size_t)slots * 16, stream)) != hipSuccess) return e;
     }
-    AdaptiveArgs ad = {};
-    if (adaptive) ad = *adaptive;
-    if (probes) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_probe<true>), stage, block, 0, stream, fc, wf, counters, ad, *probes, av);
-                  else hipLaunchKernelGGL((k_wf_generate_probe<false>), stage, block, 0, stream, fc, wf, counters, ad, *probes, av); }
-    else if (bake) { if (adaptive) hipLaunchKernelGGL((k_wf_generate_bake<true>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av);
-                else hipLaunchKernelGGL((k_wf_generate_bake<false>), stage, block, 0, stream, fc, wf, counters, ad, *bake, av); }
-    else if (adaptive) { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<true, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
-                    else hipLaunchKernelGGL((k_wf_generate<true, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }
-    else { if (lens.enable) hipLaunchKernelGGL((k_wf_generate<false, true>), stage, block, 0, stream, fc, wf, counters, ad, lens);
-           else hipLaunchKernelGGL((k_wf_generate<false, false>), stage, block, 0, stream, fc, wf, counters, ad, lens); }
+    pick(adaptive, [&](auto ADAPTIVE) {
+        if (passes.probes) hipLaunchKernelGGL((k_wf_generate_probe<ADAPTIVE.value>), stage, block, 0, stream, fc, wf, counters, ad, passes.pa, av);
+        else if (passes.bake) hipLaunchKernelGGL((k_wf_generate_bake<ADAPTIVE.value>), stage, block, 0, stream, fc, wf, counters, ad, passes.bk, av);
+        else pick(lens.enable != 0, [&](auto LENS) { hipLaunchKernelGGL((k_wf_generate<decltype(ADAPTIVE)::value, LENS.value>), stage, block, 0, stream, fc, wf, counters, ad, lens); });
+    });
     mark(STAGE_GENERATE);
     const uint32_t flags = fc.flags;
     const int iterations = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 1 : fc.max_bounces + 1;
-    // ray flags, kernel copies and launches of the traversal stages: the functions above, shared with the test hook debug_trace_queues
-    auto ray_flags = [&](int b, uint32_t& rf, uint32_t& rmask) { traversal_ray_flags(flags, b, rf, rmask); };
-    auto launch_trace = [&](dim3 grid, const WfBuffers& w, int cur, int b, uint32_t rf, uint32_t rmask) { launch_wf_trace(grid, stream, count, sc, fc, w, cur, b, rf, rmask, counters); };
-    auto launch_traverse = [&](dim3 grid, const WfBuffers& w, int nxt, int b, uint32_t rf, uint32_t rmask) { launch_wf_traverse(grid, stream, count, sc, fc, w, nxt, b, rf, rmask, counters); };
-    auto launch_shadow = [&](dim3 grid, const WfBuffers& w, int b) { launch_wf_shadow(grid, stream, count, sc, w, b, flags, fc.max_ray_length, counters); };
     // the shade kernel compiled for this frame's flags, if there is one (k_wf_shade)
     const uint32_t shade_bits = flags & kShadeFlagMask;
     const int shade_variant = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 0 : (shade_bits == kShadeDefaults ? 1 : (shade_bits == kShadeDefaultsNoLights ? 2 : 0));
@@ -1143,9 +1074,9 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     // generate -> trace(0) -> [shade(b) -> shadow(b) + trace(b + 1)] x (bounces) -> resolve: two grid-wide synchronisations per bounce
     {
         uint32_t rf, rmask;
-        ray_flags(0, rf, rmask);
+        traversal_ray_flags(flags, 0, rf, rmask);
         const dim3 g0 = cap(stage, env_trace_bps);
-        launch_trace(g0, wf_of(g0), 0, 0, rf, rmask);
+        launch_wf_trace(g0, stream, count, sc, fc, wf_of(g0), 0, 0, rf, rmask, counters);
         mark(STAGE_TRACE);
     }
     if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
@@ -1158,37 +1089,28 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         launch_shade(gs, ws, cur, b);
         mark(STAGE_SHADE);
         uint32_t rf, rmask;
-        ray_flags(b + 1, rf, rmask);
-        if (b + 1 < iterations) {
-            launch_traverse(gt, wt, cur ^ 1, b, rf, rmask);
-        } else {                                                                                      // the last vertex pushes no bounce ray
-            launch_shadow(gt, wt, b);
-        }
+        traversal_ray_flags(flags, b + 1, rf, rmask);
+        if (b + 1 < iterations) launch_wf_traverse(gt, stream, count, sc, fc, wt, cur ^ 1, b, rf, rmask, counters);
+        else launch_wf_shadow(gt, stream, count, sc, wt, b, flags, fc.max_ray_length, counters);         // the last vertex pushes no bounce ray
         mark(STAGE_SHADOW);
     }
     if (matte) {                                                        // before the resolve retires tiles: both see the call's `active` flags
-        auto launch_matte = [&](auto ranks) {
-            constexpr int R = decltype(ranks)::value;
-            if (adaptive) hipLaunchKernelGGL((k_wf_matte_resolve<R, true>), full, block, 0, stream, fc, ad, mt);
-            else hipLaunchKernelGGL((k_wf_matte_resolve<R, false>), full, block, 0, stream, fc, ad, mt);
-        };
-        switch (mt.ranks) {
-            case 2: launch_matte(std::integral_constant<int, 2>()); break;
-            case 4: launch_matte(std::integral_constant<int, 4>()); break;
-            case 6: launch_matte(std::integral_constant<int, 6>()); break;
-            default: launch_matte(std::integral_constant<int, 8>()); break;
-        }
+        pick(adaptive, [&](auto ADAPTIVE) {
+            auto launch_matte = [&](auto ranks) { hipLaunchKernelGGL((k_wf_matte_resolve<decltype(ranks)::value, decltype(ADAPTIVE)::value>), full, block, 0, stream, fc, ad, mt); };
+            switch (mt.ranks) {
+                case 2: launch_matte(std::integral_constant<int, 2>()); break;
+                case 4: launch_matte(std::integral_constant<int, 4>()); break;
+                case 6: launch_matte(std::integral_constant<int, 6>()); break;
+                default: launch_matte(std::integral_constant<int, 8>()); break;
+            }
+        });
         mark(STAGE_RESOLVE);
     }
     if (motion) {                                                       // likewise
-        if (adaptive) hipLaunchKernelGGL((k_wf_motion_resolve<true>), full, block, 0, stream, fc, wf, ad, mo);
-        else hipLaunchKernelGGL((k_wf_motion_resolve<false>), full, block, 0, stream, fc, wf, ad, mo);
+        pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_motion_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, ad, mo); });
         mark(STAGE_RESOLVE);
     }
-    if (aov) { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, true>), full, block, 0, stream, fc, wf, output, ad, av);
-               else hipLaunchKernelGGL((k_wf_resolve<false, true>), full, block, 0, stream, fc, wf, output, ad, av); }
-    else { if (adaptive) hipLaunchKernelGGL((k_wf_resolve<true, false>), full, block, 0, stream, fc, wf, output, ad, av);
-           else hipLaunchKernelGGL((k_wf_resolve<false, false>), full, block, 0, stream, fc, wf, output, ad, av); }
+    pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av); });
     mark(STAGE_RESOLVE);
     return hipGetLastError();
 }
@@ -1215,7 +1137,7 @@ hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters
     wf.seg_cap = seg + 1u;                                                              // the guard entry (two for the shadow queue)
     wf.blocks_per_shard = q.blocks_per_shard;
     wf.capacity = q.n_shadow + 1u;                                                      // slots: one per shadow ray and a guard
-    const size_t qn = (size_t)kShards * wf.seg_cap, slots = state_slots_for(wf.capacity), cnt_words = (size_t)kCounterArrays * kShards * kCounterStride;
+    const size_t qn = (size_t)kShards * wf.seg_cap, slots = state_slots_for(wf.capacity, kBlock), cnt_words = (size_t)kCounterArrays * kShards * kCounterStride;
     // host images of the buffers
     std::vector<uint32_t> h_cnt(cnt_words, kDebugSentinel);
     std::vector<float4> h_ro(qn), h_rd(qn), h_so(qn * 2), h_sd(qn * 2);

@@ -391,3 +391,106 @@ def test_after_a_load_a_moved_camera_or_a_reset_starts_anew(data):
     b.trace(3, 4)
     assert b.frames() == 4 and np.array_equal(b.read()[0], uni[3])
     b.close()
+
+
+# ---- every setter that restarts the accumulation leaves one pending restart -------------------------------------------------------------------
+SW = SH = 16
+SPT = 2
+RESTART_MESSAGE = ("accum_save: pt_set_adaptive / pt_set_aov / pt_set_lens / pt_set_bake / pt_set_probes / pt_set_matte / pt_set_motion since the last trace: "
+                   "the next trace starts anew")
+
+
+class Small:
+    """A 16 x 16 context of the scene without a map, with one feature configured; set() calls that feature's setter again: the current config
+    for adaptive, AOV, lens, matte and motion, the disabled one for bake and probes."""
+
+    def __init__(self, s, feature):
+        from gltf_renderer_amd.renderer import Renderer
+        self.s, self.r, self.feature = s, Renderer(0), feature
+        s.upload(self.r)
+        self.st = copy_settings(s.settings)
+        self.r.set_samples_per_trace(SPT)
+        self.out = self.r.create_output(SW, SH)
+        self.extra = [self.r.create_output(SW, SH) for _ in range(2)]
+        self.set()
+
+    def set(self):
+        r, p = self.r, self.s.execute_params(0)
+        {"adaptive": lambda: r.set_adaptive(2, 64, 0.0),
+         "aov": lambda: r.set_aov(*self.extra),
+         "lens": lambda: r.set_lens(0.05, 3.0),
+         "bake": lambda: r.set_bake(1e-3, enable=False),
+         "probes": lambda: r.set_probes(None, 0, enable=False),
+         "matte": lambda: r.set_matte(abi.MATTE_INSTANCE, self.extra[:1]),
+         "motion": lambda: r.set_motion(self.extra[0], list(p.world_to_view), list(p.view_to_clip))}[self.feature]()
+
+    def trace(self, frame, **change):
+        p = self.s.execute_params(frame)
+        for k, v in change.items():
+            if k == "world_to_view":
+                p.world_to_view[:] = v
+            else:
+                setattr(p, k, v)
+        self.r.trace(self.st, p, self.out)
+
+    def save_rc(self, buf=None, capacity=0):
+        img = abi.PtAccumImages(self.out.data_ptr(), None, None)
+        need = C.c_size_t(0)
+        rc = self.r.L.pt_accum_save(self.r.h, C.byref(img), SW, SH, 0, 1, 0, buf, capacity, C.byref(need))
+        return rc, need.value, self.r.L.pt_last_error(self.r.h).decode()
+
+    def save(self):
+        rc, need, _ = self.save_rc()
+        assert rc == 0
+        buf = (C.c_ubyte * need)()
+        assert self.save_rc(buf, need)[0] == 0
+        return bytes(buf)
+
+    def load(self, blob):
+        img = abi.PtAccumImages(self.out.data_ptr(), None, None)
+        assert self.r.L.pt_accum_load(self.r.h, blob, len(blob), C.byref(img)) == 0, self.r.L.pt_last_error(self.r.h).decode()
+
+    def frames(self):
+        return self.r.stats().accumulated_frames
+
+    def close(self):
+        self.r.close()
+
+
+@pytest.mark.parametrize("feature", ["adaptive", "aov", "lens", "bake", "probes", "matte", "motion"])
+def test_every_setter_leaves_one_pending_restart(feature):
+    from gltf_renderer_amd.renderer import MiptError
+    s = scenes.test_scene(SW, 16, with_env=False)
+    a = Small(s, feature)
+    a.trace(0)
+    first = a.r.readback(a.out)
+    a.trace(SPT)
+    assert a.frames() == 2 * SPT and first[..., :3].std() > 0
+    blob = a.save()                                  # two calls accumulated, nothing pending: a save goes through
+    a.set()
+    rc, _, msg = a.save_rc()
+    assert rc == NOT_READY and msg == RESTART_MESSAGE, (rc, msg)
+    # a trace refused before the restart is consumed -- the camera is the first thing looked at -- leaves it pending
+    with pytest.raises(MiptError, match="singular camera"):
+        a.trace(2 * SPT, world_to_view=[0.0] * 16)
+    rc, _, msg = a.save_rc()
+    assert rc == NOT_READY and msg == RESTART_MESSAGE and a.frames() == 2 * SPT, (rc, msg)
+    # a trace refused for an environment handle that does not exist: the save is refused afterwards as well.  (That check sits behind the
+    # reset, so the restart has already taken effect -- nothing is accumulated any more -- rather than being lost.)
+    with pytest.raises(MiptError, match="environment map handle"):
+        a.trace(2 * SPT, environment_map=5)
+    assert a.save_rc()[0] == NOT_READY
+    # the next good trace is the first of a new accumulation, and can be saved
+    a.trace(0)
+    assert a.frames() == SPT
+    assert np.array_equal(a.r.readback(a.out).view(np.uint32), first.view(np.uint32))
+    assert a.save_rc()[0] == 0
+    a.close()
+    # in a second context a load after the setter clears the pending restart: the next trace continues from the blob's count
+    b = Small(s, feature)
+    b.set()
+    b.load(blob)
+    assert b.frames() == 2 * SPT and b.save_rc()[0] == 0
+    b.trace(2 * SPT)
+    assert b.frames() == 3 * SPT
+    b.close()

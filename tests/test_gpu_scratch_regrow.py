@@ -167,6 +167,49 @@ def test_accum_scratch_grows_and_a_loaded_accumulation_continues_alike(R):
     teardown(R, a)
 
 
+# (AOVs, mattes, motion vectors, adaptive sampling): each record array is in turn in front of and behind a gap the call does not use
+PASS_STEPS = [(False, False, False, False), (False, False, True, False), (True, True, True, False), (False, True, False, False),
+              (True, False, True, True), (False, False, False, False)]
+PASS_SIZES = [(16, 16, 1), (40, 24, 3)]                                         # the second: partial tiles and a batch
+
+
+def trace_passes(t, w, h, spp, aov, matte, motion, adaptive, frame):
+    """One call of context t (a Tracing) with exactly these passes on, into fresh targets.  Returns {name: image} of every target written."""
+    r, s = t.r, t.s
+    s.width, s.height = w, h
+    r.set_samples_per_trace(spp)
+    names = ["output"] + ["albedo", "normal_depth"] * aov + ["matte"] * matte + ["motion"] * motion
+    img = {n: r.create_output(w, h) for n in names}
+    r.set_aov(img.get("albedo"), img.get("normal_depth"))
+    r.set_matte(abi.MATTE_INSTANCE, [img["matte"]] if matte else None)
+    p = s.execute_params(frame)
+    prev = camera.cm(camera.orbit_world_to_view(centre=(0.0, 0.0, 1.75), radius=3.0, inclination=1.05))      # the camera has moved a little
+    r.set_motion(img.get("motion"), prev, list(p.view_to_clip)) if motion else r.set_motion(None)
+    r.set_adaptive(2, 16, 0.05, enable=adaptive)
+    r.trace(s.settings, p, img["output"])
+    return {n: r.readback(x) for n, x in img.items()}
+
+
+def test_record_arrays_keep_their_places_across_pass_combinations(R):
+    """The AOV, matte and motion records lie behind the workspace's other arrays at fixed places, whichever of them a call uses.  One
+    long-lived context goes through the combinations at two sizes; after every step each target written equals, bit for bit, that of a
+    fresh context which does only that step."""
+    s = trace_scene()
+    a = Tracing(R, s)
+    k = 0
+    for aov, matte, motion, adaptive in PASS_STEPS:
+        for w, h, spp in PASS_SIZES:
+            b = Tracing(R, s)
+            ga, gb = (trace_passes(t, w, h, spp, aov, matte, motion, adaptive, 100 * k) for t in (a, b))
+            assert sorted(ga) == sorted(gb) and len(ga) == 1 + 2 * aov + matte + motion
+            for name in ga:
+                same(ga[name], gb[name], (name, k, w, h, spp))
+                assert ga[name].astype(np.float64).std() > 0, (name, k)        # (an all-zero target must not pass as equal)
+            k += 1
+            b.close()
+    teardown(R, a)
+
+
 # ---- the deep traversal stack ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", [abi.MODE_WAVEFRONT, abi.MODE_MEGAKERNEL], ids=["wavefront", "megakernel"])
 def test_deep_stack_grows_with_the_launch(R, mode):
