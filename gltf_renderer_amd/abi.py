@@ -307,6 +307,16 @@ class PtMotionBlurConfig(C.Structure):
         return cls(0.5, 32.0, 16, 1, 0.05)
 
 
+class PtVarianceConfig(C.Structure):
+    """pt_variance_config: the variance AOV (pt_set_variance; an extension, absent upstream)."""
+    _fields_ = [("enable", C.c_int32), ("_pad", C.c_int32), ("variance", C.c_void_p)]
+
+
+class PtNoiseSummary(C.Structure):
+    """pt_noise_summary: what pt_noise_estimate says of a whole image."""
+    _fields_ = [("tiles", C.c_uint32), ("tiles_estimated", C.c_uint32), ("tiles_above", C.c_uint32), ("mean", C.c_float), ("max", C.c_float)]
+
+
 MOTION_SNAPSHOT_NONE, MOTION_SNAPSHOT_VALID, MOTION_SNAPSHOT_STALE = 0, 1, 2
 MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
 MATTE_MAX_RANKS = 8
@@ -358,5 +368,9 @@ assert [getattr(PtMotionConfig, f).offset for f, _ in PtMotionConfig._fields_] =
 assert C.sizeof(PtReprojectConfig) == 12
 assert C.sizeof(PtMotionBlurConfig) == 20
 assert [getattr(PtMotionBlurConfig, f).offset for f, _ in PtMotionBlurConfig._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtVarianceConfig) == 16
+assert [getattr(PtVarianceConfig, f).offset for f, _ in PtVarianceConfig._fields_] == [0, 4, 8]
+assert C.sizeof(PtNoiseSummary) == 20
+assert [getattr(PtNoiseSummary, f).offset for f, _ in PtNoiseSummary._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

@@ -485,7 +485,11 @@ int select_passes(pt_ctx* ctx, const pt_settings* settings, const pt_execute_par
     p.motion = ctx->motion.enable != 0 && plain;
     if (p.motion && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors are written in the wavefront mode only");
     if (p.motion && (p.bake || p.probes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion vectors describe camera rays: not under a bake or probes");
+    // The variance AOV (pt_set_variance) likewise; it follows the output, so it works under a bake or probes as for any image.
+    p.variance = ctx->variance.enable != 0 && plain;
+    if (p.variance && megakernel) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "the variance is written in the wavefront mode only");
     if (p.aov) p.av = {nullptr, nullptr, (float4*)ctx->aov.albedo, (float4*)ctx->aov.normal_depth};
+    if (p.variance) p.va = {(float4*)ctx->variance.variance};
     if (p.probes) p.pa = probe_args(ctx);
     return PT_OK;
 }
@@ -1040,6 +1044,15 @@ int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config) {
     if (!ctx || !config) return PT_ERR_INVALID_ARGUMENT;
     if (config->enable && !config->albedo && !config->normal_depth) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "aov: enabled without a target");
     ctx->aov = *config;
+    ctx->restart_pending = true;
+    return PT_OK;
+}
+
+int pt_set_variance(pt_ctx* ctx, const pt_variance_config* config) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: config is NULL");
+    if (config->enable && !config->variance) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: the target is NULL");
+    ctx->variance = *config;
     ctx->restart_pending = true;
     return PT_OK;
 }

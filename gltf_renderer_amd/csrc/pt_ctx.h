@@ -80,7 +80,7 @@ struct pt_ctx {
     bool have_trace = false, have_accel = false, have_skin = false;
     int bounce_limit = PT_REFERENCE_MAX_BOUNCES;
     int samples_per_trace = 1;
-    // pt_set_adaptive / _aov / _lens / _bake / _probes / _matte / _motion since the last trace: the next pt_trace that gets as far as its
+    // pt_set_adaptive / _aov / _lens / _bake / _probes / _matte / _motion / _variance since the last trace: the next pt_trace that gets as far as its
     // reset starts a new accumulation (PathtraceScene consumes it; pt_accum_save refuses while it stands; pt_accum_load clears it)
     bool restart_pending = false;
     bool cull_null_shadow = false;
@@ -121,6 +121,9 @@ struct pt_ctx {
     pt::DevBuf d_motion_snap;                     // 3 float4 per triangle of the instance table, at InstanceRec::tri_offset + prim (MotionArgs::snap)
     bool motion_snap_taken = false;               // a snapshot exists; it stands for a table of ...
     std::vector<uint32_t> motion_snap_counts;     // ... these tri_count, row by row
+    // ---- the variance AOV (pt_set_variance): the config with the caller's target; pt_noise_estimate's per-tile counts and (mean, max) pairs
+    pt_variance_config variance = {0, 0, nullptr};
+    pt::DevBuf d_noise;                           // one uint32 and one float2 per tile, for one tile count
     // ---- pt_motion_blur: the per-pixel streak image V, then the tile maxima T and their neighbourhood maxima N, for one image size
     pt::DevBuf d_blur;
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
@@ -179,7 +182,7 @@ inline ProbeArgs probe_args(const pt_ctx* ctx) {
 
 // The optional passes of a call: which are on for these settings, the refusals -- no pass runs in the megakernel mode, a bake's instance,
 // the probes' atlas size, no motion vectors under a bake or probes -- and the blocks that are plain copies of the context (the AOV targets,
-// the probes).  The blocks that need the device are filled by the *_setup functions, each where its failure has its place among the call's
+// the probes, the variance target).  The blocks that need the device are filled by the *_setup functions, each where its failure has its place among the call's
 // other refusals.  adaptive_setup: the tile state and half buffer for this size and shard, fresh if the call starts an accumulation;
 // frame_cap: where that ends.  (mipt_api.hip)
 int select_passes(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* ep, WavefrontPasses& passes);

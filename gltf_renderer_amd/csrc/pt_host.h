@@ -194,6 +194,11 @@ struct MotionArgs {
     float mc[16], mp[16];     // world_to_clip of this call and of the previous frame
     float vc[16], vp[16];     // world_to_view likewise
 };
+// The variance AOV (pt_set_variance): what k_wf_variance_resolve takes as its own argument.  The pass has no record array: at resolve time
+// every sample's radiance is still in the workspace (wf.L and the pending records), and the output still holds the means before the batch.
+struct VarianceArgs {
+    float4* target;           // the caller's target, res_x * res_y: (population variance of r, g, b; of the channel sum)
+};
 // The optional passes of one wavefront trace: which are on, and the argument block of each that is (the block of a pass that is off is
 // not looked at).  PathtraceScene fills it (select_passes and the *_setup functions); launch_wavefront and wavefront_workspace_bytes read it.
 struct WavefrontPasses {
@@ -203,6 +208,7 @@ struct WavefrontPasses {
     bool probes = false; ProbeArgs pa = {};        // off likewise; on: k_wf_generate_probe starts the paths at the probes' positions (never together with `bake`)
     bool matte = false; MatteArgs mt = {};         // off: no k_wf_matte / k_wf_matte_resolve launch; on: the id table and the caller's layers
     bool motion = false; MotionArgs mo = {};       // off: no k_wf_motion / k_wf_motion_resolve launch; on: the cameras, the snapshot and the caller's target
+    bool variance = false; VarianceArgs va = {};   // off: no k_wf_variance_resolve launch; on: the caller's target (no record array: records() below does not know it)
     WorkspaceRecords records() const { return {aov, matte, motion}; }     // the record arrays the workspace holds for them (pt_workspace.h)
 };
 // bytes of the workspace launch_wavefront needs for these frame constants, stage workgroups and passes (pt_workspace.h: the layout)
@@ -251,6 +257,11 @@ struct BlurArgs {
     int reach;                    // (int)ceilf(max_radius / 16.0f): 1..4
 };
 hipError_t launch_motion_blur(const BlurArgs& a, hipStream_t stream);
+
+// ---- variance.hip: pt_noise_estimate's per-tile reduction ---------------------------------------------------------------------------
+// out[t] = (mean, max) of the per-pixel relative standard error over the in-image pixels of tile t (row-major 16 x 16 tiles), (-1, -1) for
+// a tile whose count is below 2.  counts: one uint32 per tile on the device, nullptr = `samples` everywhere.  Asynchronous.
+void launch_noise_tiles(const float4* image, const float4* variance, uint32_t w, uint32_t h, const uint32_t* counts, uint32_t samples, float2* out, hipStream_t stream);
 
 // ---- probe.hip: pt_probe_project's reduction of an octahedral atlas to spherical harmonics --------------------------------------
 // dirs: n * n float4, the texel-centre directions of an n x n octahedral map (w unused), row-major.  Asynchronous.

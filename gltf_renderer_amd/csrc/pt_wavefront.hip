@@ -941,6 +941,45 @@ __global__ __launch_bounds__(kBlock) void k_wf_motion_resolve(FrameConstants fc,
     resolve_aov_target(fc, wf, ma.rec, ma.target, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
 }
 
+// The variance AOV (pt_set_variance): the per-pixel population variance of the samples the output blends, a kernel of its own launched
+// right before k_wf_resolve on the resolve's grid.  At that point the output still holds the means before the batch, every sample's radiance
+// is still in the workspace, and the tiles' `active` flags are those the call started with.  A thread keeps the mean m and the variance V in
+// registers over the batch: the output is read once, the target read and written once.  Each sample comes through apply_pending and
+// sanitize_sample, the resolve's own functions, and m advances by blend_sample, the output's own blend -- so x and m' are the resolve's
+// values bit for bit, and nothing of m is written.  Welford's update in running-mean form (include/mipt.h states it operation by operation;
+// tests/variance_ref.py restates it).  A non-finite product is replaced by 0 (a select).  A tile retired by adaptive sampling is not written.
+PT_DEV float variance_finite_or_zero(float q) { return isfinite(q) ? q : 0.0f; }
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(kBlock) void k_wf_variance_resolve(FrameConstants fc, WfBuffers wf, const float4* __restrict__ output, AdaptiveArgs ad, VarianceArgs va) {
+    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
+    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t px, py;
+    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
+    const size_t at = (size_t)py * fc.res_x + px;
+    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
+    const int first = accumulate ? fc.accumulated_frames : 0;           // samples already in the pixel (a call that does not accumulate has one sample: zeros)
+    float4 m = make_float4(0, 0, 0, 0), V = m;
+    if (first > 0) { m = output[at]; V = va.target[at]; }
+    for (uint32_t k = 0; k < fc.spp; k++) {
+        const uint32_t slot = k * fc.pixel_slots + pslot;
+        const float4 Lq = wf.L[slot];
+        vec3 x = v3(Lq.x, Lq.y, Lq.z);
+        apply_pending(wf, slot, __float_as_uint(Lq.w), x);
+        x = sanitize_sample(fc, x);
+        const int n = first + (int)k;
+        if (n == 0) { V = make_float4(0, 0, 0, 0); m = make_float4(x.x, x.y, x.z, 1.0f); continue; }
+        const float b = fdiv(1.0f, (float)n + 1.0f);
+        const float4 mn = blend_sample(m, n, x);                        // m' = m + b * d0, the output's own blend
+        const vec3 d0 = v3(x.x - m.x, x.y - m.y, x.z - m.z), d1 = v3(x.x - mn.x, x.y - mn.y, x.z - mn.z);
+        const float qr = variance_finite_or_zero(d0.x * d1.x), qg = variance_finite_or_zero(d0.y * d1.y), qb = variance_finite_or_zero(d0.z * d1.z);
+        const float s0 = (d0.x + d0.y) + d0.z, s1 = (d1.x + d1.y) + d1.z;
+        const float qs = variance_finite_or_zero(s0 * s1);
+        V = make_float4(V.x + b * (qr - V.x), V.y + b * (qg - V.y), V.z + b * (qb - V.z), V.w + b * (qs - V.w));
+        m = mn;
+    }
+    va.target[at] = V;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // The workspace's layout is pt_workspace.h's, for the call's tiles, samples, stage workgroups and record arrays.
 size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, const WavefrontPasses& passes) {
@@ -1108,6 +1147,10 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     }
     if (motion) {                                                       // likewise
         pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_motion_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, ad, mo); });
+        mark(STAGE_RESOLVE);
+    }
+    if (passes.variance) {                                              // likewise, and before the resolve replaces the means the output holds
+        pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_variance_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, (const float4*)output, ad, passes.va); });
         mark(STAGE_RESOLVE);
     }
     pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av); });

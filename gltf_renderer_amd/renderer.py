@@ -43,7 +43,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # motion vectors and temporal reprojection (additive likewise)
            "pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject",
            # motion blur along the motion vectors (additive likewise)
-           "pt_motion_blur"]
+           "pt_motion_blur",
+           # the variance AOV and the noise report (additive likewise)
+           "pt_set_variance", "pt_noise_estimate"]
 
 
 class MiptError(RuntimeError):
@@ -138,6 +140,8 @@ def load_library():
     L.pt_set_motion.argtypes = [vp, vp]
     L.pt_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.pt_motion_blur.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
+    L.pt_set_variance.argtypes = [vp, vp]
+    L.pt_noise_estimate.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp, vp]
     _LIB = L
     return L
 
@@ -490,6 +494,40 @@ class Renderer:
         self._check(self.L.pt_motion_blur(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
                                           C.c_void_p(motion.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
         return out
+
+    def set_variance(self, variance):
+        """The variance AOV (include/mipt.h pt_set_variance): trace() keeps, beside the output, per pixel the population variance of the
+        samples (rgb per channel, w of the channel sum) in `variance`, a float32 CUDA tensor (H, W, 4) like the output, caller-owned.
+        The variance of the pixel's mean is variance / (n - 1).  variance=None turns the pass off.  The next trace() starts a new
+        accumulation.  Wavefront mode only.  The target is not part of an accum_save() blob: keep it and call set_variance() before
+        accum_load()."""
+        if variance is None:
+            self._check(self.L.pt_set_variance(self.h, C.byref(abi.PtVarianceConfig())))
+            self._variance = None
+            return
+        assert variance.is_cuda and variance.is_contiguous() and variance.dtype == self.torch.float32 and variance.dim() == 3 and variance.shape[2] == 4
+        self._check(self.L.pt_set_variance(self.h, C.byref(abi.PtVarianceConfig(1, 0, variance.data_ptr()))))
+        self._variance = variance                     # the library keeps the pointer: keep the tensor alive with the renderer
+
+    def noise_estimate(self, image, variance, samples=0, tile_samples=None, threshold=0.0):
+        """The noise report (include/mipt.h pt_noise_estimate): per 16x16 tile the mean and the max of the pixels' relative standard error,
+        from the output `image` and the target of set_variance(), both float32 CUDA tensors (H, W, 4).  samples: the count of every tile,
+        or tile_samples: (tiles_y, tiles_x) uint32 as adaptive_read() returns them (a tile below 2 reads -1 and is not estimated).
+        Returns (tile_mean, tile_max, summary): two (tiles_y, tiles_x) float32 arrays and an abi.PtNoiseSummary whose tiles_above counts
+        the tiles whose max exceeds `threshold`.  Synchronises the stream."""
+        for x in (image, variance):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == self.torch.float32 and x.dim() == 3 and x.shape == image.shape and x.shape[2] == 4
+        h, w = image.shape[:2]
+        ty, tx = (h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE
+        ts = None
+        if tile_samples is not None:
+            ts = np.ascontiguousarray(tile_samples, np.uint32)
+            assert ts.size == ty * tx
+        mean, mx = np.zeros((ty, tx), np.float32), np.zeros((ty, tx), np.float32)
+        summary = abi.PtNoiseSummary()
+        self._check(self.L.pt_noise_estimate(self.h, C.c_void_p(image.data_ptr()), C.c_void_p(variance.data_ptr()), w, h, _p(ts) if ts is not None else None,
+                                             int(samples), float(threshold), _p(mean), _p(mx), C.byref(summary)))
+        return mean, mx, summary
 
     def matte_extract(self, layers, ids, out=None):
         """pt_matte_extract: the anti-aliased mask (H, W) float32 CUDA tensor of a set of 1..64 ids over matte layers (of set_matte(), or

@@ -931,6 +931,74 @@ typedef struct pt_motion_blur_config {
 } pt_motion_blur_config;     /* 20 bytes */
 int pt_motion_blur(pt_ctx* ctx, const pt_motion_blur_config* config /* NULL = defaults */,
                    const void* color, const void* motion, uint32_t width, uint32_t height, void* out);
+/* The variance AOV (absent upstream): how noisy the accumulated image is, per pixel.  With a variance config enabled, pt_trace keeps, beside
+ * the output, a W*H float4 target V: V.rgb is the population variance, per channel, of the samples in the pixel, V.w the population variance
+ * of their channel sum (r + g) + b -- the quantity adaptive sampling's error is normalised by, so V.w carries the channels' covariance.  The
+ * sample variance is V * n / (n - 1); the variance of the pixel's mean, which is what "noise" means, is V / (n - 1), n the pixel's count.
+ * Everything below is float32 in the order written, products and sums not fused; fdiv is the correctly rounded division.
+ *   For one pixel, x is a sample's radiance as the output blends it: after the pending environment and light records are added and after
+ * the NaN / Inf paint and the luminance clamp under the call's flags.  n is the number of samples already in the pixel -- the output's
+ * count: accumulated_frames plus the sample's index in the batch, or the tile's own count under adaptive sampling.  m is the output
+ * pixel's rgb before this sample.
+ *     n == 0:  V = (0, 0, 0, 0);  m' = x
+ *     n  > 0:  b  = fdiv(1.0f, (float)n + 1.0f)
+ *              d0 = x - m                      per channel
+ *              m' = m + b * d0                 the output's own blend, recomputed, not written
+ *              d1 = x - m'
+ *              q  = d0 * d1                    per channel; a non-finite q is replaced by 0.0f (a select)
+ *              V.rgb = V.rgb + b * (q - V.rgb)
+ *              s0 = (d0.r + d0.g) + d0.b;  s1 = (d1.r + d1.g) + d1.b;  qs = s0 * s1   (non-finite -> 0.0f)
+ *              V.w   = V.w + b * (qs - V.w)
+ * This is Welford's update in running-mean form.  What follows from it: constant samples give exactly 0; a pixel with one sample holds
+ * zeros; in a CPU restatement against float64 no entry was negative and the largest relative error was 6.5e-5 at n = 2 and at most 2.7e-6
+ * for n = 3 .. 1024 (DESIGN.md section 4 has the table).
+ *   The target follows the output's counts and resets (the AOVs' rules): a batch of S samples equals S calls one by one, bit for bit; a call
+ * without FLAG_ACCUMULATE leaves zeros (a single sample has no variance); a tile shard writes only the rank's tiles; a tile retired by
+ * adaptive sampling is not written and then equals the uniform target after that tile's own count; a call with a debug output, or one past
+ * max_accumulated_frames, leaves the target untouched; under pt_set_bake and pt_set_probes it works as for any W x H image.  The output,
+ * the AOV targets, the matte layers, the motion target, every ray count and accumulated_frames are bit for bit what they are without the
+ * pass.  Wavefront mode only: a call with the pass on in PT_MODE_MEGAKERNEL fails with PT_ERR_INVALID_ARGUMENT and writes nothing.
+ *   The target is caller-owned and, together with the count, the whole state: it is not part of the blob of pt_accum_save, whose format is
+ * unchanged.  A caller who resumes keeps or restores the target and calls pt_set_variance before pt_accum_load.  pt_tiles_pack,
+ * pt_tiles_unpack and pt_exchange_frame (both modes) take the target as any float4 image. */
+typedef struct pt_variance_config {
+    int32_t enable;                 /* 0 = off (default) */
+    int32_t _pad;
+    void*   variance;               /* device, W*H float4, caller-owned like pt_execute_params.output */
+} pt_variance_config;               /* 16 bytes */
+/* PT_ERR_INVALID_ARGUMENT for a NULL config and, when enabled, a NULL target; after a refusal the old config stays and no restart is
+ * pending.  A good config forces a new accumulation on the next pt_trace, as pt_set_aov does: until that trace pt_accum_save answers
+ * PT_ERR_NOT_READY, and pt_accum_load clears the pending restart. */
+int pt_set_variance(pt_ctx* ctx, const pt_variance_config* config);
+/* The noise report: the relative standard error of an accumulated image, tile by tile.  A pure function of two images and the tiles'
+ * counts, like pt_probe_project: it reads no pt_trace state, and it synchronises the stream.  image: the output, W*H float4; variance: the
+ * target above (or any image of that layout), both device pointers.  Tiles are PT_TILE x PT_TILE on a ceil(W/16) x ceil(H/16) grid,
+ * numbered row-major.  Tile t has the count n = tile_samples[t] (a host array of global tile ids, as pt_adaptive_read returns it), or
+ * `samples` everywhere if tile_samples is NULL.  For pixel p of a tile with n >= 2, I = image[p], V = variance[p]:
+ *     s = (I.r + I.g) + I.b
+ *     e = sqrtf(V.w / (float)(n - 1)) / (1e-4f + sqrtf(fmaxf(s, 0.0f)))          a NaN counts as +infinity
+ * float32 in the order written, / the correctly rounded division, sqrtf the correctly rounded square root, fmaxf(NaN, 0) = 0.  It is the
+ * standard error of the pixel's mean under adaptive sampling's own normalisation: `threshold` here and pt_adaptive_config.threshold speak
+ * of the same quantity.
+ *   tile_max[t] is the max of e over the tile's in-image pixels (order-free, hence exact); tile_mean[t] is their float32 sum divided by
+ * their count (the order of the sum is not defined: within 256 * 2^-24 relative of any other order).  A tile with n < 2 gets -1 in both
+ * arrays and is not estimated -- this is how a sharded caller passes pt_adaptive_read's zeros for the other ranks' tiles.
+ *   The summary is computed on the host in double from the float32 tile values, each field rounded once; mean weights a tile's mean by its
+ * in-image pixel count.  With no tile estimated, mean = max = -1.
+ *   The per-tile scratch belongs to the context, is regrown on a change of size and freed by pt_destroy.  PT_ERR_INVALID_ARGUMENT with
+ * nothing written for a NULL ctx (answered before any device call), a NULL image or variance, a zero size or one above 2^30 (or more than
+ * 2^31 - 1 tiles), a non-finite or negative threshold, tile_samples == NULL with samples < 2. */
+typedef struct pt_noise_summary {
+    uint32_t tiles;                 /* ceil(W/16) * ceil(H/16) */
+    uint32_t tiles_estimated;       /* tiles with a count >= 2 */
+    uint32_t tiles_above;           /* estimated tiles whose max > threshold */
+    float    mean;                  /* pixel-weighted mean of the estimated tiles' means */
+    float    max;                   /* max of the estimated tiles' maxima */
+} pt_noise_summary;                 /* 20 bytes */
+int pt_noise_estimate(pt_ctx* ctx, const void* image, const void* variance, uint32_t width, uint32_t height,
+                      const uint32_t* tile_samples /* host, global tile ids; NULL = `samples` everywhere */, uint32_t samples, float threshold,
+                      float* tile_mean_host /* tiles floats, may be NULL */, float* tile_max_host /* likewise */,
+                      pt_noise_summary* summary /* may be NULL */);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

@@ -70,6 +70,13 @@ or with --prev-time T on a single frame (--motion-out is then optional).  A reco
   python tools/render_gltf.py figure.glb --animation 0 --sequence 0:2:24 --temporal --motion-blur 0.5 --spp 16 --out shot.png
   python tools/render_gltf.py figure.glb --animation 0 --prev-time 0.46 --time 0.5 --motion-blur 0.5 --spp 64 --out frame.png
 
+--variance-out PREFIX: the variance pass (pt_set_variance), accumulated with the frame: PREFIX.exr (32-bit float RGBA; a name ending in .npy
+gives an array) holds the variance of each pixel's mean, V / (n - 1): rgb per channel, a of the channel sum.  --noise-target X keeps tracing
+batches of --batch samples until no tile's relative standard error (pt_noise_estimate, adaptive sampling's own normalisation) exceeds X, or
+--spp is reached.  Either option prints the noise summary.  Composes with --adaptive (the tiles' own counts), --aov, --denoise, --bake,
+--probes and --matte; the target is not part of a checkpoint, so not with --checkpoint / --resume, and not with --sequence.
+  python tools/render_gltf.py scene.glb --spp 1024 --noise-target 0.02 --variance-out noise --out frame.png
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -208,6 +215,8 @@ def main():
     ap.add_argument("--matte-out", default="", metavar="PREFIX", help="with --matte: PREFIX_00.exr ... (one per layer) and the manifest PREFIX.json")
     ap.add_argument("--motion-out", default="", metavar="FILE", help="write the motion-vector pass (.exr: 32-bit float RGBA; .npy); needs --prev-time")
     ap.add_argument("--prev-time", type=float, default=None, metavar="T", help="with --motion-out or --motion-blur: the animation time of the previous frame")
+    ap.add_argument("--variance-out", default="", metavar="PREFIX", help="write PREFIX.exr (32-bit float RGBA; PREFIX.npy if it ends in .npy): the variance of each pixel's mean")
+    ap.add_argument("--noise-target", type=float, default=None, metavar="X", help="stop tracing once no tile's relative standard error exceeds X (or at --spp)")
     ap.add_argument("--sequence", default=None, metavar="T0:T1:FPS", help="render numbered frames of --animation from T0 to T1")
     ap.add_argument("--temporal", action="store_true", help="with --sequence: pt_denoise, then pt_reproject onto the previous frame")
     ap.add_argument("--motion-blur", type=float, default=None, metavar="SHUTTER", help="blur the finished frame along its motion vectors; SHUTTER in (0, 2]; needs --sequence or --prev-time")
@@ -218,6 +227,10 @@ def main():
         ap.error("--motion-out FILE needs --prev-time T")
     if a.prev_time is not None and not (a.motion_out or a.motion_blur is not None):
         ap.error("--prev-time T goes with --motion-out FILE or --motion-blur SHUTTER")
+    if a.noise_target is not None and not (math.isfinite(a.noise_target) and a.noise_target >= 0.0):
+        ap.error("--noise-target takes a finite X >= 0")
+    if (a.variance_out or a.noise_target is not None) and (a.checkpoint or a.resume or a.sequence is not None):
+        ap.error("--variance-out and --noise-target go with none of --checkpoint, --resume, --sequence: the variance is not part of a checkpoint")
     if a.motion_blur is None and (a.blur_radius is not None or a.blur_taps is not None):
         ap.error("--blur-radius and --blur-taps need --motion-blur SHUTTER")
     if a.motion_blur is not None:
@@ -355,6 +368,10 @@ def main():
     if a.prev_time is not None or sequence_times is not None:            # the camera stands still: the previous matrices are this frame's
         motion = r.create_output(w, h)
         r.set_motion(motion, p.world_to_view[:], p.view_to_clip[:])
+    variance = None
+    if a.variance_out or a.noise_target is not None:
+        variance = r.create_output(w, h)
+        r.set_variance(variance)
     blur = None
     if a.motion_blur is not None:
         blur = abi.PtMotionBlurConfig.defaults()
@@ -424,12 +441,27 @@ def main():
         r.accum_load(blob, out, aov_albedo, aov_nd)
         first = int(info.next_frame)
         print("resumed %s: %d samples, continuing with frame %d" % (a.resume, info.accumulated_frames, first))
-    if a.adaptive is None:
+    noise = None                                                         # (tile_mean, tile_max, summary) of the last pt_noise_estimate
+    if a.adaptive is None and a.noise_target is not None:
+        # trace batches until no tile's error exceeds the target or the pixels hold --spp samples
+        traced, batch = 0, max(1, min(a.batch, 64))
+        while traced < a.spp:
+            r.set_samples_per_trace(min(batch, a.spp - traced))
+            p.frame = traced
+            r.trace(st, p, out)
+            traced += min(batch, a.spp - traced)
+            if traced >= 2:
+                noise = r.noise_estimate(out, variance, samples=traced, threshold=a.noise_target)
+                if noise[2].max <= a.noise_target:
+                    break
+        uniform_samples = next_frame = traced
+    elif a.adaptive is None:
         done = info.accumulated_frames if a.resume else 0
         for frame in range(first, first + a.spp - done):
             p.frame = frame
             r.trace(st, p, out)
         next_frame = first + a.spp - done
+        uniform_samples = a.spp
     else:
         # trace batches until no tile is active or every tile holds --spp samples
         frame, active = first, (r.adaptive_read(w, h)[0] if a.resume else 1)
@@ -439,6 +471,10 @@ def main():
             r.trace(st, p, out)
             frame += min(a.batch, 64)
             active = r.adaptive_read(w, h)[0]
+            if a.noise_target is not None:
+                noise = r.noise_estimate(out, variance, tile_samples=r.adaptive_read(w, h)[1], threshold=a.noise_target)
+                if noise[2].tiles_estimated and noise[2].max <= a.noise_target:
+                    break
         next_frame = frame
         _, samples, _, _ = r.adaptive_read(w, h)
         pix = np.zeros((samples.shape[0] * abi.TILE, samples.shape[1] * abi.TILE), np.int64)
@@ -451,6 +487,25 @@ def main():
             grey = np.repeat(np.repeat((255.0 * samples / a.spp).astype(np.uint8), abi.TILE, 0), abi.TILE, 1)[:h, :w]
             gltf.write_png(a.sample_map, np.dstack([grey, grey, grey, np.full_like(grey, 255)]), 3)
     torch.cuda.synchronize()
+    if variance is not None:
+        # the counts the target stands for: the tiles' own under adaptive sampling, else the samples traced
+        counts = r.adaptive_read(w, h)[1] if a.adaptive is not None else np.full(((h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE), uniform_samples, np.uint32)
+        if counts.max() >= 2:
+            tile_mean, tile_max, ns = r.noise_estimate(out, variance, tile_samples=counts, threshold=a.noise_target or 0.0)
+            print("noise: relative standard error mean %.4g, max %.4g over %d of %d tiles%s; samples %d..%d" % (ns.mean, ns.max, ns.tiles_estimated, ns.tiles,
+                  ("; %d tiles above the target %.4g" % (ns.tiles_above, a.noise_target)) if a.noise_target is not None else "", counts.min(), counts.max()))
+        else:
+            print("noise: a single sample has no variance")
+        if a.variance_out:
+            per_pixel = np.repeat(np.repeat(counts, abi.TILE, 0), abi.TILE, 1)[:h, :w].astype(np.float32)
+            with np.errstate(all="ignore"):
+                of_mean = np.where(per_pixel[..., None] >= 2, r.readback(variance) / (per_pixel[..., None] - 1.0), 0.0).astype(np.float32)
+            path = a.variance_out if a.variance_out.lower().endswith((".npy", ".exr")) else a.variance_out + ".exr"
+            if path.lower().endswith(".npy"):
+                np.save(path, of_mean)
+            else:
+                write_exr_rgba32f(path, of_mean)
+            print("variance of the mean (rgb per channel, a of the channel sum): %s" % path)
     if a.checkpoint:                                                     # before the denoiser: the state is the noisy accumulation
         blob = r.accum_save(w, h, out, aov_albedo, aov_nd, next_frame=next_frame)
         with open(a.checkpoint, "wb") as f:
