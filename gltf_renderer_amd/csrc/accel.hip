@@ -434,7 +434,7 @@ __device__ void collapse_one(const BvhNode* __restrict__ nodes2, uint32_t binary
             slot++;
         }
     }
-    // Children in decreasing surface area: occlusion rays (any hit ends them, so they skip the distance sort) take the child they enter
+    // Children in decreasing surface area (as built: a refit requantises the boxes and keeps the slots): occlusion rays (any hit ends them, so they skip the distance sort) take the child they enter
     // farthest along the ray, the lowest slot among equals, and push the others in slot order; alpha-shadow rays walk in slot order.  Closest-hit
     // rays sort by distance anyway.  A 4-element sorting network on static indices (dynamic indexing would put the arrays in scratch).
     {
@@ -1167,6 +1167,8 @@ __global__ __launch_bounds__(256) void k_refit_packets(const InstanceRec* __rest
 
 // 3. one lane per wide node: the children's boxes are range queries of the rebuilt segment tree over the ranges the collapse
 //    recorded; the node is requantised on its new grid.  Nodes whose ranges hold no changed triangle come out bit-identical.
+//    Every child stays in the slot the collapse gave it: the slots are in decreasing area in the pose of the last full BUILD, not
+//    in the refitted one (alpha-shadow rays multiply transmissions in slot order, so a refit that re-sorted would change them).
 __global__ __launch_bounds__(256) void k_refit_wide(const SegBox* __restrict__ T, uint32_t P, const WideRanges* __restrict__ ranges,
                                                     const uint32_t* __restrict__ wide_count, Bvh4Node* __restrict__ nodes) {
     const uint32_t wi = blockIdx.x * blockDim.x + threadIdx.x;

@@ -123,6 +123,30 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the acceleration structure itself, as the device built or refitted it, for tests/accel_ref.py to check
+// node by node.  Builds or refits what is pending (ensure_accel) and drains the stream.  info: n_tris, wide_nodes, root, stack_need, the
+// scratch's seg_leaves, the builder in force (PT_BUILDER_*), scratch.fallbacks, and 1 if the collapse's ranges (scratch.wide_ranges) are there
+// -- 0 once the scratch is released or too small for this tree: they are then not read.  Each non-null host array receives its copy: nodes
+// wide_nodes x 64 B (Bvh4Node), ranges wide_nodes x 32 B (WideRanges; untouched when absent), tris n_tris x 64 B (TriPacket), shade
+// n_tris x 128 B (ShadePacket); a first call with null arrays tells the sizes.  Leaves the accumulation and a pending restart as they are.
+extern "C" int pt_debug_accel_read(pt_ctx* ctx, uint32_t info[8], void* nodes, void* ranges, void* tris, void* shade) {
+    if (!ctx || !info) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const AccelScratch& s = ctx->scratch;
+    const size_t n = ctx->n_tris, w = ctx->wide_nodes;
+    const bool have_ranges = s.wide_ranges != nullptr && s.capacity >= n && w <= s.capacity;
+    info[0] = ctx->n_tris; info[1] = ctx->wide_nodes; info[2] = (uint32_t)ctx->root; info[3] = ctx->stack_need;
+    info[4] = (uint32_t)s.seg_leaves; info[5] = (uint32_t)s.builder; info[6] = s.fallbacks; info[7] = have_ranges ? 1u : 0u;
+    if (w > n) return ctx->fail(PT_ERR_DEVICE, "pt_debug_accel_read: " + std::to_string(w) + " wide nodes over " + std::to_string(n) + " triangles");   // the arrays hold n
+    if (nodes && w) HIPOK(hipMemcpy(nodes, ctx->d_nodes.ptr, w * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
+    if (ranges && w && have_ranges) HIPOK(hipMemcpy(ranges, s.wide_ranges, w * sizeof(WideRanges), hipMemcpyDeviceToHost));
+    if (tris && n) HIPOK(hipMemcpy(tris, ctx->d_tris.ptr, n * sizeof(TriPacket), hipMemcpyDeviceToHost));
+    if (shade && n) HIPOK(hipMemcpy(shade, ctx->d_shade.ptr, n * sizeof(ShadePacket), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // test hook (not part of include/mipt.h): the motion records (pt_set_motion) pt_trace would write for caller-supplied first rays under `settings`
 // (its cull flag), `params` (the current camera, the image size) and the context's motion config (the previous camera) and snapshot --
 // k_debug_intersect's closest hit, then k_wf_motion's own record function (motion.hip k_debug_motion).  rays: 8 floats each as
