@@ -391,5 +391,24 @@ PT_DEV void flush_counters(Counters* __restrict__ counters, uint32_t lane, unsig
         if (lane == 0 && v) atomicAdd(((unsigned long long*)counters) + slot, (unsigned long long)v);
     }
 }
+// The tallies of the generate and shade stages of the wavefront arrangement do not go to the Counters struct directly: every wave of a
+// launch runs dry at the same moment, and their atomics on the struct's one 64-byte line queue up behind each other while the launch waits
+// for them.  A wave adds its sums to 64-bit words of a line of its own shard instead (kTally* = the index of the word in that line, as
+// unsigned long long; word 0 of the line is the shard counter's), and the resolve stage folds the shards' words into Counters once a
+// trace (pt_wavefront.hip, fold_shard_tallies).  64-bit words: a shard's tallies of one trace are not bounded by 2^32.
+constexpr int kTallyPrimary = 1, kTallyBounce = 2, kTallyShadow = 3, kTallyHits = 4, kTallyTaps = 5, kTallies = 5;
+PT_DEV void flush_shard_tallies(unsigned long long* __restrict__ line, uint32_t lane, unsigned n_primary, unsigned n_bounce, unsigned n_shadow, unsigned n_hits, unsigned taps) {
+#ifdef PT_PROBE_NO_FLUSH      // PROBE ONLY: the generate and shade stages count nothing -- wrong pt_stats, what the waves' closing atomics cost
+    return;
+#endif
+    unsigned vals[kTallies] = {n_primary, n_bounce, n_shadow, n_hits, taps};
+#pragma unroll
+    for (int k = 0; k < kTallies; k++) {
+        unsigned v = vals[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0 && v) atomicAdd(line + kTallyPrimary + k, (unsigned long long)v);
+    }
+}
 
 }  // namespace pt

@@ -80,7 +80,8 @@ struct WfBuffers {
     uint32_t* cnt[7];     // per shard (stride kCounterStride): entry counts of closest queue 0, closest queue 1, shadow queue (even bounces);
                           // [3], [4]: dynamic-fetch heads of the closest / shadow trace stages; [5]: shadow-queue count of odd bounces
                           // (the shadow count ping-pongs so that the fused traversal stage can zero the one the NEXT shade stage fills
-                          // while it still reads the current one); [6]: dynamic-fetch head of the shade stage
+                          // while it still reads the current one); [6]: dynamic-fetch head of the shade stage.  Only word 0 of a shard's
+                          // line is the counter; words 2 .. 11 of the [3] line hold the generate and shade stages' ray tallies (shard_tallies)
     uint32_t capacity;    // slots
     uint32_t chunks_per_shard;   // path-state arrays: 256-slot chunks per shard (unused by the kernels)
     uint32_t seg_cap;     // entries per closest-queue segment
@@ -133,6 +134,31 @@ PT_DEV ShardView shard_view(const WfBuffers& wf) {
     v.stride = wf.blocks_per_shard * kBlock;
     return v;
 }
+// Where the generate and shade stages count (flush_shard_tallies, pt_vertex.h): the spare words of the shard's line of cnt[3], the closest
+// trace stage's fetch head.  That line is quiet while either stage runs -- nothing fetches from it, the shade stage's member 0 only stores
+// word 0 -- so a launch puts ~32 atomics on each of 256 lines where it used to put ~8 000 on the one line of Counters.  launch_wavefront's
+// memset clears the words with the counters; k_wf_resolve, the last launch of every trace, folds them into Counters.  (The generate and
+// shade kernels keep their `counters` argument, now unread: the kernel-argument layout stays what it was.)
+static_assert((kTallyPrimary + kTallies) * 8 <= (int)kCounterStride * 4, "the tallies must fit the shard counter's line behind its word 0");
+PT_DEV unsigned long long* shard_tallies(const WfBuffers& wf, uint32_t shard) { return (unsigned long long*)(wf.cnt[3] + shard * kCounterStride); }
+// One wave of the resolve's workgroup 0: four shards a lane, a wave64 sum, one atomic per field.  (Atomic because the counting copies of
+// the traversal kernels and the megakernel book into the same struct.)
+PT_DEV void fold_shard_tallies(const WfBuffers& wf, Counters* __restrict__ counters) {
+    if (blockIdx.x != 0 || threadIdx.x >= 64u) return;
+    unsigned long long v[kTallies] = {0, 0, 0, 0, 0};
+    for (uint32_t s = threadIdx.x; s < kShards; s += 64u) {
+        const unsigned long long* t = shard_tallies(wf, s);
+#pragma unroll
+        for (int k = 0; k < kTallies; k++) v[k] += t[kTallyPrimary + k];
+    }
+    unsigned long long* c[kTallies] = {&counters->rays_primary, &counters->rays_bounce, &counters->rays_shadow, &counters->hits, &counters->taps};
+#pragma unroll
+    for (int k = 0; k < kTallies; k++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+        if (threadIdx.x == 0 && v[k]) atomicAdd(c[k], v[k]);
+    }
+}
 
 // Which pixel tiles a workgroup generates.  Workgroups are dispatched to the eight XCDs round-robin (XCD = blockIdx % 8), every later
 // stage launch has the same grid, and shard s = blockIdx % kShards is only ever touched by workgroups with blockIdx % 8 == s % 8:
@@ -180,8 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
             n_primary++;
         }
     }
-    LaneStats st = {0, 0, 0, 0};
-    flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
 }
 
 // Texture-space baking (pt_set_bake): the generate stage of an image whose "camera" is a surface.  Slots, tiles, shards and the queue are
@@ -217,8 +242,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate_bake(FrameConstants fc, 
             if (av.normal_depth) QST(av.rec_normal[slot], zero);
         }
     }
-    LaneStats st = {0, 0, 0, 0};
-    flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
 }
 // Test hook (pt_debug_bake_rays, mipt_debug.hip): bake_ray itself, one query {px, py, seed} per lane
 __global__ __launch_bounds__(kBlock) void k_debug_bake_rays(FrameConstants fc, BakeArgs bk, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
@@ -269,8 +293,7 @@ __global__ __launch_bounds__(kBlock, 7) void k_wf_generate_probe(FrameConstants 
             if (av.normal_depth) QST(av.rec_normal[slot], zero);
         }
     }
-    LaneStats st = {0, 0, 0, 0};
-    flush_counters(counters, threadIdx.x & 63, n_primary, 0, 0, 0, st);
+    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
 }
 // Test hook (pt_debug_probe_rays, mipt_debug.hip): probe_ray itself, one query {px, py, seed} per lane (the cells differ from lane to lane)
 __global__ __launch_bounds__(kBlock) void k_debug_probe_rays(FrameConstants fc, ProbeArgs pa, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
@@ -646,19 +669,44 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
 #endif
         }
         // ---- compaction into this shard's shadow segment and next closest-ray segment (wave-uniform control flow)
-        const uint32_t ie = queue_push(cnt_shadow, push_env);
+        // ONE reservation per wave-iteration: the env and light shadow rays share a counter (env entries first, then light entries: the
+        // order three queue_push calls gave a wave), the bounce rays' counter is independent of it, so lane 0 adds to the one and lane 1 to
+        // the other in the same atomic instruction and both bases return behind one wait -- where three queue_push calls made three dependent
+        // round trips, each also waiting for the previous push's stores.  Every queue store is issued after that wait.  A lane with nothing
+        // to add, or a wave with nothing to push, issues no atomic.
+        const unsigned long long m_env = __ballot(push_env), m_light = __ballot(push_light), m_bounce = __ballot(push_bounce);
+        const uint32_t c_env = (uint32_t)__popcll(m_env), c_shadow = c_env + (uint32_t)__popcll(m_light), c_bounce = (uint32_t)__popcll(m_bounce);
+#ifdef PT_PROBE_ONE_WAIT      // PROBE ONLY (step 0 of the single reservation): queue_push's three atomics, issued back to back before anything waits for one
+        uint32_t r_env = 0, r_light = 0, r_bounce = 0;
+        if (m_env && (int)lane64 == __ffsll((long long)m_env) - 1) r_env = atomicAdd(cnt_shadow, c_env);
+        if (m_light && (int)lane64 == __ffsll((long long)m_light) - 1) r_light = atomicAdd(cnt_shadow, c_shadow - c_env);
+        if (m_bounce && (int)lane64 == __ffsll((long long)m_bounce) - 1) r_bounce = atomicAdd(cnt_next, c_bounce);
+        const unsigned long long below = (1ull << lane64) - 1ull;
+        const uint32_t ie = (m_env ? __shfl(r_env, __ffsll((long long)m_env) - 1, 64) : 0u) + (uint32_t)__popcll(m_env & below);
+        const uint32_t il = (m_light ? __shfl(r_light, __ffsll((long long)m_light) - 1, 64) : 0u) + (uint32_t)__popcll(m_light & below);
+        const uint32_t ib = (m_bounce ? __shfl(r_bounce, __ffsll((long long)m_bounce) - 1, 64) : 0u) + (uint32_t)__popcll(m_bounce & below);
+#else
+        uint32_t reserved = 0;
+        if ((c_shadow | c_bounce) != 0u && lane64 < 2u) {
+            const uint32_t add = lane64 == 0u ? c_shadow : c_bounce;
+            if (add != 0u) reserved = atomicAdd(lane64 == 0u ? cnt_shadow : cnt_next, add);
+        }
+        const uint32_t base_shadow = (uint32_t)__builtin_amdgcn_readlane((int)reserved, 0), base_bounce = (uint32_t)__builtin_amdgcn_readlane((int)reserved, 1);
+        const unsigned long long below = (1ull << lane64) - 1ull;
+        const uint32_t ie = base_shadow + (uint32_t)__popcll(m_env & below);
+        const uint32_t il = base_shadow + c_env + (uint32_t)__popcll(m_light & below);
+        const uint32_t ib = base_bounce + (uint32_t)__popcll(m_bounce & below);
+#endif
         if (push_env) {
             QST(wf.sh_o[sbase + ie], make_float4(fu.origin_above.x, fu.origin_above.y, fu.origin_above.z, __uint_as_float(slot)));
             QST(wf.sh_d[sbase + ie], make_float4(fu.env_dir.x, fu.env_dir.y, fu.env_dir.z, __uint_as_float(kNoHint)));
             n_shadow++;
         }
-        const uint32_t il = queue_push(cnt_shadow, push_light);
         if (push_light) {
             QST(wf.sh_o[sbase + il], make_float4(fu.origin_above.x, fu.origin_above.y, fu.origin_above.z, __uint_as_float(slot | 0x80000000u)));
             QST(wf.sh_d[sbase + il], make_float4(fu.light_dir.x, fu.light_dir.y, fu.light_dir.z, __uint_as_float(kNoHint)));
             n_shadow++;
         }
-        const uint32_t ib = queue_push(cnt_next, push_bounce);
         if (push_bounce) {                                                                           // TraceBounceRay :669-678
             QST(wf.ray_o[nxt][base + ib], make_float4(fu.b_o.x, fu.b_o.y, fu.b_o.z, fc.max_ray_length));
             QST(wf.ray_d[nxt][base + ib], make_float4(fu.b_d.x, fu.b_d.y, fu.b_d.z, __uint_as_float(slot)));
@@ -669,7 +717,7 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         }
         if (!flush) chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_chunk);
     }
-    flush_counters(counters, threadIdx.x & 63, 0, n_bounce, n_shadow, n_hits, st);
+    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, 0, n_bounce, n_shadow, n_hits, st.taps);
 }
 
 // occlusion traversal of the shadow queue (TraceShadowRay :724-742); writes the transmission next to its pending term.
@@ -840,9 +888,11 @@ PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, floa
 }
 
 // AOV: the instantiations of calls with AOV targets (pt_set_aov) also blend the records k_wf_aov wrote, next to the beauty pixel; the
-// others take `av` and never look at it.
+// others take `av` and never look at it.  Being the launch that ends every trace, it also folds the stages' per-shard ray tallies into
+// `counters` (fold_shard_tallies): one wave of workgroup 0, whatever becomes of that workgroup's tile.
 template <bool ADAPTIVE, bool AOV>
-__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output, AdaptiveArgs ad, AovArgs av) {
+__global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuffers wf, float4* __restrict__ output, AdaptiveArgs ad, AovArgs av, Counters* __restrict__ counters) {
+    fold_shard_tallies(wf, counters);       // the trace's ray counts (before any thread leaves: a retired tile's block, a slot off the image)
     if (ADAPTIVE) { resolve_adaptive<AOV>(fc, wf, output, ad, av); return; }
     const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;       // pixel slot; its samples sit pixel_slots apart
     uint32_t px, py;
@@ -1153,7 +1203,7 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_variance_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, (const float4*)output, ad, passes.va); });
         mark(STAGE_RESOLVE);
     }
-    pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av); });
+    pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av, counters); });
     mark(STAGE_RESOLVE);
     return hipGetLastError();
 }
