@@ -273,6 +273,63 @@ extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const 
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_query: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the material model on caller-supplied queries, one per lane (pt_vertex.h debug_bsdf_query:
+// op 0 EVALUATE through evaluate_bsdf, 1 SAMPLE through sample_bsdf, after the vertex's prepare_bsdf; 48 input and 16 output floats per
+// query, laid out there).  Part of the contract: query i runs in lane i % 64 of wave i / 64, and the lanes of the last wave past n are not
+// active -- the sheen lobe is run or skipped by a vote of a wave's active lanes, so the caller composes the waves by ordering the queries.
+// flags: PT_FLAG_*, of which PT_FLAG_MATERIAL_DIFFUSE_WHITE and PT_FLAG_MATERIAL_MIS are read.  unit 0: the wavefront stages' build (the
+// sheen table staged into LDS), 1: the megakernel's (global memory).  Needs no scene.
+extern "C" int pt_debug_bsdf_query(pt_ctx* ctx, int unit, int op, uint32_t flags, const float* in, uint32_t n, float* out) {
+    if (!ctx || unit < 0 || unit > 1 || op < 0 || op > 1 || (n && (!in || !out))) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    const SceneRec sc = scene_fill(ctx);                   // (the BSDF reads the sheen table; stage_luts stages the sRGB table with it)
+    const size_t in_bytes = (size_t)n * 48 * 4, out_bytes = (size_t)n * 16 * 4;
+    TempBuf in_buf, out_buf;
+    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_bsdf_query: query buffers"); }
+    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
+    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_bsdf_query_wf(sc, op, flags, d_in, n, d_out, ctx->stream);
+        else launch_debug_bsdf_query_mk(sc, op, flags, d_in, n, d_out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_bsdf_query: ") + hipGetErrorString(e));
+}
+
+// test hook (not part of include/mipt.h): the punctual lights on caller-supplied queries, one per lane -- load_light, then light_ray, as the
+// shade stage runs them for the light it picked (pt_vertex.h debug_light_query), on the first num_of_lights lights of the context's table
+// (pt_scene_set_lights).  light_index: one per query, below num_of_lights; p: 3 floats per query, the shaded point; out: 8 floats per
+// query (direction, colour, cone_terms_staged: 1 where the spot cone terms were read from the staged copy, 0).  unit 0: the wavefront
+// stages' build, the first 32 lights staged into LDS with their cone terms; small_tables as the shade kernel's SMALL copy has it (every light
+// is in LDS: at most 32 lights, else PT_ERR_INVALID_ARGUMENT).  unit 1: the megakernel's (global memory; small_tables is not looked at).
+extern "C" int pt_debug_light_query(pt_ctx* ctx, int unit, int small_tables, int num_of_lights, const uint32_t* light_index, const float* p, uint32_t n, float* out) {
+    if (!ctx || unit < 0 || unit > 1 || (n && (!light_index || !p || !out))) return PT_ERR_INVALID_ARGUMENT;
+    if (num_of_lights < 0 || num_of_lights > ctx->n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_light_query: " + std::to_string(num_of_lights) + " of " + std::to_string(ctx->n_lights) + " lights");
+    if (unit == 0 && small_tables && num_of_lights > debug_light_cache_max()) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_light_query: small_tables with " + std::to_string(num_of_lights) + " lights");
+    for (uint32_t i = 0; i < n; i++)
+        if (light_index[i] >= (uint32_t)num_of_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_light_query: query " + std::to_string(i) + " names light " + std::to_string(light_index[i]) + " of " + std::to_string(num_of_lights));
+    ENTER(ctx);
+    if (n == 0) return PT_OK;
+    const SceneRec sc = scene_fill(ctx);
+    TempBuf idx_buf, p_buf, out_buf;
+    if (idx_buf.alloc((size_t)n * 4) != hipSuccess || p_buf.alloc((size_t)n * 12) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) {
+        (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_light_query: query buffers");
+    }
+    hipError_t e = hipMemcpyAsync(idx_buf.ptr, light_index, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(p_buf.ptr, p, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_light_query_wf(sc, small_tables != 0, num_of_lights, idx_buf.as<uint32_t>(), p_buf.as<float>(), n, out_buf.as<float>(), ctx->stream);
+        else launch_debug_light_query_mk(sc, idx_buf.as<uint32_t>(), p_buf.as<float>(), n, out_buf.as<float>(), ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, out_buf.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_light_query: ") + hipGetErrorString(e));
+}
+
 // test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid
 // (level 0 first), as the oracle's orc_env_create_raw takes them -- so both sides can sample a crafted pyramid.
 extern "C" int pt_debug_env_create_raw(pt_ctx* ctx, int cube_n, const uint16_t* cube_rgba16f, const float* pyramid, int* env_out) {

@@ -116,6 +116,12 @@ void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_sl
 void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
 void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+// pt_debug_bsdf_query / pt_debug_light_query (test hooks): 48 floats in and 16 out per BSDF query; an index and a point in, 8 floats out per light query
+void launch_debug_bsdf_query_wf(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+void launch_debug_bsdf_query_mk(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
+void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
+int debug_light_cache_max();             // lights the shade stage keeps in LDS (kLightCacheMax)
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream);
 // pt_debug_camera_rays / pt_lens_focus_at: d_out = 8 floats per query / 2 floats {hit, view-space depth}

@@ -194,6 +194,28 @@ void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, ui
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_env_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
 }
+// Test hook (pt_debug_bsdf_query, mipt_debug.hip): the BSDF as the megakernel runs it -- the sheen table in global memory.  Query i runs in
+// lane i % 64 of wave i / 64.
+__global__ __launch_bounds__(kBlock) void k_debug_bsdf_query_mk(SceneRec sc, int op, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_bsdf_query(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);
+}
+void launch_debug_bsdf_query_mk(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_bsdf_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, flags, d_in, n, d_out);
+}
+// Test hook (pt_debug_light_query, mipt_debug.hip): the punctual lights as the megakernel runs them -- the table in global memory, the cone
+// terms computed in place.  The host checks that every index is below the table's size.
+__global__ __launch_bounds__(kBlock) void k_debug_light_query_mk(SceneRec sc, const uint32_t* __restrict__ index, const float* __restrict__ p, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_light_query(sc, index[i], v3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]), out + (size_t)kLightQueryOut * i);
+}
+void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_light_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_index, d_p, n, d_out);
+}
 // Test hook (pt_debug_math): the kernels' own math routines on caller-supplied arguments, for the bit-for-bit comparison with the oracle's.
 // op: 0 atan2(a, b)  1 pow(a, b)  2 exp(a)  3 log2(a)  4 exp2(a)  5 sin(a)  6 cos(a)  7 a / b by fdiv  8 pow5(a)
 __global__ __launch_bounds__(256) void k_debug_math(int op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {

@@ -95,6 +95,58 @@ PT_DEV void debug_env_query(const SceneRec& sc, int op, const float* __restrict_
     }
 }
 
+// What a vertex prepares once for every BSDF evaluation at it, for the test hook pt_debug_bsdf_query: the lobe probabilities, and the
+// view-dependent sheen terms in waves that hold a sheen material -- gltf_bsdf's own condition for running the sheen lobe, which reads them.
+// The SAME three statements as shade_closest_hit runs before its first evaluate_bsdf ("prepare_bsdf" there); change both together.  They
+// stay written out there: calling this function instead moved the instruction counts of the two specialised k_wf_shade copies (19681 ->
+// 19679, 21184 -> 21185), and the shade stage is not to change for a test hook.
+PT_DEV Lobes prepare_bsdf(Surface& sp, vec3 view) {
+    const Lobes lobes = lobe_probabilities(sp, view);
+    sp.sheen_lh = sp.sheen_sv = 0.0f;
+    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition)
+    return lobes;
+}
+
+// Test hook (pt_debug_bsdf_query): one BSDF query per lane, through prepare_bsdf and evaluate_bsdf (op 0) or sample_bsdf (op 1).  Call it
+// with every lane of the wave that has a query and with no other: the sheen lobe is run or skipped by a vote of the active lanes.
+//   in  48 floats: the reference's SurfaceProperties [0,36) (albedo, alpha, metalness, roughness_squared.xy, shading normal, anisotropy
+//       tangent, bitangent, ior, specular colour, specular factor, clearcoat, clearcoat roughness, clearcoat normal, sheen colour, sheen
+//       roughness squared, transmissive; thickness and attenuation are not read), geometric normal [36,39), view [39,42), l (op 0) or
+//       u.xyz (op 1) [42,45)
+//   out 16 floats: f.rgb, pdf, l.xyz, is_transmission, use_mis (op 0: l echoed, both 0), the lobe probabilities alpha, clearcoat, sheen,
+//       specular, diffuse, transmission, 0
+constexpr int kBsdfQueryIn = 48, kBsdfQueryOut = 16;
+PT_DEV void debug_bsdf_query(const SceneRec& sc, int op, uint32_t flags, const float* __restrict__ in, float* __restrict__ out) {
+    Surface sp;
+    sp.albedo = v3(in[0], in[1], in[2]); sp.alpha = in[3]; sp.metalness = in[4]; sp.ax = in[5]; sp.ay = in[6];
+    sp.n = v3(in[7], in[8], in[9]); sp.at = v3(in[10], in[11], in[12]); sp.ab = v3(in[13], in[14], in[15]); sp.ior = in[16];
+    sp.spec_color = v3(in[17], in[18], in[19]); sp.spec_factor = in[20]; sp.clearcoat = in[21]; sp.cc_rough = in[22];
+    sp.cc_n = v3(in[23], in[24], in[25]); sp.sheen_color = v3(in[26], in[27], in[28]); sp.sheen_a = in[29]; sp.transmissive = in[30];
+    sp.emissive_texel = v3(0);
+    const vec3 ng = v3(in[36], in[37], in[38]), view = v3(in[39], in[40], in[41]), a = v3(in[42], in[43], in[44]);
+    const Lobes lobes = prepare_bsdf(sp, view);
+    vec3 f, l = a;
+    float pdf = 0;
+    bool is_tr = false, use_mis = false;
+    if (op == 0) f = evaluate_bsdf(flags, sc.sheen_e, sp, lobes, ng, view, a, pdf);
+    else f = sample_bsdf(flags, sc.sheen_e, sp, lobes, a, view, l, pdf, is_tr, use_mis);
+    out[0] = f.x; out[1] = f.y; out[2] = f.z; out[3] = pdf; out[4] = l.x; out[5] = l.y; out[6] = l.z;
+    out[7] = is_tr ? 1.0f : 0.0f; out[8] = use_mis ? 1.0f : 0.0f;
+    out[9] = lobes.alpha; out[10] = lobes.clearcoat; out[11] = lobes.sheen; out[12] = lobes.specular; out[13] = lobes.diffuse; out[14] = lobes.transmission;
+    out[15] = 0.0f;
+}
+// Test hook (pt_debug_light_query): load_light and light_ray as shade_closest_hit runs them for the light it picked.  out 8 floats:
+// direction, colour, cone_terms_staged (1: the cone terms came from the staged copy), 0.
+constexpr int kLightQueryOut = 8;
+PT_DEV void debug_light_query(const SceneRec& sc, uint32_t li, vec3 p, float* __restrict__ out) {
+    vec3 ldir, lcol;
+    bool cone_terms_staged;
+    const pt_light light = load_light(sc, li, cone_terms_staged);
+    light_ray(light, p, ldir, lcol, cone_terms_staged);
+    out[0] = ldir.x; out[1] = ldir.y; out[2] = ldir.z; out[3] = lcol.x; out[4] = lcol.y; out[5] = lcol.z;
+    out[6] = cone_terms_staged ? 1.0f : 0.0f; out[7] = 0.0f;
+}
+
 // Returns true when the path ends at this vertex for a debug output (fu.add holds beta * debug colour).
 // -DPT_TIMING (pt_wavefront.hip only; tools/shade_sections.py): cycles per section of this function, summed per wave.
 #ifdef PT_TIMING
@@ -177,7 +229,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
     }
     const Lobes lobes = lobe_probabilities(sp, view);
     sp.sheen_lh = sp.sheen_sv = 0.0f;
-    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition)
+    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition; prepare_bsdf above restates these three statements for the test hook)
     vec3 c = emissive_of(sc, mat, mh, va.tc, taps, sp.emissive_texel);                                                     // :925-926
     fu.origin_above = o_above;
     PT_TICK(2)

@@ -765,6 +765,34 @@ void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, ui
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_env_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
 }
+// Test hook (pt_debug_bsdf_query, mipt_debug.hip): the BSDF as this file's shade stage runs it -- the sheen table staged into LDS by stage_luts.
+// Query i runs in lane i % 64 of wave i / 64; every lane stages before any lane without a query leaves.
+__global__ __launch_bounds__(kBlock) void k_debug_bsdf_query_wf(SceneRec sc, int op, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    stage_luts(sc);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_bsdf_query(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);
+}
+void launch_debug_bsdf_query_wf(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_bsdf_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, flags, d_in, n, d_out);
+}
+// Test hook (pt_debug_light_query, mipt_debug.hip): the punctual lights as this file's shade stage runs them -- the first kLightCacheMax
+// lights staged into LDS with their cone terms (stage_lights), `small_tables` as k_wf_shade's SMALL.  The host checks that small_tables
+// comes with at most kLightCacheMax lights and that every index is below num_of_lights.
+__global__ __launch_bounds__(kBlock) void k_debug_light_query_wf(SceneRec sc_in, uint32_t small_tables, int num_of_lights, const uint32_t* __restrict__ index,
+                                                              const float* __restrict__ p, uint32_t n, float* __restrict__ out) {
+    SceneRec sc = sc_in; sc.small_tables = small_tables ? 1u : 0u;
+    stage_lights(sc, num_of_lights);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_light_query(sc, index[i], v3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]), out + (size_t)kLightQueryOut * i);
+}
+void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_light_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, small_tables ? 1u : 0u, num_of_lights, d_index, d_p, n, d_out);
+}
+int debug_light_cache_max() { return kLightCacheMax; }
 // First-hit AOVs (pt_set_aov): albedo, shading normal and depth of the vertex the camera ray reaches, one 32-B record per slot.  A stage
 // of its own between the primary traversal and the first shade stage -- queue 0's rays and wf.hit are intact in that window -- so that
 // the shade stage, priced by the register allocation of its one function, stays what it is.  It walks the shard's segment like every

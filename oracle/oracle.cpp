@@ -1423,6 +1423,31 @@ void orc_sample_bsdf(void* h, uint32_t flags, const float* sp36, const float* u3
     float3 b = SampleBsdf(env, sp, {u3[0], u3[1], u3[2]}, {v[0], v[1], v[2]}, l, pdf, it, um);
     out9[0] = b.x; out9[1] = b.y; out9[2] = b.z; out9[3] = pdf; out9[4] = l.x; out9[5] = l.y; out9[6] = l.z; out9[7] = it ? 1.f : 0.f; out9[8] = um ? 1.f : 0.f;
 }
+// EvaluateBsdf (op 0) / SampleBsdf (op 1) on n queries, with the layout of the product's test hook pt_debug_bsdf_query.  in: 48 floats per
+// query -- SurfaceProperties [0,36), the geometric normal [36,39), v [39,42), l (op 0) or u.xyz (op 1) [42,45), padding.  out: 16 floats per
+// query -- bsdf.rgb, pdf, l.xyz, is_transmission, use_mis (op 0: l echoed, both 0), then LayerProbabilities(sp, v): alpha, clearcoat, sheen,
+// specular, diffuse, transmission; [15] = 0.
+void orc_bsdf_query_many(void* h, int op, uint32_t flags, const float* in, uint32_t n, float* out) {
+    ShadingEnv env{&((Oracle*)h)->lut, flags};
+    for (uint32_t q = 0; q < n; q++, in += 48, out += 16) {
+        SurfaceProperties sp; memcpy(&sp, in, sizeof(sp));
+        const float3 ng = {in[36], in[37], in[38]}, v = {in[39], in[40], in[41]}, a = {in[42], in[43], in[44]};
+        float3 b, l = a; float pdf = 0; bool it = false, um = false;
+        if (op == 0) b = EvaluateBsdf(env, sp, ng, v, a, pdf);
+        else b = SampleBsdf(env, sp, a, v, l, pdf, it, um);
+        const LayerProbs p = LayerProbabilities(sp, v);
+        out[0] = b.x; out[1] = b.y; out[2] = b.z; out[3] = pdf; out[4] = l.x; out[5] = l.y; out[6] = l.z; out[7] = it ? 1.f : 0.f; out[8] = um ? 1.f : 0.f;
+        out[9] = p.alpha; out[10] = p.clearcoat; out[11] = p.sheen; out[12] = p.specular; out[13] = p.diffuse; out[14] = p.transmission; out[15] = 0.f;
+    }
+}
+// GetLightRay of lights[indices[q]] from the point p[q] on n queries, with the output layout of the product's test hook pt_debug_light_query:
+// 8 floats per query -- direction, colour, and two zeros (the hook's cone_terms_staged and pad, which the oracle has no counterpart of).
+void orc_light_query_many(const void* lights, const uint32_t* indices, const float* p, uint32_t n, float* out) {
+    for (uint32_t q = 0; q < n; q++, p += 3, out += 8) {
+        const LightRay r = GetLightRay(((const Light*)lights)[indices[q]], {p[0], p[1], p[2]});
+        out[0] = r.direction.x; out[1] = r.direction.y; out[2] = r.direction.z; out[3] = r.color.x; out[4] = r.color.y; out[5] = r.color.z; out[6] = out[7] = 0.f;
+    }
+}
 void orc_sample_texture(void* h, int tex, int sampler, const float* uv, float* out4) {
     Oracle* o = (Oracle*)h; float4 r = SampleLevel0(o->textures[tex], o->samplers[sampler], {uv[0], uv[1]}); out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
 }

@@ -83,6 +83,10 @@ def lib():
         L.orc_sample_importance_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_env_query_many.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_env_query_many.restype = None
+        L.orc_bsdf_query_many.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_bsdf_query_many.restype = None
+        L.orc_light_query_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_light_query_many.restype = None
         L.orc_decode_tangent_space.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_random.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.orc_cubemap_to_direction.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
@@ -250,6 +254,16 @@ class Oracle:
         self.L.orc_env_query_many(self.h, int(env), int(op), _p(q), len(q), _p(out))
         return out
 
+    BSDF_EVALUATE, BSDF_SAMPLE = 0, 1
+
+    def bsdf_query_many(self, op, flags, inp):
+        """EvaluateBsdf / SampleBsdf and LayerProbabilities on n queries (orc_bsdf_query_many): inp (n, 48) float32, returns (n, 16)."""
+        inp = _f(inp)
+        assert inp.ndim == 2 and inp.shape[1] == 48
+        out = np.zeros((len(inp), 16), np.float32)
+        self.L.orc_bsdf_query_many(self.h, int(op), int(flags), _p(inp), len(inp), _p(out))
+        return out
+
     def trace(self, settings, params, output, nthreads=None):
         """output: float32 array (H, W, 4), modified in place (the accumulation target)."""
         assert output.dtype == np.float32 and output.flags["C_CONTIGUOUS"]
@@ -290,6 +304,17 @@ class Oracle:
         out = np.zeros(7, np.float32)
         self.L.orc_intersect(self.h, _p(o), _p(d), tmin, tmax, ray_flags, _p(out))
         return out
+
+
+def light_query_many(lights, indices, points):
+    """GetLightRay of lights[indices[q]] (an array of abi.PtLight) from points[q] (orc_light_query_many): returns (n, 8) float32,
+    direction, colour and two zeros."""
+    idx = np.ascontiguousarray(indices, np.uint32)
+    p = _f(points).reshape(-1, 3)
+    assert len(idx) == len(p) and (len(idx) == 0 or int(idx.max()) < len(lights))
+    out = np.zeros((len(idx), 8), np.float32)
+    lib().orc_light_query_many(C.cast(lights, C.c_void_p), _p(idx), _p(p), len(idx), _p(out))
+    return out
 
 
 def tonemap(rgba, config=None, want_rgba8=False):
