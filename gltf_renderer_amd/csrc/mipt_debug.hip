@@ -330,6 +330,56 @@ extern "C" int pt_debug_light_query(pt_ctx* ctx, int unit, int small_tables, int
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_light_query: ") + hipGetErrorString(e));
 }
 
+// test hook (not part of include/mipt.h): the vertex fetch and the material evaluation of a path vertex on caller-supplied hits, one per
+// lane, through the shade stage's own functions in its order (pt_vertex.h debug_surface_query: load_shade_packet_raw, load_shade_inst, the
+// voted load_shade_packet_extra, unpack_shade_packet, material_header, get_vertex_attributes, the back-face flip, offset_ray both ways,
+// get_surface, emissive_of) and, separately, the any-hit path's candidate_alpha for the same hit.  Builds or refits what is pending.
+//   in   8 words per query: the packet index (uint32: the hit's index in the TriPacket / ShadePacket arrays, pt_debug_accel_read; below
+//        n_tris, else PT_ERR_INVALID_ARGUMENT), front (uint32: 0 or 1), u, v, the ray direction d.xyz (the view is -normalize(d)), 0
+//   out 72 floats per query:
+//        [0,24)   HitGeom after the flip: position, ng, n, t [9,12), tw [12], bt [13,16), colour [16,20), tc[0] [20,22), tc[1] [22,24)
+//        [24,55)  Surface as the reference's SurfaceProperties floats [0,31), the order of pt_debug_bsdf_query's input: albedo, alpha,
+//                 metalness, roughness_squared.xy, shading normal, anisotropy tangent, bitangent, ior, specular colour, specular factor,
+//                 clearcoat, clearcoat roughness, clearcoat normal, sheen colour, sheen roughness squared, transmissive (thickness and
+//                 attenuation, which the product does not keep, are not there)
+//        [55,58)  the emissive value, [58,61) o_above, [61,64) o_below
+//        [64]     the texture taps get_surface and emissive_of counted
+//        [65,68)  candidate_alpha's base_alpha, alpha, cutoff; [68,72) 0
+// Part of the contract: query i runs in lane i % 64 of wave i / 64, and the lanes of the last wave past n are not active -- the second
+// packet fetch, the interleaved / general texel fetch and the edge reload are behind votes of a wave's active lanes, so the caller composes
+// the waves by ordering the queries.  flags: PT_FLAG_*, of which PT_FLAG_SHADING_NORMAL_ADAPTATION and
+// PT_FLAG_MATERIAL_USE_GEOMETRIC_NORMALS are read.  unit 0: the wavefront stages' build, the lookup tables, instance rows and materials
+// staged into LDS as k_wf_shade stages them; small_tables as the shade kernel's SMALL copy has it (every row and material is in LDS: at most
+// 128 instances and 96 materials, else PT_ERR_INVALID_ARGUMENT).  unit 1: the megakernel's (global memory; small_tables is not looked at).
+extern "C" int pt_debug_surface_query(pt_ctx* ctx, int unit, int small_tables, uint32_t flags, const void* in, uint32_t n, float* out) {
+    if (!ctx || unit < 0 || unit > 1 || (n && (!in || !out))) return PT_ERR_INVALID_ARGUMENT;
+    if (unit == 0 && small_tables && ((int)ctx->instances.size() > debug_inst_cache_max() || ctx->n_materials > debug_mat_cache_max()))
+        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_surface_query: small_tables with " + std::to_string(ctx->instances.size()) + " instances and " + std::to_string(ctx->n_materials) + " materials");
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    const uint32_t* words = (const uint32_t*)in;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t tri = words[(size_t)8 * i], front = words[(size_t)8 * i + 1];
+        if (tri >= ctx->n_tris || front > 1u)
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_surface_query: query " + std::to_string(i) + " names packet " + std::to_string(tri) + " of " + std::to_string(ctx->n_tris) + ", front " + std::to_string(front));
+    }
+    if (n == 0) return PT_OK;
+    const SceneRec sc = scene_fill(ctx);
+    const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 72 * 4;
+    TempBuf in_buf, out_buf;
+    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_surface_query: query buffers"); }
+    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
+    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        if (unit == 0) launch_debug_surface_query_wf(sc, small_tables != 0, flags, d_in, n, d_out, ctx->stream);
+        else launch_debug_surface_query_mk(sc, flags, d_in, n, d_out, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_surface_query: ") + hipGetErrorString(e));
+}
+
 // test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid
 // (level 0 first), as the oracle's orc_env_create_raw takes them -- so both sides can sample a crafted pyramid.
 extern "C" int pt_debug_env_create_raw(pt_ctx* ctx, int cube_n, const uint16_t* cube_rgba16f, const float* pyramid, int* env_out) {

@@ -122,6 +122,11 @@ void launch_debug_bsdf_query_mk(const SceneRec& sc, int op, uint32_t flags, cons
 void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
 void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
 int debug_light_cache_max();             // lights the shade stage keeps in LDS (kLightCacheMax)
+// pt_debug_surface_query (test hook): 8 words in and 72 floats out per query (pt_vertex.h debug_surface_query)
+void launch_debug_surface_query_wf(const SceneRec& sc, bool small_tables, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+void launch_debug_surface_query_mk(const SceneRec& sc, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+int debug_inst_cache_max();              // instance rows / materials the shade stage keeps in LDS (kInstCacheMax, kMatCacheMax)
+int debug_mat_cache_max();
 void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream);
 // pt_debug_camera_rays / pt_lens_focus_at: d_out = 8 floats per query / 2 floats {hit, view-space depth}

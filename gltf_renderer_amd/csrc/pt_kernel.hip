@@ -216,6 +216,17 @@ void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, co
     if (n == 0) return;
     hipLaunchKernelGGL(k_debug_light_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_index, d_p, n, d_out);
 }
+// Test hook (pt_debug_surface_query, mipt_debug.hip): the vertex fetch and the material evaluation as the megakernel runs them -- every
+// table in global memory.  The host checks that every packet index is below num_tris.  Query i runs in lane i % 64 of wave i / 64.
+__global__ __launch_bounds__(kBlock) void k_debug_surface_query_mk(SceneRec sc, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_surface_query(sc, flags, in + (size_t)kSurfQueryIn * i, out + (size_t)kSurfQueryOut * i);
+}
+void launch_debug_surface_query_mk(const SceneRec& sc, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_surface_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, flags, d_in, n, d_out);
+}
 // Test hook (pt_debug_math): the kernels' own math routines on caller-supplied arguments, for the bit-for-bit comparison with the oracle's.
 // op: 0 atan2(a, b)  1 pow(a, b)  2 exp(a)  3 log2(a)  4 exp2(a)  5 sin(a)  6 cos(a)  7 a / b by fdiv  8 pow5(a)
 __global__ __launch_bounds__(256) void k_debug_math(int op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {

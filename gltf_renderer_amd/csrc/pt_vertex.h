@@ -146,6 +146,63 @@ PT_DEV void debug_light_query(const SceneRec& sc, uint32_t li, vec3 p, float* __
     out[0] = ldir.x; out[1] = ldir.y; out[2] = ldir.z; out[3] = lcol.x; out[4] = lcol.y; out[5] = lcol.z;
     out[6] = cone_terms_staged ? 1.0f : 0.0f; out[7] = 0.0f;
 }
+// Test hook (pt_debug_surface_query): the vertex fetch and the material evaluation of one hit per lane, in shade_closest_hit's order and
+// through its functions -- load_shade_packet_raw, load_shade_inst, the voted load_shade_packet_extra, unpack_shade_packet, material_header,
+// get_vertex_attributes, the back-face flip, offset_ray both ways, get_surface, emissive_of -- and, separately, the any-hit path's
+// candidate_alpha for the same hit.  The statements between the fetch and emissive_of are shade_closest_hit's own, restated here as
+// prepare_bsdf restates its three: they are not a function there, and the shade stage is not to change for a test hook; change both
+// together.  Call it with every lane of the wave that has a query and with no other: the extra packet fetch and the interleaved / general
+// and edge / interior texel fetches are behind votes of the active lanes.
+//   in   8 words: the packet index (uint32, below sc.num_tris), front (uint32, 0 or 1), u, v, the ray direction d.xyz (view = -normalize(d)), 0
+//   out 72 floats:
+//       [0,24)   HitGeom after the flip: position, ng, n, t [9,12), tw [12], bt [13,16), colour [16,20), tc[0] [20,22), tc[1] [22,24)
+//       [24,55)  Surface as the reference's SurfaceProperties floats [0,31), the order of pt_debug_bsdf_query's input: albedo, alpha, metalness,
+//                roughness_squared.xy (ax, ay), shading normal, anisotropy tangent, bitangent, ior, specular colour, specular factor,
+//                clearcoat, clearcoat roughness, clearcoat normal, sheen colour, sheen roughness squared, transmissive (thickness and
+//                attenuation are not kept by the product and are not here)
+//       [55,58)  emissive_of, [58,61) o_above, [61,64) o_below
+//       [64]     the texture taps get_surface and emissive_of counted
+//       [65,68)  candidate_alpha's base_alpha, alpha, cutoff; [68,72) 0
+constexpr int kSurfQueryIn = 8, kSurfQueryOut = 72;
+PT_DEV void debug_surface_query(const SceneRec& sc, uint32_t flags, const float* __restrict__ in, float* __restrict__ out) {
+    const uint32_t tri = __float_as_uint(in[0]);
+    const bool front = __float_as_uint(in[1]) != 0;
+    const float hu = in[2], hv = in[3];
+    const vec3 d = v3(in[4], in[5], in[6]);
+    const ShadePacket* packet_at = sc.shade + tri;
+    RawPacket packet = load_shade_packet_raw(packet_at);
+    const ShadeInst inst = load_shade_inst(sc, raw_packet_inst(packet));
+    if (__any((inst.streams & (SI_TEXCOORD1 | SI_COLOR)) != 0)) {
+        if (inst.streams & (SI_TEXCOORD1 | SI_COLOR)) load_shade_packet_extra(packet, packet_at);
+    }
+    const PacketVerts pv = unpack_shade_packet(packet);
+    const RMat* mat = sc.rmats + inst.material_id;
+    const MatHeader mh = material_header(sc, inst.material_id);
+    HitGeom va = get_vertex_attributes(sc, inst, pv, v3(1 - hu - hv, hu, hv));
+    if (!front) { va.ng = -va.ng; va.n = -va.n; va.t = -va.t; va.tw = -va.tw; }                     // :842-846
+    const vec3 o_above = offset_ray(va.position, va.ng), o_below = offset_ray(va.position, -va.ng);
+    const vec3 view = -normalize(d);
+    unsigned taps = 0, taps_any = 0;
+    const Surface sp = get_surface(sc, flags, mat, mh, va, view, taps);
+    const vec3 em = emissive_of(sc, mat, mh, va.tc, taps, sp.emissive_texel);
+    float base_alpha, alpha, cutoff;
+    candidate_alpha(sc, pv.inst, (int)tri, hu, hv, taps_any, base_alpha, alpha, cutoff);
+    out[0] = va.position.x; out[1] = va.position.y; out[2] = va.position.z; out[3] = va.ng.x; out[4] = va.ng.y; out[5] = va.ng.z;
+    out[6] = va.n.x; out[7] = va.n.y; out[8] = va.n.z; out[9] = va.t.x; out[10] = va.t.y; out[11] = va.t.z; out[12] = va.tw;
+    out[13] = va.bt.x; out[14] = va.bt.y; out[15] = va.bt.z;
+    out[16] = va.color.x; out[17] = va.color.y; out[18] = va.color.z; out[19] = va.color.w;
+    out[20] = va.tc[0].x; out[21] = va.tc[0].y; out[22] = va.tc[1].x; out[23] = va.tc[1].y;
+    float* s = out + 24;
+    s[0] = sp.albedo.x; s[1] = sp.albedo.y; s[2] = sp.albedo.z; s[3] = sp.alpha; s[4] = sp.metalness; s[5] = sp.ax; s[6] = sp.ay;
+    s[7] = sp.n.x; s[8] = sp.n.y; s[9] = sp.n.z; s[10] = sp.at.x; s[11] = sp.at.y; s[12] = sp.at.z; s[13] = sp.ab.x; s[14] = sp.ab.y; s[15] = sp.ab.z;
+    s[16] = sp.ior; s[17] = sp.spec_color.x; s[18] = sp.spec_color.y; s[19] = sp.spec_color.z; s[20] = sp.spec_factor; s[21] = sp.clearcoat; s[22] = sp.cc_rough;
+    s[23] = sp.cc_n.x; s[24] = sp.cc_n.y; s[25] = sp.cc_n.z; s[26] = sp.sheen_color.x; s[27] = sp.sheen_color.y; s[28] = sp.sheen_color.z;
+    s[29] = sp.sheen_a; s[30] = sp.transmissive;
+    out[55] = em.x; out[56] = em.y; out[57] = em.z;
+    out[58] = o_above.x; out[59] = o_above.y; out[60] = o_above.z; out[61] = o_below.x; out[62] = o_below.y; out[63] = o_below.z;
+    out[64] = (float)taps; out[65] = base_alpha; out[66] = alpha; out[67] = cutoff;
+    out[68] = out[69] = out[70] = out[71] = 0.0f;
+}
 
 // Returns true when the path ends at this vertex for a debug output (fu.add holds beta * debug colour).
 // -DPT_TIMING (pt_wavefront.hip only; tools/shade_sections.py): cycles per section of this function, summed per wave.

@@ -793,6 +793,27 @@ void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_
     hipLaunchKernelGGL(k_debug_light_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, small_tables ? 1u : 0u, num_of_lights, d_index, d_p, n, d_out);
 }
 int debug_light_cache_max() { return kLightCacheMax; }
+// Test hook (pt_debug_surface_query, mipt_debug.hip): the vertex fetch and the material evaluation as this file's shade stage runs them --
+// the sRGB, sheen and tangent tables, the instance rows and the material records staged into LDS as k_wf_shade stages them,
+// `small_tables` as k_wf_shade's SMALL.  The host checks that small_tables comes with at most kInstCacheMax instances and kMatCacheMax
+// materials and that every packet index is below num_tris.  Query i runs in lane i % 64 of wave i / 64; every lane stages before any
+// lane without a query leaves.
+__global__ __launch_bounds__(kBlock) void k_debug_surface_query_wf(SceneRec sc_in, uint32_t small_tables, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    SceneRec sc = sc_in; sc.small_tables = small_tables ? 1u : 0u;
+    stage_luts(sc);
+    stage_tangent_lut(sc);
+    stage_instances(sc);
+    stage_materials(sc);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    debug_surface_query(sc, flags, in + (size_t)kSurfQueryIn * i, out + (size_t)kSurfQueryOut * i);
+}
+void launch_debug_surface_query_wf(const SceneRec& sc, bool small_tables, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_debug_surface_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, small_tables ? 1u : 0u, flags, d_in, n, d_out);
+}
+int debug_inst_cache_max() { return (int)kInstCacheMax; }
+int debug_mat_cache_max() { return (int)kMatCacheMax; }
 // First-hit AOVs (pt_set_aov): albedo, shading normal and depth of the vertex the camera ray reaches, one 32-B record per slot.  A stage
 // of its own between the primary traversal and the first shade stage -- queue 0's rays and wf.hit are intact in that window -- so that
 // the shade stage, priced by the register allocation of its one function, stays what it is.  It walks the shard's segment like every

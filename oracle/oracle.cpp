@@ -621,6 +621,33 @@ static float MissEnvironmentPdf(const EnvMap* e, float3 direction) {
 // TraceRay (DXR semantics)
 enum { RAY_FLAG_FORCE_NON_OPAQUE = 0x2, RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH = 0x4, RAY_FLAG_SKIP_CLOSEST_HIT_SHADER = 0x8,
        RAY_FLAG_CULL_BACK_FACING_TRIANGLES = 0x10, RAY_FLAG_CULL_FRONT_FACING_TRIANGLES = 0x20 };
+// What the two any-hit shaders (:1010-1035, :1053-1079) share: the base colour of a candidate hit from its interpolated vertex colour and
+// texcoords alone (no VertexAttributes).  Also called by orc_surface_query_many.
+static float4 AnyHitBaseColor(Oracle& o, uint32_t inst, uint32_t prim, float u, float v) {
+    const Instance& in = o.instances[inst].gpu;
+    const Material& m = o.materials[in.material_id];
+    float3 w = {1 - u - v, u, v};
+    uint32_t vi[3];
+    GetIndices(o, in.index_descriptor, prim, vi);
+    float4 base = GetVertexColor(o, in.color_descriptor, vi, w);
+    float2 tc[2];
+    for (int i = 0; i < 2; i++) tc[i] = GetTexcoord(o, in.texcoord_descriptors[i], vi, w);
+    return GetBaseColor(o, m, tc, base);
+}
+// ClosestHit's statements around GetSurfaceProperties, as functions so that orc_surface_query_many runs them and not copies of them.
+static inline void FlipForBackFace(VertexAttributes& va) {                       // :842-846
+    va.geometric_normal = -va.geometric_normal;
+    va.normal = -va.normal;
+    va.tangent = -va.tangent;
+}
+static SurfaceProperties HitSurfaceProperties(Oracle& o, const SceneConstants& sc, const Material& material, const VertexAttributes& va, float3 view) {   // :853-861
+    SurfaceProperties sp = GetSurfaceProperties(o, sc, material, va, view);
+    sp.roughness_squared = hmax(sp.roughness_squared, F2(MINIMUM_ROUGHNESS));
+    sp.clearcoat_roughness = hmax(sp.clearcoat_roughness, MINIMUM_ROUGHNESS);
+    if (sc.flags & F_MATERIAL_USE_GEOMETRIC_NORMALS) { sp.shading_normal = va.geometric_normal; sp.clearcoat_normal = va.geometric_normal; }
+    return sp;
+}
+
 struct RayDesc { float3 origin; float tmin; float3 direction; float tmax; };
 struct Hit { float t; float u, v; int tri; bool front; };
 
@@ -668,29 +695,13 @@ struct Tracer {
     }
     // AnyHit, PathTracer.lib.hlsl:1010-1035: true = accept.
     bool any_hit_alpha_test(const Tri& t, float u, float v) {
-        const Instance& in = o.instances[t.inst].gpu;
-        const Material& m = o.materials[in.material_id];
-        float3 w = {1 - u - v, u, v};
-        uint32_t vi[3];
-        GetIndices(o, in.index_descriptor, t.prim, vi);
-        float4 base = GetVertexColor(o, in.color_descriptor, vi, w);
-        float2 tc[2];
-        for (int i = 0; i < 2; i++) tc[i] = GetTexcoord(o, in.texcoord_descriptors[i], vi, w);
-        base = GetBaseColor(o, m, tc, base);
-        return !(base.w < m.alpha_cutoff);
+        const Material& m = o.materials[o.instances[t.inst].gpu.material_id];
+        return !(AnyHitBaseColor(o, t.inst, t.prim, u, v).w < m.alpha_cutoff);
     }
     // ShadowAnyHit, :1053-1079: returns alpha
     float shadow_alpha(const Tri& t, float u, float v) {
-        const Instance& in = o.instances[t.inst].gpu;
-        const Material& m = o.materials[in.material_id];
-        float3 w = {1 - u - v, u, v};
-        uint32_t vi[3];
-        GetIndices(o, in.index_descriptor, t.prim, vi);
-        float4 base = GetVertexColor(o, in.color_descriptor, vi, w);
-        float2 tc[2];
-        for (int i = 0; i < 2; i++) tc[i] = GetTexcoord(o, in.texcoord_descriptors[i], vi, w);
-        base = GetBaseColor(o, m, tc, base);
-        return GetAlpha(m, base);
+        const Material& m = o.materials[o.instances[t.inst].gpu.material_id];
+        return GetAlpha(m, AnyHitBaseColor(o, t.inst, t.prim, u, v));
     }
     // mode 0: closest hit (hit group 0).  mode 1: shadow / occlusion (hit group 1).
     // Returns true when a hit is committed; for mode 1 `transmission` is the ShadowPayload.
@@ -826,19 +837,12 @@ struct Tracer {
             case DBG_TEXCOORD_1: payload.color = {va.texcoords[1].x, va.texcoords[1].y, 0}; return;
             default: break;
         }
-        if (!h.front) {                                                          // :842-846
-            va.geometric_normal = -va.geometric_normal;
-            va.normal = -va.normal;
-            va.tangent = -va.tangent;
-        }
+        if (!h.front) FlipForBackFace(va);                                       // :842-846
         float3 intersection = ray.origin + (ray.direction * h.t);                // :849
         float3 ray_origin = OffsetRay(va.position, va.geometric_normal);
         float3 ray_origin_below = OffsetRay(va.position, -va.geometric_normal);
         float3 view = -normalize(ray.direction);
-        SurfaceProperties sp = GetSurfaceProperties(o, sc, material, va, view);
-        sp.roughness_squared = hmax(sp.roughness_squared, F2(MINIMUM_ROUGHNESS));
-        sp.clearcoat_roughness = hmax(sp.clearcoat_roughness, MINIMUM_ROUGHNESS);
-        if (sc.flags & F_MATERIAL_USE_GEOMETRIC_NORMALS) { sp.shading_normal = va.geometric_normal; sp.clearcoat_normal = va.geometric_normal; }
+        SurfaceProperties sp = HitSurfaceProperties(o, sc, material, va, view);
         switch (sc.debug_output) {                                               // :863-917
             case DBG_COLOR: payload.color = sp.albedo; return;
             case DBG_ALPHA: payload.color = F3(sp.alpha); return;
@@ -1447,6 +1451,58 @@ void orc_light_query_many(const void* lights, const uint32_t* indices, const flo
         const LightRay r = GetLightRay(((const Light*)lights)[indices[q]], {p[0], p[1], p[2]});
         out[0] = r.direction.x; out[1] = r.direction.y; out[2] = r.direction.z; out[3] = r.color.x; out[4] = r.color.y; out[5] = r.color.z; out[6] = out[7] = 0.f;
     }
+}
+// The vertex fetch and the material evaluation of ClosestHit on n hits, with the output layout of the product's test hook
+// pt_debug_surface_query: GetVertexAttributes, the back-face flip, OffsetRay both ways, GetSurfaceProperties with ClosestHit's clamps,
+// GetEmissive, and the any-hit shaders' base colour and GetAlpha -- the functions pathtrace_scene calls.
+//   in   8 words per query: instance (uint32), front (uint32, 0 or 1), u, v, the ray direction d.xyz, primitive (uint32) -- the hook's
+//        record with its packet index replaced by the (instance, primitive) pair that packet holds
+//   out 72 floats per query:
+//        [0,24)   VertexAttributes after the flip: position, geometric normal, normal, tangent.xyz [9,12), tangent.w [12], bitangent
+//                 [13,16), colour [16,20), texcoords[0] [20,22), texcoords[1] [22,24)
+//        [24,55)  SurfaceProperties floats [0,31): albedo ... transmissive (thickness and attenuation, which the product does not keep, are left out)
+//        [55,58)  GetEmissive, [58,61) OffsetRay(position, ng), [61,64) OffsetRay(position, -ng)
+//        [64]     the SampleTexture calls of GetSurfaceProperties and GetEmissive
+//        [65,68)  the any-hit base colour's alpha, GetAlpha of it, the material's alpha_cutoff; [68,72) 0
+// Returns 0, or 1 + the index of the first query whose instance or primitive does not exist (nothing is written from there on).
+int orc_surface_query_many(void* h, uint32_t flags, const void* in_words, uint32_t n, float* out) {
+    Oracle& o = *(Oracle*)h;
+    SceneConstants sc = {};
+    sc.flags = flags;
+    const uint32_t* wd = (const uint32_t*)in_words;
+    const float* in = (const float*)in_words;
+    const uint64_t taps_at_entry = t_tally.taps;           // the calling thread's tally is a trace's: leave it as it was
+    for (uint32_t q = 0; q < n; q++, wd += 8, in += 8, out += 72) {
+        const uint32_t inst = wd[0], prim = wd[7];
+        if (inst >= o.instances.size() || prim >= o.instances[inst].num_of_indices / 3) { t_tally.taps = taps_at_entry; return (int)q + 1; }
+        const bool front = wd[1] != 0;
+        const float u = in[2], v = in[3];
+        const Instance& instance = o.instances[inst].gpu;
+        const Material& material = o.materials[instance.material_id];
+        VertexAttributes va = GetVertexAttributes(o, instance, prim, {1 - u - v, u, v});
+        if (!front) FlipForBackFace(va);
+        const float3 above = OffsetRay(va.position, va.geometric_normal), below = OffsetRay(va.position, -va.geometric_normal);
+        const float3 view = -normalize(float3{in[4], in[5], in[6]});
+        const uint64_t taps0 = t_tally.taps;
+        const SurfaceProperties sp = HitSurfaceProperties(o, sc, material, va, view);
+        const float3 em = GetEmissive(o, material, va.texcoords);
+        const uint64_t taps = t_tally.taps - taps0;
+        const float4 base = AnyHitBaseColor(o, inst, prim, u, v);
+        out[0] = va.position.x; out[1] = va.position.y; out[2] = va.position.z;
+        out[3] = va.geometric_normal.x; out[4] = va.geometric_normal.y; out[5] = va.geometric_normal.z;
+        out[6] = va.normal.x; out[7] = va.normal.y; out[8] = va.normal.z;
+        out[9] = va.tangent.x; out[10] = va.tangent.y; out[11] = va.tangent.z; out[12] = va.tangent.w;
+        out[13] = va.bitangent.x; out[14] = va.bitangent.y; out[15] = va.bitangent.z;
+        out[16] = va.color.x; out[17] = va.color.y; out[18] = va.color.z; out[19] = va.color.w;
+        out[20] = va.texcoords[0].x; out[21] = va.texcoords[0].y; out[22] = va.texcoords[1].x; out[23] = va.texcoords[1].y;
+        memcpy(out + 24, &sp, 31 * sizeof(float));
+        out[55] = em.x; out[56] = em.y; out[57] = em.z;
+        out[58] = above.x; out[59] = above.y; out[60] = above.z; out[61] = below.x; out[62] = below.y; out[63] = below.z;
+        out[64] = (float)taps; out[65] = base.w; out[66] = GetAlpha(material, base); out[67] = material.alpha_cutoff;
+        out[68] = out[69] = out[70] = out[71] = 0.f;
+    }
+    t_tally.taps = taps_at_entry;
+    return 0;
 }
 void orc_sample_texture(void* h, int tex, int sampler, const float* uv, float* out4) {
     Oracle* o = (Oracle*)h; float4 r = SampleLevel0(o->textures[tex], o->samplers[sampler], {uv[0], uv[1]}); out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;

@@ -87,6 +87,8 @@ def lib():
         L.orc_bsdf_query_many.restype = None
         L.orc_light_query_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_light_query_many.restype = None
+        L.orc_surface_query_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_surface_query_many.restype = C.c_int
         L.orc_decode_tangent_space.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_random.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.orc_cubemap_to_direction.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
@@ -262,6 +264,20 @@ class Oracle:
         assert inp.ndim == 2 and inp.shape[1] == 48
         out = np.zeros((len(inp), 16), np.float32)
         self.L.orc_bsdf_query_many(self.h, int(op), int(flags), _p(inp), len(inp), _p(out))
+        return out
+
+    def surface_query_many(self, flags, queries, instance, primitive):
+        """The vertex fetch and material evaluation of ClosestHit on n hits (orc_surface_query_many).  queries: (n, 8) float32 records of
+        the product's hook pt_debug_surface_query (word 0, its packet index, is not read); instance, primitive: the pair each hit is on.
+        Returns (n, 72) float32 in the hook's layout."""
+        q = np.array(_f(queries), copy=True)
+        assert q.ndim == 2 and q.shape[1] == 8
+        w = q.view(np.uint32)
+        w[:, 0] = np.asarray(instance, np.uint32)
+        w[:, 7] = np.asarray(primitive, np.uint32)
+        out = np.zeros((len(q), 72), np.float32)
+        rc = self.L.orc_surface_query_many(self.h, int(flags), _p(q), len(q), _p(out))
+        assert rc == 0, "orc_surface_query_many: query %d names an instance or primitive that does not exist" % (rc - 1)
         return out
 
     def trace(self, settings, params, output, nthreads=None):

@@ -21,6 +21,8 @@ import pytest
 
 from gltf_renderer_amd import abi
 
+from texture_ref import sample_level0, transform_rows
+
 f32 = np.float32
 WRAP, MIRROR, CLAMP = abi.ADDRESS_WRAP, abi.ADDRESS_MIRROR, abi.ADDRESS_CLAMP
 POINT, LINEAR = abi.FILTER_POINT, abi.FILTER_LINEAR
@@ -78,31 +80,7 @@ def gpu_sample(r, unit, mat_slot, tc):
     return out, taps
 
 
-# ---------------------------------------------------------------- float64 statement of SampleLevel(s, uv, 0)
-def srgb_to_linear(c):
-    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
-
-
-def address(i, n, mode):
-    """D3D texture address modes on integer texel indices (Python integer modulo: non-negative)."""
-    i = [int(k) for k in i]
-    if mode == WRAP:
-        r = [k % n for k in i]
-    elif mode == MIRROR:
-        r = [(k % (2 * n)) if (k % (2 * n)) < n else 2 * n - 1 - (k % (2 * n)) for k in i]
-    else:
-        r = [min(max(k, 0), n - 1) for k in i]
-    return np.array(r, np.int64)
-
-
-def transform_rows(rotation, offset, scale):
-    """The UV transform T * R * S as the host forms it in fp32: sin / cos correctly rounded from the fp32 angle."""
-    rot = float(f32(rotation))
-    sn, cs = (f32(math.sin(rot)), f32(math.cos(rot))) if rot != 0.0 else (f32(0), f32(1))
-    sx, sy = f32(scale[0]), f32(scale[1])
-    return (cs * sx, sn * sy, f32(offset[0]), -sn * sx, cs * sy, f32(offset[1]))
-
-
+# ---------------------------------------------------------------- float64 statement of SampleLevel(s, uv, 0): tests/texture_ref.py
 class Binding:
     """One bound material slot: texture + sampler + UV transform + UV set."""
     def __init__(self, tex, smp, xf, tex_coord):
@@ -110,51 +88,21 @@ class Binding:
 
 
 def reference(textures, bindings, bidx, tc):
-    """Float64 SampleLevel(..., 0) for each query (binding index bidx[q], UVs tc[q]).  The fp32 steps up to the texel coordinate
-    are the product's (transform without FMA, * size, non-finite -> 0, clamp to +-1e9 texels, - 0.5, floor); everything after
-    them is float64.  Returns rgba (n, 4) float64, taps (n, 4) = i0, i1, j0, j1, and per-query flags."""
+    """Float64 SampleLevel(..., 0) for each query (binding index bidx[q], UVs tc[q]), through texture_ref.sample_level0.  Returns rgba
+    (n, 4) float64, taps (n, 4) = i0, i1, j0, j1, and per-query flags."""
     n = len(bidx)
     rgba = np.zeros((n, 4), np.float64)
     taps = np.zeros((n, 4), np.int64)
-    nonfinite = np.zeros(n, bool); clamped = np.zeros(n, bool); unit_w = np.zeros(n, bool); linear = np.zeros(n, bool)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for b in np.unique(bidx):
-            q = np.nonzero(bidx == b)[0]
-            B = bindings[b]
-            data, srgb = textures[B.tex]
-            H, W = data.shape[:2]
-            au, av, flt = SAMPLERS[B.smp]
-            m00, m01, ox, m10, m11, oy = transform_rows(*TRANSFORMS[B.xf])
-            uv = tc[q][:, 2:4] if B.tex_coord else tc[q][:, 0:2]
-            u, v = uv[:, 0].astype(f32), uv[:, 1].astype(f32)
-            tu = (m00 * u + m01 * v) + ox                 # numpy float32: every operation rounded, no contraction
-            tv = (m10 * u + m11 * v) + oy
-            x, y = tu * f32(W), tv * f32(H)
-            nf = ~np.isfinite(x) | ~np.isfinite(y)
-            x = np.where(np.isfinite(x), x, f32(0)); y = np.where(np.isfinite(y), y, f32(0))
-            cl = (np.abs(x) > f32(1e9)) | (np.abs(y) > f32(1e9))
-            x = np.clip(x, f32(-1e9), f32(1e9)); y = np.clip(y, f32(-1e9), f32(1e9))
-            if flt == POINT:
-                i0 = i1 = address(np.floor(x), W, au); j0 = j1 = address(np.floor(y), H, av)
-                w = [np.ones(len(q)), np.zeros(len(q)), np.zeros(len(q)), np.zeros(len(q))]
-            else:
-                x = x - f32(0.5); y = y - f32(0.5)
-                fx0, fy0 = np.floor(x), np.floor(y)
-                fx = x.astype(np.float64) - fx0.astype(np.float64); fy = y.astype(np.float64) - fy0.astype(np.float64)
-                i0 = address(fx0, W, au); i1 = address(fx0.astype(np.int64) + 1, W, au)
-                j0 = address(fy0, H, av); j1 = address(fy0.astype(np.int64) + 1, H, av)
-                w = [(1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy]
-                unit_w[q] = (fx == 0) & (fy == 0)
-                linear[q] = True
-            def val(j, i):
-                c = data[j, i].astype(np.float64) / 255.0
-                if srgb:
-                    c[:, :3] = srgb_to_linear(c[:, :3])                   # sRGB decoded before filtering; alpha linear
-                return c
-            rgba[q] = val(j0, i0) * w[0][:, None] + val(j0, i1) * w[1][:, None] + val(j1, i0) * w[2][:, None] + val(j1, i1) * w[3][:, None]
-            taps[q] = np.stack([i0, i1, j0, j1], 1)
-            nonfinite[q] = nf; clamped[q] = cl
-    return rgba, taps, dict(nonfinite=nonfinite, clamped=clamped, unit_weights=unit_w & linear, linear=linear)
+    flags = dict(nonfinite=np.zeros(n, bool), clamped=np.zeros(n, bool), unit_weights=np.zeros(n, bool), linear=np.zeros(n, bool))
+    for b in np.unique(bidx):
+        q = np.nonzero(bidx == b)[0]
+        B = bindings[b]
+        data, srgb = textures[B.tex]
+        uv = tc[q][:, 2:4] if B.tex_coord else tc[q][:, 0:2]
+        rgba[q], taps[q], fl = sample_level0(data, srgb, SAMPLERS[B.smp], transform_rows(*TRANSFORMS[B.xf]), uv)
+        for k in flags:
+            flags[k][q] = fl[k]
+    return rgba, taps, flags
 
 
 # ---------------------------------------------------------------- coordinates
