@@ -521,7 +521,7 @@ constexpr int kPlocRadius = PT_PLOC_RADIUS, kPlocRadiusTop = PT_PLOC_RADIUS_TOP,
 constexpr uint32_t kPlocTopClusters = 16384;
 struct PlocCluster { float lo[3]; int32_t ref; float hi[3]; uint32_t count; };     // 32 B; ref < 0: leaf ~(Morton index), >= 0: temporary node id
 static_assert(sizeof(PlocCluster) == 32, "PlocCluster");
-// counters: [0] temporary nodes made, [4] / [5] cluster count of even / odd rounds, [6] reinsertion moves, [7] layout error flag, [8 + L] layout frontier size of level L
+// counters: [0] unused, [4] / [5] cluster count of even / odd rounds, [6] reinsertion moves, [7] layout error flag, [8 + L] layout frontier size of level L
 constexpr int kPlocLevelBase = 8, kPlocLayoutError = 7;
 
 __global__ __launch_bounds__(256) void k_ploc_init(const TriPacket* __restrict__ tris, uint32_t n, PlocCluster* __restrict__ c, uint32_t* __restrict__ counters,
@@ -589,10 +589,10 @@ __global__ __launch_bounds__(256) void k_ploc_nearest(const PlocCluster* __restr
     nn[i] = best_j;
 }
 
-// mutual pairs merge into the lower slot (a new temporary node); the upper slot is dropped by the compaction
+// mutual pairs merge into the lower slot; the upper slot is dropped by the compaction, which also makes the temporary node (it knows
+// the node's number).  Here the lower slot takes the union box and the joint count and keeps its own ref until then.
 __global__ __launch_bounds__(256) void k_ploc_merge(PlocCluster* __restrict__ c, const uint32_t* __restrict__ n_ptr, const uint32_t* __restrict__ nn,
-                                                    uint32_t* __restrict__ valid, int32_t* __restrict__ t_left, int32_t* __restrict__ t_right,
-                                                    uint32_t* __restrict__ t_count, uint32_t* __restrict__ counters, SegBox* __restrict__ t_box, uint32_t n_leaves) {
+                                                    uint32_t* __restrict__ valid) {
     const uint32_t n = *n_ptr;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -601,27 +601,41 @@ __global__ __launch_bounds__(256) void k_ploc_merge(PlocCluster* __restrict__ c,
     if (!mutual) { valid[i] = 1u; return; }
     if (i > j) { valid[i] = 0u; return; }
     const PlocCluster a = c[i], b = c[j];
-    const uint32_t idx = atomicAdd(counters + 0, 1u);       // (the numbering is arbitrary: the layout pass renames every node)
-    t_left[idx] = a.ref; t_right[idx] = b.ref; t_count[idx] = a.count + b.count;
     PlocCluster o;
     for (int k = 0; k < 3; k++) { o.lo[k] = fminf(a.lo[k], b.lo[k]); o.hi[k] = fmaxf(a.hi[k], b.hi[k]); }
-    o.ref = (int32_t)idx; o.count = a.count + b.count;
+    o.ref = a.ref; o.count = a.count + b.count;
     c[i] = o;
     valid[i] = 1u;
-    SegBox sb;                                              // slots [n_leaves, 2 n_leaves - 1): the temporary inner nodes
-    sb.lo[0] = o.lo[0]; sb.lo[1] = o.lo[1]; sb.lo[2] = o.lo[2]; sb._a = 0; sb.hi[0] = o.hi[0]; sb.hi[1] = o.hi[1]; sb.hi[2] = o.hi[2]; sb._b = 0;
-    t_box[n_leaves + idx] = sb;
 }
 
+// Survivors close up in order.  The lower slot of a merged pair becomes a new temporary node here.  Its number is a function of the
+// scene: the nodes of earlier rounds (n_leaves less the clusters this round started with) plus the rank of the pair's UPPER slot j
+// among the slots this round drops, j - pos[j].  (It used to come from an atomic counter.  The layout renames every node, but the
+// reinsertion's locks break ties of bit-equal gains by the node's slot -- "A next to B" and "B next to A" gain the same -- so two
+// builds of one scene could differ where two waves' atomics arrived in another order.  tests/builder_ref.py restates this numbering.)
 __global__ __launch_bounds__(256) void k_ploc_compact(const PlocCluster* __restrict__ in, const uint32_t* __restrict__ n_ptr, const uint32_t* __restrict__ valid,
-                                                      const uint32_t* __restrict__ pos, PlocCluster* __restrict__ out, uint32_t* __restrict__ n_out) {
+                                                      const uint32_t* __restrict__ pos, const uint32_t* __restrict__ nn, PlocCluster* __restrict__ out,
+                                                      uint32_t* __restrict__ n_out, int32_t* __restrict__ t_left, int32_t* __restrict__ t_right,
+                                                      uint32_t* __restrict__ t_count, SegBox* __restrict__ t_box, uint32_t n_leaves) {
     const uint32_t n = *n_ptr;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (valid[i]) {
         const float4* s4 = (const float4*)(in + i);
+        float4 a0 = s4[0], a1 = s4[1];                           // (lo, ref), (hi, count)
+        const uint32_t j = nn[i];
+        if (j > i && j < n && nn[j] == i) {                      // merged with j this round
+            const uint32_t idx = (n_leaves - n) + (j - pos[j]);
+            if (idx < n_leaves - 1u) {                           // (always: a round drops n - n_out slots and ends with n_leaves - n_out nodes)
+                t_left[idx] = __float_as_int(a0.w); t_right[idx] = in[j].ref; t_count[idx] = __float_as_uint(a1.w);
+                // slots [n_leaves, 2 n_leaves - 1) of the reinsertion's boxes: the temporary inner nodes
+                float4* b4 = (float4*)(t_box + n_leaves + idx);
+                b4[0] = make_float4(a0.x, a0.y, a0.z, 0.f); b4[1] = make_float4(a1.x, a1.y, a1.z, 0.f);
+                a0.w = __int_as_float((int32_t)idx);
+            }
+        }
         float4* d4 = (float4*)(out + pos[i]);
-        d4[0] = s4[0]; d4[1] = s4[1];
+        d4[0] = a0; d4[1] = a1;
     }
     if (i == n - 1) *n_out = pos[i] + valid[i];
 }
@@ -974,11 +988,11 @@ static hipError_t ploc_build(AccelScratch& s, uint32_t n_tris, TriPacket* d_tris
             const int a = round & 1;
             const dim3 grid((bound + 255) / 256);
             hipLaunchKernelGGL(k_ploc_nearest, grid, dim3(256), 0, stream, (const PlocCluster*)c[a], (const uint32_t*)(cnt + 4 + a), s.ploc_nn);
-            hipLaunchKernelGGL(k_ploc_merge, grid, dim3(256), 0, stream, c[a], (const uint32_t*)(cnt + 4 + a), (const uint32_t*)s.ploc_nn, s.ploc_valid, s.ploc_left,
-                               s.ploc_right, s.ploc_count, cnt, (SegBox*)s.reins_box, n_tris);
+            hipLaunchKernelGGL(k_ploc_merge, grid, dim3(256), 0, stream, c[a], (const uint32_t*)(cnt + 4 + a), (const uint32_t*)s.ploc_nn, s.ploc_valid);
             if ((e = exclusive_scan_u32(s.ploc_scan_temp, s.ploc_valid, s.ploc_pos, (size_t)bound, stream))) return e;
             hipLaunchKernelGGL(k_ploc_compact, grid, dim3(256), 0, stream, (const PlocCluster*)c[a], (const uint32_t*)(cnt + 4 + a), (const uint32_t*)s.ploc_valid,
-                               (const uint32_t*)s.ploc_pos, c[a ^ 1], cnt + 4 + (a ^ 1));
+                               (const uint32_t*)s.ploc_pos, (const uint32_t*)s.ploc_nn, c[a ^ 1], cnt + 4 + (a ^ 1), s.ploc_left, s.ploc_right, s.ploc_count,
+                               (SegBox*)s.reins_box, n_tris);
         }
         uint32_t n_cur = 0;
         if ((e = hipMemcpyAsync(&n_cur, cnt + 4 + (round & 1), 4, hipMemcpyDeviceToHost, stream))) return e;

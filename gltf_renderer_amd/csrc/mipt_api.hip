@@ -233,6 +233,7 @@ public:
         ctx->have_accel = true;
         ctx->accel_state = ACCEL_CLEAN;
         ctx->accel_built = true;
+        ctx->accel_last_was_refit = refit;
         std::fill(ctx->touched.begin(), ctx->touched.end(), (uint8_t)0);
         // The build reports the most stack entries any ray can hold in this tree (a node pushes its other children).  A lane holds 64
         // on chip (LDS + scratch).  A tree that needs more -- long chains of coincident centroids; the reference's driver BVH logs and

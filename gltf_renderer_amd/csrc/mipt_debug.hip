@@ -147,6 +147,24 @@ extern "C" int pt_debug_accel_read(pt_ctx* ctx, uint32_t info[8], void* nodes, v
     return PT_OK;
 }
 
+// test hook (not part of include/mipt.h): the sorted Morton keys of the last full build -- scratch.keys_b, which the sort writes and nothing
+// overwrites afterwards -- for tests/builder_ref.py morton_keys to be compared on its own.  Builds what is pending and drains the stream.
+// out: n uint64, n == n_tris.  An error once the scratch is released or too small for this tree, after a refit (the keys are those of the
+// pose of the build), and for fewer than two triangles (no key is computed).
+extern "C" int pt_debug_accel_keys(pt_ctx* ctx, uint64_t* out, size_t n) {
+    if (!ctx || (n && !out)) return PT_ERR_INVALID_ARGUMENT;
+    ENTER(ctx);
+    if (int r = ensure_accel(ctx)) return r;
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const AccelScratch& s = ctx->scratch;
+    if (n != ctx->n_tris) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_accel_keys: " + std::to_string(n) + " keys asked for, the tree has " + std::to_string(ctx->n_tris) + " triangles");
+    if (n < 2) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_accel_keys: a build of fewer than two triangles computes no key");
+    if (!s.keys_b || s.capacity < n) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_accel_keys: the build's scratch has been released");
+    if (ctx->accel_last_was_refit) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_accel_keys: the last operation was a refit; the keys are those of the last full build");
+    HIPOK(hipMemcpy(out, s.keys_b, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // test hook (not part of include/mipt.h): the motion records (pt_set_motion) pt_trace would write for caller-supplied first rays under `settings`
 // (its cull flag), `params` (the current camera, the image size) and the context's motion config (the previous camera) and snapshot --
 // k_debug_intersect's closest hit, then k_wf_motion's own record function (motion.hip k_debug_motion).  rays: 8 floats each as

@@ -62,6 +62,7 @@ struct pt_ctx {
     std::vector<uint8_t> touched;             // per instance
     pt::DevBuf d_touched;
     uint32_t accel_refits = 0, accel_builds = 0;
+    bool accel_last_was_refit = false;        // the last thing BuildAccel did: the scratch's sorted keys are those of the last full build (pt_debug_accel_keys)
     std::vector<int> free_buffers, free_textures, free_envs;      // destroyed handles, reused by the next create
 
     std::vector<pt::EnvDevice*> envs;

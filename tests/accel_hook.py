@@ -1,5 +1,6 @@
 """Test helper: the acceleration structure as the device holds it -- pt_debug_accel_read, a test hook of libmipt.so that is not part of
-include/mipt.h (csrc/mipt_debug.hip).  tests/accel_ref.py checks what it returns."""
+include/mipt.h (csrc/mipt_debug.hip).  tests/accel_ref.py checks what it returns; accel_keys reads the sorted Morton keys of the last full
+build (pt_debug_accel_keys) for tests/builder_ref.py."""
 import ctypes as C
 import numpy as np
 
@@ -24,3 +25,16 @@ def accel_read(renderer):
     ranges = np.zeros((w, 32), np.uint8) if info[7] else None
     call(nodes, ranges, tris, shade)
     return info.copy(), nodes, ranges, tris, shade
+
+
+def accel_keys(renderer):
+    """Builds what is pending, then -> [n_tris] uint64, the sorted Morton keys of the last full build.  Raises RuntimeError with the library's
+    message after a refit, once the scratch is released, and for fewer than two triangles."""
+    f = renderer.L.pt_debug_accel_keys
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    f.restype = C.c_int
+    n = int(accel_read(renderer)[0][0])
+    out = np.zeros(n, np.uint64)
+    rc = f(renderer.h, out.ctypes.data_as(C.c_void_p), n)
+    if rc != 0: raise RuntimeError("pt_debug_accel_keys: %d %s" % (rc, renderer.L.pt_last_error(renderer.h).decode()))
+    return out

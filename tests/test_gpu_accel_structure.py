@@ -1,6 +1,7 @@
 """The acceleration structure the device builds, read back (pt_debug_accel_read, tests/accel_hook.py) and checked node by node by
 tests/accel_ref.py check_tree (its docstring lists every invariant and where each bound comes from; tests/test_accel_check_host.py shows that
 each can fail).  Run with -m gpu on an MI355X.  No ray is traced here: a case is a build (or a refit) plus a host check.
+This file asks whether the device built A correct tree; WHICH tree -- the one the builder is meant to build -- is tests/test_gpu_builder_topology.py.
 
 For all three builders (PT_BUILDER_LBVH, _PLOC, _PLOC_REINSERT), in a fresh context each:
   sizes      seeded random soups in three instances (non-indexed; 16- or 32-bit indices under a rotation and an uneven scale; mirrored) of
