@@ -1,4 +1,6 @@
-// bake.hip -- texture-space baking (pt_set_bake, include/mipt.h): the coverage map's UV rasteriser and pt_bake_dilate's passes.
+// bake.hip -- texture-space baking (pt_set_bake, include/mipt.h): the coverage map's UV rasteriser, pt_bake_dilate's passes, and the host side:
+// the setter, bake_setup -- which rebuilds the map when it no longer stands for the call's atlas size, config and state of the tree (pt_ctx's
+// bake_ready, bake_w / bake_h, bake_built, bake_accel), for pt_trace and the hook pt_debug_bake_rays -- and the two entry points that read it.
 //
 // Coverage: which triangle owns each texel of the W x H atlas -- the covering triangle with the least (instance, primitive) pair.  The
 // rasteriser runs over the built tree's TriPacket / ShadePacket arrays (UVs and ids are de-indexed there).  A chart may be two triangles
@@ -12,6 +14,9 @@
 //   k_bake_bins<1>  the same walk again: the triangle whose key the texel holds writes its index into the owner map.  (instance, primitive)
 //                   names one triangle, so a texel has one writer and the map depends on neither triangle order nor scheduling.
 // Compiled without floating-point contraction (Makefile): the edge functions are pt_bake.h's, rounding for rounding tests/bake_ref.py's.
+#include <cmath>
+
+#include "pt_ctx.h"
 #include "pt_bake.h"
 
 namespace pt {
@@ -169,4 +174,78 @@ hipError_t launch_bake_dilate(float4* image, const uint32_t* owner, uint32_t w, 
     return hipGetLastError();
 }
 
+int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake) {
+    const uint64_t accel = (uint64_t)ctx->accel_builds + ctx->accel_refits;
+    const size_t texels = (size_t)width * height;
+    if (!ctx->bake_ready || ctx->bake_w != width || ctx->bake_h != height || memcmp(&ctx->bake_built, &ctx->bake, sizeof(pt_bake_config)) != 0 || ctx->bake_accel != accel) {
+        ctx->bake_ready = false;
+        hipError_t e = ctx->d_bake_keys.reserve(ctx->stream, texels * 8, texels * 8);
+        if (e == hipSuccess) e = ctx->d_bake_owner.reserve(ctx->stream, texels * 4, texels * 4);
+        const size_t scratch = bake_coverage_scratch_bytes(ctx->n_tris);
+        if (e == hipSuccess) e = ctx->d_bake_scratch.reserve(ctx->stream, scratch, scratch + scratch / 8);
+        if (e != hipSuccess) return grow_failed(ctx, e, "bake coverage map: " + std::to_string(texels * 12 + scratch) + " bytes");
+        const BakeRaster r = {ctx->d_tris.as<TriPacket>(), ctx->d_shade.as<ShadePacket>(), ctx->d_instances.as<InstanceRec>(), ctx->n_tris, width, height,
+                              ctx->bake.tex_coord, ctx->bake.instance};
+        std::string why;
+        e = bake_coverage_build(r, ctx->d_bake_keys.as<unsigned long long>(), ctx->d_bake_owner.as<uint32_t>(), ctx->d_bake_scratch.ptr, ctx->stream, why);
+        if (e != hipSuccess) return why.empty() ? ctx->fail(PT_ERR_DEVICE, std::string("bake coverage map: ") + hipGetErrorString(e)) : ctx->fail(PT_ERR_CAPACITY, "bake coverage map: " + why);
+        ctx->bake_w = width; ctx->bake_h = height; ctx->bake_built = ctx->bake; ctx->bake_accel = accel; ctx->bake_ready = true;
+    }
+    bake.owner = ctx->d_bake_owner.as<uint32_t>(); bake.tris = ctx->d_tris.as<TriPacket>(); bake.shade = ctx->d_shade.as<ShadePacket>();
+    bake.surface_offset = ctx->bake.surface_offset; bake.tex_coord = ctx->bake.tex_coord;
+    return PT_OK;
+}
+
 }  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: config is NULL");
+    if (config->enable) {
+        if (config->tex_coord != 0 && config->tex_coord != 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: tex_coord must be 0 or 1");
+        if (config->instance < -1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance must be -1 or a row of the instance table");
+        if (!std::isfinite(config->surface_offset) || !(config->surface_offset > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: surface_offset must be finite and > 0");
+        if (ctx->probes.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: probes are enabled (pt_set_probes): a trace renders one atlas or the other");
+    }
+    ctx->bake = *config;
+    ctx->restart_pending = true;
+    return PT_OK;
+}
+
+int pt_bake_coverage(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* instance_out, uint32_t* primitive_out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
+    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_coverage: size differs from the coverage map's");
+    ENTER(ctx);
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    const size_t n = (size_t)width * height;
+    std::vector<unsigned long long> keys(n);
+    HIPOK(hipMemcpy(keys.data(), ctx->d_bake_keys.ptr, n * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        const bool none = keys[i] == ~0ull;
+        if (instance_out) instance_out[i] = none ? -1 : (int32_t)(keys[i] >> 32);
+        if (primitive_out) primitive_out[i] = none ? 0xffffffffu : (uint32_t)keys[i];
+    }
+    return PT_OK;
+}
+
+int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, int passes) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!image) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: null image");
+    if (width == 0 || height == 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: bad size");
+    if (passes < 1 || passes > 64) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: passes outside 1..64");
+    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
+    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: size differs from the coverage map's");
+    ENTER(ctx);
+    const size_t n = (size_t)width * height, need = n * 16 + 2 * n;
+    if (const hipError_t e = ctx->d_bake_dilate.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "bake_dilate scratch: " + std::to_string(need) + " bytes");
+    HIPOK(launch_bake_dilate((float4*)image, ctx->d_bake_owner.as<uint32_t>(), width, height, passes, ctx->d_bake_dilate.as<float4>(),
+                             ctx->d_bake_dilate.as<uint8_t>() + n * 16, ctx->stream));
+    return PT_OK;
+}
+
+}  // extern "C"

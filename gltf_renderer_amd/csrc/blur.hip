@@ -128,11 +128,6 @@ __global__ __launch_bounds__(kBlurLanes) void k_blur_gather(const BlurArgs a) {
     a.out[p] = make_float4(sr / sw, sg / sw, sb / sw, c.w);
 }
 
-bool blur_ranges_overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
 }  // namespace
 
 hipError_t launch_motion_blur(const BlurArgs& a, hipStream_t stream) {
@@ -161,7 +156,7 @@ int pt_motion_blur(pt_ctx* ctx, const pt_motion_blur_config* config, const void*
     if (cfg.taps < 2 || cfg.taps > 64) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion_blur: taps outside 2..64");
     if (!std::isfinite(cfg.depth_softness) || !(cfg.depth_softness > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion_blur: depth_softness must be finite and > 0");
     const size_t n = (size_t)width * height, bytes = n * 16;
-    if (blur_ranges_overlap(out, color, bytes) || blur_ranges_overlap(out, motion, bytes))
+    if (ranges_overlap(out, bytes, color, bytes) || ranges_overlap(out, bytes, motion, bytes))
         return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion_blur: out overlaps an input (there is no in-place mode)");
     ENTER(ctx);
     BlurArgs a;

@@ -5,10 +5,10 @@
 //   k_dn_pass      pass i: 25 taps at spacing 2^i, dy outer, dx inner, sequential sums -- from one signal image to the other
 //   k_dn_pass<1>   the last pass, which multiplies the albedo back and writes the caller's image (invalid pixels: the input's bits)
 // Compiled without floating-point contraction (Makefile), with IEEE division and square root: apart from expf the arithmetic is that of
-// the float32 restatement, rounding for rounding.
-#include <hip/hip_runtime.h>
+// the float32 restatement, rounding for rounding.  (tools/denoise_host_rehearsal.py compiles the file's first anonymous namespace.)
+#include <cmath>
 
-#include "pt_host.h"
+#include "pt_ctx.h"
 
 namespace pt {
 namespace {
@@ -158,3 +158,34 @@ hipError_t launch_denoise(const pt_denoise_config& cfg, const float4* color, con
 }
 
 }  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config, const void* color, const void* albedo, const void* normal_depth,
+               uint32_t width, uint32_t height, void* out) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!color || !albedo || !normal_depth || !out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: null image");
+    if (width == 0 || height == 0 || width > (1u << 30) || height > (1u << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: bad size");
+    pt_denoise_config cfg = {5, 1, 7, 0.02f, 1.0f};
+    if (config) cfg = *config;
+    if (cfg.iterations < 0 || cfg.iterations > 6) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: iterations outside 0..6");
+    if (cfg.normal_power_log2 < 0 || cfg.normal_power_log2 > 10) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: normal_power_log2 outside 0..10");
+    if (!std::isfinite(cfg.sigma_depth) || !(cfg.sigma_depth > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_depth must be finite and > 0");
+    if (!std::isfinite(cfg.sigma_color) || cfg.sigma_color < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_color must be finite and >= 0");
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    if (ranges_overlap(out, bytes, albedo, bytes) || ranges_overlap(out, bytes, normal_depth, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out aliases a guide image");
+    if (out != color && ranges_overlap(out, bytes, color, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out overlaps color without being color");
+    ENTER(ctx);
+    if (cfg.iterations == 0) {                  // the identity: a copy, or nothing in place
+        if (out != color) HIPOK(hipMemcpyAsync(out, color, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return PT_OK;
+    }
+    if (3 * bytes != ctx->d_denoise.cap) HIPOK(ctx->d_denoise.realloc(ctx->stream, 3 * bytes));      // for this size alone: a smaller image reallocates too
+    float4* s = ctx->d_denoise.as<float4>();
+    HIPOK(launch_denoise(cfg, (const float4*)color, (const float4*)albedo, (const float4*)normal_depth, width, height, (float4*)out, s, s + n, s + 2 * n, ctx->stream));
+    return PT_OK;
+}
+
+}  // extern "C"

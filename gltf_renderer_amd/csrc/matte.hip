@@ -1,8 +1,9 @@
-// matte.hip -- ID mattes (pt_set_matte, include/mipt.h): the entry points that need no path-tracing kernel.
+// matte.hip -- ID mattes (pt_set_matte, include/mipt.h): the entry points that need no path-tracing kernel, and a call's matte_setup.
 //
 //   pt_matte_id       MurmurHash3_x86_32 (seed 0) of a name, then the exponent fix (pt_matte.h): Cryptomatte's id of a name.  Host only.
-//   pt_set_matte      checks and keeps the config and the caller's ids; the device table of ids is made by the next pt_trace (mipt_api.hip),
-//                     which knows the instance and material tables the ids are for.
+//   pt_set_matte      checks and keeps the config and the caller's ids, and marks the device table of ids stale (matte_table_kind = -1).
+//   matte_setup       makes that table for the pt_trace that calls it (mipt_api.hip PathtraceScene), which knows the instance and material
+//                     tables the ids are for -- unless it stands for this kind and this many rows -- and fills what the matte kernels take.
 //   pt_matte_extract  k_matte_extract: one lane per pixel reads the pixel's K / 2 float4 and adds up, in rank order, the coverages whose id
 //                     is in the caller's set.  The set (at most 64 ids, fixed on the host) travels in the kernel's arguments: the lanes of
 //                     a wave compare against scalar registers, nothing is allocated or copied, and the call is one launch on the stream.
@@ -42,6 +43,30 @@ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 void launch_matte_extract(const float4* const layers[4], int ranks, uint32_t pixels, const MatteExtractIds& ids, int count, float* mask, hipStream_t stream) {
     hipLaunchKernelGGL(k_matte_extract, dim3((pixels + kExtractBlock - 1) / kExtractBlock), dim3(kExtractBlock), 0, stream, layers[0], layers[1], layers[2], layers[3],
                        ranks, pixels, ids, count, mask);
+}
+
+int matte_setup(pt_ctx* ctx, MatteArgs& matte) {
+    const int kind = ctx->matte.kind;
+    const size_t rows = kind == PT_MATTE_MATERIAL ? (size_t)ctx->n_materials : ctx->instances.size();
+    if (ctx->matte_table_kind != kind || ctx->matte_table_rows != rows) {
+        // row i: the caller's id if it gave one, else the id of the default name "instance_<i>" / "material_<i>"
+        ctx->matte_table_kind = -1;
+        std::vector<uint32_t> table(rows ? rows : 1, 0u);
+        for (size_t i = 0; i < rows; i++) {
+            if (i < ctx->matte_user_ids.size()) { table[i] = ctx->matte_user_ids[i]; continue; }
+            const std::string name = (kind == PT_MATTE_MATERIAL ? "material_" : "instance_") + std::to_string(i);
+            table[i] = pt_matte_id(name.data(), name.size());
+        }
+        // a trace in flight may still read the old table: the copy goes behind it on the stream, a larger table drains it first (DevBuf)
+        const size_t bytes = table.size() * 4;
+        if (const hipError_t e = ctx->d_matte_ids.reserve(ctx->stream, bytes, bytes + bytes / 2)) return grow_failed(ctx, e, "matte id table: " + std::to_string(bytes) + " bytes");
+        if (const hipError_t e = staged_upload(ctx, ctx->d_matte_ids.ptr, table.data(), bytes)) return ctx->fail(PT_ERR_DEVICE, std::string("matte id table: ") + hipGetErrorString(e));
+        ctx->matte_table_kind = kind; ctx->matte_table_rows = rows;
+    }
+    matte.rec = nullptr; matte.ids = ctx->d_matte_ids.as<uint32_t>(); matte.n_ids = (uint32_t)rows;
+    matte.kind = kind; matte.ranks = ctx->matte.ranks;
+    for (int j = 0; j < 4; j++) matte.layers[j] = j < ctx->matte.ranks / 2 ? (float4*)ctx->matte.layers[j] : nullptr;
+    return PT_OK;
 }
 
 }  // namespace pt
@@ -89,7 +114,7 @@ int pt_set_matte(pt_ctx* ctx, const pt_matte_config* config, const uint32_t* ids
     ctx->matte = *config;
     ctx->matte_user_ids.resize((size_t)config->id_count);
     for (int i = 0; i < config->id_count; i++) ctx->matte_user_ids[(size_t)i] = matte_fix(ids[i]);
-    ctx->matte_table_kind = -1;                    // the device table is made anew by the next matte pt_trace
+    ctx->matte_table_kind = -1;                    // the device table is made anew by the next matte pt_trace (matte_setup)
     ctx->restart_pending = true;
     return PT_OK;
 }

@@ -7,10 +7,13 @@
 //   class GpuSkin      <- Source/GpuSkin.{h,cpp}: Create / Run
 //   class EnvironmentMap <- Source/EnvironmentMap.{h,cpp}: CreateEnvironmentMap (cube + importance only)
 //   ResourceTable      <- the bindless descriptor heap (DescriptorAllocator.h), as raw device pointers
-// This file is the product: context lifetime, resources, scene tables, trace, skin, post, accumulation, exchange.  The context itself is
+// This file is the core of the product: context lifetime, resources, scene tables, trace (with select_passes, where a call's optional passes
+// are weighed against each other), camera and lens, adaptive sampling and pt_accum_*, skin, post, exchange.  A feature that has a file keeps
+// its setter, *_setup and entry points there (bake, probe, matte, motion, blur, variance, denoise .hip).  The context itself is
 // in pt_ctx.h, the owner of its device arrays in dev_buf.h, the test hooks (pt_debug_*) in mipt_debug.hip.
 // There is no CPU fallback anywhere in this file: every compute entry point launches HIP kernels.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,10 +23,8 @@
 
 using namespace pt;
 
-namespace {
-
-// Host -> device through a pinned slot of the ring, asynchronous on the context's stream.
-hipError_t staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes) {
+// (pt_ctx.h)
+hipError_t pt::staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (bytes == 0) return hipSuccess;
     StagingRing& r = ctx->staging;
     const int k = r.next;
@@ -44,6 +45,13 @@ hipError_t staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes) 
     r.pending[k] = true;
     return hipSuccess;
 }
+int pt::grow_failed(pt_ctx* ctx, hipError_t e, const std::string& what) {
+    if (e != hipErrorOutOfMemory) return ctx->fail(PT_ERR_DEVICE, std::string("hipStreamSynchronize(ctx->stream): ") + hipGetErrorString(e));
+    (void)hipGetLastError();
+    return ctx->fail(PT_ERR_OUT_OF_MEMORY, what);
+}
+
+namespace {
 
 template <typename T>
 hipError_t upload_table(pt_ctx* ctx, DevBuf& d, const std::vector<T>& h) {
@@ -53,13 +61,6 @@ hipError_t upload_table(pt_ctx* ctx, DevBuf& d, const std::vector<T>& h) {
     return staged_upload(ctx, d.ptr, h.data(), h.size() * sizeof(T));
 }
 
-// What a grow that answers an exhausted device with PT_ERR_OUT_OF_MEMORY and its own text returns (anything else DevBuf::realloc
-// fails with is its synchronise)
-int grow_failed(pt_ctx* ctx, hipError_t e, const std::string& what) {
-    if (e != hipErrorOutOfMemory) return ctx->fail(PT_ERR_DEVICE, std::string("hipStreamSynchronize(ctx->stream): ") + hipGetErrorString(e));
-    (void)hipGetLastError();
-    return ctx->fail(PT_ERR_OUT_OF_MEMORY, what);
-}
 // The adaptive tile state (`tiles` AdaptiveTile) and half buffer (`px` float4), reallocated together when either is too small; what they
 // held is gone then, and with it what pt_adaptive_read could show (PathtraceScene and pt_accum_load fill them next)
 int adaptive_state(pt_ctx* ctx, size_t tiles, size_t px) {
@@ -125,6 +126,12 @@ size_t format_stride(int f) {
         case PT_FORMAT_JOINT_WEIGHT: return 16;
         default: return 0;
     }
+}
+
+// A material's texture slots in the order of RMat::tex (pt_types.h SLOT_*)
+std::array<const pt_texture_sample*, SLOT_COUNT> material_slots(const pt_material& s) {
+    return {&s.normal, &s.albedo, &s.metallic_roughness, &s.occlusion, &s.emissive, &s.specular, &s.specular_color, &s.clearcoat,
+            &s.clearcoat_roughness, &s.clearcoat_normal, &s.anisotropy, &s.sheen_color, &s.sheen_roughness, &s.transmission, &s.thickness};
 }
 
 // Workgroups per stage launch.  256 CUs hold 6 resident 256-thread workgroups of the trace stages (LDS- and VGPR-limited): 1536
@@ -510,50 +517,6 @@ int adaptive_setup(pt_ctx* ctx, const pt_execute_params* ep, const FrameConstant
     ctx->ad_my_tiles = fc.my_tiles; ctx->ad_ready = true;
     return PT_OK;
 }
-int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake) {
-    const uint64_t accel = (uint64_t)ctx->accel_builds + ctx->accel_refits;
-    const size_t texels = (size_t)width * height;
-    if (!ctx->bake_ready || ctx->bake_w != width || ctx->bake_h != height || memcmp(&ctx->bake_built, &ctx->bake, sizeof(pt_bake_config)) != 0 || ctx->bake_accel != accel) {
-        ctx->bake_ready = false;
-        hipError_t e = ctx->d_bake_keys.reserve(ctx->stream, texels * 8, texels * 8);
-        if (e == hipSuccess) e = ctx->d_bake_owner.reserve(ctx->stream, texels * 4, texels * 4);
-        const size_t scratch = bake_coverage_scratch_bytes(ctx->n_tris);
-        if (e == hipSuccess) e = ctx->d_bake_scratch.reserve(ctx->stream, scratch, scratch + scratch / 8);
-        if (e != hipSuccess) return grow_failed(ctx, e, "bake coverage map: " + std::to_string(texels * 12 + scratch) + " bytes");
-        const BakeRaster r = {ctx->d_tris.as<TriPacket>(), ctx->d_shade.as<ShadePacket>(), ctx->d_instances.as<InstanceRec>(), ctx->n_tris, width, height,
-                              ctx->bake.tex_coord, ctx->bake.instance};
-        std::string why;
-        e = bake_coverage_build(r, ctx->d_bake_keys.as<unsigned long long>(), ctx->d_bake_owner.as<uint32_t>(), ctx->d_bake_scratch.ptr, ctx->stream, why);
-        if (e != hipSuccess) return why.empty() ? ctx->fail(PT_ERR_DEVICE, std::string("bake coverage map: ") + hipGetErrorString(e)) : ctx->fail(PT_ERR_CAPACITY, "bake coverage map: " + why);
-        ctx->bake_w = width; ctx->bake_h = height; ctx->bake_built = ctx->bake; ctx->bake_accel = accel; ctx->bake_ready = true;
-    }
-    bake.owner = ctx->d_bake_owner.as<uint32_t>(); bake.tris = ctx->d_tris.as<TriPacket>(); bake.shade = ctx->d_shade.as<ShadePacket>();
-    bake.surface_offset = ctx->bake.surface_offset; bake.tex_coord = ctx->bake.tex_coord;
-    return PT_OK;
-}
-int matte_setup(pt_ctx* ctx, MatteArgs& matte) {
-    const int kind = ctx->matte.kind;
-    const size_t rows = kind == PT_MATTE_MATERIAL ? (size_t)ctx->n_materials : ctx->instances.size();
-    if (ctx->matte_table_kind != kind || ctx->matte_table_rows != rows) {
-        // row i: the caller's id if it gave one, else the id of the default name "instance_<i>" / "material_<i>"
-        ctx->matte_table_kind = -1;
-        std::vector<uint32_t> table(rows ? rows : 1, 0u);
-        for (size_t i = 0; i < rows; i++) {
-            if (i < ctx->matte_user_ids.size()) { table[i] = ctx->matte_user_ids[i]; continue; }
-            const std::string name = (kind == PT_MATTE_MATERIAL ? "material_" : "instance_") + std::to_string(i);
-            table[i] = pt_matte_id(name.data(), name.size());
-        }
-        // a trace in flight may still read the old table: the copy goes behind it on the stream, a larger table drains it first (DevBuf)
-        const size_t bytes = table.size() * 4;
-        if (const hipError_t e = ctx->d_matte_ids.reserve(ctx->stream, bytes, bytes + bytes / 2)) return grow_failed(ctx, e, "matte id table: " + std::to_string(bytes) + " bytes");
-        if (const hipError_t e = staged_upload(ctx, ctx->d_matte_ids.ptr, table.data(), bytes)) return ctx->fail(PT_ERR_DEVICE, std::string("matte id table: ") + hipGetErrorString(e));
-        ctx->matte_table_kind = kind; ctx->matte_table_rows = rows;
-    }
-    matte.rec = nullptr; matte.ids = ctx->d_matte_ids.as<uint32_t>(); matte.n_ids = (uint32_t)rows;
-    matte.kind = kind; matte.ranks = ctx->matte.ranks;
-    for (int j = 0; j < 4; j++) matte.layers[j] = j < ctx->matte.ranks / 2 ? (float4*)ctx->matte.layers[j] : nullptr;
-    return PT_OK;
-}
 int ensure_accel(pt_ctx* ctx) {
     return ctx->accel_state != ACCEL_CLEAN || !ctx->accel_built || ctx->instances_dirty ? Pathtracer::BuildAccel(ctx) : PT_OK;
 }
@@ -747,10 +710,7 @@ int pt_scene_set_materials(pt_ctx* ctx, const pt_material* m, int count) {
                                                 ", the new table has " + std::to_string(count) + " (replace the instances first)");
     ENTER(ctx);
     for (int i = 0; i < count; i++) {
-        const pt_texture_sample* slots[15] = {&m[i].normal, &m[i].albedo, &m[i].metallic_roughness, &m[i].occlusion, &m[i].emissive, &m[i].specular,
-                                              &m[i].specular_color, &m[i].clearcoat, &m[i].clearcoat_roughness, &m[i].clearcoat_normal, &m[i].anisotropy,
-                                              &m[i].sheen_color, &m[i].sheen_roughness, &m[i].transmission, &m[i].thickness};
-        for (auto* s : slots) {
+        for (auto* s : material_slots(m[i])) {
             if (s->descriptor < -1 || s->descriptor >= (int)ctx->textures.size() || (s->descriptor >= 0 && !ctx->textures[s->descriptor].texels))
                 return ctx->fail(PT_ERR_BAD_HANDLE, "material texture descriptor out of range or destroyed");
             if (s->sampler < 0 || s->sampler >= (int)ctx->samplers.size()) return ctx->fail(PT_ERR_BAD_HANDLE, "material sampler out of range");
@@ -772,9 +732,7 @@ int pt_scene_set_materials(pt_ctx* ctx, const pt_material* m, int count) {
         r.anisotropy_cos = (float)cos((double)s.anisotropy_rotation); r.anisotropy_sin = (float)sin((double)s.anisotropy_rotation);   // correctly rounded, like the kernels' (pt_math.h pt_sincos)
         memcpy(r.sheen_color_factor, s.sheen_color_factor, 12); r.sheen_roughness_factor = s.sheen_roughness_factor;
         r.transmission_factor = s.transmission_factor;
-        const pt_texture_sample* slots[SLOT_COUNT] = {&s.normal, &s.albedo, &s.metallic_roughness, &s.occlusion, &s.emissive, &s.specular,
-                                                      &s.specular_color, &s.clearcoat, &s.clearcoat_roughness, &s.clearcoat_normal, &s.anisotropy,
-                                                      &s.sheen_color, &s.sheen_roughness, &s.transmission, &s.thickness};
+        const auto slots = material_slots(s);
         for (int k = 0; k < SLOT_COUNT; k++) {
             const pt_texture_sample& a = *slots[k];
             RTex& t = r.tex[k];
@@ -1049,15 +1007,6 @@ int pt_set_aov(pt_ctx* ctx, const pt_aov_config* config) {
     return PT_OK;
 }
 
-int pt_set_variance(pt_ctx* ctx, const pt_variance_config* config) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: config is NULL");
-    if (config->enable && !config->variance) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: the target is NULL");
-    ctx->variance = *config;
-    ctx->restart_pending = true;
-    return PT_OK;
-}
-
 int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "lens: config is NULL");
@@ -1069,116 +1018,6 @@ int pt_set_lens(pt_ctx* ctx, const pt_lens_config* config) {
     }
     ctx->lens = *config;
     ctx->restart_pending = true;
-    return PT_OK;
-}
-
-int pt_set_bake(pt_ctx* ctx, const pt_bake_config* config) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: config is NULL");
-    if (config->enable) {
-        if (config->tex_coord != 0 && config->tex_coord != 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: tex_coord must be 0 or 1");
-        if (config->instance < -1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: instance must be -1 or a row of the instance table");
-        if (!std::isfinite(config->surface_offset) || !(config->surface_offset > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: surface_offset must be finite and > 0");
-        if (ctx->probes.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake: probes are enabled (pt_set_probes): a trace renders one atlas or the other");
-    }
-    ctx->bake = *config;
-    ctx->restart_pending = true;
-    return PT_OK;
-}
-
-int pt_bake_coverage(pt_ctx* ctx, uint32_t width, uint32_t height, int32_t* instance_out, uint32_t* primitive_out) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
-    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_coverage: size differs from the coverage map's");
-    ENTER(ctx);
-    HIPOK(hipStreamSynchronize(ctx->stream));
-    const size_t n = (size_t)width * height;
-    std::vector<unsigned long long> keys(n);
-    HIPOK(hipMemcpy(keys.data(), ctx->d_bake_keys.ptr, n * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) {
-        const bool none = keys[i] == ~0ull;
-        if (instance_out) instance_out[i] = none ? -1 : (int32_t)(keys[i] >> 32);
-        if (primitive_out) primitive_out[i] = none ? 0xffffffffu : (uint32_t)keys[i];
-    }
-    return PT_OK;
-}
-
-int pt_bake_dilate(pt_ctx* ctx, void* image, uint32_t width, uint32_t height, int passes) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!image) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: null image");
-    if (width == 0 || height == 0) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: bad size");
-    if (passes < 1 || passes > 64) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: passes outside 1..64");
-    if (!ctx->bake_ready) return ctx->fail(PT_ERR_NOT_READY, "no bake trace yet");
-    if (width != ctx->bake_w || height != ctx->bake_h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bake_dilate: size differs from the coverage map's");
-    ENTER(ctx);
-    const size_t n = (size_t)width * height, need = n * 16 + 2 * n;
-    if (const hipError_t e = ctx->d_bake_dilate.reserve(ctx->stream, need, need)) return grow_failed(ctx, e, "bake_dilate scratch: " + std::to_string(need) + " bytes");
-    HIPOK(launch_bake_dilate((float4*)image, ctx->d_bake_owner.as<uint32_t>(), width, height, passes, ctx->d_bake_dilate.as<float4>(),
-                             ctx->d_bake_dilate.as<uint8_t>() + n * 16, ctx->stream));
-    return PT_OK;
-}
-
-int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* positions_xyz) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: config is NULL");
-    if (!config->enable) {                        // nothing else of a disabled config is looked at; the layout and the positions go
-        ctx->probes.enable = 0;
-        ctx->restart_pending = true;
-        return PT_OK;
-    }
-    if (!positions_xyz) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: positions_xyz is NULL");
-    if (config->resolution < 16 || config->resolution > 1024 || config->resolution % 16 != 0)
-        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: resolution must be a multiple of 16 in 16..1024");
-    if (config->count < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: count must be >= 1");
-    if (config->columns < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns must be >= 1");
-    if (!std::isfinite(config->max_distance) || !(config->max_distance > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: max_distance must be finite and > 0");
-    uint64_t w, h;
-    probe_atlas_size(*config, w, h);
-    if (w > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns * resolution = " + std::to_string(w) + " exceeds 2^30");
-    if (h > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: rows * resolution = " + std::to_string(h) + " (count / columns rows) exceeds 2^30");
-    for (int64_t i = 0; i < (int64_t)config->count * 3; i++)
-        if (!std::isfinite(positions_xyz[i])) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the position of probe " + std::to_string(i / 3) + " is not finite");
-    if (ctx->bake.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: a bake is enabled (pt_set_bake): a trace renders one atlas or the other");
-    ENTER(ctx);
-    const size_t bytes = (size_t)config->count * 12;
-    // a trace in flight may still read the old positions: the copy goes behind it on the stream, a larger array drains it first (DevBuf)
-    if (const hipError_t e = ctx->d_probe_pos.reserve(ctx->stream, bytes, bytes)) {
-        if (ctx->d_probe_pos.ptr == nullptr) { ctx->probes.enable = 0; ctx->restart_pending = true; }     // the old array went with the failed growth
-        return grow_failed(ctx, e, "probe positions: " + std::to_string(bytes) + " bytes");
-    }
-    if (const hipError_t e = staged_upload(ctx, ctx->d_probe_pos.ptr, positions_xyz, bytes)) {
-        ctx->probes.enable = 0; ctx->restart_pending = true;               // the array may hold part of either set: back to the camera
-        return ctx->fail(PT_ERR_DEVICE, std::string("probe positions: ") + hipGetErrorString(e));
-    }
-    ctx->probes = *config;
-    ctx->restart_pending = true;
-    return PT_OK;
-}
-
-int pt_probe_project(pt_ctx* ctx, const void* atlas_device, uint32_t width, uint32_t height, int kind, float* sh_host) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!atlas_device || !sh_host) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: NULL argument");
-    if (kind != PT_PROBE_SH_RADIANCE && kind != PT_PROBE_SH_IRRADIANCE) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: kind must be PT_PROBE_SH_RADIANCE or PT_PROBE_SH_IRRADIANCE");
-    if (!ctx->probes.enable) return ctx->fail(PT_ERR_NOT_READY, "probe_project: no probes are set");
-    uint64_t w, h;
-    probe_atlas_size(ctx->probes, w, h);
-    if (width != w || height != h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: the atlas is " + std::to_string(w) + " x " + std::to_string(h));
-    ENTER(ctx);
-    const uint32_t n = (uint32_t)ctx->probes.resolution, count = (uint32_t)ctx->probes.count;
-    if (ctx->probe_dirs_n != n) {
-        const size_t bytes = (size_t)n * n * 16;
-        ctx->probe_dirs_n = 0;
-        if (const hipError_t e = ctx->d_probe_dirs.reserve(ctx->stream, bytes, bytes)) return grow_failed(ctx, e, "probe direction table: " + std::to_string(bytes) + " bytes");
-        launch_probe_dirs(ctx->d_probe_dirs.as<float4>(), n, ctx->stream);
-        HIPOK(hipGetLastError());
-        ctx->probe_dirs_n = n;
-    }
-    const size_t out_bytes = (size_t)count * 27 * 4;
-    if (const hipError_t e = ctx->d_probe_sh.reserve(ctx->stream, out_bytes, out_bytes)) return grow_failed(ctx, e, "probe coefficients: " + std::to_string(out_bytes) + " bytes");
-    launch_probe_project((const float4*)atlas_device, ctx->d_probe_dirs.as<float4>(), n, count, (uint32_t)ctx->probes.columns, kind, ctx->d_probe_sh.as<float>(), ctx->stream);
-    HIPOK(hipGetLastError());
-    HIPOK(hipMemcpyAsync(sh_host, ctx->d_probe_sh.ptr, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPOK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
 
@@ -1197,10 +1036,7 @@ int pt_lens_focus_at(pt_ctx* ctx, const pt_settings* settings, const pt_execute_
     camera_constants(cam, params, fc);
     TempBuf d_out, d_deep;
     if (d_out.alloc(8) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: result buffer"); }
-    if (const uint32_t entries = deep_stack_entries(ctx)) {
-        if (d_deep.alloc((size_t)entries * 256 * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "lens_focus_at: deep stack"); }
-        sc.deep_stack = d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = 256;
-    }
+    if (int r = temp_deep_stack(ctx, sc, d_deep, 256, "lens_focus_at: deep stack")) return r;
     launch_lens_focus(sc, fc, cam.lens, px, py, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, d_out.as<float>(), ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
     float res[2] = {0.0f, 0.0f};
     hipError_t e = hipGetLastError();
@@ -1319,37 +1155,6 @@ int pt_tonemap(pt_ctx* ctx, const pt_tonemap_config* cfg, const void* device_rgb
     HIPOK(hipStreamSynchronize(ctx->stream));
     if (host_rgb) HIPOK(hipMemcpy(host_rgb, d_rgb, n * 12, hipMemcpyDeviceToHost));
     if (host_rgba8) HIPOK(hipMemcpy(host_rgba8, d_q, n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// ---- the a-trous denoiser over the first-hit AOVs (denoise.hip) ----------------------------------------------------------------
-static bool images_overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
-int pt_denoise(pt_ctx* ctx, const pt_denoise_config* config, const void* color, const void* albedo, const void* normal_depth,
-               uint32_t width, uint32_t height, void* out) {
-    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
-    if (!color || !albedo || !normal_depth || !out) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: null image");
-    if (width == 0 || height == 0 || width > (1u << 30) || height > (1u << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: bad size");
-    pt_denoise_config cfg = {5, 1, 7, 0.02f, 1.0f};
-    if (config) cfg = *config;
-    if (cfg.iterations < 0 || cfg.iterations > 6) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: iterations outside 0..6");
-    if (cfg.normal_power_log2 < 0 || cfg.normal_power_log2 > 10) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: normal_power_log2 outside 0..10");
-    if (!std::isfinite(cfg.sigma_depth) || !(cfg.sigma_depth > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_depth must be finite and > 0");
-    if (!std::isfinite(cfg.sigma_color) || cfg.sigma_color < 0.0f) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigma_color must be finite and >= 0");
-    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
-    if (images_overlap(out, albedo, bytes) || images_overlap(out, normal_depth, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out aliases a guide image");
-    if (out != color && images_overlap(out, color, bytes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "denoise: out overlaps color without being color");
-    ENTER(ctx);
-    if (cfg.iterations == 0) {                  // the identity: a copy, or nothing in place
-        if (out != color) HIPOK(hipMemcpyAsync(out, color, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        return PT_OK;
-    }
-    if (3 * bytes != ctx->d_denoise.cap) HIPOK(ctx->d_denoise.realloc(ctx->stream, 3 * bytes));      // for this size alone: a smaller image reallocates too
-    float4* s = ctx->d_denoise.as<float4>();
-    HIPOK(launch_denoise(cfg, (const float4*)color, (const float4*)albedo, (const float4*)normal_depth, width, height, (float4*)out, s, s + n, s + 2 * n, ctx->stream));
     return PT_OK;
 }
 

@@ -1,12 +1,40 @@
 // mipt_debug.hip -- the test hooks of libmipt.so (pt_debug_*, not part of include/mipt.h): the product's own device code run on the
 // caller's queries, for tests/ and tools/ to compare with the oracle.  Host code only: this file has no kernel; what the hooks launch is in
-// pt_kernel.hip and pt_wavefront.hip.  The product itself is mipt_api.hip.
+// pt_kernel.hip, pt_wavefront.hip and motion.hip.  The product itself is mipt_api.hip and the feature files beside it.
 #include <cstdio>
 #include <cstdlib>
 
 #include "pt_ctx.h"
 
 using namespace pt;
+
+namespace {
+
+// The shape the per-lane query hooks share.  Every input and output gets a temporary device array; the inputs are copied up on the context's
+// stream, `launch(d_in, d_out)` runs on the device arrays (in the order given) and answers PT_OK or its own refusal, the outputs are copied
+// back and the stream drained.  An output with a null host pointer is scratch the kernel writes and nobody reads; one with `preload` starts
+// from the caller's values.  hook, noun: "<hook>: <noun>" is the text beside PT_ERR_OUT_OF_MEMORY, "<hook>: <HIP's>" beside PT_ERR_DEVICE.
+struct QueryIn { const void* host; size_t bytes; };
+struct QueryOut { void* host; size_t bytes; bool preload = false; };
+using QueryBufs = std::vector<TempBuf>;
+template <typename Launch>
+int run_query(pt_ctx* ctx, const std::string& hook, const char* noun, std::initializer_list<QueryIn> ins, std::initializer_list<QueryOut> outs, Launch launch) {
+    QueryBufs d_in(ins.size()), d_out(outs.size());
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < ins.size() && e == hipSuccess; k++) e = d_in[k].alloc(ins.begin()[k].bytes);
+    for (size_t k = 0; k < outs.size() && e == hipSuccess; k++) e = d_out[k].alloc(outs.begin()[k].bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, hook + ": " + noun); }
+    for (size_t k = 0; k < ins.size() && e == hipSuccess; k++) e = hipMemcpyAsync(d_in[k].ptr, ins.begin()[k].host, ins.begin()[k].bytes, hipMemcpyHostToDevice, ctx->stream);
+    for (size_t k = 0; k < outs.size() && e == hipSuccess; k++)
+        if (const QueryOut& o = outs.begin()[k]; o.preload) e = hipMemcpyAsync(d_out[k].ptr, o.host, o.bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) { if (int r = launch(d_in, d_out)) return r; e = hipGetLastError(); }
+    for (size_t k = 0; k < outs.size() && e == hipSuccess; k++)
+        if (const QueryOut& o = outs.begin()[k]; o.host) e = hipMemcpyAsync(o.host, d_out[k].ptr, o.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, hook + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
 
 // diagnostic (not part of include/mipt.h): how many materials of the current table read the interleaved footprint
 extern "C" int pt_debug_interleaved_materials(const pt_ctx* ctx) {
@@ -32,13 +60,10 @@ extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, co
     ENTER(ctx);
     FrameConstants fc;
     camera_constants(cam, params, fc);
-    TempBuf d_q, d_out;
-    if (d_q.alloc((size_t)n * 12) != hipSuccess || d_out.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_camera_rays: buffers"); }
-    hipError_t e = hipMemcpyAsync(d_q.ptr, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_camera_rays(fc, cam.lens, d_q.as<uint32_t>(), n, d_out.as<float>(), ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_camera_rays: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_camera_rays", "buffers", {{queries, (size_t)n * 12}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        launch_debug_camera_rays(fc, cam.lens, d_in[0].as<uint32_t>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the rays pt_trace would start for the queries {px, py, seed} under the context's bake (pt_set_bake, which must
@@ -57,13 +82,10 @@ extern "C" int pt_debug_bake_rays(pt_ctx* ctx, const pt_settings* settings, cons
     FrameConstants fc;
     memset(&fc, 0, sizeof(fc));
     fc.res_x = params->width; fc.res_y = params->height;
-    TempBuf d_q, d_out;
-    if (d_q.alloc((size_t)n * 12) != hipSuccess || d_out.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_bake_rays: buffers"); }
-    hipError_t e = hipMemcpyAsync(d_q.ptr, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_bake_rays(fc, bk, d_q.as<uint32_t>(), n, d_out.as<float>(), ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_bake_rays: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_bake_rays", "buffers", {{queries, (size_t)n * 12}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        launch_debug_bake_rays(fc, bk, d_in[0].as<uint32_t>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the rays pt_trace would start for the queries {px, py, seed} under the context's probes (pt_set_probes,
@@ -82,13 +104,10 @@ extern "C" int pt_debug_probe_rays(pt_ctx* ctx, const pt_settings* settings, con
     memset(&fc, 0, sizeof(fc));
     fc.res_x = params->width; fc.res_y = params->height;
     const ProbeArgs pa = probe_args(ctx);
-    TempBuf d_q, d_out;
-    if (d_q.alloc((size_t)n * 12) != hipSuccess || d_out.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_probe_rays: buffers"); }
-    hipError_t e = hipMemcpyAsync(d_q.ptr, queries, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_probe_rays(fc, pa, d_q.as<uint32_t>(), n, d_out.as<float>(), ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_probe_rays: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_probe_rays", "buffers", {{queries, (size_t)n * 12}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        launch_debug_probe_rays(fc, pa, d_in[0].as<uint32_t>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
@@ -100,27 +119,22 @@ extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, ui
     if (n == 0) return PT_OK;
     SceneRec sc = scene_fill(ctx);
     const uint32_t lanes = (n + 255u) & ~255u;
-    TempBuf rays_buf, out_buf, deep_buf;
-    if (rays_buf.alloc((size_t)n * 32) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: ray buffers"); }
-    if (const uint32_t entries = deep_stack_entries(ctx)) {
-        if (deep_buf.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_intersect: deep stack"); }
-        sc.deep_stack = deep_buf.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = lanes;
-    }
-    float *d_rays = rays_buf.as<float>(), *d_out = out_buf.as<float>();
-    hipError_t e = hipMemcpyAsync(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream); e = hipGetLastError(); }
-    if (e == hipSuccess && getenv("MIPT_DEBUG_INTERSECT_TIMING")) {           // probe (tools/ray_order_probe.py): the same launch timed, 5 repeats
-        hipEvent_t ev[2]; hipEventCreate(&ev[0]); hipEventCreate(&ev[1]);
-        hipEventRecord(ev[0], ctx->stream);
-        for (int k = 0; k < 5; k++) launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream);
-        hipEventRecord(ev[1], ctx->stream); hipEventSynchronize(ev[1]);
-        float ms = 0; hipEventElapsedTime(&ms, ev[0], ev[1]);
-        fprintf(stderr, "pt_debug_intersect: %u rays, %.3f ms per launch, %.1f Mrays/s\n", n, ms / 5, n / (ms / 5) * 1e-3);
-        hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_intersect: ") + hipGetErrorString(e));
+    TempBuf deep_buf;
+    return run_query(ctx, "pt_debug_intersect", "ray buffers", {{rays, (size_t)n * 32}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& in_buf, const QueryBufs& out_buf) -> int {
+        if (int r = temp_deep_stack(ctx, sc, deep_buf, lanes, "pt_debug_intersect: deep stack")) return r;
+        float *d_rays = in_buf[0].as<float>(), *d_out = out_buf[0].as<float>();
+        launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream);
+        if (hipPeekAtLastError() == hipSuccess && getenv("MIPT_DEBUG_INTERSECT_TIMING")) {           // probe (tools/ray_order_probe.py): the same launch timed, 5 repeats
+            hipEvent_t ev[2]; hipEventCreate(&ev[0]); hipEventCreate(&ev[1]);
+            hipEventRecord(ev[0], ctx->stream);
+            for (int k = 0; k < 5; k++) launch_debug_intersect(sc, d_rays, n, ray_flags, mode, d_out, ctx->stream);
+            hipEventRecord(ev[1], ctx->stream); hipEventSynchronize(ev[1]);
+            float ms = 0; hipEventElapsedTime(&ms, ev[0], ev[1]);
+            fprintf(stderr, "pt_debug_intersect: %u rays, %.3f ms per launch, %.1f Mrays/s\n", n, ms / 5, n / (ms / 5) * 1e-3);
+            hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
+        }
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the acceleration structure itself, as the device built or refitted it, for tests/accel_ref.py to check
@@ -181,20 +195,12 @@ extern "C" int pt_debug_motion(pt_ctx* ctx, const pt_settings* settings, const p
     MotionArgs mo;
     motion_setup(ctx, cam.world_to_clip, params, mo);
     const uint32_t lanes = (n + 255u) & ~255u;
-    TempBuf rays_buf, out_buf, deep_buf;
-    if (rays_buf.alloc((size_t)n * 32) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_motion: ray buffers"); }
-    if (const uint32_t entries = deep_stack_entries(ctx)) {
-        if (deep_buf.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_motion: deep stack"); }
-        sc.deep_stack = deep_buf.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = lanes;
-    }
-    hipError_t e = hipMemcpyAsync(rays_buf.ptr, rays, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        launch_debug_motion(sc, mo, rays_buf.as<float>(), n, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, out_buf.as<float>(), ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, out_buf.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_motion: ") + hipGetErrorString(e));
+    TempBuf deep_buf;
+    return run_query(ctx, "pt_debug_motion", "ray buffers", {{rays, (size_t)n * 32}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) -> int {
+        if (int r = temp_deep_stack(ctx, sc, deep_buf, lanes, "pt_debug_motion: deep stack")) return r;
+        launch_debug_motion(sc, mo, d_in[0].as<float>(), n, (settings->flags & PT_FLAG_CULL_BACKFACE) ? 1u : 0u, d_out[0].as<float>(), ctx->stream);   // RF_CULL_BACK (RayGeneration :747)
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
@@ -217,12 +223,8 @@ extern "C" int pt_debug_trace_queues(pt_ctx* ctx, const float* closest, const ui
     ENTER(ctx);
     if (int r = ensure_accel(ctx)) return r;
     SceneRec sc = scene_fill(ctx);                         // has_env = 0: the traversal stages draw no environment samples
-    TempBuf d_deep;
-    if (const uint32_t entries = deep_stack_entries(ctx)) {    // the deep stack as pt_trace sets it up, for this launch's grid
-        const size_t lanes = (size_t)256 * blocks_per_shard * 256;
-        if (d_deep.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_trace_queues: deep stack"); }
-        sc.deep_stack = d_deep.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
-    }
+    TempBuf d_deep;                                        // the deep stack as pt_trace sets it up, for this launch's grid
+    if (int r = temp_deep_stack(ctx, sc, d_deep, (size_t)256 * blocks_per_shard * 256, "pt_debug_trace_queues: deep stack")) return r;
     const DebugQueues q = {closest, closest_shard, n_c, shadow, shadow_shard, shadow_is_light, n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
                            out_closest, out_shadow, out_cnt, out_stray};
     std::string why;
@@ -245,23 +247,12 @@ extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* ma
     ENTER(ctx);
     if (n == 0) return PT_OK;
     const SceneRec sc = scene_fill(ctx);                   // (the sampler reads the materials and the lookup tables)
-    TempBuf ms_buf, tc_buf, out_buf, taps_buf;
-    if (ms_buf.alloc((size_t)n * 8) != hipSuccess || tc_buf.alloc((size_t)n * 16) != hipSuccess || out_buf.alloc((size_t)n * 16) != hipSuccess ||
-        taps_buf.alloc((size_t)n * 20) != hipSuccess) {
-        (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_sample_texture: query buffers");
-    }
-    uint32_t* d_ms = ms_buf.as<uint32_t>(); float *d_tc = tc_buf.as<float>(), *d_out = out_buf.as<float>(); int32_t* d_taps = taps_buf.as<int32_t>();
-    hipError_t e = hipMemcpyAsync(d_ms, mat_slot, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tc, tc, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_sample_texture_wf(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
-        else launch_debug_sample_texture_mk(sc, d_ms, d_tc, n, d_out, d_taps, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && out_taps) e = hipMemcpyAsync(out_taps, d_taps, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_sample_texture: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_sample_texture", "query buffers", {{mat_slot, (size_t)n * 8}, {tc, (size_t)n * 16}}, {{out_rgba, (size_t)n * 16}, {out_taps, (size_t)n * 20}},
+                     [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        if (unit == 0) launch_debug_sample_texture_wf(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), d_out[1].as<int32_t>(), ctx->stream);
+        else launch_debug_sample_texture_mk(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), d_out[1].as<int32_t>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the environment light on caller-supplied queries, one per lane (pt_vertex.h debug_env_query:
@@ -276,19 +267,11 @@ extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const 
     memset(&sc, 0, sizeof(sc));
     scene_set_env(sc, *ctx->envs[env]);
     const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 16 * 4;
-    TempBuf in_buf, out_buf;
-    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_env_query: query buffers"); }
-    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
-    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, ctx->stream);      // unused outputs keep the caller's values
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in, n, d_out, ctx->stream);
-        else launch_debug_env_query_mk(sc, op, d_in, n, d_out, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_env_query: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_env_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes, true}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {   // (true: unused outputs keep the caller's values)
+        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        else launch_debug_env_query_mk(sc, op, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the material model on caller-supplied queries, one per lane (pt_vertex.h debug_bsdf_query:
@@ -303,18 +286,11 @@ extern "C" int pt_debug_bsdf_query(pt_ctx* ctx, int unit, int op, uint32_t flags
     if (n == 0) return PT_OK;
     const SceneRec sc = scene_fill(ctx);                   // (the BSDF reads the sheen table; stage_luts stages the sRGB table with it)
     const size_t in_bytes = (size_t)n * 48 * 4, out_bytes = (size_t)n * 16 * 4;
-    TempBuf in_buf, out_buf;
-    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_bsdf_query: query buffers"); }
-    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
-    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_bsdf_query_wf(sc, op, flags, d_in, n, d_out, ctx->stream);
-        else launch_debug_bsdf_query_mk(sc, op, flags, d_in, n, d_out, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_bsdf_query: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_bsdf_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        if (unit == 0) launch_debug_bsdf_query_wf(sc, op, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        else launch_debug_bsdf_query_mk(sc, op, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the punctual lights on caller-supplied queries, one per lane -- load_light, then light_ray, as the
@@ -332,20 +308,11 @@ extern "C" int pt_debug_light_query(pt_ctx* ctx, int unit, int small_tables, int
     ENTER(ctx);
     if (n == 0) return PT_OK;
     const SceneRec sc = scene_fill(ctx);
-    TempBuf idx_buf, p_buf, out_buf;
-    if (idx_buf.alloc((size_t)n * 4) != hipSuccess || p_buf.alloc((size_t)n * 12) != hipSuccess || out_buf.alloc((size_t)n * 32) != hipSuccess) {
-        (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_light_query: query buffers");
-    }
-    hipError_t e = hipMemcpyAsync(idx_buf.ptr, light_index, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p_buf.ptr, p, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_light_query_wf(sc, small_tables != 0, num_of_lights, idx_buf.as<uint32_t>(), p_buf.as<float>(), n, out_buf.as<float>(), ctx->stream);
-        else launch_debug_light_query_mk(sc, idx_buf.as<uint32_t>(), p_buf.as<float>(), n, out_buf.as<float>(), ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, out_buf.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_light_query: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_light_query", "query buffers", {{light_index, (size_t)n * 4}, {p, (size_t)n * 12}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        if (unit == 0) launch_debug_light_query_wf(sc, small_tables != 0, num_of_lights, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        else launch_debug_light_query_mk(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): the vertex fetch and the material evaluation of a path vertex on caller-supplied hits, one per
@@ -384,18 +351,11 @@ extern "C" int pt_debug_surface_query(pt_ctx* ctx, int unit, int small_tables, u
     if (n == 0) return PT_OK;
     const SceneRec sc = scene_fill(ctx);
     const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 72 * 4;
-    TempBuf in_buf, out_buf;
-    if (in_buf.alloc(in_bytes) != hipSuccess || out_buf.alloc(out_bytes) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, "pt_debug_surface_query: query buffers"); }
-    float *d_in = in_buf.as<float>(), *d_out = out_buf.as<float>();
-    hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (unit == 0) launch_debug_surface_query_wf(sc, small_tables != 0, flags, d_in, n, d_out, ctx->stream);
-        else launch_debug_surface_query_mk(sc, flags, d_in, n, d_out, ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, std::string("pt_debug_surface_query: ") + hipGetErrorString(e));
+    return run_query(ctx, "pt_debug_surface_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
+        if (unit == 0) launch_debug_surface_query_wf(sc, small_tables != 0, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        else launch_debug_surface_query_mk(sc, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        return PT_OK;
+    });
 }
 
 // test hook (not part of include/mipt.h): an environment map from a given cube mip 0 (6 x n x n RGBA16F) and a whole 1024^2 sum pyramid

@@ -3,7 +3,7 @@
 //   pt_motion_snapshot  k_motion_snapshot: one lane per packet of the built tree copies (v0, e1, e2) to the packet's instance-major address
 //                       instances[inst].tri_offset + prim, which no rebuild or reordering of the tree changes: the previous pose of every
 //                       triangle, 48 bytes each.  The context keeps the row count and every row's triangle count the snapshot stands for.
-//   pt_set_motion       checks and keeps the config; pt_trace (mipt_api.hip) reads it through motion_setup.
+//   pt_set_motion       checks and keeps the config; pt_trace (mipt_api.hip PathtraceScene) reads it through motion_setup, below.
 //   pt_reproject        k_reproject: one lane per pixel, four taps of the previous frame at the pixel's motion vector, no LDS.  A pure function
 //                       of its images; tests/motion_ref.py restates it in numpy float32, rounding for rounding.
 //   pt_debug_motion     (mipt_debug.hip) launches k_debug_motion: k_debug_intersect's closest hit, then pt_motion.h motion_record.
@@ -97,11 +97,6 @@ __global__ __launch_bounds__(kBlock) void k_reproject(ReprojectArgs a) {
     const float al = fmaxf(1.0f / n, a.alpha_min);
     a.out_color[p] = make_float4(hr + al * (c.x - hr), hg + al * (c.y - hg), hb + al * (c.z - hb), c.w);
     a.out_length[p] = n;
-}
-
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
 }
 
 }  // namespace

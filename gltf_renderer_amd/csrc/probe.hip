@@ -1,5 +1,6 @@
-// probe.hip -- light-probe baking (pt_set_probes, include/mipt.h): pt_probe_project's reduction of the octahedral atlas to nine
-// spherical-harmonic coefficients per channel and probe.
+// probe.hip -- light-probe baking (include/mipt.h): pt_set_probes, which checks the config and keeps it with the probes' positions on the
+// device (what a call makes of them -- probe_atlas_size, probe_args -- is inline in pt_ctx.h, for select_passes and a hook read it too), and
+// pt_probe_project's reduction of the octahedral atlas to nine spherical-harmonic coefficients per channel and probe.
 //
 //   c[lm][ch] = (4 pi / n^2) * sum over the probe's n x n texels of L(i, j)[ch] * Y_lm(w(i, j))
 //
@@ -10,6 +11,9 @@
 //                    16, so 16 consecutive lanes read 256 contiguous bytes of an atlas row (float4 loads) and the whole table row.  27 partial
 //                    sums per lane (9 coefficients x rgb), reduced over the wave by shuffles, over the four waves through LDS.
 // Compiled without floating-point contraction (Makefile): products and sums are the float32 operations tests/probe_ref.py bounds.
+#include <cmath>
+
+#include "pt_ctx.h"
 #include "pt_probe.h"
 
 namespace pt {
@@ -83,3 +87,73 @@ void launch_probe_project(const float4* atlas, const float4* dirs, uint32_t n, u
 }
 
 }  // namespace pt
+
+using namespace pt;
+
+extern "C" {
+
+int pt_set_probes(pt_ctx* ctx, const pt_probe_config* config, const float* positions_xyz) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: config is NULL");
+    if (!config->enable) {                        // nothing else of a disabled config is looked at; the layout and the positions go
+        ctx->probes.enable = 0;
+        ctx->restart_pending = true;
+        return PT_OK;
+    }
+    if (!positions_xyz) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: positions_xyz is NULL");
+    if (config->resolution < 16 || config->resolution > 1024 || config->resolution % 16 != 0)
+        return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: resolution must be a multiple of 16 in 16..1024");
+    if (config->count < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: count must be >= 1");
+    if (config->columns < 1) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns must be >= 1");
+    if (!std::isfinite(config->max_distance) || !(config->max_distance > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: max_distance must be finite and > 0");
+    uint64_t w, h;
+    probe_atlas_size(*config, w, h);
+    if (w > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: columns * resolution = " + std::to_string(w) + " exceeds 2^30");
+    if (h > (1ull << 30)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: rows * resolution = " + std::to_string(h) + " (count / columns rows) exceeds 2^30");
+    for (int64_t i = 0; i < (int64_t)config->count * 3; i++)
+        if (!std::isfinite(positions_xyz[i])) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: the position of probe " + std::to_string(i / 3) + " is not finite");
+    if (ctx->bake.enable) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probes: a bake is enabled (pt_set_bake): a trace renders one atlas or the other");
+    ENTER(ctx);
+    const size_t bytes = (size_t)config->count * 12;
+    // a trace in flight may still read the old positions: the copy goes behind it on the stream, a larger array drains it first (DevBuf)
+    if (const hipError_t e = ctx->d_probe_pos.reserve(ctx->stream, bytes, bytes)) {
+        if (ctx->d_probe_pos.ptr == nullptr) { ctx->probes.enable = 0; ctx->restart_pending = true; }     // the old array went with the failed growth
+        return grow_failed(ctx, e, "probe positions: " + std::to_string(bytes) + " bytes");
+    }
+    if (const hipError_t e = staged_upload(ctx, ctx->d_probe_pos.ptr, positions_xyz, bytes)) {
+        ctx->probes.enable = 0; ctx->restart_pending = true;               // the array may hold part of either set: back to the camera
+        return ctx->fail(PT_ERR_DEVICE, std::string("probe positions: ") + hipGetErrorString(e));
+    }
+    ctx->probes = *config;
+    ctx->restart_pending = true;
+    return PT_OK;
+}
+
+int pt_probe_project(pt_ctx* ctx, const void* atlas_device, uint32_t width, uint32_t height, int kind, float* sh_host) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!atlas_device || !sh_host) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: NULL argument");
+    if (kind != PT_PROBE_SH_RADIANCE && kind != PT_PROBE_SH_IRRADIANCE) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: kind must be PT_PROBE_SH_RADIANCE or PT_PROBE_SH_IRRADIANCE");
+    if (!ctx->probes.enable) return ctx->fail(PT_ERR_NOT_READY, "probe_project: no probes are set");
+    uint64_t w, h;
+    probe_atlas_size(ctx->probes, w, h);
+    if (width != w || height != h) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "probe_project: the atlas is " + std::to_string(w) + " x " + std::to_string(h));
+    ENTER(ctx);
+    const uint32_t n = (uint32_t)ctx->probes.resolution, count = (uint32_t)ctx->probes.count;
+    if (ctx->probe_dirs_n != n) {
+        const size_t bytes = (size_t)n * n * 16;
+        ctx->probe_dirs_n = 0;
+        if (const hipError_t e = ctx->d_probe_dirs.reserve(ctx->stream, bytes, bytes)) return grow_failed(ctx, e, "probe direction table: " + std::to_string(bytes) + " bytes");
+        launch_probe_dirs(ctx->d_probe_dirs.as<float4>(), n, ctx->stream);
+        HIPOK(hipGetLastError());
+        ctx->probe_dirs_n = n;
+    }
+    const size_t out_bytes = (size_t)count * 27 * 4;
+    if (const hipError_t e = ctx->d_probe_sh.reserve(ctx->stream, out_bytes, out_bytes)) return grow_failed(ctx, e, "probe coefficients: " + std::to_string(out_bytes) + " bytes");
+    launch_probe_project((const float4*)atlas_device, ctx->d_probe_dirs.as<float4>(), n, count, (uint32_t)ctx->probes.columns, kind, ctx->d_probe_sh.as<float>(), ctx->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(sh_host, ctx->d_probe_sh.ptr, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPOK(hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
+}  // extern "C"

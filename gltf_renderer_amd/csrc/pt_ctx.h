@@ -1,5 +1,5 @@
-// pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what both of its translation units need of it: mipt_api.hip (the product)
-// and mipt_debug.hip (the test hooks).  Internal to those two.
+// pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what the translation units with entry points need of it: mipt_api.hip (the
+// core of the product), a feature's own file (bake, probe, matte, motion, blur, variance, denoise .hip) and mipt_debug.hip (the test hooks).
 #pragma once
 #include <cstring>
 #include <string>
@@ -152,6 +152,16 @@ struct pt_ctx {
 
 namespace pt {
 
+// Host -> device through a pinned slot of the context's ring, asynchronous on its stream.  grow_failed: what a grow that answers an exhausted
+// device with PT_ERR_OUT_OF_MEMORY and its own text returns (anything else DevBuf::realloc fails with is its synchronise).  (mipt_api.hip)
+hipError_t staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes);
+int grow_failed(pt_ctx* ctx, hipError_t e, const std::string& what);
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte: the entry points that take several device images refuse aliases by it
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
 // The camera of a call, from pt_execute_params and the lens config: world_to_clip as pt_trace compares it between calls, its inverse and
 // view_to_world (fp64, rounded once) and the lens as camera_ray takes it (include/mipt.h pt_set_lens).  PathtraceScene, pt_lens_focus_at
 // and the hook pt_debug_camera_rays all come through here, so that the rays they speak of are the same rays.  (mipt_api.hip)
@@ -165,10 +175,11 @@ void camera_constants(const CameraSetup& cam, const pt_execute_params* ep, Frame
 
 // The bake of a call (pt_set_bake): the coverage map for a width x height atlas -- built now unless it stands for this size, config and
 // state of the tree -- and what k_wf_generate_bake takes.  After ensure_accel.  pt_trace and the hook pt_debug_bake_rays both come through
-// here.  (mipt_api.hip)
+// here.  (bake.hip)
 int bake_setup(pt_ctx* ctx, uint32_t width, uint32_t height, BakeArgs& bake);
 
-// The probes of a call (pt_set_probes) as k_wf_generate_probe takes them, and the atlas they make (mipt_api.hip)
+// The probes of a call (pt_set_probes, probe.hip) as k_wf_generate_probe takes them, and the atlas they make: inline, for select_passes
+// (mipt_api.hip) and the hook pt_debug_probe_rays read them too
 inline void probe_atlas_size(const pt_probe_config& c, uint64_t& w, uint64_t& h) {
     w = (uint64_t)c.columns * (uint64_t)c.resolution;
     h = (((uint64_t)c.count + (uint64_t)c.columns - 1) / (uint64_t)c.columns) * (uint64_t)c.resolution;
@@ -190,7 +201,7 @@ int select_passes(pt_ctx* ctx, const pt_settings* settings, const pt_execute_par
 int adaptive_setup(pt_ctx* ctx, const pt_execute_params* ep, const FrameConstants& fc, int frame_cap, AdaptiveArgs& adaptive);
 
 // The mattes of a call (pt_set_matte): the device table of ids -- made now unless it stands for this kind and this many rows -- and what
-// k_wf_matte / k_wf_matte_resolve take.  (mipt_api.hip)
+// k_wf_matte / k_wf_matte_resolve take.  (matte.hip)
 int matte_setup(pt_ctx* ctx, MatteArgs& matte);
 
 // The motion vectors of a call (pt_set_motion): the two cameras, the snapshot if it is valid for the current instance table, the caller's
@@ -238,6 +249,15 @@ inline void scene_set_env(SceneRec& sc, const EnvDevice& ed) {
 inline uint32_t deep_stack_entries(const pt_ctx* ctx) {
     const uint32_t on_chip = (uint32_t)traversal_stack_capacity();
     return ctx->stack_need > on_chip ? (ctx->stack_need - on_chip + 7u) & ~7u : 0u;
+}
+// The deep stack of one call outside pt_trace (which keeps its own in d_deep), if the tree needs one: deep_stack_entries(ctx) entries for
+// each of `lanes` lanes in `buf`, attached to `sc`.  what: the text beside PT_ERR_OUT_OF_MEMORY when the device has no room for it.
+inline int temp_deep_stack(pt_ctx* ctx, SceneRec& sc, TempBuf& buf, size_t lanes, const char* what) {
+    const uint32_t entries = deep_stack_entries(ctx);
+    if (entries == 0) return PT_OK;
+    if (buf.alloc((size_t)entries * lanes * 4) != hipSuccess) { (void)hipGetLastError(); return ctx->fail(PT_ERR_OUT_OF_MEMORY, what); }
+    sc.deep_stack = buf.as<int32_t>(); sc.deep_entries = entries; sc.deep_lanes = (uint32_t)lanes;
+    return PT_OK;
 }
 
 }  // namespace pt

@@ -1,5 +1,6 @@
-// variance.hip -- pt_noise_estimate: how noisy an accumulated image is, tile by tile, from the image and the variance target of
-// pt_set_variance (include/mipt.h states it operation by operation; tests/variance_ref.py restates it in numpy float32).  A pure function
+// variance.hip -- the variance AOV outside the wavefront pipeline: pt_set_variance, which checks and keeps the config, and
+// pt_noise_estimate: how noisy an accumulated image is, tile by tile, from the image and the variance target of pt_set_variance
+// (include/mipt.h states it operation by operation; tests/variance_ref.py restates it in numpy float32).  A pure function
 // of two images and the tiles' sample counts.  One launch on the context's stream, over 16 x 16 tiles (PT_TILE) numbered row-major:
 //   k_noise_tiles     one 256-lane workgroup per tile, one lane per pixel.  A tile whose count is below 2 writes (-1, -1) and leaves
 //                     (block-uniform).  Otherwise every in-image lane forms its pixel's relative standard error e; the tile's max and sum are
@@ -67,6 +68,15 @@ void launch_noise_tiles(const float4* image, const float4* variance, uint32_t w,
 using namespace pt;
 
 extern "C" {
+
+int pt_set_variance(pt_ctx* ctx, const pt_variance_config* config) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (!config) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: config is NULL");
+    if (config->enable && !config->variance) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "variance: the target is NULL");
+    ctx->variance = *config;
+    ctx->restart_pending = true;
+    return PT_OK;
+}
 
 int pt_noise_estimate(pt_ctx* ctx, const void* image, const void* variance, uint32_t width, uint32_t height, const uint32_t* tile_samples, uint32_t samples,
                       float threshold, float* tile_mean_host, float* tile_max_host, pt_noise_summary* summary) {

@@ -10,10 +10,12 @@ pt_debug_trace_queues (tests/ray_hook.py trace_queues) launches those kernels, t
   c. both drivers against the float64 restatement of the any-hit rules (tests/traversal_ref.py) on the layered alpha scene, and on
      scenes.test_scene (LINEAR-filtered alpha) against the oracle within the sampler's tolerance;
   d. queue shapes: per-shard counts around the wave, refill and workgroup sizes, at every blocks_per_shard a frame uses;
-  e. the deep stack under the stage grid, lanes tracing several rays in a row on one deep-stack column.
+  e. the deep stack under the stage grid, lanes tracing several rays in a row on one deep-stack column; the deep stacks that
+     pt_debug_intersect, pt_debug_motion and pt_lens_focus_at bring for one call.
 
 No test assumes a visiting order.  Only the value the shadow stage WRITES is visible through the hook (the transmission of a committed ray, 1
 otherwise); "committed" itself is compared through pt_debug_intersect."""
+import ctypes as C
 import importlib.util
 import os
 
@@ -21,6 +23,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, scenes
+import lens_ref as lr
 import traversal_ref as tr
 import traversal_scenes as tscenes
 from ray_hook import (gpu_intersect, dxr_flags, trace_queues, shadow_rays_of, shadow_counter, TQ_TRACE, TQ_SHADOW, TQ_FUSED, TQ_SENTINEL, CNT_HEAD_CLOSEST,
@@ -351,6 +354,57 @@ def test_deep_stack_columns_serve_several_rays_in_a_row(bps):
         assert np.array_equal(v, np.where(ga[:, 0] > 0, np.float32(0), np.float32(1))) and stray[0] == 0 and stray[1] == 0
         r.stats()
         print("deep chain, %s, %d workgroups per shard: stack need %d, deep pushes %d" % (name, bps, q.bvh_stack_need, q.deep_stack_pushes))
+    r.close()
+
+
+def _params_hook(r, name, st, params, rows, width):
+    """pt_debug_camera_rays (rows [n, 3] uint32 {px, py, seed}) or pt_debug_motion (rows [n, 8] float32 rays): -> [n, 8] float32."""
+    rows = np.ascontiguousarray(rows).reshape(-1, width)
+    out = np.zeros((len(rows), 8), np.float32)
+    f = getattr(r.L, name)
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    f.restype = C.c_int
+    rc = f(r.h, C.byref(st), C.byref(params), rows.ctypes.data_as(C.c_void_p), len(rows), out.ctypes.data_as(C.c_void_p))
+    assert rc == 0, (name, rc, r.L.pt_last_error(r.h))
+    return out
+
+
+def test_every_one_call_deep_stack_serves_a_tree_that_needs_it(oracle_lib):
+    """pt_debug_intersect, pt_debug_motion and pt_lens_focus_at each bring a deep stack of their own for one call, through one helper
+    (pt_ctx.h temp_deep_stack).  The deep-chain scene with the LBVH builder needs one: its stack need is above the 64 entries a lane
+    holds on chip.  On the camera rays of 16 pixels (pt_debug_camera_rays, lens off, seed 0):
+      a. pt_debug_motion's instance, primitive, u, v (out[4:8]) are pt_debug_intersect's (mode 0), bit for bit;
+      b. focus_at at the ray's image position is the view-space depth zo + t * dn of that hook hit (float64, t the hook's), within
+         tests/lens_ref.py's bound -- as test_focus_at_is_the_view_space_depth_of_the_hooks_ray (tests/test_gpu_lens.py) computes it."""
+    from gltf_renderer_amd.renderer import Renderer
+    s, n_tris = tscenes._deep_chain_scene()
+    W, H = s.width, s.height
+    assert (W, H) == (32, 32)
+    r = Renderer(); r.set_accel_builder(abi.BUILDER_LBVH); s.upload(r); r.build_accel()
+    q = r.stats()
+    deep = q.bvh_stack_capacity - 64                                     # the entries beyond the on-chip ones
+    assert deep > 0 and q.bvh_stack_need > q.bvh_stack_capacity - deep, (q.bvh_stack_need, q.bvh_stack_capacity)
+    st, params = s.settings, s.execute_params(0)
+    rf = RF_CULL_BACK if st.flags & CULL else 0
+    picks = [(x, y) for y in (3, 11, 19, 27) for x in (2, 10, 18, 26)]
+    r.set_lens(0, 1, enable=False)
+    rays = _params_hook(r, "pt_debug_camera_rays", st, params, np.array([(x, y, 0) for x, y in picks], np.uint32), 3)
+    g = gpu_intersect(r, rays, rf, 0)
+    assert np.all(g[:, 0] > 0) and np.all(g[:, 1] > 0)                   # every ray hits the nearest sheet
+    m = _params_hook(r, "pt_debug_motion", st, params, rays, 8)
+    assert np.array_equal(bits(m[:, 4:8]), bits(g[:, [4, 5, 2, 3]])), (m[:, 4:8], g[:, [4, 5, 2, 3]])
+    cam = lr.Camera(params.world_to_view, params.view_to_clip, W, H)
+    sx, sy = lr.jittered(lr.randoms(oracle_lib, W, H, range(1)), W, H)
+    for k, (x, y) in enumerate(picks):
+        got = r.focus_at(st, params, float(sx[0, y, x]), float(sy[0, y, x]))
+        assert got is not None, (x, y)
+        od, dd = rays[k, 0:3].astype(np.float64), rays[k, 4:7].astype(np.float64)
+        zo, dn = float((od - cam.c) @ cam.F), float(dd @ cam.F)
+        want = zo + float(g[k, 1]) * dn
+        P = od + dd * float(g[k, 1])
+        print("pixel (%d, %d): focus_at %.9g, zo + t dn %.9g" % (x, y, got, want))
+        assert abs(got - want) <= float(lr.bound(od[None], cam.c[None], P[None], want)[0]), (x, y, got, want)
+    r.stats()                                                            # raises if a push was dropped
     r.close()
 
 

@@ -11,6 +11,9 @@ for f in pt_wavefront pt_kernel accel; do
   /opt/rocm/bin/hipcc $FLAGS $X -c $f.hip -o /tmp/variant_$NAME/$f.o &
 done
 wait
+# everything else the library links, as the Makefile lists and builds it
+REST=$(make -s print-objs | tr ' ' '\n' | grep -vxE '(pt_wavefront|pt_kernel|accel)\.o' | tr '\n' ' ')
+make -s $REST
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../variants/libmipt_$NAME.so /tmp/variant_$NAME/pt_wavefront.o /tmp/variant_$NAME/pt_kernel.o /tmp/variant_$NAME/accel.o \
-  mipt_api.o mipt_debug.o sort_scan.o envmap.o skin_tonemap.o exchange.o denoise.o bake.o probe.o matte.o host/image_decode.o host/gltf_scene.o host/accum_state.o -ldl
+  $REST -ldl
 echo built variants/libmipt_$NAME.so

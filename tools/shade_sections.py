@@ -1,7 +1,6 @@
 """Diagnostic (GPU box): cycles per section of the shade stage's closest-hit function, from a library built with -DPT_TIMING
 (variants/libmipt_timing.so = the library with pt_wavefront.hip compiled -DPT_TIMING).  Prints the share of each section.
-build:  cd gltf_renderer_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -DPT_TIMING -c pt_wavefront.hip -o /tmp/wf_t.o &&
-        hipcc -shared -fPIC --offload-arch=gfx950 -o ../../variants/libmipt_timing.so /tmp/wf_t.o mipt_api.o mipt_debug.o pt_kernel.o accel.o envmap.o skin_tonemap.o host/*.o"""
+build:  tools/build_variant.sh timing -DPT_TIMING   (it links the Makefile's own object list)"""
 import ctypes as C, os, shutil, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
