@@ -1,6 +1,7 @@
 // mipt_debug.hip -- the test hooks of libmipt.so (pt_debug_*, not part of include/mipt.h): the product's own device code run on the
 // caller's queries, for tests/ and tools/ to compare with the oracle.  Host code only: this file has no kernel; what the hooks launch is in
-// pt_kernel.hip, pt_wavefront.hip and motion.hip.  The product itself is mipt_api.hip and the feature files beside it.
+// debug_wf.hip and debug_mk.hip (compiled as pt_wavefront.hip and pt_kernel.hip are) and motion.hip.  The product itself is mipt_api.hip and
+// the feature files beside it.
 #include <cstdio>
 #include <cstdlib>
 
@@ -34,6 +35,9 @@ int run_query(pt_ctx* ctx, const std::string& hook, const char* noun, std::initi
     return e == hipSuccess ? PT_OK : ctx->fail(PT_ERR_DEVICE, hook + ": " + hipGetErrorString(e));
 }
 
+// the per-lane query kernels of unit 0: the wavefront stages' build (tables in LDS), 1: the megakernel's (global memory)
+DebugQueryLaunch queries_of(int unit) { return unit == 0 ? debug_queries_wf() : debug_queries_mk(); }
+
 }  // namespace
 
 // diagnostic (not part of include/mipt.h): how many materials of the current table read the interleaved footprint
@@ -50,7 +54,7 @@ extern "C" int pt_debug_interleaved_emissive(const pt_ctx* ctx) {          // ..
 }
 
 // test hook (not part of include/mipt.h): the camera rays pt_trace would generate for the queries {px, py, seed} under `params` and the context's
-// lens (pt_set_lens) -- camera_ray itself, one query per lane (pt_kernel.hip k_debug_camera_rays).  queries: 3 uint32 each, out: 8 floats each
+// lens (pt_set_lens) -- camera_ray itself, one query per lane (debug_wf.hip k_debug_rays).  queries: 3 uint32 each, out: 8 floats each
 // (origin, tmin, direction, tmax), host arrays.  Needs no scene; leaves the accumulation and a pending restart as they are.
 extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
     if (!ctx || !settings || !params || (n && (!queries || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
@@ -67,8 +71,8 @@ extern "C" int pt_debug_camera_rays(pt_ctx* ctx, const pt_settings* settings, co
 }
 
 // test hook (not part of include/mipt.h): the rays pt_trace would start for the queries {px, py, seed} under the context's bake (pt_set_bake, which must
-// be on) on a params->width x height atlas -- bake_ray itself, the generate kernel's ray function, one query per lane (pt_wavefront.hip
-// k_debug_bake_rays).  Builds the tree and the coverage map as that pt_trace would.  queries: 3 uint32 each, out: 8 floats each (origin, tmin,
+// be on) on a params->width x height atlas -- bake_ray itself, the generate kernel's ray function, one query per lane (debug_wf.hip
+// k_debug_rays).  Builds the tree and the coverage map as that pt_trace would.  queries: 3 uint32 each, out: 8 floats each (origin, tmin,
 // direction, tmax; zeros with tmax = -1 for an uncovered texel), host arrays.  Leaves the accumulation and a pending restart as they are.
 extern "C" int pt_debug_bake_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
     if (!ctx || !settings || !params || (n && (!queries || !out)) || params->width == 0 || params->height == 0) return PT_ERR_INVALID_ARGUMENT;
@@ -90,7 +94,7 @@ extern "C" int pt_debug_bake_rays(pt_ctx* ctx, const pt_settings* settings, cons
 
 // test hook (not part of include/mipt.h): the rays pt_trace would start for the queries {px, py, seed} under the context's probes (pt_set_probes,
 // which must be on) on their atlas, which params->width x height must be -- probe_ray itself, the generate kernel's ray function, one query
-// per lane (pt_wavefront.hip k_debug_probe_rays).  queries: 3 uint32 each, out: 8 floats each (origin, tmin, direction, tmax; zeros with
+// per lane (debug_wf.hip k_debug_rays).  queries: 3 uint32 each, out: 8 floats each (origin, tmin, direction, tmax; zeros with
 // tmax = -1 for a cell without a probe), host arrays.  Leaves the accumulation and a pending restart as they are.
 extern "C" int pt_debug_probe_rays(pt_ctx* ctx, const pt_settings* settings, const pt_execute_params* params, const uint32_t* queries, uint32_t n, float* out) {
     if (!ctx || !settings || !params || (n && (!queries || !out))) return PT_ERR_INVALID_ARGUMENT;
@@ -111,7 +115,7 @@ extern "C" int pt_debug_probe_rays(pt_ctx* ctx, const pt_settings* settings, con
 }
 
 // test hook (not part of include/mipt.h): what the product's traversal finds for caller-supplied rays (host arrays: 8 floats per ray in,
-// 8 floats per ray out, pt_kernel.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
+// 8 floats per ray out, debug_mk.hip k_debug_intersect).  mode 0 = TraceRay's closest hit, 1 = TraceShadowRay's occlusion search.
 extern "C" int pt_debug_intersect(pt_ctx* ctx, const float* rays, uint32_t n, uint32_t ray_flags, int mode, float* out) {
     if (!ctx || (n && (!rays || !out)) || mode < 0 || mode > 1) return PT_ERR_INVALID_ARGUMENT;
     ENTER(ctx);
@@ -204,7 +208,7 @@ extern "C" int pt_debug_motion(pt_ctx* ctx, const pt_settings* settings, const p
 }
 
 // test hook (not part of include/mipt.h): the traversal kernels pt_trace launches in the wavefront mode -- which 0: k_wf_trace, 1: k_wf_shadow,
-// 2: the fused k_wf_traverse -- on queues the caller fills (pt_wavefront.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
+// 2: the fused k_wf_traverse -- on queues the caller fills (debug_wf.hip debug_trace_queues; host arrays).  closest: n_c rays of 8 floats
 // (origin, tmin = 0: the queue format has none, direction, tmax) with the shard 0..255 each is queued in (the caller's order within a shard is
 // the queue's); shadow: n_s rays of 6 floats (origin, direction) with shard and is_light bit, one shadow_tmax for all.  flags: PT_FLAG_*;
 // bounce: of the closest rays (which 0, 2; the fused launch needs bounce >= 1 and takes the shadow rays of bounce - 1) or of the shadow rays
@@ -249,8 +253,7 @@ extern "C" int pt_debug_sample_texture(pt_ctx* ctx, int unit, const uint32_t* ma
     const SceneRec sc = scene_fill(ctx);                   // (the sampler reads the materials and the lookup tables)
     return run_query(ctx, "pt_debug_sample_texture", "query buffers", {{mat_slot, (size_t)n * 8}, {tc, (size_t)n * 16}}, {{out_rgba, (size_t)n * 16}, {out_taps, (size_t)n * 20}},
                      [&](const QueryBufs& d_in, const QueryBufs& d_out) {
-        if (unit == 0) launch_debug_sample_texture_wf(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), d_out[1].as<int32_t>(), ctx->stream);
-        else launch_debug_sample_texture_mk(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), d_out[1].as<int32_t>(), ctx->stream);
+        queries_of(unit).sample_texture(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), d_out[1].as<int32_t>(), ctx->stream);
         return PT_OK;
     });
 }
@@ -268,8 +271,7 @@ extern "C" int pt_debug_env_query(pt_ctx* ctx, int env, int unit, int op, const 
     scene_set_env(sc, *ctx->envs[env]);
     const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 16 * 4;
     return run_query(ctx, "pt_debug_env_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes, true}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {   // (true: unused outputs keep the caller's values)
-        if (unit == 0) launch_debug_env_query_wf(sc, op, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
-        else launch_debug_env_query_mk(sc, op, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        queries_of(unit).env_query(sc, op, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
         return PT_OK;
     });
 }
@@ -287,8 +289,7 @@ extern "C" int pt_debug_bsdf_query(pt_ctx* ctx, int unit, int op, uint32_t flags
     const SceneRec sc = scene_fill(ctx);                   // (the BSDF reads the sheen table; stage_luts stages the sRGB table with it)
     const size_t in_bytes = (size_t)n * 48 * 4, out_bytes = (size_t)n * 16 * 4;
     return run_query(ctx, "pt_debug_bsdf_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
-        if (unit == 0) launch_debug_bsdf_query_wf(sc, op, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
-        else launch_debug_bsdf_query_mk(sc, op, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        queries_of(unit).bsdf_query(sc, op, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
         return PT_OK;
     });
 }
@@ -309,8 +310,7 @@ extern "C" int pt_debug_light_query(pt_ctx* ctx, int unit, int small_tables, int
     if (n == 0) return PT_OK;
     const SceneRec sc = scene_fill(ctx);
     return run_query(ctx, "pt_debug_light_query", "query buffers", {{light_index, (size_t)n * 4}, {p, (size_t)n * 12}}, {{out, (size_t)n * 32}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
-        if (unit == 0) launch_debug_light_query_wf(sc, small_tables != 0, num_of_lights, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), ctx->stream);
-        else launch_debug_light_query_mk(sc, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        queries_of(unit).light_query(sc, small_tables != 0, num_of_lights, d_in[0].as<uint32_t>(), d_in[1].as<float>(), n, d_out[0].as<float>(), ctx->stream);
         return PT_OK;
     });
 }
@@ -352,8 +352,7 @@ extern "C" int pt_debug_surface_query(pt_ctx* ctx, int unit, int small_tables, u
     const SceneRec sc = scene_fill(ctx);
     const size_t in_bytes = (size_t)n * 8 * 4, out_bytes = (size_t)n * 72 * 4;
     return run_query(ctx, "pt_debug_surface_query", "query buffers", {{in, in_bytes}}, {{out, out_bytes}}, [&](const QueryBufs& d_in, const QueryBufs& d_out) {
-        if (unit == 0) launch_debug_surface_query_wf(sc, small_tables != 0, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
-        else launch_debug_surface_query_mk(sc, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
+        queries_of(unit).surface_query(sc, small_tables != 0, flags, d_in[0].as<float>(), n, d_out[0].as<float>(), ctx->stream);
         return PT_OK;
     });
 }

@@ -112,38 +112,9 @@ struct StageTimers {
     std::vector<uint8_t> kind;           // STAGE_* of the k-th launch
     size_t used = 0;                     // launches recorded by the last pt_trace
 };
-void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
-void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
-void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-// pt_debug_bsdf_query / pt_debug_light_query (test hooks): 48 floats in and 16 out per BSDF query; an index and a point in, 8 floats out per light query
-void launch_debug_bsdf_query_wf(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-void launch_debug_bsdf_query_mk(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
-void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
-int debug_light_cache_max();             // lights the shade stage keeps in LDS (kLightCacheMax)
-// pt_debug_surface_query (test hook): 8 words in and 72 floats out per query (pt_vertex.h debug_surface_query)
-void launch_debug_surface_query_wf(const SceneRec& sc, bool small_tables, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-void launch_debug_surface_query_mk(const SceneRec& sc, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
-int debug_inst_cache_max();              // instance rows / materials the shade stage keeps in LDS (kInstCacheMax, kMatCacheMax)
-int debug_mat_cache_max();
-void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream);
-// pt_debug_camera_rays / pt_lens_focus_at: d_out = 8 floats per query / 2 floats {hit, view-space depth}
-void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+// pt_lens_focus_at: d_out = 2 floats {hit, view-space depth}
 void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream);
-// pt_debug_trace_queues (test hook): host arrays.  closest: 8 floats per ray (origin, tmin = 0, direction, tmax); shadow: 6 floats per ray (origin,
-// direction).  out_closest: 8 floats per ray as pt_debug_intersect writes them (all kDebugSentinel bits where the kernel wrote no hit record);
-// out_shadow: the transmission written beside ray i's pending term; out_cnt: the counter words [shard][0..6] after the launch;
-// out_stray: {hit entries, pending records} outside the rays' own that no longer hold the sentinel.
-struct DebugQueues {
-    const float* closest; const uint32_t* closest_shard; uint32_t n_closest;
-    const float* shadow; const uint32_t* shadow_shard; const uint8_t* shadow_is_light; uint32_t n_shadow;
-    float shadow_tmax;
-    uint32_t flags; int bounce; uint32_t blocks_per_shard; int which;
-    float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
-};
-hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
 // Adaptive sampling (pt_set_adaptive): the state of one of this rank's tiles, indexed by the rank-local tile (the resolve block).
 // An active tile holds the context's accumulated_frames samples; a retired one keeps the count it retired with.
 struct AdaptiveTile {
@@ -227,11 +198,39 @@ size_t wavefront_workspace_bytes(const FrameConstants& fc, int stage_blocks, con
 // lens: pt_set_lens as k_wf_generate takes it (enable == 0: the pinhole)
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const WavefrontPasses& passes);
+
+// ---- debug_wf.hip / debug_mk.hip: the device side of the test hooks (mipt_debug.hip), compiled as pt_wavefront.hip / pt_kernel.hip are ----
+// The per-lane query hooks, one text (pt_debug_kernels.h) in both builds: sampler; environment light (8 floats in, 16 out per query); BSDF
+// (48 in, 16 out); punctual lights (an index and a point in, 8 out); vertex fetch and material evaluation (8 words in, 72 out).  Only
+// the wavefront build looks at small_tables; the three sizes below are its shade stage's LDS copies (kLightCacheMax, kInstCacheMax, kMatCacheMax).
+struct DebugQueryLaunch {
+    void (*sample_texture)(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream);
+    void (*env_query)(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+    void (*bsdf_query)(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+    void (*light_query)(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream);
+    void (*surface_query)(const SceneRec& sc, bool small_tables, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
+};
+DebugQueryLaunch debug_queries_wf(), debug_queries_mk();     // (functions: a const table of host functions would be emitted as device data too)
+int debug_light_cache_max(), debug_inst_cache_max(), debug_mat_cache_max();
+void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream);
+// pt_debug_camera_rays: d_out = 8 floats per query {px, py, seed}, camera_ray's ray
+void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
 // pt_debug_bake_rays: d_out = 8 floats per query {px, py, seed}, bake_ray's ray; zeros with tmax = -1 for an uncovered texel or one off the atlas
 void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
-
 // pt_debug_probe_rays: d_out = 8 floats per query {px, py, seed}, probe_ray's ray; zeros with tmax = -1 for an absent probe or a texel off the atlas
 void launch_debug_probe_rays(const FrameConstants& fc, const ProbeArgs& probes, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream);
+// pt_debug_trace_queues (test hook): host arrays.  closest: 8 floats per ray (origin, tmin = 0, direction, tmax); shadow: 6 floats per ray (origin,
+// direction).  out_closest: 8 floats per ray as pt_debug_intersect writes them (all kDebugSentinel bits where the kernel wrote no hit record);
+// out_shadow: the transmission written beside ray i's pending term; out_cnt: the counter words [shard][0..6] after the launch;
+// out_stray: {hit entries, pending records} outside the rays' own that no longer hold the sentinel.
+struct DebugQueues {
+    const float* closest; const uint32_t* closest_shard; uint32_t n_closest;
+    const float* shadow; const uint32_t* shadow_shard; const uint8_t* shadow_is_light; uint32_t n_shadow;
+    float shadow_tmax;
+    uint32_t flags; int bounce; uint32_t blocks_per_shard; int which;
+    float* out_closest; float* out_shadow; uint32_t* out_cnt; uint32_t* out_stray;
+};
+hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why);
 
 // ---- matte.hip: pt_matte_extract's mask of a set of ids ----------------------------------------------------------------------------
 constexpr int kMatteExtractMaxIds = 64;

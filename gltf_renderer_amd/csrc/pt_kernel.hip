@@ -17,6 +17,8 @@
 //
 // Work mapping (both): a rank renders the 16x16 tiles t with t % tile_rank_count == tile_rank; slot s of a
 // rank is pixel (s & 255) of its (s >> 8)-th tile, one wave64 per 8x8 quadrant (coherent primary rays).
+//
+// Product code only: the test hooks that run this file's arrangement are compiled with its flags in debug_mk.hip.
 #include "pt_vertex.h"
 #include "pt_host.h"
 
@@ -114,43 +116,6 @@ void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensA
     else hipLaunchKernelGGL(pt_megakernel<false>, grid, block, 0, stream, sc, fc, output, counters, lens);
 }
 
-// Test hook (pt_debug_intersect): the product's traversal on caller-supplied rays, one ray per lane -- what TraceRay / TraceShadowRay find,
-// without the shading around them.  rays: 8 floats each (origin, tmin, direction, tmax); out: 8 floats each (committed, t, u, v, instance,
-// primitive, front face, transmission).
-__global__ __launch_bounds__(kBlock) void k_debug_intersect(SceneRec sc, const float* __restrict__ rays, uint32_t n, uint32_t rf, int mode, float* __restrict__ out) {
-    __shared__ int s_stack[kStackLds * kBlock];
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float* q = rays + (size_t)i * 8;
-    Ray r; r.o = v3(q[0], q[1], q[2]); r.tmin = q[3]; r.d = v3(q[4], q[5], q[6]); r.tmax = q[7];
-    HitRec hit; LaneStats st = {0, 0, 0, 0, 0};
-    float transmission = (mode == 1 && (rf & RF_FORCE_NON_OPAQUE)) ? 1.0f : 0.0f;
-    const bool got = traverse<false>(sc, s_stack + threadIdx.x, r, rf, 0xff, mode, hit, transmission, st);
-    float* o = out + (size_t)i * 8;
-    const bool have = got && hit.tri >= 0;
-    o[0] = got ? 1.0f : 0.0f; o[1] = have ? hit.t : 0.0f; o[2] = have ? hit.u : 0.0f; o[3] = have ? hit.v : 0.0f;
-    o[4] = have ? (float)sc.tris[hit.tri].inst : -1.0f; o[5] = have ? (float)sc.tris[hit.tri].prim : -1.0f; o[6] = (have && hit.front) ? 1.0f : 0.0f;
-    o[7] = transmission;
-}
-void launch_debug_intersect(const SceneRec& sc, const float* d_rays, uint32_t n, uint32_t rf, int mode, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_intersect, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_rays, n, rf, mode, d_out);
-}
-
-// Test hook (pt_debug_camera_rays): the camera rays pt_trace generates, one query {px, py, seed} per lane, through camera_ray itself under the
-// context's lens.  out: 8 floats per query (origin, tmin, direction, tmax).
-__global__ __launch_bounds__(kBlock) void k_debug_camera_rays(FrameConstants fc, LensArgs lens, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    int rc = 0;
-    const Ray r = camera_ray(fc, lens, queries[3 * (size_t)i + 2], queries[3 * (size_t)i], queries[3 * (size_t)i + 1], rc);
-    float* o = out + (size_t)i * 8;
-    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
-}
-void launch_debug_camera_rays(const FrameConstants& fc, const LensArgs& lens, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, lens, d_queries, n, d_out);
-}
 // Autofocus (pt_lens_focus_at): the pinhole ray through image position (sx, sy) -- no jitter, no lens -- and TraceRay's closest hit along it.
 // One lane works; out[0] = 1 for a hit, out[1] = its view-space depth zo + t * dn (include/mipt.h pt_set_lens; lens.c and lens.F are used).
 __global__ __launch_bounds__(kBlock) void k_lens_focus(SceneRec sc, FrameConstants fc, LensArgs lens, float sx, float sy, uint32_t rf, float* __restrict__ out) {
@@ -168,99 +133,6 @@ __global__ __launch_bounds__(kBlock) void k_lens_focus(SceneRec sc, FrameConstan
 void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream) {
     hipLaunchKernelGGL(k_lens_focus, dim3(1), dim3(kBlock), 0, stream, sc, fc, lens, sx, sy, rf, d_out);
 }
-
-// Test hook (pt_debug_sample_texture, mipt_debug.hip): the sampler as the megakernel runs it -- sRGB table and material records in global memory.
-__global__ __launch_bounds__(kBlock) void k_debug_sample_texture_mk(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
-                                                                 uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const vec2 uv[2] = {{tc[4 * i], tc[4 * i + 1]}, {tc[4 * i + 2], tc[4 * i + 3]}};
-    int32_t t5[5];
-    const vec4 r = debug_sample_query(sc, mat_slot[2 * i], (int)mat_slot[2 * i + 1], uv, t5);
-    out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
-    for (int c = 0; c < 5; c++) taps[5 * i + c] = t5[c];
-}
-void launch_debug_sample_texture_mk(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_sample_texture_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
-}
-// Test hook (pt_debug_env_query, mipt_debug.hip): the environment light as the megakernel runs it -- the whole pyramid in global memory.
-__global__ __launch_bounds__(kBlock) void k_debug_env_query_mk(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_env_query(sc, op, in + (size_t)kEnvQueryIn * i, out + (size_t)kEnvQueryOut * i, importance_lds_top());
-}
-void launch_debug_env_query_mk(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_env_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
-}
-// Test hook (pt_debug_bsdf_query, mipt_debug.hip): the BSDF as the megakernel runs it -- the sheen table in global memory.  Query i runs in
-// lane i % 64 of wave i / 64.
-__global__ __launch_bounds__(kBlock) void k_debug_bsdf_query_mk(SceneRec sc, int op, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_bsdf_query(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);
-}
-void launch_debug_bsdf_query_mk(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_bsdf_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, flags, d_in, n, d_out);
-}
-// Test hook (pt_debug_light_query, mipt_debug.hip): the punctual lights as the megakernel runs them -- the table in global memory, the cone
-// terms computed in place.  The host checks that every index is below the table's size.
-__global__ __launch_bounds__(kBlock) void k_debug_light_query_mk(SceneRec sc, const uint32_t* __restrict__ index, const float* __restrict__ p, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_light_query(sc, index[i], v3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]), out + (size_t)kLightQueryOut * i);
-}
-void launch_debug_light_query_mk(const SceneRec& sc, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_light_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_index, d_p, n, d_out);
-}
-// Test hook (pt_debug_surface_query, mipt_debug.hip): the vertex fetch and the material evaluation as the megakernel runs them -- every
-// table in global memory.  The host checks that every packet index is below num_tris.  Query i runs in lane i % 64 of wave i / 64.
-__global__ __launch_bounds__(kBlock) void k_debug_surface_query_mk(SceneRec sc, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_surface_query(sc, flags, in + (size_t)kSurfQueryIn * i, out + (size_t)kSurfQueryOut * i);
-}
-void launch_debug_surface_query_mk(const SceneRec& sc, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_surface_query_mk, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, flags, d_in, n, d_out);
-}
-// Test hook (pt_debug_math): the kernels' own math routines on caller-supplied arguments, for the bit-for-bit comparison with the oracle's.
-// op: 0 atan2(a, b)  1 pow(a, b)  2 exp(a)  3 log2(a)  4 exp2(a)  5 sin(a)  6 cos(a)  7 a / b by fdiv  8 pow5(a)
-__global__ __launch_bounds__(256) void k_debug_math(int op, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float x = a[i], y = b[i];
-    float r = 0, s, c;
-    switch (op) {
-        case 0: r = pt_atan2(x, y); break;
-        case 1: r = hpow(x, y); break;
-        case 2: r = pt_exp(x); break;
-        case 3: r = co_log2(x); break;
-        case 4: r = co_exp2(x); break;
-        case 5: pt_sincos(x, s, c); r = s; break;
-        case 6: pt_sincos(x, s, c); r = c; break;
-        case 7: r = fdiv(x, y); break;
-        case 8: r = hpow5(x); break;
-    }
-    out[i] = r;
-}
-}  // namespace pt
-extern "C" int pt_debug_math(int op, const float* a, const float* b, float* out, uint32_t n) {
-    if (n == 0) return 0;
-    float *da = nullptr, *db = nullptr, *dc = nullptr;
-    int rc = -3;
-    if (hipMalloc(&da, (size_t)n * 4) == hipSuccess && hipMalloc(&db, (size_t)n * 4) == hipSuccess && hipMalloc(&dc, (size_t)n * 4) == hipSuccess &&
-        hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db, b, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(pt::k_debug_math, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, (const float*)da, (const float*)db, dc, n);
-        if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dc, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-    }
-    hipFree(da); hipFree(db); hipFree(dc);
-    return rc;
-}
-namespace pt {
 
 // (sin, cos) table of the packed tangent angle, filled by the decoder's own expression (pt_shading.h)
 __global__ __launch_bounds__(256) void k_tangent_lut(float2* __restrict__ out) {

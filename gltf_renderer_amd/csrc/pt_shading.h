@@ -410,6 +410,7 @@ PT_DEV RTex material_slot012(const SceneRec& sc, uint32_t mid, int slot) {      
     return load_rtex(&sc.rmats[mid].tex[slot]);
 }
 #else
+PT_DEV void stage_materials(const SceneRec&) {}
 PT_DEV MatHeader material_header(const SceneRec& sc, uint32_t mid) { return load_mat_header(sc.rmats + mid); }
 PT_DEV RTex material_slot012(const SceneRec& sc, uint32_t mid, int slot) { return load_rtex(&sc.rmats[mid].tex[slot]); }
 #endif

@@ -17,13 +17,13 @@
 // Determinism: a pixel's radiance is accumulated in its own slot in a fixed order (hit terms, then the
 // env-shadow term, then the light-shadow term of that vertex), independent of queue order, so frames are
 // bit-reproducible and N tile shards compose bit-exactly.
+//
+// Product code only: the test hooks that run this file's stages are compiled with its flags in debug_wf.hip (pt_wavefront.h: what they share).
 #define PT_LUT_LDS 1          // every stage kernel of this file stages the sRGB table into LDS (pt_shading.h stage_luts)
-#include <algorithm>
-#include <cstring>
 #include <type_traits>
 
 #include "pt_vertex.h"
-#include "pt_host.h"
+#include "pt_wavefront.h"
 #include "pt_workspace.h"
 #include "pt_bake.h"
 #include "pt_probe.h"
@@ -53,43 +53,7 @@ extern "C" int pt_debug_read_util(unsigned long long* out16, int reset) {
 #endif
 namespace pt {
 
-// (kShards, kXcds, kCounterStride and kCounterArrays: pt_workspace.h, with the layout they size)
-constexpr uint32_t kMissTri = 0x7fffffffu;
-constexpr uint32_t kNoHint = 0xffffffffu;
-
-struct WfBuffers {
-    // per slot (one path per pixel of this rank)
-    float4* L;            // xyz radiance so far; w = bits: bit 0 env term pending, bit 1 light term pending
-    float4* beta_pdf;     // unused (beta and throughput travel in q_beta / q_thr): no kernel reads or writes these two; they keep the
-    float4* thr_misc;     // kernel-argument layout
-    float4* pend;         // [2 * slot] xyz pending env-NEE term (beta-weighted), w = its shadow transmission (written by the shadow stage);
-                          // [2 * slot + 1] the same for the punctual-light term: one 32-B piece per path
-    // closest-ray queues (ping-pong), kShards segments of seg_cap entries: (o.xyz, tmax), (d.xyz, slot)
-    float4* ray_o[2];
-    float4* ray_d[2];
-    float4* q_beta[2];    // the path's (beta, prev_pdf) and (throughput, misc bits) travel with its closest-ray entry -- written
-    float4* q_thr[2];     // compacted, read coalesced -- instead of living in slot-indexed arrays
-    float4* hit;          // per entry of the current queue: t, u, v, bits: tri | front << 31 (kMissTri: miss)
-    float4* env_a;        // per entry of the current closest queue: the vertex's environment light sample, drawn by the traversal stage that
-    float4* env_b;        // traces the entry (env_prepass): (direction, pdf), (radiance, -)
-    // shadow queue, kShards segments of 2 * seg_cap entries: (o.xyz, bits: slot | is_light << 31), (d.xyz, tmax)
-    float4* sh_o;
-    float4* sh_d;         // (d.xyz, kNoHint; the rays' tmax is the constant max_ray_length)
-    uint32_t* sh_c;       // unused, nullptr (kernel-argument layout)
-    uint32_t* occ_cache;  // unused, nullptr (kernel-argument layout)
-    uint32_t* cnt[7];     // per shard (stride kCounterStride): entry counts of closest queue 0, closest queue 1, shadow queue (even bounces);
-                          // [3], [4]: dynamic-fetch heads of the closest / shadow trace stages; [5]: shadow-queue count of odd bounces
-                          // (the shadow count ping-pongs so that the fused traversal stage can zero the one the NEXT shade stage fills
-                          // while it still reads the current one); [6]: dynamic-fetch head of the shade stage.  Only word 0 of a shard's
-                          // line is the counter; words 2 .. 11 of the [3] line hold the generate and shade stages' ray tallies (shard_tallies)
-    uint32_t capacity;    // slots
-    uint32_t chunks_per_shard;   // path-state arrays: 256-slot chunks per shard (unused by the kernels)
-    uint32_t seg_cap;     // entries per closest-queue segment
-    uint32_t blocks_per_shard;
-    uint32_t gen_region_tiles, gen_rounds;     // k_wf_generate: (unused, 0), workgroup-rounds to cover the (tile, sample) pairs
-};
-
-
+// (WfBuffers, kMissTri, kNoHint and shadow_counter: pt_wavefront.h, shared with the test hooks of debug_wf.hip)
 // Queue entries are written once and read once, a stage apart, by then long evicted from the 4-MiB L2s: they are moved with the
 // non-temporal hint (QLD / QST) so that they do not push the tree's nodes and triangle packets out on their way through.  The per-path
 // state records are accessed plainly.
@@ -244,22 +208,6 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate_bake(FrameConstants fc, 
     }
     flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
 }
-// Test hook (pt_debug_bake_rays, mipt_debug.hip): bake_ray itself, one query {px, py, seed} per lane
-__global__ __launch_bounds__(kBlock) void k_debug_bake_rays(FrameConstants fc, BakeArgs bk, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t px = queries[3 * (size_t)i], py = queries[3 * (size_t)i + 1];
-    int rc = 0;
-    Ray r;
-    r.o = v3(0); r.d = v3(0); r.tmin = 0; r.tmax = -1.0f;
-    if (px < fc.res_x && py < fc.res_y) bake_ray(fc, bk, queries[3 * (size_t)i + 2], px, py, rc, r);
-    float* o = out + (size_t)i * 8;
-    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
-}
-void launch_debug_bake_rays(const FrameConstants& fc, const BakeArgs& bake, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_bake_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, bake, d_queries, n, d_out);
-}
 
 // Light-probe baking (pt_set_probes): the generate stage of an atlas whose "camera" is a set of points -- k_wf_generate_bake with another ray.
 // Slots, tiles, shards and the queue are k_wf_generate's; the ray of a (texel, sample) is probe_ray's (pt_probe.h).  The resolution is a
@@ -295,29 +243,12 @@ __global__ __launch_bounds__(kBlock, 7) void k_wf_generate_probe(FrameConstants 
     }
     flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
 }
-// Test hook (pt_debug_probe_rays, mipt_debug.hip): probe_ray itself, one query {px, py, seed} per lane (the cells differ from lane to lane)
-__global__ __launch_bounds__(kBlock) void k_debug_probe_rays(FrameConstants fc, ProbeArgs pa, const uint32_t* __restrict__ queries, uint32_t n, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t px = queries[3 * (size_t)i], py = queries[3 * (size_t)i + 1];
-    int rc = 0;
-    Ray r;
-    r.o = v3(0); r.d = v3(0); r.tmin = 0; r.tmax = -1.0f;
-    if (px < fc.res_x && py < fc.res_y) probe_ray<false>(fc, pa, queries[3 * (size_t)i + 2], px, py, rc, r);
-    float* o = out + (size_t)i * 8;
-    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.tmin; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.tmax;
-}
-void launch_debug_probe_rays(const FrameConstants& fc, const ProbeArgs& probes, const uint32_t* d_queries, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_probe_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fc, probes, d_queries, n, d_out);
-}
 
 // Wave-persistent "while-while" traversal of one shard segment with dynamic ray fetch (pt_traverse.h).
 // MODE 0: closest hits of queue `cur` -> wf.hit.  MODE 1: occlusion of the shadow queue -> pend_*.w.
 #ifndef PT_REFILL
 #define PT_REFILL 32          // idle lanes that trigger a refill from the shard queue (swept 8..64 on MI355X: 48 was best in round 1; re-swept after the sample pre-pass: 16 / 24 / 32 / 40 / 48 / 56 -> 5470 / 5507 / 5538 / 5536 / 5500 / 5275 Mrays/s)
 #endif
-PT_DEV int shadow_counter(int bounce) { return (bounce & 1) ? 5 : 2; }
 template <bool COUNT, int MODE>
 PT_DEV void trace_persistent(const SceneRec& sc, const WfBuffers& wf, int* my_stack, const ShardView& sv, int cur, uint32_t rf_closest, uint32_t rmask,
                              uint32_t flags, LaneStats& st, float shadow_tmax = 0.0f) {
@@ -732,88 +663,6 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_shadow(SceneRec s
     else if (st.overflow | st.deep) flush_rare(counters, st);
 }
 
-// Test hook (pt_debug_sample_texture, mipt_debug.hip): the sampler as this file's stages run it -- sRGB table and material records in LDS.
-__global__ __launch_bounds__(kBlock) void k_debug_sample_texture_wf(SceneRec sc, const uint32_t* __restrict__ mat_slot, const float* __restrict__ tc,
-                                                                 uint32_t n, float* __restrict__ out, int32_t* __restrict__ taps) {
-    stage_luts(sc);
-    stage_materials(sc);
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const vec2 uv[2] = {{tc[4 * i], tc[4 * i + 1]}, {tc[4 * i + 2], tc[4 * i + 3]}};
-    int32_t t5[5];
-    const vec4 r = debug_sample_query(sc, mat_slot[2 * i], (int)mat_slot[2 * i + 1], uv, t5);
-    out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
-    for (int c = 0; c < 5; c++) taps[5 * i + c] = t5[c];
-}
-void launch_debug_sample_texture_wf(const SceneRec& sc, const uint32_t* d_mat_slot, const float* d_tc, uint32_t n, float* d_out, int32_t* d_taps, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_sample_texture_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, d_mat_slot, d_tc, n, d_out, d_taps);
-}
-// Test hook (pt_debug_env_query, mipt_debug.hip): the environment light as this file's stages run it -- the three coarsest level pairs of the
-// importance pyramid staged, as env_prepass stages them, into LDS of the traversal stack's type and size.  Every lane stages before any
-// lane without a query leaves.
-__global__ __launch_bounds__(kBlock) void k_debug_env_query_wf(SceneRec sc, int op, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    __shared__ int s_stack[kStackLds * kBlock];
-    static_assert((size_t)kStackLds * kBlock * sizeof(int) >= (size_t)kImpLdsFloat4 * sizeof(float4), "the traversal stack's LDS must hold the importance pyramid's coarse levels");
-    float4* top = (float4*)s_stack;
-    stage_importance_top_into(sc, top);
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_env_query(sc, op, in + (size_t)kEnvQueryIn * i, out + (size_t)kEnvQueryOut * i, top);
-}
-void launch_debug_env_query_wf(const SceneRec& sc, int op, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_env_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, d_in, n, d_out);
-}
-// Test hook (pt_debug_bsdf_query, mipt_debug.hip): the BSDF as this file's shade stage runs it -- the sheen table staged into LDS by stage_luts.
-// Query i runs in lane i % 64 of wave i / 64; every lane stages before any lane without a query leaves.
-__global__ __launch_bounds__(kBlock) void k_debug_bsdf_query_wf(SceneRec sc, int op, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    stage_luts(sc);
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_bsdf_query(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);
-}
-void launch_debug_bsdf_query_wf(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_bsdf_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, op, flags, d_in, n, d_out);
-}
-// Test hook (pt_debug_light_query, mipt_debug.hip): the punctual lights as this file's shade stage runs them -- the first kLightCacheMax
-// lights staged into LDS with their cone terms (stage_lights), `small_tables` as k_wf_shade's SMALL.  The host checks that small_tables
-// comes with at most kLightCacheMax lights and that every index is below num_of_lights.
-__global__ __launch_bounds__(kBlock) void k_debug_light_query_wf(SceneRec sc_in, uint32_t small_tables, int num_of_lights, const uint32_t* __restrict__ index,
-                                                              const float* __restrict__ p, uint32_t n, float* __restrict__ out) {
-    SceneRec sc = sc_in; sc.small_tables = small_tables ? 1u : 0u;
-    stage_lights(sc, num_of_lights);
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_light_query(sc, index[i], v3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]), out + (size_t)kLightQueryOut * i);
-}
-void launch_debug_light_query_wf(const SceneRec& sc, bool small_tables, int num_of_lights, const uint32_t* d_index, const float* d_p, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_light_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, small_tables ? 1u : 0u, num_of_lights, d_index, d_p, n, d_out);
-}
-int debug_light_cache_max() { return kLightCacheMax; }
-// Test hook (pt_debug_surface_query, mipt_debug.hip): the vertex fetch and the material evaluation as this file's shade stage runs them --
-// the sRGB, sheen and tangent tables, the instance rows and the material records staged into LDS as k_wf_shade stages them,
-// `small_tables` as k_wf_shade's SMALL.  The host checks that small_tables comes with at most kInstCacheMax instances and kMatCacheMax
-// materials and that every packet index is below num_tris.  Query i runs in lane i % 64 of wave i / 64; every lane stages before any
-// lane without a query leaves.
-__global__ __launch_bounds__(kBlock) void k_debug_surface_query_wf(SceneRec sc_in, uint32_t small_tables, uint32_t flags, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
-    SceneRec sc = sc_in; sc.small_tables = small_tables ? 1u : 0u;
-    stage_luts(sc);
-    stage_tangent_lut(sc);
-    stage_instances(sc);
-    stage_materials(sc);
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    debug_surface_query(sc, flags, in + (size_t)kSurfQueryIn * i, out + (size_t)kSurfQueryOut * i);
-}
-void launch_debug_surface_query_wf(const SceneRec& sc, bool small_tables, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_debug_surface_query_wf, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, sc, small_tables ? 1u : 0u, flags, d_in, n, d_out);
-}
-int debug_inst_cache_max() { return (int)kInstCacheMax; }
-int debug_mat_cache_max() { return (int)kMatCacheMax; }
 // First-hit AOVs (pt_set_aov): albedo, shading normal and depth of the vertex the camera ray reaches, one 32-B record per slot.  A stage
 // of its own between the primary traversal and the first shade stage -- queue 0's rays and wf.hit are intact in that window -- so that
 // the shade stage, priced by the register allocation of its one function, stays what it is.  It walks the shard's segment like every
@@ -1101,32 +950,22 @@ static WfBuffers carve(void* workspace, const WorkspaceLayout& l, uint32_t slots
 int traversal_stack_capacity() { return kStackLds + kStackSpill; }
 size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_per_shard_for(stage_blocks) * kBlock; }
 
-// ---- the traversal stages' ray flags, kernel copies and launches: ONE statement of each, called by launch_wavefront and by the test hook
-// debug_trace_queues below, so that the hook launches what a frame launches.
-// Ray flags and instance mask of the closest-hit rays of bounce b.
-static void traversal_ray_flags(uint32_t flags, int b, uint32_t& rf, uint32_t& rmask) {
-    rmask = 0xff;
-    if (b == 0) rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_BACK : 0;                              // RayGeneration :747
-    else {                                                                                            // TraceBounceRay :671-672
-        rf = (flags & PT_FLAG_CULL_BACKFACE) ? RF_CULL_FRONT : 0;
-        rmask = (flags & PT_FLAG_INDIRECT_ENVIRONMENT_ONLY) ? 0 : 0xff;
-    }
-}
+// ---- the traversal stages' kernel copies and launches (pt_wavefront.h: declared there, with the ray flags, for the test hook too)
 // the traversal kernels compiled for rays with no flags, if that is what the frame's settings give them
 static bool traversal_defaults(uint32_t flags) { return (flags & kTravFlagMask) == 0; }
 // A run-time bool as a compile-time one: f(std::true_type()) or f(std::false_type()), so that a launch line is written once for both
 // kernel copies.  pick2: two of them.
 template <class F> static void pick(bool a, F&& f) { if (a) f(std::true_type()); else f(std::false_type()); }
 template <class F> static void pick2(bool a, bool b, F&& f) { pick(a, [&](auto A) { pick(b, [&](auto B) { f(A, B); }); }); }
-static void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
-                            uint32_t rmask, Counters* counters) {
+void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
+                     uint32_t rmask, Counters* counters) {
     pick2(count, traversal_defaults(fc.flags), [&](auto COUNT, auto DEFAULTS) { hipLaunchKernelGGL((k_wf_trace<COUNT.value, DEFAULTS.value>), grid, dim3(kBlock), 0, stream, sc, fc, w, cur, b, rf, rmask, counters); });
 }
-static void launch_wf_traverse(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int nxt, int b, uint32_t rf,
-                               uint32_t rmask, Counters* counters) {
+void launch_wf_traverse(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int nxt, int b, uint32_t rf,
+                        uint32_t rmask, Counters* counters) {
     pick2(count, traversal_defaults(fc.flags), [&](auto COUNT, auto DEFAULTS) { hipLaunchKernelGGL((k_wf_traverse<COUNT.value, DEFAULTS.value>), grid, dim3(kBlock), 0, stream, sc, fc, w, nxt, b, rf, rmask, fc.flags, counters); });
 }
-static void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const WfBuffers& w, int b, uint32_t flags, float tmax, Counters* counters) {
+void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const WfBuffers& w, int b, uint32_t flags, float tmax, Counters* counters) {
     pick(count, [&](auto COUNT) { hipLaunchKernelGGL(k_wf_shadow<COUNT.value>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters); });
 }
 
@@ -1255,133 +1094,6 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
     pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av, counters); });
     mark(STAGE_RESOLVE);
     return hipGetLastError();
-}
-
-// Test hook (pt_debug_trace_queues, mipt_debug.hip): the traversal kernels of a frame -- k_wf_trace, k_wf_shadow or the fused k_wf_traverse, through
-// the launch functions above -- on queues the caller filled.  Owns a small WfBuffers: the seven counter arrays, one closest queue with its hit
-// array, the shadow queue and the pending records, nothing else (sc.has_env must be 0, so no environment buffers are read).
-// Every output word holds kDebugSentinel before the launch and each shard's segment ends in a guard entry nobody may write.
-// `bounce` is the closest rays' bounce (which 0, 2) or the shadow rays' (which 1); the fused launch takes the shadow rays of bounce - 1 with it,
-// as in a frame.  Synchronises the stream.
-constexpr uint32_t kDebugSentinel = 0x7fc5a5a5u;           // a quiet NaN with a payload no kernel produces
-hipError_t debug_trace_queues(const SceneRec& sc, const DebugQueues& q, Counters* counters, bool count, hipStream_t stream, std::string& why) {
-    why.clear();
-    const int cur = q.bounce & 1;                                                       // the closest queue of that bounce (launch_wavefront)
-    const int shadow_bounce = q.which == 2 ? q.bounce - 1 : q.bounce;
-    const int scnt = (shadow_bounce & 1) ? 5 : 2;                                       // shadow_counter(), which is device code
-    std::vector<uint32_t> n_c(kShards, 0), n_s(kShards, 0);
-    for (uint32_t i = 0; i < q.n_closest; i++) n_c[q.closest_shard[i]]++;
-    for (uint32_t i = 0; i < q.n_shadow; i++) n_s[q.shadow_shard[i]]++;
-    uint32_t seg = 0;
-    for (uint32_t s = 0; s < kShards; s++) seg = std::max(seg, std::max(n_c[s], (n_s[s] + 1u) / 2u));
-    WfBuffers wf;
-    std::memset(&wf, 0, sizeof(wf));
-    wf.seg_cap = seg + 1u;                                                              // the guard entry (two for the shadow queue)
-    wf.blocks_per_shard = q.blocks_per_shard;
-    wf.capacity = q.n_shadow + 1u;                                                      // slots: one per shadow ray and a guard
-    const size_t qn = (size_t)kShards * wf.seg_cap, slots = state_slots_for(wf.capacity, kBlock), cnt_words = (size_t)kCounterArrays * kShards * kCounterStride;
-    // host images of the buffers
-    std::vector<uint32_t> h_cnt(cnt_words, kDebugSentinel);
-    std::vector<float4> h_ro(qn), h_rd(qn), h_so(qn * 2), h_sd(qn * 2);
-    const float sentinel = *(const float*)&kDebugSentinel;
-    const float4 sent4 = make_float4(sentinel, sentinel, sentinel, sentinel);
-    std::vector<float4> h_hit(qn, sent4), h_pend(slots * 2, sent4);
-    std::memset(h_ro.data(), 0, qn * 16); std::memset(h_rd.data(), 0, qn * 16); std::memset(h_so.data(), 0, qn * 32); std::memset(h_sd.data(), 0, qn * 32);
-    std::vector<uint32_t> at_c(q.n_closest), at_s(q.n_shadow), fill(kShards, 0);
-    for (uint32_t i = 0; i < q.n_closest; i++) {
-        const uint32_t s = q.closest_shard[i];
-        const size_t e = (size_t)s * wf.seg_cap + fill[s]++;
-        const float* r = q.closest + (size_t)i * 8;
-        h_ro[e] = make_float4(r[0], r[1], r[2], r[7]);
-        h_rd[e] = make_float4(r[4], r[5], r[6], *(const float*)&i);                     // (d.w = the path's slot: unused by the traversal)
-        at_c[i] = (uint32_t)e;
-    }
-    std::fill(fill.begin(), fill.end(), 0u);
-    for (uint32_t i = 0; i < q.n_shadow; i++) {
-        const uint32_t s = q.shadow_shard[i];
-        const size_t e = (size_t)s * wf.seg_cap * 2 + fill[s]++;
-        const float* r = q.shadow + (size_t)i * 6;
-        const uint32_t bits = i | (q.shadow_is_light[i] ? 0x80000000u : 0u);
-        h_so[e] = make_float4(r[0], r[1], r[2], *(const float*)&bits);
-        h_sd[e] = make_float4(r[3], r[4], r[5], *(const float*)&kNoHint);
-        at_s[i] = (uint32_t)e;
-    }
-    for (uint32_t s = 0; s < kShards; s++) {
-        if (q.which != 1) h_cnt[(size_t)cur * kShards * kCounterStride + s * kCounterStride] = n_c[s];      // (a counter no launched kernel reads keeps the sentinel)
-        if (q.which != 0) h_cnt[(size_t)scnt * kShards * kCounterStride + s * kCounterStride] = n_s[s];
-        h_cnt[(size_t)3 * kShards * kCounterStride + s * kCounterStride] = 0;           // the fetch heads: in a frame the shade stage rewinds them
-        h_cnt[(size_t)4 * kShards * kCounterStride + s * kCounterStride] = 0;
-    }
-    char* d_all = nullptr;
-    const size_t b_cnt = cnt_words * 4, b_q = qn * 16;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t total = up(b_cnt) + 3 * up(b_q) + 2 * up(b_q * 2) + up(slots * 32);
-    if (hipMalloc((void**)&d_all, total) != hipSuccess) { (void)hipGetLastError(); why = "queue buffers"; return hipErrorOutOfMemory; }
-    char* p = d_all;
-    auto take = [&](size_t b) { char* r = p; p += up(b); return r; };
-    uint32_t* d_cnt = (uint32_t*)take(b_cnt);
-    for (int k = 0; k < kCounterArrays; k++) wf.cnt[k] = d_cnt + (size_t)k * kShards * kCounterStride;
-    wf.ray_o[cur] = (float4*)take(b_q); wf.ray_d[cur] = (float4*)take(b_q); wf.hit = (float4*)take(b_q);
-    wf.sh_o = (float4*)take(b_q * 2); wf.sh_d = (float4*)take(b_q * 2);
-    wf.pend = (float4*)take(slots * 32);
-    hipError_t e = hipMemcpyAsync(d_cnt, h_cnt.data(), b_cnt, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.ray_o[cur], h_ro.data(), b_q, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.ray_d[cur], h_rd.data(), b_q, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.hit, h_hit.data(), b_q, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.sh_o, h_so.data(), b_q * 2, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.sh_d, h_sd.data(), b_q * 2, hipMemcpyHostToDevice, stream);
-    if (!e) e = hipMemcpyAsync(wf.pend, h_pend.data(), slots * 32, hipMemcpyHostToDevice, stream);
-    if (!e) {
-        FrameConstants fc;
-        std::memset(&fc, 0, sizeof(fc));
-        fc.flags = q.flags; fc.max_ray_length = q.shadow_tmax;
-        uint32_t rf, rmask;
-        traversal_ray_flags(q.flags, q.bounce, rf, rmask);
-        const dim3 grid(kShards * wf.blocks_per_shard);
-        if (q.which == 0) launch_wf_trace(grid, stream, count, sc, fc, wf, cur, q.bounce, rf, rmask, counters);
-        else if (q.which == 1) launch_wf_shadow(grid, stream, count, sc, wf, q.bounce, q.flags, q.shadow_tmax, counters);
-        else launch_wf_traverse(grid, stream, count, sc, fc, wf, cur, q.bounce - 1, rf, rmask, counters);
-        e = hipGetLastError();
-    }
-    std::vector<TriPacket> h_tris(sc.num_tris);
-    if (!e) e = hipMemcpyAsync(h_cnt.data(), d_cnt, b_cnt, hipMemcpyDeviceToHost, stream);
-    if (!e) e = hipMemcpyAsync(h_hit.data(), wf.hit, b_q, hipMemcpyDeviceToHost, stream);
-    if (!e) e = hipMemcpyAsync(h_pend.data(), wf.pend, slots * 32, hipMemcpyDeviceToHost, stream);
-    if (!e && sc.num_tris) e = hipMemcpyAsync(h_tris.data(), sc.tris, (size_t)sc.num_tris * sizeof(TriPacket), hipMemcpyDeviceToHost, stream);
-    if (!e) e = hipStreamSynchronize(stream);
-    hipFree(d_all);
-    if (e) { why = hipGetErrorString(e); return e; }
-    // ---- translate
-    auto is_sentinel = [](float v) { uint32_t b; std::memcpy(&b, &v, 4); return b == kDebugSentinel; };
-    auto untouched = [&](const float4& v) { return is_sentinel(v.x) && is_sentinel(v.y) && is_sentinel(v.z) && is_sentinel(v.w); };
-    std::vector<uint8_t> expected(qn, 0);
-    for (uint32_t i = 0; i < q.n_closest; i++) {
-        float* o = q.out_closest + (size_t)i * 8;
-        const float4 h = h_hit[at_c[i]];
-        expected[at_c[i]] = 1;
-        if (untouched(h)) { for (int k = 0; k < 8; k++) o[k] = sentinel; continue; }
-        uint32_t bits; std::memcpy(&bits, &h.w, 4);
-        const bool hit = bits != kMissTri && (bits & 0x7fffffffu) < sc.num_tris;
-        o[0] = hit ? 1.0f : 0.0f; o[1] = hit ? h.x : 0.0f; o[2] = hit ? h.y : 0.0f; o[3] = hit ? h.z : 0.0f;
-        if (hit) { const TriPacket& t = h_tris[bits & 0x7fffffffu]; o[4] = (float)t.inst; o[5] = (float)t.prim; o[6] = (bits >> 31) ? 1.0f : 0.0f; }
-        else { o[4] = -1.0f; o[5] = -1.0f; o[6] = 0.0f; if (bits != kMissTri) o[0] = sentinel; }                 // (a triangle index out of range: never a valid answer)
-        o[7] = 0.0f;
-    }
-    uint32_t stray_hit = 0, stray_pend = 0;
-    for (size_t k = 0; k < qn; k++) if (!expected[k] && !untouched(h_hit[k])) stray_hit++;
-    std::vector<uint8_t> target(slots * 2, 0);
-    for (uint32_t i = 0; i < q.n_shadow; i++) {
-        const size_t k = 2 * (size_t)i + (q.shadow_is_light[i] ? 1u : 0u);
-        target[k] = 1;
-        q.out_shadow[i] = h_pend[k].w;
-    }
-    for (size_t k = 0; k < slots * 2; k++) {
-        const float4& v = h_pend[k];
-        if (!is_sentinel(v.x) || !is_sentinel(v.y) || !is_sentinel(v.z) || (!target[k] && !is_sentinel(v.w))) stray_pend++;
-    }
-    q.out_stray[0] = stray_hit; q.out_stray[1] = stray_pend;
-    for (uint32_t s = 0; s < kShards; s++) for (int k = 0; k < kCounterArrays; k++) q.out_cnt[s * kCounterArrays + k] = h_cnt[(size_t)k * kShards * kCounterStride + s * kCounterStride];
-    return hipSuccess;
 }
 
 }  // namespace pt

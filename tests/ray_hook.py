@@ -26,7 +26,7 @@ def gpu_intersect(renderer, rays, ray_flags=0, mode=0):
 
 TQ_TRACE, TQ_SHADOW, TQ_FUSED = 0, 1, 2                     # pt_debug_trace_queues `which`
 TQ_SENTINEL = 0x7fc5a5a5                                    # the bits every output word holds before the launch (a NaN no kernel produces)
-CNT_CLOSEST0, CNT_CLOSEST1, CNT_SHADOW_EVEN, CNT_HEAD_CLOSEST, CNT_HEAD_SHADOW, CNT_SHADOW_ODD, CNT_HEAD_SHADE = range(7)   # pt_wavefront.hip WfBuffers::cnt
+CNT_CLOSEST0, CNT_CLOSEST1, CNT_SHADOW_EVEN, CNT_HEAD_CLOSEST, CNT_HEAD_SHADOW, CNT_SHADOW_ODD, CNT_HEAD_SHADE = range(7)   # pt_wavefront.h WfBuffers::cnt
 
 
 def shadow_counter(bounce):
