@@ -149,12 +149,22 @@ PT_DEV RTex load_rtex(const RTex* p) {                      // 3 x dwordx4, issu
 // skips those unless some lane is there.  (Textures are allocated 4 bytes long so that a width-1 texture's pair stays inside.)
 struct TexTaps { const uint32_t *p0, *p1; int i0, i1, ia, width; float w00, w10, w01, w11; uint32_t srgb; bool edge; };
 struct TexQuad { uint32_t t00, t10, t01, t11; };
-PT_DEV TexTaps texture_taps(const RTex& t, const vec2 tc[2]) {
+// Where a vertex's two UV sets are while its textures are sampled.  `UV` in the sampling functions below is either a pointer to the pair
+// (HitGeom::tc: the per-lane choice between its two members makes the compiler keep the pair in scratch) or ParkedUv, the lane's column
+// of the shade stage's LDS parking (pt_vertex.h ParkLds): set s at at[s * kParkLanes], one ds_read_b64 at the chosen address.  A
+// caller's UV source (UvInPlace / ParkedUv) hands out either through of(HitGeom), asked at every use, as `a.tc` stood there before.
+constexpr int kParkLanes = 256;                            // the parking's row length: the shade workgroup (kBlock, pt_traverse.h)
+struct HitGeom;
+struct ParkedUv { const float2* at; PT_DEV ParkedUv of(const HitGeom&) const { return *this; } };
+PT_DEV vec2 uv_of(const vec2* tc, bool second) { return second ? tc[1] : tc[0]; }
+PT_DEV vec2 uv_of(const ParkedUv p, bool second) { const float2 v = p.at[second ? kParkLanes : 0]; return {v.x, v.y}; }
+template <class UV>
+PT_DEV TexTaps texture_taps(const RTex& t, const UV tc) {
     // No fused multiply-add in here: the compiler contracts each inlined copy of this function on its own, and two textures with the
     // same transform and size must get the same texels and weights to the bit (a material's interleaved footprint is fetched with the
     // albedo texture's taps).  Plain products and sums are also what the CPU oracle computes.
 #pragma clang fp contract(off)
-    const vec2 uv = (t.flags & RT_TEXCOORD1) ? tc[1] : tc[0];
+    const vec2 uv = uv_of(tc, (t.flags & RT_TEXCOORD1) != 0);
     const float tu = t.m00 * uv.x + t.m01 * uv.y + t.ox;
     const float tv = t.m10 * uv.x + t.m11 * uv.y + t.oy;
     const int au = (int)((t.flags >> 1) & 3u), av = (int)((t.flags >> 3) & 3u);
@@ -200,7 +210,8 @@ PT_DEV vec4 resolve_taps(const TexTaps& k, uint32_t t00, uint32_t t10, uint32_t 
 }
 PT_DEV vec4 resolve_taps(const TexTaps& k, const TexQuad& q, const float* srgb_lut) { return resolve_taps(k, q.t00, q.t10, q.t01, q.t11, srgb_lut); }
 // SampleTexture (Material.hlsli:90-96) of one material slot.
-PT_DEV vec4 sample_slot(const SceneRec& sc, const RMat* m, int slot, const vec2 tc[2], unsigned& taps) {
+template <class UV>
+PT_DEV vec4 sample_slot(const SceneRec& sc, const RMat* m, int slot, const UV tc, unsigned& taps) {
     const RTex t = load_rtex(&m->tex[slot]);
     const TexTaps k = texture_taps(t, tc);
     taps++;
@@ -260,6 +271,7 @@ struct HitGeom {                       // VertexAttributes, PathTracer.lib.hlsl:
     vec4 color;
     vec2 tc[2];
 };
+struct UvInPlace { PT_DEV const vec2* of(const HitGeom& a) const { return a.tc; } };
 // What a hit needs of its instance row: 96 B instead of the 240-B InstanceRec, so that the rows of up to kInstCacheMax instances
 // fit in LDS in the shade stage and the instance is no longer a second dependent global fetch behind the shading packet.
 struct ShadeInst {
@@ -431,7 +443,8 @@ PT_DEV vec3 normal_from_sample(vec4 s, float scale, vec3 gn, vec3 t, vec3 b) {  
     return normalize(to_world(t, b, gn, nm));
 }
 // `fetched`: the filtered emissive texel when it came with the interleaved footprint (RM_TRIO_EMISSIVE, get_surface), else ignored
-PT_DEV vec3 emissive_of(const SceneRec& sc, const RMat* m, const MatHeader& h, const vec2 tc[2], unsigned& taps, vec3 fetched) {   // :151-159
+template <class UV>
+PT_DEV vec3 emissive_of(const SceneRec& sc, const RMat* m, const MatHeader& h, const UV tc, unsigned& taps, vec3 fetched) {   // :151-159
     vec3 e = h.emissive_factor;
     if (h.bound_mask & RM_TRIO_EMISSIVE) { taps++; return e * fetched; }
     if (slot_bound(h.bound_mask, SLOT_EMISSIVE)) e = e * xyz(sample_slot(sc, m, SLOT_EMISSIVE, tc, taps));
@@ -453,7 +466,8 @@ struct PbrTexels {
 // The three usual PBR textures are fetched as ONE batch: their slot records are loaded together, their twelve texel
 // gathers are issued together (unbound slots read a 1x1 white texel, so there is no branch to split the batch).
 // get_surface and the sampler's test hook (pt_debug_sample_texture) both fetch through this function.
-PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHeader& h, const vec2 tc[2]) {
+template <class UV>
+PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHeader& h, const UV tc) {
     PbrTexels f;
     f.emissive = vec4{0, 0, 0, 0};
     // Materials whose three textures share one footprint (RM_TRIO, the usual glTF PBR set) read it from the interleaved copy: one set
@@ -502,9 +516,11 @@ PT_DEV PbrTexels fetch_pbr_texels(const SceneRec& sc, uint32_t mid, const MatHea
     f.m00 = m00; f.m10 = m10; f.m01 = m01; f.m11 = m11;
     return f;
 }
-PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, const MatHeader& h, const HitGeom& a, vec3 view, unsigned& taps) {
+// `uvs`: where the hit's two UV sets are -- in `a` (UvInPlace) or where the caller parked them (ParkedUv)
+template <class UVS = UvInPlace>
+PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, const MatHeader& h, const HitGeom& a, vec3 view, unsigned& taps, const UVS uvs = UVS()) {
     Surface s;
-    const PbrTexels f = fetch_pbr_texels(sc, (uint32_t)(m - sc.rmats), h, a.tc);
+    const PbrTexels f = fetch_pbr_texels(sc, (uint32_t)(m - sc.rmats), h, uvs.of(a));
     s.emissive_texel = xyz(f.emissive);
     const TexTaps &k_alb = f.k_alb, &k_nrm = f.k_nrm, &k_mr = f.k_mr;
     const uint32_t a00 = f.a00, a10 = f.a10, a01 = f.a01, a11 = f.a11, n00 = f.n00, n10 = f.n10, n01 = f.n01, n11 = f.n11, m00 = f.m00, m10 = f.m10, m01 = f.m01, m11 = f.m11;
@@ -537,19 +553,19 @@ PT_DEV Surface get_surface(const SceneRec& sc, uint32_t flags, const RMat* m, co
     s.transmissive = h.transmission_factor;                                                       // :228-235
 #ifndef PT_PROBE_BASE_ONLY
     if ((h.bound_mask & ((1u << SLOT_COUNT) - 1u)) >> SLOT_SPECULAR) {   // any of the rarely-bound extension textures (slots 5..14)
-        if (slot_bound(h.bound_mask, SLOT_SPECULAR)) s.spec_factor *= sample_slot(sc, m, SLOT_SPECULAR, a.tc, taps).w;
-        if (slot_bound(h.bound_mask, SLOT_SPECULAR_COLOR)) s.spec_color = s.spec_color * xyz(sample_slot(sc, m, SLOT_SPECULAR_COLOR, a.tc, taps));
-        if (slot_bound(h.bound_mask, SLOT_CLEARCOAT)) s.clearcoat *= sample_slot(sc, m, SLOT_CLEARCOAT, a.tc, taps).x;
-        if (slot_bound(h.bound_mask, SLOT_CLEARCOAT_ROUGHNESS)) s.cc_rough *= sample_slot(sc, m, SLOT_CLEARCOAT_ROUGHNESS, a.tc, taps).y;
+        if (slot_bound(h.bound_mask, SLOT_SPECULAR)) s.spec_factor *= sample_slot(sc, m, SLOT_SPECULAR, uvs.of(a), taps).w;
+        if (slot_bound(h.bound_mask, SLOT_SPECULAR_COLOR)) s.spec_color = s.spec_color * xyz(sample_slot(sc, m, SLOT_SPECULAR_COLOR, uvs.of(a), taps));
+        if (slot_bound(h.bound_mask, SLOT_CLEARCOAT)) s.clearcoat *= sample_slot(sc, m, SLOT_CLEARCOAT, uvs.of(a), taps).x;
+        if (slot_bound(h.bound_mask, SLOT_CLEARCOAT_ROUGHNESS)) s.cc_rough *= sample_slot(sc, m, SLOT_CLEARCOAT_ROUGHNESS, uvs.of(a), taps).y;
         if (slot_bound(h.bound_mask, SLOT_CLEARCOAT_NORMAL))
-            s.cc_n = normal_from_sample(sample_slot(sc, m, SLOT_CLEARCOAT_NORMAL, a.tc, taps), h.clearcoat_normal_scale, a.n, a.t, a.bt);
+            s.cc_n = normal_from_sample(sample_slot(sc, m, SLOT_CLEARCOAT_NORMAL, uvs.of(a), taps), h.clearcoat_normal_scale, a.n, a.t, a.bt);
         if (slot_bound(h.bound_mask, SLOT_ANISOTROPY)) {   // GetAnisotropyStrengthAndDirection (Material.hlsli:246-262)
-            vec4 t = sample_slot(sc, m, SLOT_ANISOTROPY, a.tc, taps);
+            vec4 t = sample_slot(sc, m, SLOT_ANISOTROPY, uvs.of(a), taps);
             av = v3(t.x * 2 - 1, t.y * 2 - 1, t.z);
         }
-        if (slot_bound(h.bound_mask, SLOT_SHEEN_COLOR)) s.sheen_color = s.sheen_color * xyz(sample_slot(sc, m, SLOT_SHEEN_COLOR, a.tc, taps));
-        if (slot_bound(h.bound_mask, SLOT_SHEEN_ROUGHNESS)) sheen_rough *= sample_slot(sc, m, SLOT_SHEEN_ROUGHNESS, a.tc, taps).w;
-        if (slot_bound(h.bound_mask, SLOT_TRANSMISSION)) s.transmissive *= sample_slot(sc, m, SLOT_TRANSMISSION, a.tc, taps).x;
+        if (slot_bound(h.bound_mask, SLOT_SHEEN_COLOR)) s.sheen_color = s.sheen_color * xyz(sample_slot(sc, m, SLOT_SHEEN_COLOR, uvs.of(a), taps));
+        if (slot_bound(h.bound_mask, SLOT_SHEEN_ROUGHNESS)) sheen_rough *= sample_slot(sc, m, SLOT_SHEEN_ROUGHNESS, uvs.of(a), taps).w;
+        if (slot_bound(h.bound_mask, SLOT_TRANSMISSION)) s.transmissive *= sample_slot(sc, m, SLOT_TRANSMISSION, uvs.of(a), taps).x;
         if (slot_bound(h.bound_mask, SLOT_THICKNESS)) taps++;   // thickness is loaded upstream but unused (quirk q14)
     }
 #endif

@@ -33,6 +33,28 @@ struct Followups {
     uint32_t hint_env, hint_light;
 };
 
+// Where a vertex's two UV sets are from the vertex fetch until the last texture of the vertex is sampled (`Park`, a template argument of
+// shade_closest_hit).  Every texture picks its set per lane (RT_TEXCOORD1), and a per-lane choice between two members of HitGeom makes the
+// compiler keep the pair in scratch: a scratch_load and a wait for vector memory at the head of every texture's address computation.
+//   ParkRegisters  the sets stay in HitGeom: the megakernel and the test hooks' kernels, which have no LDS to spare beside their traversal
+//                  stack, compile to what they were without the policy (tools/kernel_asm_diff.py: every one of them identical).
+//   ParkLds        the shade stage (k_wf_shade): the sets are written once to the lane's column of an LDS array float2[set][lane] -- a
+//                  wave's accesses are conflict-free -- and texture_taps reads the chosen one with a single ds_read_b64, on the LDS
+//                  counter, not behind vmcnt.  HitGeom::tc is then indexed by constants only and lives in registers.
+// Parking more of the vertex's long-lived values this way (L, ps.thr, the environment sample, the follow-ups' origins, directions and
+// pending terms, o_below) was measured and bought nothing: profiles/EXPERIMENTS.md, "Shade stage: the UV sets parked in LDS".
+static_assert(kParkLanes == kBlock, "the parking's rows are one shade workgroup long");
+struct ParkRegisters {
+    PT_DEV UvInPlace uv(const HitGeom&) const { return UvInPlace(); }
+};
+struct ParkLds {
+    float2* col;                                           // this lane's column: set s at col[s * kBlock]
+    PT_DEV ParkedUv uv(const HitGeom& va) const {
+        col[0] = make_float2(va.tc[0].x, va.tc[0].y); col[kBlock] = make_float2(va.tc[1].x, va.tc[1].y);
+        return ParkedUv{col};
+    }
+};
+
 // The environment-map branch of Miss, in three parts (shade_miss and the test hook pt_debug_env_query call them): the radiance along
 // `dir`, the solid-angle pdf with which environment_light_sample would have drawn it, and the balance-heuristic weight.
 PT_DEV vec3 miss_environment_color(const SceneRec& sc, float environment_intensity, vec3 dir) {
@@ -218,9 +240,11 @@ extern __device__ unsigned long long pt_timing[12];
 // in flight together with the caller's own fetches; `packet_at` = where the rest is.
 // PRE: `pre` is the vertex's environment light sample, drawn ahead of time with this vertex's random numbers (wavefront pipeline:
 // the in-place code, its LDS tables and its registers are not compiled in); otherwise it is drawn here.
-template <bool PRE = false>
+// `park`: where the UV sets are while the vertex's textures are sampled (ParkRegisters / ParkLds above).
+template <bool PRE = false, class Park = ParkRegisters>
 PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint32_t seed, uint32_t px, uint32_t py, const Ray& ray, const HitRec& hit,
-                              const RawPacket& packet_in, const ShadePacket* packet_at, PathState& ps, Followups& fu, unsigned& taps, const EnvSample* pre = nullptr) {
+                              const RawPacket& packet_in, const ShadePacket* packet_at, PathState& ps, Followups& fu, unsigned& taps, const EnvSample* pre = nullptr,
+                              const Park park = Park()) {
     const uint32_t flags = fc.flags;
     fu.add = v3(0); fu.overwrite = false; fu.counted_shadow = 0; fu.light_index = 0; fu.hint_env = fu.hint_light = 0xffffffffu;
     fu.q_env = fu.q_light = fu.q_bounce = false;
@@ -258,7 +282,8 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
     const vec3 intersection = ray.o + (ray.d * hit.t);                                               // :849
     const vec3 o_above = offset_ray(va.position, va.ng), o_below = offset_ray(va.position, -va.ng);
     const vec3 view = -normalize(ray.d);
-    Surface sp = get_surface(sc, flags, mat, mh, va, view, taps);
+    const auto uvs = park.uv(va);
+    Surface sp = get_surface(sc, flags, mat, mh, va, view, taps, uvs);
     PT_TICK(1)
     if (dbg >= PT_DEBUG_OUTPUT_COLOR && dbg <= PT_DEBUG_OUTPUT_TRANSMISSIVE) {                       // :863-917
         vec3 c;
@@ -287,7 +312,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
     const Lobes lobes = lobe_probabilities(sp, view);
     sp.sheen_lh = sp.sheen_sv = 0.0f;
     if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition; prepare_bsdf above restates these three statements for the test hook)
-    vec3 c = emissive_of(sc, mat, mh, va.tc, taps, sp.emissive_texel);                                                     // :925-926
+    vec3 c = emissive_of(sc, mat, mh, uvs.of(va), taps, sp.emissive_texel);                                                // :925-926
     fu.origin_above = o_above;
     PT_TICK(2)
     // environment NEE :929-942 (SampleEnvironmentMap :688-703)

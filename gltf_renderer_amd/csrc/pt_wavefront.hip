@@ -450,6 +450,11 @@ constexpr uint32_t kShadeDefaultsNoLights = PT_FLAG_SHADOW_RAYS | PT_FLAG_ENVIRO
 constexpr uint32_t kShadeDefaults = kShadeDefaultsNoLights | PT_FLAG_POINT_LIGHTS;
 // SMALL: the scene's instance rows, materials and lights all fit the LDS copies (<= 128 / 96 / 32: every BASELINE config): as a constant this
 // removes the global-memory branch of every table lookup (shade stage 8.70 -> 8.52 ms per launch).
+// LDS of a workgroup, 54 784 B: the tables take 50 688 B (sRGB and sheen tables 2 048, tangent angles 8 192, 128 instance rows 12 288,
+// 96 materials x 17 float4 26 112, 32 lights 2 048; the dead s_hand is compiled out) and the parking of the two UV sets 4 096 B (ParkLds,
+// pt_vertex.h: float2[2][256]).  256 VGPRs put two workgroups on a CU; their 109 568 B fit its 160 KiB, and every copy's code object says
+// Occupancy 2.  With the parking no copy selects between the UV sets in scratch: the two specialised copies have no scratch frame at all
+// (it was 100 B), and the shade stage went from 8.01 to 7.38 ms per 8-spp launch, images bit-identical.
 template <uint32_t SPECIAL, bool SMALL>
 __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc_in, FrameConstants fc_in, WfBuffers wf, int cur, int bounce, Counters* __restrict__ counters) {
     SceneRec sc = sc_in; sc.small_tables = SMALL ? 1u : 0u;
@@ -494,6 +499,8 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     uint32_t held = kNoHeld;
     __shared__ uint32_t s_hand[kBlock];                              // the hand-over slots, 64 per wave
     uint32_t* hand = s_hand + (threadIdx.x & ~63u);
+    __shared__ float2 s_park[2 * kBlock];                            // the UV sets of the hit each lane is shading: [set][lane]
+    const ParkLds park = {s_park + threadIdx.x};
     for (;;) {
         const bool more = chunk < n;
         const unsigned long long held_mask = __ballot(held != kNoHeld);
@@ -583,7 +590,7 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
                 uint32_t px, py;
                 slot_pixel(fc, slot, px, py);
                 n_hits++;
-                const bool done = shade_closest_hit<true>(sc, fc, sample_seed(fc, slot_sample(fc, slot)), px, py, ray, hit, packet, packet_at, ps, fu, st.taps, &es);
+                const bool done = shade_closest_hit<true>(sc, fc, sample_seed(fc, slot_sample(fc, slot)), px, py, ray, hit, packet, packet_at, ps, fu, st.taps, &es, park);
                 if (fu.overwrite) L = v3(0);
                 L += fu.add;
                 n_shadow += fu.counted_shadow;
