@@ -317,6 +317,16 @@ class PtNoiseSummary(C.Structure):
     _fields_ = [("tiles", C.c_uint32), ("tiles_estimated", C.c_uint32), ("tiles_above", C.c_uint32), ("mean", C.c_float), ("max", C.c_float)]
 
 
+class PtDenoiseVarianceConfig(C.Structure):
+    """pt_denoise_variance_config: the a-trous filter steered by the variance AOV (pt_denoise_variance; an extension, absent upstream)."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("normal_power_log2", C.c_int32),
+                ("sigma_depth", C.c_float), ("sigma_variance", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        return cls(5, 1, 7, 0.02, 4.0)
+
+
 MOTION_SNAPSHOT_NONE, MOTION_SNAPSHOT_VALID, MOTION_SNAPSHOT_STALE = 0, 1, 2
 MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
 MATTE_MAX_RANKS = 8
@@ -372,5 +382,7 @@ assert C.sizeof(PtVarianceConfig) == 16
 assert [getattr(PtVarianceConfig, f).offset for f, _ in PtVarianceConfig._fields_] == [0, 4, 8]
 assert C.sizeof(PtNoiseSummary) == 20
 assert [getattr(PtNoiseSummary, f).offset for f, _ in PtNoiseSummary._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtDenoiseVarianceConfig) == 20
+assert [getattr(PtDenoiseVarianceConfig, f).offset for f, _ in PtDenoiseVarianceConfig._fields_] == [0, 4, 8, 12, 16]
 assert C.sizeof(PtAccumImages) == 24
 assert C.sizeof(PtAccumInfo) == 64

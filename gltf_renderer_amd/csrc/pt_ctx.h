@@ -1,5 +1,5 @@
 // pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what the translation units with entry points need of it: mipt_api.hip (the
-// core of the product), a feature's own file (bake, probe, matte, motion, blur, variance, denoise .hip) and mipt_debug.hip (the test hooks).
+// core of the product), a feature's own file (bake, probe, matte, motion, blur, variance, denoise, denoise_variance .hip) and mipt_debug.hip (the test hooks).
 #pragma once
 #include <cstring>
 #include <string>
@@ -129,6 +129,9 @@ struct pt_ctx {
     pt::DevBuf d_blur;
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
+    // ---- pt_denoise_variance: two signal images (S.rgb, v) and the guide image, one float4 a pixel each, the plane of vt, one float a pixel,
+    // and one uint32 per tile for the counts; for one image size.  Its own, so that alternating the two filters reallocates nothing
+    pt::DevBuf d_denoise_variance;
 
     // ---- Pathtracer cross-frame state (Source/Pathtracer.h:152-153)
     float previous_world_to_clip[16] = {0};

@@ -45,7 +45,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # motion blur along the motion vectors (additive likewise)
            "pt_motion_blur",
            # the variance AOV and the noise report (additive likewise)
-           "pt_set_variance", "pt_noise_estimate"]
+           "pt_set_variance", "pt_noise_estimate",
+           # the denoiser steered by the variance (additive likewise)
+           "pt_denoise_variance"]
 
 
 class MiptError(RuntimeError):
@@ -142,6 +144,7 @@ def load_library():
     L.pt_motion_blur.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     L.pt_set_variance.argtypes = [vp, vp]
     L.pt_noise_estimate.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp, vp]
+    L.pt_denoise_variance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     _LIB = L
     return L
 
@@ -528,6 +531,28 @@ class Renderer:
         self._check(self.L.pt_noise_estimate(self.h, C.c_void_p(image.data_ptr()), C.c_void_p(variance.data_ptr()), w, h, _p(ts) if ts is not None else None,
                                              int(samples), float(threshold), _p(mean), _p(mx), C.byref(summary)))
         return mean, mx, summary
+
+    def denoise_variance(self, color, albedo, normal_depth, variance, samples=0, tile_samples=None, out=None, config=None):
+        """The a-trous filter steered by the variance AOV (include/mipt.h pt_denoise_variance): color, albedo, normal_depth and variance
+        are float32 CUDA tensors (H, W, 4) -- the output of trace() and the targets of set_aov() and set_variance(), or any images of
+        those layouts.  samples: the count of every tile, or tile_samples: (tiles_y, tiles_x) uint32 as adaptive_read() returns them (the
+        pixels of a tile below 2 come out as they went in).  out: where the result goes (None = a new tensor; `color` itself filters in
+        place); config: abi.PtDenoiseVarianceConfig (None = the defaults).  Asynchronous on the context's stream.  Returns the output
+        tensor."""
+        t = self.torch
+        if out is None:
+            out = t.empty_like(color)
+        for x in (color, albedo, normal_depth, variance, out):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+        h, w = color.shape[:2]
+        ts = None
+        if tile_samples is not None:
+            ts = np.ascontiguousarray(tile_samples, np.uint32)
+            assert ts.size == ((h + abi.TILE - 1) // abi.TILE) * ((w + abi.TILE - 1) // abi.TILE)
+        self._check(self.L.pt_denoise_variance(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
+                                               C.c_void_p(albedo.data_ptr()), C.c_void_p(normal_depth.data_ptr()), C.c_void_p(variance.data_ptr()),
+                                               w, h, _p(ts) if ts is not None else None, int(samples), C.c_void_p(out.data_ptr())))
+        return out
 
     def matte_extract(self, layers, ids, out=None):
         """pt_matte_extract: the anti-aliased mask (H, W) float32 CUDA tensor of a set of 1..64 ids over matte layers (of set_matte(), or

@@ -999,6 +999,57 @@ int pt_noise_estimate(pt_ctx* ctx, const void* image, const void* variance, uint
                       const uint32_t* tile_samples /* host, global tile ids; NULL = `samples` everywhere */, uint32_t samples, float threshold,
                       float* tile_mean_host /* tiles floats, may be NULL */, float* tile_max_host /* likewise */,
                       pt_noise_summary* summary /* may be NULL */);
+/* The denoiser steered by the variance (absent upstream): the spatial filter of SVGF (Schied et al., "Spatiotemporal Variance-Guided
+ * Filtering", 2017) over an image, its first-hit AOVs and the variance target above.  The denoiser above is blind to the variance: its colour term is
+ * relative to the two pixels' luminance, its sigma halves every pass, and it cannot know whether a pixel holds 2 samples or 2000 -- so it
+ * blurs a converged frame and treats tiles that adaptive sampling retired at different counts alike.  Here the colour term is normalised by
+ * the measured variance of the two pixels' means, and that variance is carried through every pass with the squared weights: as the image
+ * gets cleaner the filter switches itself off.  One pure function of four images and the tiles' counts, like the denoiser above, pt_reproject and
+ * pt_motion_blur: it reads no pt_trace state.  C = color, A = albedo, N = normal_depth, V = variance, all device pointers to W * H float4,
+ * caller-owned; V has the layout pt_set_variance writes; out == color filters in place.  The pixel's count is that of its PT_TILE x PT_TILE
+ * tile: tile_samples[t] (a host array of global tile ids, row-major, as pt_adaptive_read returns it), or `samples` everywhere if
+ * tile_samples is NULL, as for pt_noise_estimate.  The counts are consumed before the call returns; the filter itself is enqueued on the
+ * context's stream, asynchronous like pt_trace.  The scratch (two signal images and a guide image of W * H float4, one W * H float plane,
+ * the tiles' counts) belongs to the context and is not the other denoiser's: reallocated when the size changes, freed by pt_destroy.
+ *   All arithmetic is float32, in the order written, nothing fused; / and sqrt are correctly rounded, exp is the only function whose
+ * rounding is not defined.
+ *   Prepare, per pixel: a', S, n, z and cov are exactly as the denoiser above defines them.  With n_t the count of the pixel's tile and
+ *     k = (float)(n_t - 1):
+ *         u_c = (V.c / k) / (a'_c a'_c)   for c = r, g, b          the variance of the mean of the demodulated channel
+ *         v   = (u_r + u_g) + u_b
+ *     The pixel is VALID iff it is valid for the denoiser above, n_t >= 2, and v is finite and >= 0 (a NaN is invalid).  V.w is not used:
+ *     demodulation is per channel, so the variance of the raw channel sum does not survive it; and for two pixels of equal mean the sum of
+ *     squared channel differences has the expectation v_p + v_q whatever the channels' covariance.  An invalid pixel is never a neighbour
+ *     -- by a select, not by a product -- and leaves the call with out = C, all four channels bit for bit.
+ *   Pass i = 0 .. iterations - 1, step s = 2^i, on the current S and v:
+ *     1. Prefilter, for a valid p: the taps are q = p + (dx, dy) at unit spacing, dx, dy in -1 .. 1, dy outer, dx inner; taps outside the
+ *        image or invalid are skipped.  With k3 = (1/4, 1/2, 1/4) and g = k3[dy] k3[dx]:
+ *            vt_p = (sum of g v_q) / (sum of g), the sums sequential in tap order.
+ *     2. Filter: the taps, their order, h, wn and ez are the denoiser's above.  With sv2 = sigma_variance sigma_variance and d = S_p - S_q:
+ *            ec = ((dr dr + dg dg) + db db) / (sv2 (vt_p + vt_q) + 1e-8);  0 when sigma_variance == 0
+ *            w  = ((h[dy] h[dx]) wn) exp(-(ez + ec))
+ *        and, sequential in tap order, sw += w, sc += w S_q (per channel), sv += (w w) v_q; then
+ *            S'_p = sc / sw   and   v'_p = sv / (sw sw).
+ *        sigma_variance does not shrink from pass to pass; the variance does.
+ *   After the passes a valid pixel gets out.rgb = S a' and out.w = C.w.  iterations = 0 gives out = C bit for bit everywhere.
+ *   A known limit: at 2 samples a pixel under heavy-tailed noise the variance estimate is itself too noisy to steer anything (on the
+ * synthetic scene of tests/denoise_variance_ref.py: RMSE 0.106 against the other denoiser's 0.075); for frames of very few samples the denoiser
+ * above remains the tool.  From 8 samples on this one is ahead, and it alone leaves a converged frame alone.
+ * PT_ERR_INVALID_ARGUMENT, with nothing written: a NULL ctx (answered before any device call), a NULL image, a zero width or height, a
+ * width or height above 2^30 (or more than 2^31 - 1 tiles), a config value outside the ranges below, tile_samples == NULL with samples < 2,
+ * out overlapping albedo, normal_depth or variance (or color without being color). */
+typedef struct pt_denoise_variance_config {
+    int32_t iterations;         /* 0..6 passes; pass i taps at spacing 2^i.  default 5 */
+    int32_t demodulate;         /* non-zero: filter colour / albedo', multiply back.  default 1 */
+    int32_t normal_power_log2;  /* 0..10: normal weight = max(0, n_p . n_q)^(2^k) by k squarings.  default 7 */
+    float   sigma_depth;        /* finite, > 0.  default 0.02 */
+    float   sigma_variance;     /* finite, >= 0; 0 = colour term off.  default 4 (SVGF's luminance sigma) */
+} pt_denoise_variance_config;   /* 20 bytes */
+int pt_denoise_variance(pt_ctx* ctx, const pt_denoise_variance_config* config /* NULL = defaults */,
+                        const void* color, const void* albedo, const void* normal_depth, const void* variance,
+                        uint32_t width, uint32_t height,
+                        const uint32_t* tile_samples /* host, global tile ids; NULL = `samples` everywhere */, uint32_t samples,
+                        void* out);
 /* Null shadow rays.  The reference traces every NEE shadow ray before it evaluates the BSDF (PathTracer.lib.hlsl:932, 948), also
  * when the sample then contributes nothing (light behind the surface, black texel, light out of range).  With culling enabled a
  * shadow ray whose weighted contribution is exactly (0,0,0) is not traced: the image is unchanged (T * 0 adds nothing), the ray

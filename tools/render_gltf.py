@@ -77,6 +77,13 @@ batches of --batch samples until no tile's relative standard error (pt_noise_est
 --probes and --matte; the target is not part of a checkpoint, so not with --checkpoint / --resume, and not with --sequence.
   python tools/render_gltf.py scene.glb --spp 1024 --noise-target 0.02 --variance-out noise --out frame.png
 
+--denoise-variance [ITERATIONS]: the a-trous filter steered by the variance pass (pt_denoise_variance, 5 passes unless given) on the
+accumulated frame, where --denoise runs: before --dilate, --motion-blur and tone mapping; turns on the AOVs and the variance pass, uses the
+tiles' own counts under --adaptive and the samples traced otherwise, and keeps the noisy frame as <out>_noisy.png.  It leaves a converged
+frame alone, which --denoise blurs; below about 4 samples a pixel --denoise is the better tool.  Not together with --denoise, --sequence,
+--checkpoint or --resume.
+  python tools/render_gltf.py scene.glb --spp 256 --adaptive 0.05 --denoise-variance --out frame.png
+
 Camera: an orbit camera fitted to the scene's bounds (the reference's default controller, CameraController.h:42-49);
 settings: the application defaults (Main.cpp:462-474) with --bounces."""
 import argparse
@@ -193,6 +200,8 @@ def main():
     ap.add_argument("--sample-map", default="")
     ap.add_argument("--aov", default="", metavar="PREFIX")
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS")
+    ap.add_argument("--denoise-variance", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS",
+                    help="the a-trous filter steered by the variance pass (pt_denoise_variance); not with --denoise, --sequence, --checkpoint, --resume")
     ap.add_argument("--checkpoint", default="", metavar="FILE", help="write the accumulation to FILE after the last sample")
     ap.add_argument("--resume", default="", metavar="FILE", help="continue the accumulation of FILE; --spp is the total")
     ap.add_argument("--aperture", type=float, default=0.0, metavar="R", help="thin-lens aperture radius in world units (0 = pinhole); with --resume, repeat the lens options of the run that wrote the checkpoint")
@@ -231,6 +240,10 @@ def main():
         ap.error("--noise-target takes a finite X >= 0")
     if (a.variance_out or a.noise_target is not None) and (a.checkpoint or a.resume or a.sequence is not None):
         ap.error("--variance-out and --noise-target go with none of --checkpoint, --resume, --sequence: the variance is not part of a checkpoint")
+    if a.denoise_variance is not None and (a.denoise is not None or a.sequence is not None or a.checkpoint or a.resume):
+        ap.error("--denoise-variance goes with none of --denoise, --sequence, --checkpoint, --resume: one filter a frame, and the variance is not part of a checkpoint")
+    if a.denoise_variance is not None and not (0 <= a.denoise_variance <= 6):
+        ap.error("--denoise-variance takes 0..6 passes")
     if a.motion_blur is None and (a.blur_radius is not None or a.blur_taps is not None):
         ap.error("--blur-radius and --blur-taps need --motion-blur SHUTTER")
     if a.motion_blur is not None:
@@ -357,7 +370,7 @@ def main():
         print("bake %d x %d: UV set %d, %s, surface offset %.6g" % (w, h, a.bake_uv, "every instance" if a.bake_instance < 0 else "instance %d" % a.bake_instance, offset))
     out = r.create_output(w, h)
     aov_albedo = aov_nd = None
-    if a.aov or a.denoise is not None or a.temporal:
+    if a.aov or a.denoise is not None or a.denoise_variance is not None or a.temporal:
         aov_albedo, aov_nd = r.create_output(w, h), r.create_output(w, h)
         r.set_aov(aov_albedo, aov_nd)
     matte_layers = None
@@ -369,7 +382,7 @@ def main():
         motion = r.create_output(w, h)
         r.set_motion(motion, p.world_to_view[:], p.view_to_clip[:])
     variance = None
-    if a.variance_out or a.noise_target is not None:
+    if a.variance_out or a.noise_target is not None or a.denoise_variance is not None:
         variance = r.create_output(w, h)
         r.set_variance(variance)
     blur = None
@@ -517,6 +530,15 @@ def main():
         cfg = abi.PtDenoiseConfig.default()
         cfg.iterations = a.denoise
         r.denoise(out, aov_albedo, aov_nd, out=out, config=cfg)          # in place: the AOVs are only read
+    if a.denoise_variance is not None:                                   # where --denoise runs; `counts` is what the noise report above used
+        _, noisy8 = r.tonemap(out, want_rgba8=True)
+        gltf.write_png(noisy_path(a.out), noisy8, 3)
+        cfg = abi.PtDenoiseVarianceConfig.default()
+        cfg.iterations = a.denoise_variance
+        if counts.max() >= 2:
+            r.denoise_variance(out, aov_albedo, aov_nd, variance, tile_samples=counts, out=out, config=cfg)      # in place: the rest is only read
+        else:
+            print("--denoise-variance: a single sample has no variance, the frame stays as it is")
     if a.bake is not None:
         cover = r.bake_coverage(w, h)[0] >= 0
         print("bake: %d of %d texels covered (%.1f %%)" % (int(cover.sum()), w * h, 100.0 * cover.mean()))
