@@ -52,7 +52,11 @@ __global__ __launch_bounds__(kBlock) void k_debug_bsdf_query(SceneRec sc, int op
     stage_luts(sc);
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    debug_bsdf_query(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);
+#ifdef PT_LUT_LDS
+    debug_bsdf_query<ParkLds>(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);       // the shade stage's form of the BSDF
+#else
+    debug_bsdf_query<ParkRegisters>(sc, op, flags, in + (size_t)kBsdfQueryIn * i, out + (size_t)kBsdfQueryOut * i);  // the megakernel's
+#endif
 }
 void launch_debug_bsdf_query(const SceneRec& sc, int op, uint32_t flags, const float* d_in, uint32_t n, float* d_out, hipStream_t stream) {
     if (n == 0) return;

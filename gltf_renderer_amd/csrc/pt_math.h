@@ -141,7 +141,7 @@ PT_DEV void pt_sincos(float x, float& s, float& c) {
 // they cost 7.7 ms of a 22.6 ms launch (measured: ocml's double atan2, log2, exp2 are long).  These: atan2 nothing measurable; pow / exp
 // 0.35 ms on the Sponza-class scene, whose curtains (3 % of the hits) put a sheen lane into most waves of the shade stage -- v_log_f32 /
 // v_exp_f32 were 3 instructions per pow, this is ~55 (0.8 ms before the view-dependent half of the sheen lobe was hoisted out of the three
-// evaluations a hit makes, pt_shading.h prepare_sheen; as real calls instead of inlined code 1.0 ms).
+// evaluations a hit makes, pt_shading.h prepare_bsdf; as real calls instead of inlined code 1.0 ms).
 PT_DEV float co_atan2(float y, float x) {
     if (!(x == x) || !(y == y)) return __builtin_nanf("");
     const float ax = fabsf(x), ay = fabsf(y), mx = fmaxf(ax, ay), mn = fminf(ax, ay);

@@ -366,7 +366,23 @@ struct Surface {                       // live subset of SurfaceProperties (Bsdf
     vec3 spec_color; float spec_factor, clearcoat, cc_rough;
     vec3 cc_n, sheen_color; float sheen_a, transmissive;
     vec3 emissive_texel;                                  // RM_TRIO_EMISSIVE materials: the filtered emissive texel, fetched with the PBR footprint
-    float sheen_lh, sheen_sv;                             // SheenL(alpha, 1/2) and SheenShadowing(alpha, n.v): the same in every evaluation at this vertex (prepare_sheen)
+};
+// What every BSDF evaluation at a vertex reads that depends on the surface and the view direction alone, not on the light direction: filled
+// once per vertex by prepare_bsdf (below, after the lobe logic) and handed to the three evaluations a hit makes -- the environment sample,
+// the punctual light and the sampled bounce direction, each under a divergent condition of its own, so that the compiler shares nothing
+// between them by itself.  Every member is the expression the evaluation had in place, with the same operators, operand order and helper,
+// of arguments that are the same bits at the vertex as in the evaluation: the same bits out, NaN and infinity cases included.
+struct BsdfView {
+    vec3 vl;                           // to_local(at, ab, n, v); vl.z IS dot(n, v) -- the same three products summed in the same order
+    float coat_w;                      // fresnel_coat_w(clearcoat, dot(n, v)): FresnelCoat's lerp factor ((sic) shading normal; the lobe probability keeps cc_n)
+    vec3 f0;                           // FresnelMix's f0: min((1 - ior) / (1 + ior) squared times the specular colour, 1)
+    vec3 diffuse;                      // albedo / pi
+    float a2, v_len;                   // ax * ay; length(ax vl.x, ay vl.y, vl.z): the view half of aniso_specular_brdf's visibility
+    float cc_a2, cc_1ma2, cc_sv;       // the clearcoat's a^2, 1 - a^2 and sqrt(a^2 + (1 - a^2) n.v^2): the view half of ggx_corr_v
+    // the sheen lobe's: the clamped alpha and max3(sheen colour) always; the rest only in waves that hold a sheen material (zeros otherwise,
+    // never read): SheenL(alpha, 1/2), SheenShadowing(alpha, n.v), and -- where the colour's maximum is not 0 -- the view's albedo-scaling E
+    float sheen_a, sheen_max, sheen_lh, sheen_sv, sheen_ev;
+    bool no_sheen;                     // sheen colour exactly (+-0, +-0, +-0)
 };
 struct MatHeader {                     // the 128-B head of RMat in registers (8 x dwordx4 issued together)
     uint32_t flags; int32_t alpha_mode; float metalness_factor, roughness_factor;
@@ -638,18 +654,33 @@ PT_DEV float ggx_corr_v(float a, float ndl, float ndv, float hdl, float hdv) {  
     return fdiv(num, den);
 }
 PT_DEV float specular_brdf(float a, float ndl, float ndv, float ndh, float hdl, float hdv) { return ggx_corr_v(a, ndl, ndv, hdl, hdv) * ggx_d(a, ndh); }  // :87-90
-PT_DEV float ggx_aniso_d(float ax, float ay, vec3 h) {                                                         // :93-99
-    float a2 = ax * ay;
+// ggx_d and ggx_corr_v of the clearcoat with what the vertex prepared (BsdfView): a2 = a * a, one_m_a2 = 1 - a2 and
+// sv = sqrtf(a2 + (1 - a2) * ndv * ndv), ggx_corr_v's view half.  The same statements as above with those three read instead of formed.
+PT_DEV float ggx_d_a2(float a2, float ndh) {
+    float den = ndh * ndh * (a2 - 1) + 1;
+    den *= kPi * den;
+    return fdiv(a2 * heavyside(ndh), den);
+}
+PT_DEV float ggx_corr_v_view(float a2, float one_m_a2, float sv, float ndl, float ndv, float hdl, float hdv) {
+    float num = 0.5f * heavyside(hdl) * heavyside(hdv);
+    float den = fabsf(ndv) * sqrtf(a2 + one_m_a2 * ndl * ndl);
+    den += fabsf(ndl) * sv;
+    return fdiv(num, den);
+}
+// `a2` = ax * ay
+PT_DEV float ggx_aniso_d(float ax, float ay, float a2, vec3 h) {                                               // :93-99
     vec3 f = v3(ay * h.x, ax * h.y, a2 * h.z);
     float w2 = fdiv(a2, dot(f, f));
     return fdiv(heavyside(h.z) * a2 * w2 * w2, kPi);
 }
-PT_DEV float aniso_specular_brdf(float ax, float ay, vec3 v, vec3 h, vec3 l) {                                 // :117-130
+PT_DEV float aniso_view_length(float ax, float ay, vec3 v) { return length(v3(ax * v.x, ay * v.y, v.z)); }
+// `v_len` = aniso_view_length(ax, ay, v), `d` = ggx_aniso_d(ax, ay, ax * ay, h)
+PT_DEV float aniso_specular_brdf(float ax, float ay, vec3 v, float v_len, vec3 h, vec3 l, float d) {           // :117-130
     float hdv = dot(h, v), hdl = dot(h, l);
     float num = 0.5f * heavyside(hdv) * heavyside(hdl);
-    float vv = fabsf(l.z) * length(v3(ax * v.x, ay * v.y, v.z));
+    float vv = fabsf(l.z) * v_len;
     float ll = fabsf(v.z) * length(v3(ax * l.x, ay * l.y, l.z));
-    return fdiv(num, vv + ll) * ggx_aniso_d(ax, ay, h);
+    return fdiv(num, vv + ll) * d;
 }
 PT_DEV float fresnel_coat_w(float weight, float ndv) {            // FresnelCoat's lerp factor, IOR 1.5 (:157-163)
     float f0 = (1 - 1.5f) / (1 + 1.5f);
@@ -668,20 +699,14 @@ PT_DEV float sheen_shadowing(float alpha, float c, float l_half) {              
     return pt_exp(2 * l_half - sheen_l(alpha, 1 - c));
 }
 PT_DEV float sheen_alpha(const Surface& s) { return clampf(s.sheen_a, 0.000001f, 1); }
-// The parts of SheenBrdf that do not depend on the light direction, once per vertex instead of once per evaluation (three a hit: the two
-// light samples and the sampled direction): SheenL(alpha, 1/2) and the view direction's shadowing term -- 2 to 4 of the lobe's 5 to 7 pows
-// and one of its two exps.  Pure functions of the same arguments: the same bits as evaluating them in place.
-PT_DEV void prepare_sheen(Surface& s, vec3 v) {
-    const float sa = sheen_alpha(s);
-    s.sheen_lh = sheen_l(sa, 0.5f);
-    s.sheen_sv = sheen_shadowing(sa, to_local(s.at, s.ab, s.n, v).z, s.sheen_lh);
-}
-PT_DEV float sheen_brdf(const Surface& s, float alpha, float ndl, float ndv, float ndh) {                      // :166-173,195-203
+// `sv`, `l_half`: SheenShadowing(alpha, n.v) and SheenL(alpha, 1/2), the parts of SheenBrdf that do not depend on the light direction
+// (BsdfView::sheen_sv, sheen_lh) -- 2 to 4 of the lobe's 5 to 7 pows and one of its two exps
+PT_DEV float sheen_brdf(float sv, float l_half, float alpha, float ndl, float ndv, float ndh) {                // :166-173,195-203
     float inv_r = fdiv(1.0f, alpha);
     float sin2h = 1 - ndh * ndh;
     float d = fdiv((2 + inv_r) * hpow(sin2h, inv_r * 0.5f), 2 * kPi);
     // SheenBrdf passes (n_dot_v, n_dot_l) into SheenVisibility(alpha, n_dot_l, n_dot_v): swapped names, same product
-    float vis = clampf(fdiv(1.0f, (1 + s.sheen_sv + sheen_shadowing(alpha, ndl, s.sheen_lh)) * 4 * ndv * ndl), 0, 1);
+    float vis = clampf(fdiv(1.0f, (1 + sv + sheen_shadowing(alpha, ndl, l_half)) * 4 * ndv * ndl), 0, 1);
     return d * vis;
 }
 PT_DEV float sheen_e(const float* lut, float alpha, float cos_theta) {   // Bsdf.hlsli:204-208: bilinear, clamp, 16x16
@@ -699,67 +724,89 @@ PT_DEV float sheen_e(const float* lut, float alpha, float cos_theta) {   // Bsdf
 }
 PT_DEV float modulate_roughness(float a, float ior) { return clampf(lerpf(0, a, saturate(2 * (ior - 1))), kMinRoughness, 1.0f); }   // :216-220
 
+// What the pdf (bsdf_pdf, transmission_pdf) and the value (gltf_bsdf) of ONE evaluation both form from its light direction: computed once by
+// half_vectors and handed to both.  Where the two wrote a term differently (4 * dot(v, h) in the pdf, dot(h, v) in the value) both forms stay.
+struct BsdfHalf {
+    vec3 h, hl;                        // normalize(v + l) and to_local(at, ab, n, h)
+    float vdh4, d;                     // 4 * dot(v, h); ggx_aniso_d(ax, ay, hl)
+    // the thin-surface transmission's (modes 0 and 2; zeros in mode 1, never read): the modulated roughness, l mirrored to the view's side
+    // of the surface, the half vector with it, n . that half vector and ggx_d of the two
+    float tr_a; vec3 tr_l, tr_h; float tr_ndh, tr_d;
+};
+PT_DEV BsdfHalf half_vectors(const Surface& s, const BsdfView& bv, vec3 v, vec3 l, bool trans) {
+    BsdfHalf k;
+    k.h = normalize(v + l);
+    k.hl = to_local(s.at, s.ab, s.n, k.h);
+    k.vdh4 = 4 * dot(v, k.h);
+    k.d = ggx_aniso_d(s.ax, s.ay, bv.a2, k.hl);
+    k.tr_a = 0; k.tr_l = v3(0); k.tr_h = v3(0); k.tr_ndh = 0; k.tr_d = 0;
+    if (trans) {
+        k.tr_a = modulate_roughness(s.ay, s.ior);
+        k.tr_l = l - 2 * dot(s.n, l) * s.n;
+        k.tr_h = normalize(v + k.tr_l);
+        k.tr_ndh = dot(s.n, k.tr_h);
+        k.tr_d = ggx_d(k.tr_a, k.tr_ndh);
+    }
+    return k;
+}
+
 // GltfBsdf, both overloads (Bsdf.hlsli:241-325).  mode 0: overload without the flag (all terms);
 // mode 1: is_transmission == false; mode 2: is_transmission == true.
-PT_DEV vec3 gltf_bsdf(const float* lut, const Surface& s, vec3 v, vec3 l, int mode) {
+// `bv`: the vertex's light-independent terms (prepare_bsdf); `k`: this evaluation's half vectors (half_vectors(s, bv, v, l, mode != 1)).
+PT_DEV vec3 gltf_bsdf(const float* lut, const Surface& s, const BsdfView& bv, const BsdfHalf& k, vec3 v, vec3 l, int mode) {
     vec3 n = s.n;
-    vec3 h = normalize(v + l);
-    vec3 vl = to_local(s.at, s.ab, n, v), hl = to_local(s.at, s.ab, n, h), ll = to_local(s.at, s.ab, n, l);
+    vec3 h = k.h;
+    vec3 vl = bv.vl, hl = k.hl, ll = to_local(s.at, s.ab, n, l);
     float hdl = dot(h, l), hdv = dot(h, v);
     float h_dot_abs_l = dot(normalize(v3(ll.x, ll.y, fabsf(ll.z)) + vl), vl);
     bool refl = mode != 2, trans = mode != 1;
     // the coat first (it is the LAST term of the shader's expression, :318-324): its inputs are the world-space n, v, h, l, which
     // nothing after it needs -- evaluated at the end they stayed live through the whole function in a kernel that has no register to spare
-    float cndv = dot(n, v), cndh = dot(n, h), cndl = dot(n, l);                    // (sic) shading normal
+    float cndv = vl.z, cndh = dot(n, h), cndl = dot(n, l);                         // (sic) shading normal; dot(n, v) is vl.z
 #ifndef PT_PROBE_BASE_ONLY
-    const float cc = refl ? saturate(cndl) * specular_brdf(s.cc_rough, cndl, cndv, cndh, hdl, hdv) : 0.f;
+    // SpecularBrdf(cc_rough, ...) = ggx_corr_v * ggx_d, :87-90
+    const float cc = refl ? saturate(cndl) * (ggx_corr_v_view(bv.cc_a2, bv.cc_1ma2, bv.cc_sv, cndl, cndv, hdl, hdv) * ggx_d_a2(bv.cc_a2, cndh)) : 0.f;
 #else
     const float cc = 0.f;
 #endif
-    const float coat_w = fresnel_coat_w(s.clearcoat, cndv);
-    float spec = refl ? saturate(ll.z) * aniso_specular_brdf(s.ax, s.ay, vl, hl, ll) : 0.f;
-    vec3 diffuse = refl ? saturate(ll.z) * (s.albedo / kPi) : v3(0);
+    const float coat_w = bv.coat_w;
+    float spec = refl ? saturate(ll.z) * aniso_specular_brdf(s.ax, s.ay, vl, bv.v_len, hl, ll, k.d) : 0.f;
+    vec3 diffuse = refl ? saturate(ll.z) * bv.diffuse : v3(0);
     vec3 transmission = v3(0);
 #ifndef PT_PROBE_BASE_ONLY
-    if (trans) {                                           // ThinSurfaceTransmissionBtdf :222-228
-        float a = modulate_roughness(s.ay, s.ior);
-        vec3 lr = l - 2 * dot(n, l) * n;
-        vec3 hr = normalize(v + lr);
-        transmission = saturate(-ll.z) * (s.albedo * specular_brdf(a, dot(n, lr), dot(n, v), dot(n, hr), dot(hr, lr), dot(hr, v)));
+    if (trans) {                                           // ThinSurfaceTransmissionBtdf :222-228; SpecularBrdf = ggx_corr_v * ggx_d, dot(n, v) is vl.z
+        const vec3 lr = k.tr_l, hr = k.tr_h;
+        transmission = saturate(-ll.z) * (s.albedo * (ggx_corr_v(k.tr_a, dot(n, lr), vl.z, dot(hr, lr), dot(hr, v)) * k.tr_d));
     }
 #endif
     diffuse = lerp3(diffuse, transmission, s.transmissive);
-    // FresnelMix :137-144
-    float f0s = fdiv(1 - s.ior, 1 + s.ior);
-    vec3 f0 = v3(f0s);
-    f0 *= f0 * s.spec_color;
-    f0 = hmin(f0, v3(1));
-    vec3 fr = schlick3(f0, h_dot_abs_l);
+    vec3 fr = schlick3(bv.f0, h_dot_abs_l);                                         // FresnelMix :137-144
     vec3 dielectric = (1 - s.spec_factor * max3(fr)) * diffuse + s.spec_factor * fr * v3(spec);
     vec3 metal = refl ? v3(spec) * schlick3(s.albedo, hdv) : v3(0);                // ConductorFresnel :146-149
     vec3 material = lerp3(dielectric, metal, s.metalness);
-    float sa = sheen_alpha(s);
-    float ms = max3(s.sheen_color);                                               // SheenMix :210-214
+    const float sa = bv.sheen_a;
+    const float ms = bv.sheen_max;                                                 // SheenMix :210-214
     // A material WITHOUT sheen (sheen colour exactly (0,0,0): every material that does not use KHR_materials_sheen) in a wave that holds no
     // sheen material skips the sheen BRDF -- two pow, three SheenL, the exponentials: ~150 instructions, three evaluations a hit -- and gets
     // the SAME bits: the layer term is 0 * sheen_brdf, which is +0 whenever sheen_brdf is finite and NaN otherwise, and sheen_brdf =
     // saturate(.) * D * V with V clamped to [0, 1] (a NaN clamps to 0) and D = (2 + 1/a) pow(1 - ndh^2, 1/(2a)) / 2 pi, finite unless the pow's
     // base is negative or NaN (|ndh| a rounding above 1, a NaN normal); the albedo scaling is 1 - 0 * E = 1 exactly.
-    const bool no_sheen = s.sheen_color.x == 0.0f && s.sheen_color.y == 0.0f && s.sheen_color.z == 0.0f;
+    // A wave that gets past this vote had a vote that said the same at the vertex: its lanes are among the vertex's, so bv's sheen terms are set.
+    const bool no_sheen = bv.no_sheen;
     if (!__any(!no_sheen)) {
         const float sin2h = 1 - hl.z * hl.z;
         const float layer = (refl && !(sin2h >= 0.0f)) ? __builtin_nanf("") : 0.0f;
         material = v3(layer) + material * 1.0f;
     } else {
 #ifndef PT_PROBE_BASE_ONLY
-        vec3 sheen = refl ? v3(saturate(ll.z) * sheen_brdf(s, sa, ll.z, vl.z, hl.z)) : v3(0);
+        vec3 sheen = refl ? v3(saturate(ll.z) * sheen_brdf(bv.sheen_sv, bv.sheen_lh, sa, ll.z, vl.z, hl.z)) : v3(0);
 #else      // PROBE ONLY (tools/build_variant.sh): what the extension lobes cost a hit that has none; wrong for materials that do
         vec3 sheen = v3(0);
 #endif
         // Without sheen (ms == 0) both terms are 1 - 0 * E = 1 exactly (E is always finite: sheen_e clamps NaN coordinates):
         // skip the eight table gathers.
         float scaling = 1.0f;
-        if (ms != 0.0f) scaling = hmin(1.0f - ms * sheen_e(lut, sa, vl.z), 1.0f - ms * sheen_e(lut, sa, ll.z));
+        if (ms != 0.0f) scaling = hmin(1.0f - ms * bv.sheen_ev, 1.0f - ms * sheen_e(lut, sa, ll.z));
         material = s.sheen_color * sheen + material * scaling;
     }
     return lerp3(material, v3(cc), coat_w);                                         // FresnelCoat(1.5, ...)
@@ -859,47 +906,109 @@ PT_DEV Lobes lobe_probabilities(const Surface& s, vec3 v) {                     
     p.diffuse = remaining;
     return p;
 }
-PT_DEV float transmission_pdf(const Surface& s, vec3 v, vec3 l) {                                             // :489-500
-    float a = modulate_roughness(s.ay, s.ior);
-    l = l - 2 * dot(s.n, l) * s.n;
-    vec3 h = normalize(v + l);
-    float pdf = ggx_normal_pdf(a, s.n, h);
-    pdf = fdiv(pdf, 4 * dot(v, h));
+// The light-independent terms of BsdfView other than the sheen lobe's three (sheen_lh, sheen_sv, sheen_ev: formed only in waves that hold
+// a sheen material, prepare_bsdf / view_of).  The transmission's roughness is NOT here: whether an evaluation is a transmission is decided by its light direction, so no vote at
+// the vertex can say that a wave never takes that mode; half_vectors forms it once per evaluation that does.
+PT_DEV void bsdf_view_terms(const float* lut, const Surface& s, vec3 v, BsdfView& bv) {
+    bv.vl = to_local(s.at, s.ab, s.n, v);
+    bv.coat_w = fresnel_coat_w(s.clearcoat, bv.vl.z);
+    float f0s = fdiv(1 - s.ior, 1 + s.ior);                                        // FresnelMix :137-144
+    vec3 f0 = v3(f0s);
+    f0 *= f0 * s.spec_color;
+    f0 = hmin(f0, v3(1));
+    bv.f0 = f0;
+    bv.diffuse = s.albedo / kPi;
+    bv.a2 = s.ax * s.ay;
+    bv.v_len = aniso_view_length(s.ax, s.ay, bv.vl);
+    {
+        const float a = s.cc_rough, ndv = bv.vl.z;                                 // ggx_corr_v's statements
+        float a2 = a * a;
+        bv.cc_a2 = a2; bv.cc_1ma2 = 1 - a2;
+        bv.cc_sv = sqrtf(a2 + (1 - a2) * ndv * ndv);
+    }
+    bv.sheen_a = sheen_alpha(s);
+    bv.sheen_max = max3(s.sheen_color);
+    bv.no_sheen = s.sheen_color.x == 0.0f && s.sheen_color.y == 0.0f && s.sheen_color.z == 0.0f;
+    bv.sheen_ev = 0.0f;
+}
+// ... and the view's albedo-scaling E, for a wave that holds a sheen material
+PT_DEV void bsdf_view_sheen_e(const float* lut, BsdfView& bv) {
+    if (bv.sheen_max != 0.0f) bv.sheen_ev = sheen_e(lut, bv.sheen_a, bv.vl.z);
+}
+// What a vertex prepares for every BSDF evaluation at it: shade_closest_hit and the test hook pt_debug_bsdf_query both prepare a vertex
+// through this function and no other way.  Returns the lobe probabilities, which keep their own Fresnel term on the CLEARCOAT normal
+// (:540) where the value's coat weight is on the shading normal (:323).  SheenL(alpha, 1/2) and the view's shadowing term are formed in
+// waves that hold a sheen material -- gltf_bsdf's own condition for running the lobe that reads them.
+// VERTEX (a kernel's choice, pt_vertex.h ParkLds / ParkRegisters): the other light-independent terms are formed here too, once; without
+// it every evaluation forms them for itself (view_of below), which is what a kernel with no register to keep them in wants.  The same
+// expressions of the same arguments either way: the same bits.
+template <bool VERTEX>
+PT_DEV Lobes prepare_bsdf(const float* lut, const Surface& s, vec3 v, BsdfView& bv) {
+    const Lobes lobes = lobe_probabilities(s, v);
+    if (VERTEX) bsdf_view_terms(lut, s, v, bv);
+    bv.sheen_lh = bv.sheen_sv = 0.0f;
+    if (__any(!(s.sheen_color.x == 0.0f && s.sheen_color.y == 0.0f && s.sheen_color.z == 0.0f))) {
+        const float sa = VERTEX ? bv.sheen_a : sheen_alpha(s);
+        const float ndv = VERTEX ? bv.vl.z : to_local(s.at, s.ab, s.n, v).z;
+        bv.sheen_lh = sheen_l(sa, 0.5f);
+        bv.sheen_sv = sheen_shadowing(sa, ndv, bv.sheen_lh);
+        if (VERTEX) bsdf_view_sheen_e(lut, bv);
+    }
+    return lobes;
+}
+template <bool VERTEX>
+PT_DEV BsdfView view_of(const float* lut, const Surface& s, vec3 v, const BsdfView& prepared) {
+    BsdfView bv = prepared;
+    if (!VERTEX) {
+        bsdf_view_terms(lut, s, v, bv);
+        if (__any(!bv.no_sheen)) bsdf_view_sheen_e(lut, bv);
+    }
+    return bv;
+}
+// `k` = half_vectors(s, bv, v, l, is_transmission)
+PT_DEV float transmission_pdf(const BsdfHalf& k, vec3 v) {                                                   // :489-500
+    float pdf = k.tr_d * k.tr_ndh;                                                                           // ggx_normal_pdf(a, n, h) with the mirrored l
+    pdf = fdiv(pdf, 4 * dot(v, k.tr_h));
     return pdf;
 }
-PT_DEV float bsdf_pdf(const Surface& s, vec3 v, vec3 l, bool is_transmission, const Lobes& p) {               // :555-565
-    if (is_transmission) return p.transmission * transmission_pdf(s, v, l);
-    vec3 h = normalize(v + l);
-    float vdh4 = 4 * dot(v, h);
+PT_DEV float bsdf_pdf(const Surface& s, const BsdfHalf& k, vec3 v, vec3 l, bool is_transmission, const Lobes& p) {   // :555-565
+    if (is_transmission) return p.transmission * transmission_pdf(k, v);
+    vec3 h = k.h;
+    float vdh4 = k.vdh4;
     float cc = ggx_normal_pdf(s.cc_rough, s.cc_n, h);                                                        // ClearcoatPdf :408-416
     cc = fdiv(cc, vdh4);
     float pdf = p.clearcoat * cc;
     float cosp = cosine_hemisphere_pdf(s.n, l);
     pdf += p.sheen * cosp;                                                                                   // SheenPdf :423-426
-    vec3 lh = to_local(s.at, s.ab, s.n, h);                                                                  // SpecularPdf :444-460
-    float sp = ggx_aniso_d(s.ax, s.ay, lh) * lh.z;
+    vec3 lh = k.hl;                                                                                          // SpecularPdf :444-460
+    float sp = k.d * lh.z;
     sp = fdiv(sp, vdh4);
     pdf += p.specular * sp;
     pdf += p.diffuse * cosp;                                                                                 // DiffusePdf :467-470
     return pdf;
 }
-PT_DEV vec3 evaluate_bsdf(uint32_t flags, const float* lut, const Surface& s, const Lobes& p, vec3 ng, vec3 v, vec3 l, float& pdf) {   // :567-593
+// `prepared`: prepare_bsdf<VERTEX>'s
+template <bool VERTEX>
+PT_DEV vec3 evaluate_bsdf(uint32_t flags, const float* lut, const Surface& s, const BsdfView& prepared, const Lobes& p, vec3 ng, vec3 v, vec3 l, float& pdf) {   // :567-593
     if (flags & PT_FLAG_MATERIAL_DIFFUSE_WHITE) {
         float ndl = saturate(dot(s.n, l));
         pdf = fdiv(ndl, kPi);
         return v3(fdiv(ndl, kPi));
     }
+    const BsdfView bv = view_of<VERTEX>(lut, s, v, prepared);
     if (flags & PT_FLAG_MATERIAL_MIS) {
         bool is_transmission = (dot(ng, l) * dot(ng, v)) < 0;
-        pdf = bsdf_pdf(s, v, l, is_transmission, p);
-        return s.alpha * gltf_bsdf(lut, s, v, l, is_transmission ? 2 : 1);
+        const BsdfHalf k = half_vectors(s, bv, v, l, is_transmission);
+        pdf = bsdf_pdf(s, k, v, l, is_transmission, p);
+        return s.alpha * gltf_bsdf(lut, s, bv, k, v, l, is_transmission ? 2 : 1);
     }
     float ndl = saturate(dot(s.n, l));
     pdf = fdiv(ndl, kPi);
     pdf *= s.alpha;
-    return s.alpha * gltf_bsdf(lut, s, v, l, 0);
+    return s.alpha * gltf_bsdf(lut, s, bv, half_vectors(s, bv, v, l, true), v, l, 0);
 }
-PT_DEV vec3 sample_bsdf(uint32_t flags, const float* lut, const Surface& s, const Lobes& p, vec3 u, vec3 v, vec3& l, float& pdf,
+template <bool VERTEX>
+PT_DEV vec3 sample_bsdf(uint32_t flags, const float* lut, const Surface& s, const BsdfView& prepared, const Lobes& p, vec3 u, vec3 v, vec3& l, float& pdf,
                         bool& is_transmission, bool& use_mis) {                                             // :595-667
     if (flags & PT_FLAG_MATERIAL_DIFFUSE_WHITE) {
         use_mis = true; is_transmission = false;
@@ -949,8 +1058,10 @@ PT_DEV vec3 sample_bsdf(uint32_t flags, const float* lut, const Surface& s, cons
             l = l - 2 * dot(s.n, l) * s.n;
             is_transmission = true;
         }
-        pdf = bsdf_pdf(s, v, l, is_transmission, p);
-        return s.alpha * gltf_bsdf(lut, s, v, l, is_transmission ? 2 : 1);
+        const BsdfView bv = view_of<VERTEX>(lut, s, v, prepared);
+        const BsdfHalf k = half_vectors(s, bv, v, l, is_transmission);
+        pdf = bsdf_pdf(s, k, v, l, is_transmission, p);
+        return s.alpha * gltf_bsdf(lut, s, bv, k, v, l, is_transmission ? 2 : 1);
     }
     if (u.x > s.alpha) {
         l = -v; use_mis = false; pdf = (1 - s.alpha); is_transmission = true;
@@ -960,7 +1071,8 @@ PT_DEV vec3 sample_bsdf(uint32_t flags, const float* lut, const Surface& s, cons
     l = sample_cosine_hemisphere(s.n, u.y, u.z);
     pdf = cosine_hemisphere_pdf(s.n, l);
     pdf *= s.alpha;
-    return s.alpha * gltf_bsdf(lut, s, v, l, 0);
+    const BsdfView bv = view_of<VERTEX>(lut, s, v, prepared);
+    return s.alpha * gltf_bsdf(lut, s, bv, half_vectors(s, bv, v, l, true), v, l, 0);
 }
 
 // ---------------------------------------------------------------- lights (Lights.hlsli:26-61)

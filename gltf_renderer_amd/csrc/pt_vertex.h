@@ -45,9 +45,11 @@ struct Followups {
 // pending terms, o_below) was measured and bought nothing: profiles/EXPERIMENTS.md, "Shade stage: the UV sets parked in LDS".
 static_assert(kParkLanes == kBlock, "the parking's rows are one shade workgroup long");
 struct ParkRegisters {
+    static constexpr bool kBsdfViewPerVertex = false;
     PT_DEV UvInPlace uv(const HitGeom&) const { return UvInPlace(); }
 };
 struct ParkLds {
+    static constexpr bool kBsdfViewPerVertex = true;
     float2* col;                                           // this lane's column: set s at col[s * kBlock]
     PT_DEV ParkedUv uv(const HitGeom& va) const {
         col[0] = make_float2(va.tc[0].x, va.tc[0].y); col[kBlock] = make_float2(va.tc[1].x, va.tc[1].y);
@@ -117,20 +119,9 @@ PT_DEV void debug_env_query(const SceneRec& sc, int op, const float* __restrict_
     }
 }
 
-// What a vertex prepares once for every BSDF evaluation at it, for the test hook pt_debug_bsdf_query: the lobe probabilities, and the
-// view-dependent sheen terms in waves that hold a sheen material -- gltf_bsdf's own condition for running the sheen lobe, which reads them.
-// The SAME three statements as shade_closest_hit runs before its first evaluate_bsdf ("prepare_bsdf" there); change both together.  They
-// stay written out there: calling this function instead moved the instruction counts of the two specialised k_wf_shade copies (19681 ->
-// 19679, 21184 -> 21185), and the shade stage is not to change for a test hook.
-PT_DEV Lobes prepare_bsdf(Surface& sp, vec3 view) {
-    const Lobes lobes = lobe_probabilities(sp, view);
-    sp.sheen_lh = sp.sheen_sv = 0.0f;
-    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition)
-    return lobes;
-}
-
-// Test hook (pt_debug_bsdf_query): one BSDF query per lane, through prepare_bsdf and evaluate_bsdf (op 0) or sample_bsdf (op 1).  Call it
-// with every lane of the wave that has a query and with no other: the sheen lobe is run or skipped by a vote of the active lanes.
+// Test hook (pt_debug_bsdf_query): one BSDF query per lane, through prepare_bsdf (pt_shading.h: the function shade_closest_hit prepares a
+// vertex with) and evaluate_bsdf (op 0) or sample_bsdf (op 1).  Call it with every lane of the wave that has a query and with no other: the
+// sheen terms are prepared, and the sheen lobe is run or skipped, by votes of the active lanes.
 //   in  48 floats: the reference's SurfaceProperties [0,36) (albedo, alpha, metalness, roughness_squared.xy, shading normal, anisotropy
 //       tangent, bitangent, ior, specular colour, specular factor, clearcoat, clearcoat roughness, clearcoat normal, sheen colour, sheen
 //       roughness squared, transmissive; thickness and attenuation are not read), geometric normal [36,39), view [39,42), l (op 0) or
@@ -138,6 +129,7 @@ PT_DEV Lobes prepare_bsdf(Surface& sp, vec3 view) {
 //   out 16 floats: f.rgb, pdf, l.xyz, is_transmission, use_mis (op 0: l echoed, both 0), the lobe probabilities alpha, clearcoat, sheen,
 //       specular, diffuse, transmission, 0
 constexpr int kBsdfQueryIn = 48, kBsdfQueryOut = 16;
+template <class Park>
 PT_DEV void debug_bsdf_query(const SceneRec& sc, int op, uint32_t flags, const float* __restrict__ in, float* __restrict__ out) {
     Surface sp;
     sp.albedo = v3(in[0], in[1], in[2]); sp.alpha = in[3]; sp.metalness = in[4]; sp.ax = in[5]; sp.ay = in[6];
@@ -146,12 +138,14 @@ PT_DEV void debug_bsdf_query(const SceneRec& sc, int op, uint32_t flags, const f
     sp.cc_n = v3(in[23], in[24], in[25]); sp.sheen_color = v3(in[26], in[27], in[28]); sp.sheen_a = in[29]; sp.transmissive = in[30];
     sp.emissive_texel = v3(0);
     const vec3 ng = v3(in[36], in[37], in[38]), view = v3(in[39], in[40], in[41]), a = v3(in[42], in[43], in[44]);
-    const Lobes lobes = prepare_bsdf(sp, view);
+    constexpr bool kVertex = Park::kBsdfViewPerVertex;
+    BsdfView bv;
+    const Lobes lobes = prepare_bsdf<kVertex>(sc.sheen_e, sp, view, bv);
     vec3 f, l = a;
     float pdf = 0;
     bool is_tr = false, use_mis = false;
-    if (op == 0) f = evaluate_bsdf(flags, sc.sheen_e, sp, lobes, ng, view, a, pdf);
-    else f = sample_bsdf(flags, sc.sheen_e, sp, lobes, a, view, l, pdf, is_tr, use_mis);
+    if (op == 0) f = evaluate_bsdf<kVertex>(flags, sc.sheen_e, sp, bv, lobes, ng, view, a, pdf);
+    else f = sample_bsdf<kVertex>(flags, sc.sheen_e, sp, bv, lobes, a, view, l, pdf, is_tr, use_mis);
     out[0] = f.x; out[1] = f.y; out[2] = f.z; out[3] = pdf; out[4] = l.x; out[5] = l.y; out[6] = l.z;
     out[7] = is_tr ? 1.0f : 0.0f; out[8] = use_mis ? 1.0f : 0.0f;
     out[9] = lobes.alpha; out[10] = lobes.clearcoat; out[11] = lobes.sheen; out[12] = lobes.specular; out[13] = lobes.diffuse; out[14] = lobes.transmission;
@@ -171,8 +165,8 @@ PT_DEV void debug_light_query(const SceneRec& sc, uint32_t li, vec3 p, float* __
 // Test hook (pt_debug_surface_query): the vertex fetch and the material evaluation of one hit per lane, in shade_closest_hit's order and
 // through its functions -- load_shade_packet_raw, load_shade_inst, the voted load_shade_packet_extra, unpack_shade_packet, material_header,
 // get_vertex_attributes, the back-face flip, offset_ray both ways, get_surface, emissive_of -- and, separately, the any-hit path's
-// candidate_alpha for the same hit.  The statements between the fetch and emissive_of are shade_closest_hit's own, restated here as
-// prepare_bsdf restates its three: they are not a function there, and the shade stage is not to change for a test hook; change both
+// candidate_alpha for the same hit.  The statements between the fetch and emissive_of are shade_closest_hit's own, restated here:
+// they are not a function there, and the shade stage is not to change for a test hook; change both
 // together.  Call it with every lane of the wave that has a query and with no other: the extra packet fetch and the interleaved / general
 // and edge / interior texel fetches are behind votes of the active lanes.
 //   in   8 words: the packet index (uint32, below sc.num_tris), front (uint32, 0 or 1), u, v, the ray direction d.xyz (view = -normalize(d)), 0
@@ -309,9 +303,9 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
         fu.add = ps.beta * (dot(view, sp.n) > 0 ? v3(0, 1, 0) : v3(1, 0, 0));
         return true;
     }
-    const Lobes lobes = lobe_probabilities(sp, view);
-    sp.sheen_lh = sp.sheen_sv = 0.0f;
-    if (__any(sp.sheen_color.x != 0.0f || sp.sheen_color.y != 0.0f || sp.sheen_color.z != 0.0f)) prepare_sheen(sp, view);   // (gltf_bsdf's own condition; prepare_bsdf above restates these three statements for the test hook)
+    constexpr bool kVertex = Park::kBsdfViewPerVertex;                   // the light-independent terms of the up-to-three evaluations below: once here, or in each
+    BsdfView bv;
+    const Lobes lobes = prepare_bsdf<kVertex>(sc.sheen_e, sp, view, bv);
     vec3 c = emissive_of(sc, mat, mh, uvs.of(va), taps, sp.emissive_texel);                                                // :925-926
     fu.origin_above = o_above;
     PT_TICK(2)
@@ -329,7 +323,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
         vec3 contrib = v3(0);
         if (any_gt0(lcol)) {
             float bp = 0;
-            vec3 f = evaluate_bsdf(flags, sc.sheen_e, sp, lobes, va.ng, view, ldir, bp);
+            vec3 f = evaluate_bsdf<kVertex>(flags, sc.sheen_e, sp, bv, lobes, va.ng, view, ldir, bp);
             float mis = fdiv(light_pdf, light_pdf + bp);
             contrib = (mis * f * lcol) / light_pdf;
         }
@@ -357,7 +351,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
         vec3 contrib = v3(0);
         if (any_gt0(lcol)) {
             float bp = 0;
-            vec3 f = evaluate_bsdf(flags, sc.sheen_e, sp, lobes, va.ng, view, ldir, bp);
+            vec3 f = evaluate_bsdf<kVertex>(flags, sc.sheen_e, sp, bv, lobes, va.ng, view, ldir, bp);
             contrib = (lcol * f) / pdf;
         }
         if ((flags & PT_FLAG_SHADOW_RAYS) && !(flags & PT_FLAG_INDIRECT_ENVIRONMENT_ONLY)) {
@@ -374,7 +368,7 @@ PT_DEV bool shade_closest_hit(const SceneRec& sc, const FrameConstants& fc, uint
         bool is_tr = false, use_mis = false;
         float bp = 1;
         vec3 l = v3(0);
-        vec3 f = sample_bsdf(flags, sc.sheen_e, sp, lobes, v3(r.x, r.y, r.z), view, l, bp, is_tr, use_mis);
+        vec3 f = sample_bsdf<kVertex>(flags, sc.sheen_e, sp, bv, lobes, v3(r.x, r.y, r.z), view, l, bp, is_tr, use_mis);
         vec3 weight = bp != 0 ? f / bp : v3(0);
         vec3 throughput = ps.thr * weight;
         if (dbg >= PT_DEBUG_OUTPUT_BOUNCE_DIRECTION && dbg <= PT_DEBUG_BOUNCE_IS_TRANSMISSION) {     // :969-990
