@@ -38,6 +38,16 @@ extern "C" int pt_debug_read_timing(unsigned long long* out12, int reset) {
     if (reset) { unsigned long long z[12] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(pt::pt_timing), z, 96); }
     return 0;
 }
+// [8] / [9]: cycles a shade wave is parked behind the queue records of its chunk (round A) and behind what they name -- the packet head
+// and the path's state records (round B); [10]: wave-iterations.  Each stamp drains vmcnt, so the rounds are timed apart, not overlapped.
+// Since the hit record and the slot word are prefetched there is one round, stamped as [8]; [9] stays 0.
+// (The stamp starts BEFORE the round's loads are issued: the compiler puts its own wait at the first use of a result, and it is free to
+// schedule that use ahead of a stamp that follows the loads.)
+#define PT_WAIT_BEGIN() unsigned long long _a = __builtin_readcyclecounter();
+#define PT_WAIT_STAMP(K) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long _b = __builtin_readcyclecounter(); _wait[K] += _b - _a; _a = _b; }
+#else
+#define PT_WAIT_BEGIN()
+#define PT_WAIT_STAMP(K)
 #endif
 #ifdef PT_UTIL_PROBE             // diagnostic build only (tools/util_probe.py): wave-iterations and active lanes of the traversal phases
 namespace pt { __device__ unsigned long long pt_util[16]; }
@@ -64,6 +74,17 @@ PT_DEV void nt_store(float4& p, const float4 v) { nt_v4f q; q.x = v.x; q.y = v.y
 PT_DEV void nt_store(uint32_t& p, const uint32_t v) { __builtin_nontemporal_store(v, &p); }
 #define QLD(p) nt_load(p)
 #define QST(p, v) nt_store((p), (v))
+// A load that writes LDS and no register (gfx950 global_load_lds_dword / _dwordx4): every active lane's BYTES bytes at `src` land at
+// wave_base + lane * BYTES; a lane that is masked off writes nothing.  It counts in vmcnt like any load.  lds_fetch_queue: the queues' non-temporal
+// policy (the `nt` bit QLD's loads carry: 2).
+#define PT_LDS_FETCH(src, wave_base, BYTES, POLICY) \
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), (__attribute__((address_space(3))) void*)(wave_base), BYTES, 0, POLICY)
+PT_DEV void lds_fetch_queue(const float4* src, float4* wave_base) { PT_LDS_FETCH(src, wave_base, 16, 2); }
+PT_DEV void lds_fetch_queue(const uint32_t* src, uint32_t* wave_base) { PT_LDS_FETCH(src, wave_base, 4, 2); }
+// s_waitcnt with one counter at zero and the other two left alone (gfx9 encoding: vmcnt [3:0] and [15:14], expcnt [6:4], lgkmcnt [11:8]);
+// as the builtin, so that the compiler's own wait insertion sees it, and nothing that touches memory moves across it.
+PT_DEV void wait_vector_memory() { __builtin_amdgcn_s_waitcnt(0x0f70); asm volatile("" ::: "memory"); }
+PT_DEV void wait_lds() { asm volatile("" ::: "memory"); __builtin_amdgcn_s_waitcnt(0xc07f); asm volatile("" ::: "memory"); }
 
 #define PEND_ENV(s) wf.pend[2u * (s)]
 #define PEND_LIGHT(s) wf.pend[2u * (s) + 1u]
@@ -450,11 +471,20 @@ constexpr uint32_t kShadeDefaultsNoLights = PT_FLAG_SHADOW_RAYS | PT_FLAG_ENVIRO
 constexpr uint32_t kShadeDefaults = kShadeDefaultsNoLights | PT_FLAG_POINT_LIGHTS;
 // SMALL: the scene's instance rows, materials and lights all fit the LDS copies (<= 128 / 96 / 32: every BASELINE config): as a constant this
 // removes the global-memory branch of every table lookup (shade stage 8.70 -> 8.52 ms per launch).
-// LDS of a workgroup, 54 784 B: the tables take 50 688 B (sRGB and sheen tables 2 048, tangent angles 8 192, 128 instance rows 12 288,
-// 96 materials x 17 float4 26 112, 32 lights 2 048; the dead s_hand is compiled out) and the parking of the two UV sets 4 096 B (ParkLds,
-// pt_vertex.h: float2[2][256]).  256 VGPRs put two workgroups on a CU; their 109 568 B fit its 160 KiB, and every copy's code object says
-// Occupancy 2.  With the parking no copy selects between the UV sets in scratch: the two specialised copies have no scratch frame at all
+// LDS of a workgroup, 59 904 B: the tables take 50 688 B (sRGB and sheen tables 2 048, tangent angles 8 192, 128 instance rows 12 288,
+// 96 materials x 17 float4 26 112, 32 lights 2 048; the dead s_hand is compiled out), the parking of the two UV sets 4 096 B (ParkLds,
+// pt_vertex.h: float2[2][256]) and the prefetch of the next chunk's hit records and slot words 5 120 B (s_pre below: 16 + 4 B a lane).
+// 256 VGPRs put two workgroups on a CU; their 119 808 B fit its 160 KiB, and every copy's code object says Occupancy 2.
+// With the parking no copy selects between the UV sets in scratch: the two specialised copies have no scratch frame at all
 // (it was 100 B), and the shade stage went from 8.01 to 7.38 ms per 8-spp launch, images bit-identical.
+// the shading packet a queue entry's hit word names; a miss reads packet 0 and uses nothing of it
+PT_DEV const ShadePacket* packet_of(const SceneRec& sc, uint32_t hb) {
+#ifdef PT_PROBE_NO_PACKET     // PROBE ONLY: every hit reads one of 64 packets -- wrong geometry, what the shading-packet gathers cost
+    return sc.shade + (hb == kMissTri ? 0u : (hb & 63u));
+#else
+    return sc.shade + (hb == kMissTri ? 0u : (hb & 0x7fffffffu));
+#endif
+}
 template <uint32_t SPECIAL, bool SMALL>
 __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc_in, FrameConstants fc_in, WfBuffers wf, int cur, int bounce, Counters* __restrict__ counters) {
     SceneRec sc = sc_in; sc.small_tables = SMALL ? 1u : 0u;
@@ -486,9 +516,39 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     // 1080p frame: 5.27 rounds' worth of work took 6 rounds).
     uint32_t* shade_head = wf.cnt[6] + sv.shard * kCounterStride;
     const uint32_t lane64 = threadIdx.x & 63u;
-    uint32_t chunk = 0;
+    // What gates the addresses of a chunk's other fetches -- the hit record (its word 3 names the shading packet) and the slot word of ray_d
+    // (it names the path's state records) -- is asked for ONE CHUNK AHEAD, by loads that write the wave's own LDS buffer (lds_fetch_queue: no
+    // register holds them meanwhile; the kernel has none to spare).  Iteration k issues entry(k+1) at its top, as soon as k's copy is read out
+    // -- chunk k+1 was reserved by the tail of iteration k-1, in the same atomic instruction as the queue space, so its index is there without
+    // a wait.  Iteration k+1 then starts from two ds_reads and issues everything else at once -- ray_o, ray_d, env_a / env_b, q_beta / q_thr,
+    // the packet head, L and the pending records -- in ONE round trip where there were two dependent ones.  The buffer is wave-private and
+    // lane-linear, so the loop has no barrier; lanes past the queue's end fetch nothing; no address is read that was not read before.
+    // (Fetching the packet head ahead as well, into five more pieces of 16 B a lane, was measured and was slower: profiles/EXPERIMENTS.md,
+    // "Shade stage: the next chunk's hit record and slot word prefetched into LDS".)
+    __shared__ float4 s_pre[kBlock + kBlock / 4];                    // [lane of the workgroup] wf.hit; behind it [lane of the workgroup] the slot words, 4 B each
+    // (a wave's 64 lanes are contiguous in each image: a load's destination is a wave-uniform base, held in scalar registers like the sources')
+    const uint32_t wave_lane0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+    float4* const pre_wave = s_pre + wave_lane0;
+    uint32_t* const pre_slot_wave = (uint32_t*)(s_pre + kBlock) + wave_lane0;
+    // A lane's byte offset into the hit image and into a queue record array alike.  Formed anew wherever it is used, from a copy of the lane
+    // number the compiler cannot see through: hoisted out of the loop it is one live register more across the vertex, and the timed copy for
+    // punctual lights then spills.
+    const auto lane_bytes = [&]() { uint32_t l = lane64; asm volatile("" : "+v"(l)); return l * 16u; };
+    const auto fetch_entry = [&](uint32_t c, uint32_t lb) {         // c: wave-uniform
+        if (c + lane64 < n) {
+            lds_fetch_queue((const float4*)((const char*)(wf.hit + base + c) + lb), pre_wave);
+            lds_fetch_queue((const uint32_t*)((const char*)(wf.ray_d[cur] + base + c) + 12 + lb), pre_slot_wave);
+        }
+    };
+    uint32_t chunk = 0, next_chunk = 0;
     if (lane64 == 0) chunk = atomicAdd(shade_head, 64u);
     chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);
+    if (chunk < n) {                                                 // the wave's first chunk: nothing to hide its fetches behind
+        if (lane64 == 0) next_chunk = atomicAdd(shade_head, 64u);
+        fetch_entry(chunk, lane_bytes());
+        wait_vector_memory();
+    }
+    next_chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_chunk);
     // DEAD CODE, kept on purpose: `defer_on`, `held`, `flush`, `s_hand` and `set_aside` are what is left of an experiment that set hits on
     // rare materials (sheen) aside and shaded them together, a wave's notes packed onto free lanes through LDS.  It was measured and
     // rejected, and its switch is gone: defer_on is false, so flush and set_aside are always false, held is always kNoHeld, and the block
@@ -501,13 +561,14 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
     uint32_t* hand = s_hand + (threadIdx.x & ~63u);
     __shared__ float2 s_park[2 * kBlock];                            // the UV sets of the hit each lane is shading: [set][lane]
     const ParkLds park = {s_park + threadIdx.x};
+#ifdef PT_TIMING
+    unsigned long long _wait[3] = {0, 0, 0};
+#endif
     for (;;) {
         const bool more = chunk < n;
         const unsigned long long held_mask = __ballot(held != kNoHeld);
         if (!more && held_mask == 0) break;
         const bool flush = defer_on && (!more || __popcll(held_mask) >= kDeferFlush);       // (wave-uniform)
-        uint32_t next_chunk = 0;
-        if (!flush && lane64 == 0) next_chunk = atomicAdd(shade_head, 64u);
         const uint32_t i = flush ? held : chunk + lane64;
         const bool active = flush ? held != kNoHeld : i < n;
         if (flush) held = kNoHeld;
@@ -517,7 +578,7 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         uint32_t slot = 0;
         PathState ps;
         ps.beta = v3(0); ps.thr = v3(0); ps.prev_pdf = 0; ps.rc = 0; ps.bounce = 0; ps.prev_mis = false;
-        // ---- 1. everything the entry needs, fetched in one round trip
+        // ---- 1. the prefetched hit record and slot word from LDS; everything else the entry needs, fetched in one round trip
         float4 o = make_float4(0, 0, 0, 0), d = o, h = o, bp = o, tm = o, Lq = o, pe = o, pl = o;
         uint32_t hb = kMissTri;
         const ShadePacket* packet_at = sc.shade;
@@ -525,22 +586,25 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         EnvSample es;
         es.dir = v3(0, 0, 1); es.pdf = 1; es.color = v3(0);
         const bool with_state = bounce != 0;          // (wave-uniform: `bounce` is a kernel argument)
+        const uint32_t lb = lane_bytes();
         if (active) {
-            o = QLD(wf.ray_o[cur][base + i]); d = QLD(wf.ray_d[cur][base + i]); h = QLD(wf.hit[base + i]);
+            h = *(const float4*)((const char*)pre_wave + lb); slot = *(const uint32_t*)((const char*)pre_slot_wave + lb / 4u);
+        }
+        // the next chunk's entry goes where this one's was: once that is read out, and BEFORE the gathers below -- the first use of any of
+        // their results waits for every load in flight, so the LDS loads must not be the youngest
+        wait_lds();
+        fetch_entry(next_chunk, lb);
+        if (active) {
+            PT_WAIT_BEGIN()
+            o = QLD(wf.ray_o[cur][base + i]); d = QLD(wf.ray_d[cur][base + i]);
             // the vertex's environment light sample, drawn by the traversal stage (env_prepass); without an environment the sample is
             // the constant the in-place code produces.  Fetched with the entry whether or not this vertex will use it: no extra round trip.
             if (env_prepass_wanted(sc, fc, bounce)) {
                 const float4 ea = QLD(wf.env_a[base + i]), eb = QLD(wf.env_b[base + i]);
                 es.dir = v3(ea.x, ea.y, ea.z); es.pdf = ea.w; es.color = v3(eb.x, eb.y, eb.z);
             }
-            slot = __float_as_uint(d.w);
-            // the hit's shading packet depends on the queue entry only, like the path state below: one round trip for both
             hb = __float_as_uint(h.w);
-#ifdef PT_PROBE_NO_PACKET     // PROBE ONLY: every hit reads one of 64 packets -- wrong geometry, what the shading-packet gathers cost
-            packet_at = sc.shade + (hb == kMissTri ? 0u : (hb & 63u));
-#else
-            packet_at = sc.shade + (hb == kMissTri ? 0u : (hb & 0x7fffffffu));
-#endif
+            packet_at = packet_of(sc, hb);
             packet = load_shade_packet_raw(packet_at);
             if (with_state) {
                 bp = QLD(wf.q_beta[cur][base + i]); tm = QLD(wf.q_thr[cur][base + i]);
@@ -548,6 +612,10 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
                 Lq = wf.L[slot]; pe = PEND_ENV(slot); pl = PEND_LIGHT(slot);
 #endif
             }
+            PT_WAIT_STAMP(0)
+#ifdef PT_TIMING
+            _wait[2]++;
+#endif
         }
         // ---- 2. (dead: defer_on is false; the rejected set-aside of rare hits, kept for k_wf_shade's code generation -- see above)
         bool set_aside = false;
@@ -611,7 +679,11 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         // order three queue_push calls gave a wave), the bounce rays' counter is independent of it, so lane 0 adds to the one and lane 1 to
         // the other in the same atomic instruction and both bases return behind one wait -- where three queue_push calls made three dependent
         // round trips, each also waiting for the previous push's stores.  Every queue store is issued after that wait.  A lane with nothing
-        // to add, or a wave with nothing to push, issues no atomic.
+        // to add issues no atomic.  Lane 2 reserves the chunk after next from the shard's head in the same instruction (nothing once the
+        // queue's end is in sight): the index is back, behind the same wait, a whole iteration before entry(k+2) is asked for.  That wait is
+        // also the one that covers the LDS loads of this iteration's top before the next iteration reads them -- explicit, for the iterations
+        // that add nothing -- and it stands where no queue store is in flight yet.
+        const bool reserve_chunk = !flush && next_chunk < n;
         const unsigned long long m_env = __ballot(push_env), m_light = __ballot(push_light), m_bounce = __ballot(push_bounce);
         const uint32_t c_env = (uint32_t)__popcll(m_env), c_shadow = c_env + (uint32_t)__popcll(m_light), c_bounce = (uint32_t)__popcll(m_bounce);
 #ifdef PT_PROBE_ONE_WAIT      // PROBE ONLY (step 0 of the single reservation): queue_push's three atomics, issued back to back before anything waits for one
@@ -623,18 +695,23 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
         const uint32_t ie = (m_env ? __shfl(r_env, __ffsll((long long)m_env) - 1, 64) : 0u) + (uint32_t)__popcll(m_env & below);
         const uint32_t il = (m_light ? __shfl(r_light, __ffsll((long long)m_light) - 1, 64) : 0u) + (uint32_t)__popcll(m_light & below);
         const uint32_t ib = (m_bounce ? __shfl(r_bounce, __ffsll((long long)m_bounce) - 1, 64) : 0u) + (uint32_t)__popcll(m_bounce & below);
+        uint32_t r_head = 0;
+        if (reserve_chunk && lane64 == 0) r_head = atomicAdd(shade_head, 64u);
+        const uint32_t chunk_after_next = reserve_chunk ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_head) : next_chunk;
 #else
         uint32_t reserved = 0;
-        if ((c_shadow | c_bounce) != 0u && lane64 < 2u) {
-            const uint32_t add = lane64 == 0u ? c_shadow : c_bounce;
-            if (add != 0u) reserved = atomicAdd(lane64 == 0u ? cnt_shadow : cnt_next, add);
+        if (lane64 < 3u) {
+            const uint32_t add = lane64 == 0u ? c_shadow : (lane64 == 1u ? c_bounce : (reserve_chunk ? 64u : 0u));
+            if (add != 0u) reserved = atomicAdd(lane64 == 0u ? cnt_shadow : (lane64 == 1u ? cnt_next : shade_head), add);
         }
         const uint32_t base_shadow = (uint32_t)__builtin_amdgcn_readlane((int)reserved, 0), base_bounce = (uint32_t)__builtin_amdgcn_readlane((int)reserved, 1);
+        const uint32_t chunk_after_next = reserve_chunk ? (uint32_t)__builtin_amdgcn_readlane((int)reserved, 2) : next_chunk;
         const unsigned long long below = (1ull << lane64) - 1ull;
         const uint32_t ie = base_shadow + (uint32_t)__popcll(m_env & below);
         const uint32_t il = base_shadow + c_env + (uint32_t)__popcll(m_light & below);
         const uint32_t ib = base_bounce + (uint32_t)__popcll(m_bounce & below);
 #endif
+        wait_vector_memory();
         if (push_env) {
             QST(wf.sh_o[sbase + ie], make_float4(fu.origin_above.x, fu.origin_above.y, fu.origin_above.z, __uint_as_float(slot)));
             QST(wf.sh_d[sbase + ie], make_float4(fu.env_dir.x, fu.env_dir.y, fu.env_dir.z, __uint_as_float(kNoHint)));
@@ -653,9 +730,12 @@ __global__ __launch_bounds__(kBlock, PT_SHADE_WAVES) void k_wf_shade(SceneRec sc
             QST(wf.q_thr[nxt][base + ib], make_float4(fu.b_thr.x, fu.b_thr.y, fu.b_thr.z, __uint_as_float(misc)));
             n_bounce++;
         }
-        if (!flush) chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_chunk);
+        if (!flush) { chunk = next_chunk; next_chunk = chunk_after_next; }
     }
     flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, 0, n_bounce, n_shadow, n_hits, st.taps);
+#ifdef PT_TIMING
+    if (lane64 == 0) { for (int k = 0; k < 3; k++) atomicAdd(&pt_timing[8 + k], _wait[k]); }
+#endif
 }
 
 // occlusion traversal of the shadow queue (TraceShadowRay :724-742); writes the transmission next to its pending term.

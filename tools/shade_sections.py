@@ -1,6 +1,7 @@
 """Diagnostic (GPU box): cycles per section of the shade stage's closest-hit function, from a library built with -DPT_TIMING
 (variants/libmipt_timing.so = the library with pt_wavefront.hip compiled -DPT_TIMING).  Prints the share of each section.
-build:  tools/build_variant.sh timing -DPT_TIMING   (it links the Makefile's own object list)"""
+Also prints what a wave waits for at the top of a chunk, per wave-iteration (the stamps in k_wf_shade's loop).
+build:  ONLY=pt_wavefront tools/build_variant.sh timing -DPT_TIMING   (it links the Makefile's own object list)"""
 import ctypes as C, os, shutil, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -23,3 +24,5 @@ tot = sum(buf[k] for k in range(8)); n = buf[11]
 print("wave-hits %d, cycles per wave-hit %.0f" % (n, tot / max(n, 1)))
 for k in range(8):
     print("  %-40s %6.1f %%   %8.0f cycles" % (names[k], 100.0 * buf[k] / tot, buf[k] / max(n, 1)))
+nw = max(buf[10], 1)
+print("wave-iterations %d; parked per wave-iteration, each round of fetches drained on its own: the first %.0f cycles, the second (0 once a chunk has one) %.0f cycles" % (buf[10], buf[8] / nw, buf[9] / nw))
