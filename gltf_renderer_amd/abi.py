@@ -307,6 +307,15 @@ class PtMotionBlurConfig(C.Structure):
         return cls(0.5, 32.0, 16, 1, 0.05)
 
 
+class PtBloomConfig(C.Structure):
+    """pt_bloom_config (pt_bloom)."""
+    _fields_ = [("iterations", C.c_int32), ("strength", C.c_float), ("threshold", C.c_float)]
+
+    @classmethod
+    def defaults(cls):
+        return cls(4, 0.01, 0.0)
+
+
 class PtVarianceConfig(C.Structure):
     """pt_variance_config: the variance AOV (pt_set_variance; an extension, absent upstream)."""
     _fields_ = [("enable", C.c_int32), ("_pad", C.c_int32), ("variance", C.c_void_p)]
@@ -378,6 +387,8 @@ assert [getattr(PtMotionConfig, f).offset for f, _ in PtMotionConfig._fields_] =
 assert C.sizeof(PtReprojectConfig) == 12
 assert C.sizeof(PtMotionBlurConfig) == 20
 assert [getattr(PtMotionBlurConfig, f).offset for f, _ in PtMotionBlurConfig._fields_] == [0, 4, 8, 12, 16]
+assert C.sizeof(PtBloomConfig) == 12
+assert [getattr(PtBloomConfig, f).offset for f, _ in PtBloomConfig._fields_] == [0, 4, 8]
 assert C.sizeof(PtVarianceConfig) == 16
 assert [getattr(PtVarianceConfig, f).offset for f, _ in PtVarianceConfig._fields_] == [0, 4, 8]
 assert C.sizeof(PtNoiseSummary) == 20

@@ -1,5 +1,5 @@
 // pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what the translation units with entry points need of it: mipt_api.hip (the
-// core of the product), a feature's own file (bake, probe, matte, motion, blur, variance, denoise, denoise_variance .hip) and mipt_debug.hip (the test hooks).
+// core of the product), a feature's own file (bake, probe, matte, motion, blur, bloom, variance, denoise, denoise_variance .hip) and mipt_debug.hip (the test hooks).
 #pragma once
 #include <cstring>
 #include <string>
@@ -127,6 +127,8 @@ struct pt_ctx {
     pt::DevBuf d_noise;                           // one uint32 and one float2 per tile, for one tile count
     // ---- pt_motion_blur: the per-pixel streak image V, then the tile maxima T and their neighbourhood maxima N, for one image size
     pt::DevBuf d_blur;
+    // ---- pt_bloom: the mip chain, levels 1 .. n one after the other, one float4 a texel, for one image size and level count
+    pt::DevBuf d_bloom;
     // ---- pt_denoise: two ping-pong signal images and the guide image, one float4 a pixel each, for one image size
     pt::DevBuf d_denoise;
     // ---- pt_denoise_variance: two signal images (S.rgb, v) and the guide image, one float4 a pixel each, the plane of vt, one float a pixel,

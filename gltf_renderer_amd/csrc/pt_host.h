@@ -268,6 +268,28 @@ struct BlurArgs {
 };
 hipError_t launch_motion_blur(const BlurArgs& a, hipStream_t stream);
 
+// ---- bloom.hip: pt_bloom's down and up steps over the mip chain ----------------------------------------------------------------------
+// One step as a kernel takes it: level `src` (wi x hi) into level `dst` (wo x ho), 16 x 16 tiles numbered row-major, tiles_x a row.  color,
+// strength: the last up step's own pixel and scale (dst is then the caller's out); threshold: the first down step's prefilter.
+struct BloomStep {
+    const float4 *src, *color;
+    float4* dst;
+    uint32_t wi, hi, wo, ho, tiles_x;
+    float strength, threshold;
+};
+// chain: levels 1 .. n one after the other, lw[k - 1] x lh[k - 1] float4 each -- context-owned scratch.  n >= 1.  out is color or does not
+// overlap it.  Asynchronous: n down steps, then n up steps.
+struct BloomArgs {
+    const float4* color;
+    float4 *chain, *out;
+    uint32_t w, h;
+    int n;
+    uint32_t lw[8], lh[8];
+    float strength, threshold;
+};
+int bloom_levels(uint32_t w, uint32_t h, int iterations, uint32_t* lw, uint32_t* lh, size_t* texels);
+hipError_t launch_bloom(const BloomArgs& a, hipStream_t stream);
+
 // ---- variance.hip: pt_noise_estimate's per-tile reduction ---------------------------------------------------------------------------
 // out[t] = (mean, max) of the per-pixel relative standard error over the in-image pixels of tile t (row-major 16 x 16 tiles), (-1, -1) for
 // a tile whose count is below 2.  counts: one uint32 per tile on the device, nullptr = `samples` everywhere.  Asynchronous.

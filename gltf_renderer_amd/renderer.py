@@ -47,7 +47,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buf
            # the variance AOV and the noise report (additive likewise)
            "pt_set_variance", "pt_noise_estimate",
            # the denoiser steered by the variance (additive likewise)
-           "pt_denoise_variance"]
+           "pt_denoise_variance",
+           # the reference's bloom (additive likewise)
+           "pt_bloom"]
 
 
 class MiptError(RuntimeError):
@@ -145,6 +147,7 @@ def load_library():
     L.pt_set_variance.argtypes = [vp, vp]
     L.pt_noise_estimate.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp, vp]
     L.pt_denoise_variance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
+    L.pt_bloom.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     _LIB = L
     return L
 
@@ -496,6 +499,20 @@ class Renderer:
         h, w = color.shape[:2]
         self._check(self.L.pt_motion_blur(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
                                           C.c_void_p(motion.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
+        return out
+
+    def bloom(self, color, out=None, config=None):
+        """The reference's dual-filter bloom over a mip pyramid (include/mipt.h pt_bloom): out = color + strength * the blurred, prefiltered
+        `color`, a float32 CUDA tensor (H, W, 4).  out: where the result goes (None = a new tensor; `color` itself filters in place).
+        config: abi.PtBloomConfig (None = the defaults).  Asynchronous on the context's stream.  Returns the output tensor."""
+        t = self.torch
+        if out is None:
+            out = t.empty_like(color)
+        for x in (color, out):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+        h, w = color.shape[:2]
+        self._check(self.L.pt_bloom(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()), w, h,
+                                    C.c_void_p(out.data_ptr())))
         return out
 
     def set_variance(self, variance):

@@ -931,6 +931,47 @@ typedef struct pt_motion_blur_config {
 } pt_motion_blur_config;     /* 20 bytes */
 int pt_motion_blur(pt_ctx* ctx, const pt_motion_blur_config* config /* NULL = defaults */,
                    const void* color, const void* motion, uint32_t width, uint32_t height, void* out);
+/* Bloom: the reference's dual-filter bloom over a mip pyramid (Bloom::Execute, Source/Bloom.cpp:57-164, with BloomDownsample.cs.hlsl and
+ * BloomUpsample.cs.hlsl; the filters are those of "Bandwidth-Efficient Rendering", Marius Bjorge).  A pure function of one image, like
+ * pt_denoise and pt_motion_blur: it reads no pt_trace state.  color, out: caller-owned device pointers to W*H float4; the call is enqueued
+ * on the context's stream and is asynchronous.  out == color filters in place: the last step reads only the pyramid and each lane's own
+ * pixel.  Everything below is float32 in the order written, products and sums not fused; / is the correctly rounded division.
+ *   Sizes.  (w_0, h_0) = (W, H);  w_k = max(w_{k-1} / 2, 1), h_k likewise (the reference's NextMipSize).  n = the number of levels
+ * k = 1 .. iterations, stopping after the first level that is 1 x 1; a 1 x 1 image has n = 0.  If n = 0 or strength == 0, out = color, all
+ * four channels bit for bit.
+ *   Prefilter, applied to each texel of color as it is fetched (there is no level 0 in memory).  Per channel
+ *     b = (c > 0) ? fminf(c, 65504.0f) : 0.0f                  a select: NaN, negatives and -0 become +0, +infinity becomes 65504
+ * 65504 is the largest value of the reference's R16G16B16A16_FLOAT chain; with it no sum below can overflow.  With threshold > 0:
+ *     L = fmaxf(fmaxf(b.r, b.g), b.b);  k = L > threshold ? (L - threshold) / L : 0.0f;  b = b * k
+ *   Bilinear tap S(T, u, v) of a level T of w x h texels, clamp addressing:
+ *     sx = u * (float)w - 0.5f;  x0f = floorf(sx);  fx = sx - x0f
+ *     x0 = clamp((int)x0f, 0, w - 1);  x1 = clamp((int)x0f + 1, 0, w - 1);  y likewise
+ *     a = T[y0][x0] + fx * (T[y0][x1] - T[y0][x0]);  b = the same on row y1;  S = a + fy * (b - a)
+ *   Down into a level of wo x ho, pixel (x, y):
+ *     u = ((float)x + 0.5f) / (float)wo, v likewise;  ox = 0.5f / (float)wo;  oy = 0.5f / (float)ho
+ *     r = 4.0f * S(u, v);  then r = r + S(.) for (u + ox, v + oy), (u - ox, v - oy), (u - ox, v + oy), (u + ox, v - oy), in that order
+ *     M = r / 8.0f
+ * M_1 = down(prefiltered color);  M_k = down(M_{k-1}).
+ *   Up into wo x ho, u and v as above, ox = 1.0f / (float)wo, oy = 1.0f / (float)ho:
+ *     r = S(u + ox, v);  then + S(u - ox, v);  then + S(u, v + oy);  then + S(u, v - oy);  r = r * 2.0f
+ *     then + S(u + ox, v + oy), S(u - ox, v + oy), S(u + ox, v - oy), S(u - ox, v - oy), in that order;  U = r / 12.0f
+ *   Pyramid walk.  For i = n - 1 .. 1:  M_i = up(M_{i+1}).  This REPLACES M_i, as upstream does with output_scale = 0: it is the dual-filter
+ * blur, not an accumulating pyramid.  Last step, at full size: U = up(M_1); a pixel with a non-finite component in c.rgb is copied, all
+ * four channels bit for bit; otherwise out.rgb = c.rgb + strength * U and out.w = c.w.
+ *   Against upstream.  The chain here is float32 where upstream's is half, and upstream's sampler weights are the hardware's fixed-point
+ * ones, so parity with real D3D output is unpinned, as everywhere else in this project.  A non-finite pixel neither spreads nor changes.
+ * Tiles another rank renders are black and darken their neighbours' glow: run it after the exchange.  float32 against the same text in
+ * float64, at the defaults: 1.7e-8 to 3.2e-8 of the image's maximum on the test images (tests/test_bloom_host.py has the bound).
+ *   Scratch (the chain: levels 1 .. n, one float4 a texel for 16-byte loads) belongs to the context, is regrown on a change of size and
+ * freed by pt_destroy.  PT_ERR_INVALID_ARGUMENT with nothing written for a NULL ctx (answered before any device call), a NULL image, a
+ * zero size or one above 2^30 (or W * H above 2^31 - 1), a config value out of range, out overlapping color without being color. */
+typedef struct pt_bloom_config {
+    int32_t iterations;  /* 0..8 pyramid levels; default 4 (Rasterizer.h:15 bloom_radius).  0 = out is color bit for bit */
+    float   strength;    /* finite, >= 0; default 0.01 (Rasterizer.h:14).  0 = out is color bit for bit */
+    float   threshold;   /* finite, >= 0; default 0 = off, as upstream, which has none */
+} pt_bloom_config;       /* 12 bytes */
+int pt_bloom(pt_ctx* ctx, const pt_bloom_config* config /* NULL = defaults */,
+             const void* color, uint32_t width, uint32_t height, void* out);
 /* The variance AOV (absent upstream): how noisy the accumulated image is, per pixel.  With a variance config enabled, pt_trace keeps, beside
  * the output, a W*H float4 target V: V.rgb is the population variance, per channel, of the samples in the pixel, V.w the population variance
  * of their channel sum (r + g) + b -- the quantity adaptive sampling's error is normalised by, so V.w carries the channels' covariance.  The

@@ -1,0 +1,223 @@
+"""CPU-only checks of pt_bloom (include/mipt.h): the symbol and the config mirror against the header, the call that answers without a device,
+and the restatement (tests/bloom_ref.py) that tests/test_gpu_bloom.py holds the GPU to -- its own properties.
+
+Where a property is not exact its tolerance comes from the float64 run of the same restatement, not from the GPU:
+  * Energy.  An impulse of 1 at (32, 32) of a 64 x 64 image, 3 levels: in float64 the glow covers 1936 texels (44 x 44) and sums to 1 within
+    3e-16 -- the taps' weights sum to 1 at every step and nothing reaches the border.  In float32 a texel goes through 3 down steps of 10
+    roundings (two lerps of 3, 4 sums; the products by 4 and the quotient by 8 are exact) and 3 up steps of 14 (two lerps, 7 sums, the
+    quotient by 12; the product by 2 is exact): 72 roundings, each at most 2^-24 of the larger of the (non-negative) values it combines.
+    Every such value is at most the sum of a tap's four texels, so the image's sum moves by at most 4 * 72 * 2^-24 = 1.8e-5.  Measured 8e-9.
+  * Constant image.  A constant image of 3.7 comes back exactly in float64 (the glow is float32(3.7) to the last bit); in float32 within
+    2 ulp of float32(3.7): a lerp between equal texels is exact, the sums 4c + c + c + c + c and their quotient by 8 are exact, and of an up
+    step's operations only 2 * 4c + c + c + c + c (three of those sums round: 9c, 10c and 11c are not multiples of c's ulp) and the quotient
+    by 12 round, which measured leaves 12c / 12 within 2 ulp of c.  Levels below the first reproduce the constant exactly the same way, so
+    the figure does not grow with the level count.
+  * float32 against float64.  out = c + s * U with U behind n levels, 24 n roundings as counted above, and two more for s * U and the sum:
+    |out32 - out64| <= 2^-24 * ((1 + s) * max|c| + s * (24 n + 1) * max U).  Measured, as a share of the image's maximum, at the defaults:
+    between 1.7e-8 and 3.2e-8 over 17 x 33, 40 x 3, 2 x 1, 67 x 35, 130 x 70, and 2 x 1 and 64 x 64 with iterations 8; 1 x 1 has no level and
+    is a copy.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from gltf_renderer_amd import abi, renderer
+from tests import bloom_ref as bl
+
+f32, f64, u32 = np.float32, np.float64, np.uint32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = [(17, 33), (40, 3), (1, 1), (2, 1), (67, 35), (130, 70)]
+
+
+def header():
+    return open(os.path.join(ROOT, "include", "mipt.h")).read()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(u32)
+
+
+def test_the_symbol_is_exported_and_declared():
+    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
+    assert re.search(r"\bint\s+pt_bloom\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_bloom_config\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*\w*\s*,"
+                     r"\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*void\s*\*\s*\w*\s*\)\s*;", text)
+    assert text.index("pt_motion_blur(") < text.index("pt_bloom(")                # after pt_motion_blur
+    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)                   # additive: the version stays
+    assert hasattr(renderer.load_library(), "pt_bloom") and "pt_bloom" in renderer.EXPORTS
+    assert callable(getattr(renderer.Renderer, "bloom"))
+
+
+def test_the_config_mirror_matches_the_header():
+    m = re.search(r"typedef struct pt_bloom_config \{(.*?)\} pt_bloom_config;", header(), re.S)
+    assert m, "include/mipt.h lacks pt_bloom_config"
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    fields = re.findall(r"(float|int32_t)\s+([a-z_]+)\s*;", body)
+    assert fields == [("int32_t", "iterations"), ("float", "strength"), ("float", "threshold")]
+    A = abi.PtBloomConfig
+    assert [n for n, _ in A._fields_] == [n for _, n in fields]
+    assert [t for _, t in A._fields_] == [C.c_float if t == "float" else C.c_int32 for t, _ in fields]
+    assert C.sizeof(A) == 12 and [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8]
+    d = A.defaults()
+    assert (d.iterations, f32(d.strength), f32(d.threshold)) == (4, f32(0.01), f32(0.0))
+    assert (d.iterations, d.strength, d.threshold) == tuple(f32(v) if isinstance(v, float) else v for v in bl.DEFAULTS.values())
+    h = header()
+    for words in ("Bloom::Execute", "Bloom.cpp:57-164", "float32 where upstream's is half", "fixed-point", "parity with real D3D output is unpinned",
+                  "neither spreads nor changes", "after the exchange", "REPLACES"):
+        assert words in h, words                                  # what a caller has to know is stated where a caller reads it
+
+
+def test_a_null_context_answers_minus_one_without_a_device():
+    L = renderer.load_library()
+    img = [np.full((4, 4, 4), 2.0, f32) for _ in range(2)]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert L.pt_bloom(None, None, p(img[0]), 4, 4, p(img[1])) == -1
+    cfg = abi.PtBloomConfig.defaults()
+    assert L.pt_bloom(None, C.byref(cfg), p(img[0]), 4, 4, p(img[0])) == -1
+    assert L.pt_bloom(None, None, None, 0, 0, None) == -1
+    assert all((a == 2.0).all() for a in img)
+
+
+# ---- the restatement -------------------------------------------------------------------------------------------------------------------
+def test_level_sizes_follow_next_mip_size_and_stop_at_one_by_one():
+    assert bl.level_sizes(17, 33, 4) == [(8, 16), (4, 8), (2, 4), (1, 2)]
+    assert bl.level_sizes(40, 3, 8) == [(20, 1), (10, 1), (5, 1), (2, 1), (1, 1)]               # the height collapses at level 1
+    assert bl.level_sizes(1, 1, 4) == [] and bl.level_sizes(2, 1, 4) == [(1, 1)] and bl.level_sizes(1920, 1080, 0) == []
+    assert bl.level_sizes(1920, 1080, 4) == [(960, 540), (480, 270), (240, 135), (120, 67)]
+    assert len(bl.level_sizes(1 << 30, 1, 8)) == 8
+
+
+@pytest.mark.parametrize("size", [(17, 33), (1, 1)])
+def test_no_levels_and_no_strength_return_the_inputs_bits(size):
+    w, h = size
+    color = bl.random_field(np.random.default_rng(3 * w), w, h)
+    for kw in (dict(iterations=0), dict(strength=0.0), dict(iterations=0, strength=0.0, threshold=2.0)):
+        out, info = bl.bloom(color, **dict(bl.DEFAULTS, **kw))
+        assert np.array_equal(bits(out), bits(color)), kw
+    out, info = bl.bloom(color)
+    assert (len(info["sizes"]) == 0) == (size == (1, 1))
+    assert np.array_equal(bits(out), bits(color)) == (size == (1, 1))                          # a 1 x 1 image is a copy; 17 x 33 does glow
+
+
+def test_a_non_finite_pixel_neither_spreads_nor_changes():
+    w, h = 40, 24
+    rng = np.random.default_rng(9)
+    base = (rng.random((h, w, 4)) * 4).astype(f32)
+    for special, chan in ((np.nan, 0), (-np.inf, 2), (np.nan, 1)):
+        bad, zero = base.copy(), base.copy()
+        bad[11, 17, chan] = special
+        zero[11, 17, chan] = 0
+        kw = dict(iterations=3, strength=0.5, threshold=0.0)
+        got, info = bl.bloom(bad, **kw)
+        want, _ = bl.bloom(zero, **kw)
+        assert info["nonfinite"].sum() == 1 and info["nonfinite"][11, 17]
+        others = ~info["nonfinite"]
+        assert np.array_equal(bits(got[others]), bits(want[others]))
+        assert np.array_equal(bits(got[11, 17]), bits(bad[11, 17]))                            # itself: copied, all four channels
+        assert (bits(got[others][:, :3]) != bits(bad[others][:, :3])).any(axis=-1).all()      # ... while everything else did get its glow
+    # a non-finite alpha is no reason to copy: w is passed through and rgb gets the glow
+    odd = base.copy(); odd[5, 5, 3] = np.nan
+    got, info = bl.bloom(odd, iterations=3, strength=0.5)
+    assert not info["nonfinite"].any() and np.isnan(got[5, 5, 3]) and np.all(got[5, 5, :3] > odd[5, 5, :3])
+
+
+def test_plus_infinity_counts_as_65504():
+    w, h = 17, 33
+    base = (np.random.default_rng(4).random((h, w, 4)) * 4).astype(f32)
+    a, b = base.copy(), base.copy()
+    a[20, 8, 1] = np.inf
+    b[20, 8, 1] = 65504.0
+    ga, ia = bl.bloom(a, iterations=4, strength=1.0)
+    gb, ib = bl.bloom(b, iterations=4, strength=1.0)
+    assert np.array_equal(bits(ia["glow"]), bits(ib["glow"])) and ia["clamped"][20, 8] and ia["nonfinite"][20, 8] and not ib["clamped"].any()
+    rest = ~ia["nonfinite"]
+    assert np.array_equal(bits(ga[rest]), bits(gb[rest])) and np.array_equal(bits(ga[20, 8]), bits(a[20, 8]))
+    # above 65504 and finite: clamped in the glow, and the pixel itself keeps its own value plus the glow
+    c = base.copy(); c[20, 8, 1] = 3.0e5
+    gc, ic = bl.bloom(c, iterations=4, strength=1.0)
+    assert np.array_equal(bits(ic["glow"]), bits(ib["glow"])) and gc[20, 8, 1] == f32(f32(3.0e5) + ic["glow"][20, 8, 1])
+
+
+def test_an_impulse_keeps_its_energy():
+    """Tolerances: the module's docstring."""
+    imp = np.zeros((64, 64, 4), f32)
+    imp[32, 32, :3] = 1.0
+    _, i64 = bl.bloom(imp, 3, 1.0, 0.0, f64)
+    _, i32 = bl.bloom(imp, 3, 1.0, 0.0)
+    for info in (i64, i32):
+        assert [int((info["glow"][..., c] > 0).sum()) for c in range(3)] == [1936] * 3
+        ys, xs = np.nonzero(info["glow"][..., 0] > 0)
+        assert (ys.min(), ys.max(), xs.min(), xs.max()) == (10, 53, 10, 53)                     # 44 x 44, clear of the border
+    s64, s32 = float(i64["glow"][..., 0].sum()), float(i32["glow"][..., 0].astype(f64).sum())
+    print("impulse: float64 sum - 1 = %.2e, float32 sum - 1 = %.2e" % (s64 - 1, s32 - 1))
+    assert abs(s64 - 1) <= 1e-13 and abs(s32 - 1) <= 4 * 72 * 2.0 ** -24
+
+
+@pytest.mark.parametrize("size", [(20, 31), (17, 33), (64, 64)])
+def test_a_constant_image_comes_back_within_two_ulp(size):
+    """Tolerances: the module's docstring."""
+    w, h = size
+    const = np.full((h, w, 4), 3.7, f32)
+    c = f32(3.7)
+    for iterations in (1, 4, 8):
+        _, i64 = bl.bloom(const, iterations, 1.0, 0.0, f64)
+        _, i32 = bl.bloom(const, iterations, 1.0, 0.0)
+        e64 = np.abs(i64["glow"] - f64(c)).max() / f64(c)
+        e32 = np.abs(i32["glow"].astype(f64) - f64(c)).max() / f64(np.spacing(c))
+        print(size, iterations, "float64 relative %.1e, float32 %.1f ulp" % (e64, e32))
+        assert e64 <= 1e-15 and e32 <= 2.0
+
+
+def test_float32_stays_within_its_rounding_bound_of_float64():
+    """The bound: the module's docstring."""
+    shares = []
+    for (w, h), iterations in [(s, 4) for s in SIZES] + [((2, 1), 8), ((64, 64), 8)]:
+        color = bl.random_field(np.random.default_rng(w), w, h)
+        o32, i32 = bl.bloom(color, iterations)
+        o64, i64 = bl.bloom(color, iterations, dtype=f64)
+        n = len(i32["sizes"])
+        if n == 0:
+            assert np.array_equal(bits(o32), bits(color))
+            continue
+        fin = ~i32["nonfinite"]
+        cmax, umax, s = np.abs(color[fin][:, :3]).max().astype(f64), i64["glow"].max(), f64(f32(0.01))
+        bound = 2.0 ** -24 * ((1 + s) * cmax + s * (24 * n + 1) * umax)
+        err = np.abs(o32[fin][:, :3].astype(f64) - o64[fin][:, :3]).max()
+        shares.append(err / cmax)
+        print((w, h), iterations, "levels %d: |float32 - float64| = %.2e of the image's maximum, bound %.2e" % (n, err / cmax, bound / cmax))
+        assert err <= bound
+    assert len(shares) == 7
+
+
+def test_iterations_above_the_available_levels_equal_the_clamped_run():
+    color = bl.random_field(np.random.default_rng(40), 40, 3)
+    a, ia = bl.bloom(color, 8, 0.5)
+    b, ib = bl.bloom(color, 5, 0.5)
+    assert len(ia["sizes"]) == 5 and ia["sizes"][-1] == (1, 1) and np.array_equal(bits(a), bits(b))
+    c, ic = bl.bloom(color, 4, 0.5)
+    assert len(ic["sizes"]) == 4 and not np.array_equal(bits(a), bits(c))
+
+
+def test_thresholds():
+    w, h = 17, 33
+    color = bl.random_field(np.random.default_rng(2), w, h)
+    plain, _ = bl.bloom(color, 3, 0.25)
+    zero, iz = bl.bloom(color, 3, 0.25, 0.0)
+    assert np.array_equal(bits(plain), bits(zero)) and not iz["below"].any()
+    # a real one: part of the image feeds the glow, and the glow is dimmer than without it
+    some, info = bl.bloom(color, 3, 0.25, 0.75)
+    share = (~info["below"] & ~info["nonfinite"]).sum() / (~info["nonfinite"]).sum()
+    assert 0.1 < share < 0.9 and np.all(info["glow"] <= iz["glow"]) and (info["glow"] < iz["glow"]).any()
+    # above everything the prefilter lets through (65504): nothing feeds the glow, U = +0, and c + strength * (+0) has c's bits -- except
+    # for c = -0, which the sum turns into +0
+    color[3, 3, :3] = (-0.0, 0.5, -0.0)
+    high, ih = bl.bloom(color, 3, 0.25, 1.0e5)
+    assert ih["below"].all() and not ih["glow"].any()
+    fin = ~ih["nonfinite"]
+    neg_zero = bits(color[..., :3]) == 0x80000000
+    keep = fin[..., None] & ~neg_zero
+    assert np.array_equal(bits(high[..., :3])[keep], bits(color[..., :3])[keep])
+    assert np.array_equal(bits(high[3, 3]), bits(np.array((0.0, 0.5, 0.0, color[3, 3, 3]), f32)))
+    assert np.array_equal(bits(high[~fin]), bits(color[~fin])) and np.array_equal(bits(high[..., 3]), bits(color[..., 3]))

@@ -70,6 +70,12 @@ or with --prev-time T on a single frame (--motion-out is then optional).  A reco
   python tools/render_gltf.py figure.glb --animation 0 --sequence 0:2:24 --temporal --motion-blur 0.5 --spp 16 --out shot.png
   python tools/render_gltf.py figure.glb --animation 0 --prev-time 0.46 --time 0.5 --motion-blur 0.5 --spp 64 --out frame.png
 
+--bloom [STRENGTH]: the reference's bloom (pt_bloom: a dual-filter blur over a mip pyramid, added to the frame STRENGTH times; 0.01 unless
+given, the reference's default), applied last before tone mapping: after --denoise, --denoise-variance, --temporal and --motion-blur, in
+--sequence mode to every frame.  --bloom-radius N sets the pyramid levels (0..8, default 4: each level doubles the reach), --bloom-threshold T
+lets only what is brighter than T glow (default 0 = everything, as upstream).  Not with --bake or --probes: an atlas is not a picture.
+  python tools/render_gltf.py lantern.glb --spp 256 --denoise --bloom 0.04 --bloom-radius 6 --out frame.png
+
 --variance-out PREFIX: the variance pass (pt_set_variance), accumulated with the frame: PREFIX.exr (32-bit float RGBA; a name ending in .npy
 gives an array) holds the variance of each pixel's mean, V / (n - 1): rgb per channel, a of the channel sum.  --noise-target X keeps tracing
 batches of --batch samples until no tile's relative standard error (pt_noise_estimate, adaptive sampling's own normalisation) exceeds X, or
@@ -231,7 +237,21 @@ def main():
     ap.add_argument("--motion-blur", type=float, default=None, metavar="SHUTTER", help="blur the finished frame along its motion vectors; SHUTTER in (0, 2]; needs --sequence or --prev-time")
     ap.add_argument("--blur-radius", type=float, default=None, metavar="R", help="with --motion-blur: cap of the half streak in pixels (1..64, default 32)")
     ap.add_argument("--blur-taps", type=int, default=None, metavar="N", help="with --motion-blur: taps along the streak (2..64, default 16)")
+    ap.add_argument("--bloom", type=float, nargs="?", const=0.01, default=None, metavar="STRENGTH", help="add the reference's bloom to the finished frame; STRENGTH >= 0 (0.01 unless given)")
+    ap.add_argument("--bloom-radius", type=int, default=None, metavar="N", help="with --bloom: pyramid levels (0..8, default 4)")
+    ap.add_argument("--bloom-threshold", type=float, default=None, metavar="T", help="with --bloom: only what is brighter than T glows (default 0 = everything, as upstream)")
     a = ap.parse_args()
+    if a.bloom is None and (a.bloom_radius is not None or a.bloom_threshold is not None):
+        ap.error("--bloom-radius and --bloom-threshold need --bloom [STRENGTH]")
+    if a.bloom is not None:
+        if not (math.isfinite(a.bloom) and a.bloom >= 0.0):
+            ap.error("--bloom takes a finite strength >= 0")
+        if a.bloom_radius is not None and not (0 <= a.bloom_radius <= 8):
+            ap.error("--bloom-radius takes 0..8 levels")
+        if a.bloom_threshold is not None and not (math.isfinite(a.bloom_threshold) and a.bloom_threshold >= 0.0):
+            ap.error("--bloom-threshold takes a finite T >= 0")
+        if a.bake is not None or a.probes is not None:
+            ap.error("--bloom goes with neither --bake nor --probes: an atlas is not a picture")
     if a.motion_out and a.prev_time is None:
         ap.error("--motion-out FILE needs --prev-time T")
     if a.prev_time is not None and not (a.motion_out or a.motion_blur is not None):
@@ -393,6 +413,14 @@ def main():
             blur.max_radius = a.blur_radius
         if a.blur_taps is not None:
             blur.taps = a.blur_taps
+    bloom = None
+    if a.bloom is not None:
+        bloom = abi.PtBloomConfig.defaults()
+        bloom.strength = a.bloom
+        if a.bloom_radius is not None:
+            bloom.iterations = a.bloom_radius
+        if a.bloom_threshold is not None:
+            bloom.threshold = a.bloom_threshold
 
     def write_frame(path, image):
         if path.lower().endswith(".exr"):
@@ -428,11 +456,13 @@ def main():
                 shown = r.denoise(out, aov_albedo, aov_nd, config=dn)
             if blur is not None:                                         # after the filters; the history above stays unblurred
                 shown = r.motion_blur(shown, motion, config=blur)
+            if bloom is not None:                                        # last before tone mapping; into a new image: `shown` may be the history
+                shown = r.bloom(shown, config=bloom)
             write_frame(numbered_path(a.out, i), shown)
         torch.cuda.synchronize()
         s = r.stats()
         print("%s: %d frames %s .. %s, t = %.4g .. %.4g, %d spp each%s, last trace %.2f ms" % (a.path, len(sequence_times), numbered_path(a.out, 0),
-              numbered_path(a.out, len(sequence_times) - 1), sequence_times[0], sequence_times[-1], a.spp, (", denoised and reprojected" if a.temporal else "") + (", motion blur at shutter %g" % a.motion_blur if blur is not None else ""), s.trace_ms))
+              numbered_path(a.out, len(sequence_times) - 1), sequence_times[0], sequence_times[-1], a.spp, (", denoised and reprojected" if a.temporal else "") + (", motion blur at shutter %g" % a.motion_blur if blur is not None else "") + (", bloom at strength %g" % a.bloom if bloom is not None else ""), s.trace_ms))
         return
     adaptive_cfg = None if a.adaptive is None else (min(a.min_spp, a.spp), a.spp, a.adaptive)
     if adaptive_cfg is not None:
@@ -547,6 +577,9 @@ def main():
     if blur is not None:                                                 # after the denoiser, before tone mapping
         out = r.motion_blur(out, motion, config=blur)
         print("motion blur (t = %.4g -> %.4g): shutter %g, half streak <= %g px, %d taps" % (a.prev_time, a.time, blur.shutter, blur.max_radius, blur.taps))
+    if bloom is not None:                                                # last before tone mapping
+        out = r.bloom(out, out=out, config=bloom)                        # in place: the last step reads the pyramid and its own pixel
+        print("bloom: strength %g, %d levels, threshold %g" % (bloom.strength, bloom.iterations, bloom.threshold))
     if a.probe_sh:
         np.save(a.probe_sh, r.probe_project(out, abi.PROBE_SH_IRRADIANCE if a.irradiance else abi.PROBE_SH_RADIANCE))
         print("probe SH (%s): %s" % ("irradiance" if a.irradiance else "radiance", a.probe_sh))
