@@ -547,12 +547,15 @@ int pt_create(int device, void* hip_stream, const float* sheen_e_16x16, pt_ctx**
         double c = i / 255.0;
         srgb[i] = (float)(c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4));
     }
+    // The fills go on the context's stream, where the kernels that read or overwrite this memory run: hipMemset on the null stream need
+    // not be done when it returns, and a non-blocking stream does not wait for the null stream.  (The copies are from pageable memory:
+    // done when hipMemcpy returns.)
     bool ok = ctx->d_sheen.realloc(ctx->stream, 256 * 4) == hipSuccess && ctx->d_srgb.realloc(ctx->stream, 256 * 4) == hipSuccess &&
               ctx->d_counters.realloc(ctx->stream, sizeof(Counters)) == hipSuccess && ctx->d_white.realloc(ctx->stream, 16) == hipSuccess &&
-              hipMemset(ctx->d_white.ptr, 0xff, 16) == hipSuccess &&
+              hipMemsetAsync(ctx->d_white.ptr, 0xff, 16, ctx->stream) == hipSuccess &&
               hipMemcpy(ctx->d_sheen.ptr, sheen_e_16x16, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(ctx->d_srgb.ptr, srgb, 256 * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemset(ctx->d_counters.ptr, 0, sizeof(Counters)) == hipSuccess &&
+              hipMemsetAsync(ctx->d_counters.ptr, 0, sizeof(Counters), ctx->stream) == hipSuccess &&
               ctx->d_tangent_lut.realloc(ctx->stream, 1024 * sizeof(float2)) == hipSuccess &&
               build_tangent_lut(ctx->d_tangent_lut.as<float2>(), ctx->stream) == hipSuccess;
     for (int i = 0; i < 2 && ok; i++)
@@ -609,7 +612,7 @@ int pt_buffer_create(pt_ctx* ctx, const void* host, size_t bytes, int format, in
     ENTER(ctx);
     void* d = nullptr;
     HIPOK(hipMalloc(&d, bytes + 16));
-    hipError_t e = host ? hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) : hipMemset(d, 0, bytes);
+    hipError_t e = host ? hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(d, 0, bytes, ctx->stream);   // (the fill: on the stream of the kernels that write it next)
     if (e) { hipFree(d); return ctx->fail(PT_ERR_DEVICE, std::string("pt_buffer_create: ") + hipGetErrorString(e)); }
     const BufferRec rec = {d, (uint32_t)format, (uint32_t)bytes};
     *handle_out = take_slot(ctx->buffers, ctx->free_buffers, rec);

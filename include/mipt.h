@@ -345,7 +345,8 @@ const char* pt_last_error(const pt_ctx* ctx);
 int pt_abi_version(void);
 
 /* Vertex / index streams: Mesh::Create sub-allocations + descriptors (Source/Mesh.cpp:103-190).
- * host may be NULL (DynamicMesh outputs, Source/Mesh.cpp:236-290). */
+ * host may be NULL (DynamicMesh outputs, Source/Mesh.cpp:236-290): the buffer is then zero-filled on the context's stream, ahead of
+ * the pt_skin_run that writes it. */
 int pt_buffer_create(pt_ctx* ctx, const void* host, size_t bytes, int format, int* handle_out);
 int pt_buffer_update(pt_ctx* ctx, int handle, const void* host, size_t bytes);
 int pt_buffer_read(pt_ctx* ctx, int handle, void* host, size_t bytes);
