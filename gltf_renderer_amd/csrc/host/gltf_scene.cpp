@@ -322,15 +322,17 @@ uint32_t encode_tangent_space(const float n_in[3], const float t[4]) {          
 }
 
 // ---- base64 (data URIs)
-bool base64_decode(const char* s, size_t n, std::vector<uint8_t>& out) {
-    static int8_t table[256];
-    static bool ready = false;
-    if (!ready) {
-        memset(table, -1, sizeof(table));
+struct Base64Table {
+    int8_t t[256];
+    Base64Table() {
+        memset(t, -1, sizeof(t));
         const char* al = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-        for (int i = 0; i < 64; i++) table[(uint8_t)al[i]] = (int8_t)i;
-        ready = true;
+        for (int i = 0; i < 64; i++) t[(uint8_t)al[i]] = (int8_t)i;
     }
+};
+bool base64_decode(const char* s, size_t n, std::vector<uint8_t>& out) {
+    static const Base64Table b64;    // built in the declaration: several threads may load their first data URI at once
+    const int8_t* table = b64.t;
     out.clear();
     out.reserve(n * 3 / 4);
     uint32_t acc = 0; int bits = 0;

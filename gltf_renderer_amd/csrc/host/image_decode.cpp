@@ -77,22 +77,26 @@ bool inflate_codes(BitReader& br, const Huff& lit, const Huff& dist, std::vector
     }
 }
 
-bool raw_inflate(BitReader& br, std::vector<uint8_t>& out, std::string& err) {
-    static Huff fixed_lit, fixed_dist;
-    static bool fixed_ready = false;
-    if (!fixed_ready) {
+struct FixedHuff {                  // the fixed code of RFC 1951 3.2.6
+    Huff lit, dist;
+    FixedHuff() {
         uint8_t l[288];
         int i = 0;
         for (; i < 144; i++) l[i] = 8;
         for (; i < 256; i++) l[i] = 9;
         for (; i < 280; i++) l[i] = 7;
         for (; i < 288; i++) l[i] = 8;
-        fixed_lit.build(l, 288);
+        lit.build(l, 288);
         uint8_t d[30];
         for (i = 0; i < 30; i++) d[i] = 5;
-        fixed_dist.build(d, 30);
-        fixed_ready = true;
+        dist.build(d, 30);
     }
+};
+
+bool raw_inflate(BitReader& br, std::vector<uint8_t>& out, std::string& err) {
+    static const FixedHuff fixed;    // built in the declaration: several threads may decode their first image at once
+    const Huff& fixed_lit = fixed.lit;
+    const Huff& fixed_dist = fixed.dist;
     int last;
     do {
         last = (int)br.bits(1);
@@ -1003,14 +1007,15 @@ bool decode_exr(const uint8_t* data, size_t n, ImageF& out, std::string& err, bo
 // =================================================================================================== writers
 namespace {
 
-uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
-    static uint32_t table[256];
-    static bool ready = false;
-    if (!ready) {
-        for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xedb88320u ^ (c >> 1) : c >> 1; table[i] = c; }
-        ready = true;
+struct CrcTable {
+    uint32_t t[256];
+    CrcTable() {
+        for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xedb88320u ^ (c >> 1) : c >> 1; t[i] = c; }
     }
-    for (size_t i = 0; i < n; i++) crc = table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
+};
+uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
+    static const CrcTable table;     // built in the declaration: several threads may write their first image at once
+    for (size_t i = 0; i < n; i++) crc = table.t[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
     return crc;
 }
 void put_be32(std::vector<uint8_t>& v, uint32_t x) { v.push_back((uint8_t)(x >> 24)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x); }

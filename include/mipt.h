@@ -18,7 +18,8 @@
  *
  * Conventions: every function returns PT_OK (0) or a negative pt_status; pt_last_error() gives
  * the message.  No exceptions or aborts cross the boundary.  One caller thread per context
- * (as the reference: Source/Renderer.cpp:215-227).  All device work is enqueued on the HIP stream
+ * (as the reference: Source/Renderer.cpp:215-227); what is per context, per thread and process-wide: INTEGRATION.md, "Threads".
+ * All device work is enqueued on the HIP stream
  * given to pt_create and is asynchronous unless stated; pt_readback / pt_tonemap / pt_get_stats
  * synchronise that stream.
  */

@@ -10,6 +10,7 @@
  *
  * Conventions as in mipt.h: int status (PT_OK = 0), no exceptions across the boundary, plain pointers and sizes.
  * Pointers returned by gs_get_* stay valid until gs_free; the scene is single-threaded like the reference's.
+ * One thread per scene at a time, different scenes on different threads at once: INTEGRATION.md, "Threads".
  */
 #ifndef MIPT_SCENE_H
 #define MIPT_SCENE_H
