@@ -244,12 +244,7 @@ int pt_bloom(pt_ctx* ctx, const pt_bloom_config* config, const void* color, uint
         return PT_OK;
     }
     const size_t need = texels * 16;
-    if (need != ctx->d_bloom.cap) {                          // for this size and level count alone: a smaller chain reallocates too
-        if (const hipError_t e = ctx->d_bloom.realloc(ctx->stream, need)) {
-            (void)hipGetLastError();
-            return ctx->fail(e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, "bloom: " + std::to_string(need) + " bytes of scratch");
-        }
-    }
+    if (const int rc = exact_scratch(ctx, ctx->d_bloom, need, "bloom")) return rc;      // for this size and level count alone
     a.color = (const float4*)color; a.out = (float4*)out; a.chain = ctx->d_bloom.as<float4>();
     a.w = width; a.h = height;
     a.strength = cfg.strength; a.threshold = cfg.threshold;

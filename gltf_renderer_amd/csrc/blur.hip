@@ -164,12 +164,7 @@ int pt_motion_blur(pt_ctx* ctx, const pt_motion_blur_config* config, const void*
     a.tiles_x = (width + PT_TILE - 1) / PT_TILE; a.tiles_y = (height + PT_TILE - 1) / PT_TILE;
     const size_t tiles = (size_t)a.tiles_x * a.tiles_y;
     const size_t need = bytes + 2 * tiles * 16;         // V, then T, then N
-    if (need != ctx->d_blur.cap) {                      // for this size alone: a smaller image reallocates too
-        if (const hipError_t e = ctx->d_blur.realloc(ctx->stream, need)) {
-            (void)hipGetLastError();
-            return ctx->fail(e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, "motion_blur: " + std::to_string(need) + " bytes of scratch");
-        }
-    }
+    if (const int rc = exact_scratch(ctx, ctx->d_blur, need, "motion_blur")) return rc;      // for this size alone
     a.color = (const float4*)color; a.motion = (const float4*)motion; a.out = (float4*)out;
     a.V = ctx->d_blur.as<float4>(); a.T = a.V + n; a.N = a.T + tiles;
     a.half_shutter = 0.5f * cfg.shutter; a.max_radius = cfg.max_radius; a.depth_softness = cfg.depth_softness;

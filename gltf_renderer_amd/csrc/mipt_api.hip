@@ -9,7 +9,7 @@
 //   ResourceTable      <- the bindless descriptor heap (DescriptorAllocator.h), as raw device pointers
 // This file is the core of the product: context lifetime, resources, scene tables, trace (with select_passes, where a call's optional passes
 // are weighed against each other), camera and lens, adaptive sampling and pt_accum_*, skin, post, exchange.  A feature that has a file keeps
-// its setter, *_setup and entry points there (bake, probe, matte, motion, blur, variance, denoise, denoise_variance .hip).  The context itself is
+// its setter, *_setup and entry points there (bake, probe, matte, motion, blur, variance, denoise .hip).  The context itself is
 // in pt_ctx.h, the owner of its device arrays in dev_buf.h, the test hooks (pt_debug_*) in mipt_debug.hip.
 // There is no CPU fallback anywhere in this file: every compute entry point launches HIP kernels.
 #include <algorithm>

@@ -1,5 +1,5 @@
 // pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what the translation units with entry points need of it: mipt_api.hip (the
-// core of the product), a feature's own file (bake, probe, matte, motion, blur, bloom, variance, denoise, denoise_variance .hip) and mipt_debug.hip (the test hooks).
+// core of the product), a feature's own file (bake, probe, matte, motion, blur, bloom, variance, denoise .hip) and mipt_debug.hip (the test hooks).
 #pragma once
 #include <cstring>
 #include <string>
@@ -161,6 +161,13 @@ namespace pt {
 // device with PT_ERR_OUT_OF_MEMORY and its own text returns (anything else DevBuf::realloc fails with is its synchronise).  (mipt_api.hip)
 hipError_t staged_upload(pt_ctx* ctx, void* dst, const void* src, size_t bytes);
 int grow_failed(pt_ctx* ctx, hipError_t e, const std::string& what);
+// A post filter's scratch stands for one size alone: exactly `need` bytes, reallocated when it holds any other amount (a smaller image
+// reallocates too).  who: the filter's name, the prefix of its text beside PT_ERR_OUT_OF_MEMORY
+inline int exact_scratch(pt_ctx* ctx, DevBuf& d, size_t need, const char* who) {
+    if (need == d.cap) return PT_OK;
+    const hipError_t e = d.realloc(ctx->stream, need);
+    return e == hipSuccess ? PT_OK : grow_failed(ctx, e, std::string(who) + ": " + std::to_string(need) + " bytes of scratch");
+}
 // Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte: the entry points that take several device images refuse aliases by it
 inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;

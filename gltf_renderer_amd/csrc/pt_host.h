@@ -96,11 +96,6 @@ struct SkinArgs {
 void launch_skin(const SkinArgs& a, bool use_mfma, hipStream_t stream);
 void launch_tonemap(const float4* in, uint32_t w, uint32_t h, const pt_tonemap_config& cfg, float* out_rgb, uint32_t* out_rgba8, hipStream_t stream);
 
-// ---- denoise.hip: pt_denoise's kernels.  ping / pong / guide: w * h float4 each (context-owned scratch); out may be color.  iterations >= 1
-// (the API answers 0 with a copy).  Asynchronous.
-hipError_t launch_denoise(const pt_denoise_config& cfg, const float4* color, const float4* albedo, const float4* normal_depth, uint32_t w, uint32_t h,
-                          float4* out, float4* ping, float4* pong, float4* guide, hipStream_t stream);
-
 // ---- pt_wavefront.hip / pt_kernel.hip ---------------------------------------------------------
 size_t traversal_grid_lanes(int stage_blocks);   // lanes of the widest traversal launch of a wavefront trace with that many stage workgroups
 constexpr uint32_t kDeepStackMax = 1024;      // most stack entries a tree may ask for (64 on chip + a deep stack in memory); a clustered tree beyond it is rebuilt as a radix tree

@@ -90,12 +90,7 @@ int pt_noise_estimate(pt_ctx* ctx, const void* image, const void* variance, uint
     ENTER(ctx);
     // the scratch: (mean, max) per tile, then the tiles' counts; for this tile count alone
     const size_t need = (size_t)tiles * (sizeof(float2) + sizeof(uint32_t));
-    if (need != ctx->d_noise.cap) {
-        if (const hipError_t e = ctx->d_noise.realloc(ctx->stream, need)) {
-            (void)hipGetLastError();
-            return ctx->fail(e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE, "noise_estimate: " + std::to_string(need) + " bytes of scratch");
-        }
-    }
+    if (const int rc = exact_scratch(ctx, ctx->d_noise, need, "noise_estimate")) return rc;
     float2* d_out = ctx->d_noise.as<float2>();
     uint32_t* d_counts = tile_samples ? (uint32_t*)(d_out + tiles) : nullptr;
     // the caller's counts stay valid until this call returns, and it returns behind the stream

@@ -2,7 +2,8 @@
 """Run ON THE GPU BOX: what pt_denoise costs at 1920 x 1080 on the 8-spp images of config 3 (the Sponza-class scene), timed from outside
 with stream events -- pt_stats does not grow for it.  For iterations 1, 3 and 5: the median of CALLS calls after WARMUP warm-ups, and
 the share of the L2 gather rate that figure stands for (a pass reads 25 taps x 32 B per pixel through L2; MI355X_MICROARCH: 16.8 TB/s).
-Beside it the single-sample pt_trace launch of the same build, the cost a user weighs the filter against.
+Beside it the single-sample pt_trace launch of the same build, the cost a user weighs the filter against.  The kernels are the VAR = false
+instantiations of gltf_renderer_amd/csrc/denoise.hip (k_at_prepare, k_at_pass).
 usage: python tools/denoise_probe.py [--calls 30] [--size 1920 1080] [--json FILE]"""
 import argparse
 import json

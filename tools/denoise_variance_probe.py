@@ -3,7 +3,9 @@
 pt_denoise on the same images in the same process, both at their defaults, timed from outside with stream events as
 tools/denoise_probe.py does: ROUNDS rounds of the two filters in turn, each the median of CALLS enqueues after WARMUP warm-ups.  The
 bytes suggest a ratio near 1.2: a tap moves 36 B through L2 where pt_denoise's moves 32 B, and a 9-tap prefilter pass comes on top.
-MIPT_LIBRARY (gltf_renderer_amd/renderer.py) times another build of the library in the same way.
+Both filters are instantiations of one kernel family (gltf_renderer_amd/csrc/denoise.hip: k_at_prepare, k_at_prefilter, k_at_pass,
+k_at_pass_lds), so a change there is measured on both by one run.  MIPT_LIBRARY (gltf_renderer_amd/renderer.py) times another build of the
+library in the same way.
 usage: python tools/denoise_variance_probe.py [--calls 30] [--rounds 2] [--size 1920 1080] [--iterations 5] [--json FILE]"""
 import argparse
 import json
