@@ -8,7 +8,9 @@ to what the reference uploads to its GPU:
   PtMaterial      <- Renderer::GpuMaterial       Source/Renderer.h:88-171
   PtMeshInstance  <- Pathtracer::GpuMeshInstance Source/Pathtracer.h:131-140
   PtBone          <- GpuSkin::Bone               Source/GpuSkin.h:12-15
-Sizes are asserted at import.
+Their sizes are asserted at import; every mirror, these and the extensions', is held to its typedef by the compiler
+(tests/test_host_abi.py), and so is PROTOTYPES, the one statement of the header's functions.  bind() gives a table
+to ctypes.  Importable without torch, the library or a GPU.
 """
 import ctypes as C
 
@@ -367,33 +369,99 @@ assert C.sizeof(PtLight) == 64
 assert C.sizeof(PtTextureSample) == 32
 assert C.sizeof(PtMaterial) == 640
 assert C.sizeof(PtMeshInstance) == 156
-assert C.sizeof(PtInstanceDesc) == 176
-assert C.sizeof(PtExecuteParams) == 168
 assert C.sizeof(PtBone) == 128
-assert C.sizeof(PtStats) == 152
-assert C.sizeof(PtAdaptiveConfig) == 16
-assert C.sizeof(PtAovConfig) == 24
-assert C.sizeof(PtDenoiseConfig) == 20
-assert C.sizeof(PtLensConfig) == 20
-assert [getattr(PtLensConfig, f).offset for f, _ in PtLensConfig._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtBakeConfig) == 16
-assert [getattr(PtBakeConfig, f).offset for f, _ in PtBakeConfig._fields_] == [0, 4, 8, 12]
-assert C.sizeof(PtProbeConfig) == 20
-assert [getattr(PtProbeConfig, f).offset for f, _ in PtProbeConfig._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtMatteConfig) == 48
-assert [getattr(PtMatteConfig, f).offset for f, _ in PtMatteConfig._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtMotionConfig) == 144
-assert [getattr(PtMotionConfig, f).offset for f, _ in PtMotionConfig._fields_] == [0, 4, 8, 16, 80]
-assert C.sizeof(PtReprojectConfig) == 12
-assert C.sizeof(PtMotionBlurConfig) == 20
-assert [getattr(PtMotionBlurConfig, f).offset for f, _ in PtMotionBlurConfig._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtBloomConfig) == 12
-assert [getattr(PtBloomConfig, f).offset for f, _ in PtBloomConfig._fields_] == [0, 4, 8]
-assert C.sizeof(PtVarianceConfig) == 16
-assert [getattr(PtVarianceConfig, f).offset for f, _ in PtVarianceConfig._fields_] == [0, 4, 8]
-assert C.sizeof(PtNoiseSummary) == 20
-assert [getattr(PtNoiseSummary, f).offset for f, _ in PtNoiseSummary._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtDenoiseVarianceConfig) == 20
-assert [getattr(PtDenoiseVarianceConfig, f).offset for f, _ in PtDenoiseVarianceConfig._fields_] == [0, 4, 8, 12, 16]
-assert C.sizeof(PtAccumImages) == 24
-assert C.sizeof(PtAccumInfo) == 64
+# every other mirror's size, offsets and field types are held to the headers by the compiler (tests/test_host_abi.py)
+
+
+# ---- prototypes ------------------------------------------------------------------------------
+# Every function of include/mipt.h: name -> (restype, argtypes).  The one statement of the C prototypes on the Python side: bind() gives
+# them to ctypes, renderer.EXPORTS is this table's names, and tests/test_host_abi.py has the compiler compare every row with the header.
+# A pointer is c_void_p unless the callers pass byref() of one scalar: c_void_p takes byref(), None, ctypes arrays, bytes and data_ptr() ints.
+_vp, _ci, _u32, _u64, _sz, _f32 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float
+_out = C.POINTER
+PROTOTYPES = {
+    "pt_abi_version": (_ci, []),
+    "pt_create": (_ci, [_ci, _vp, _vp, _out(_vp)]),
+    "pt_destroy": (None, [_vp]),
+    "pt_last_error": (C.c_char_p, [_vp]),
+    "pt_buffer_create": (_ci, [_vp, _vp, _sz, _ci, _out(_ci)]),
+    "pt_buffer_update": (_ci, [_vp, _ci, _vp, _sz]),
+    "pt_buffer_read": (_ci, [_vp, _ci, _vp, _sz]),
+    "pt_buffer_destroy": (_ci, [_vp, _ci]),
+    "pt_texture_create": (_ci, [_vp, _vp, _ci, _ci, _ci, _out(_ci)]),
+    "pt_texture_destroy": (_ci, [_vp, _ci]),
+    "pt_sampler_create": (_ci, [_vp, _vp, _out(_ci)]),
+    "pt_scene_set_materials": (_ci, [_vp, _vp, _ci]),
+    "pt_scene_set_lights": (_ci, [_vp, _vp, _ci]),
+    "pt_scene_set_instances": (_ci, [_vp, _vp, _ci]),
+    "pt_env_create": (_ci, [_vp, _vp, _ci, _ci, _out(_ci)]),
+    "pt_env_read": (_ci, [_vp, _ci, _out(_ci), _vp, _vp]),
+    "pt_env_destroy": (_ci, [_vp, _ci]),
+    "pt_build_accel": (_ci, [_vp]),
+    "pt_accel_request_rebuild": (_ci, [_vp]),
+    "pt_set_accel_builder": (_ci, [_vp, _ci]),
+    "pt_skin_run": (_ci, [_vp, _vp, _vp, _ci]),
+    "pt_trace": (_ci, [_vp, _vp, _vp]),
+    "pt_set_bounce_limit": (_ci, [_vp, _ci]),
+    "pt_set_samples_per_trace": (_ci, [_vp, _ci]),
+    "pt_set_null_shadow_culling": (_ci, [_vp, _ci]),
+    "pt_enable_counters": (_ci, [_vp, _ci]),
+    "pt_enable_stage_timing": (_ci, [_vp, _ci]),
+    "pt_set_kernel_mode": (_ci, [_vp, _ci, _ci]),
+    "pt_get_stats": (_ci, [_vp, _vp]),
+    "pt_reset_stats": (_ci, [_vp]),
+    "pt_readback": (_ci, [_vp, _vp, _u32, _u32, _vp]),
+    "pt_tonemap": (_ci, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    # multi-GPU exchange
+    "pt_exchange_unique_id": (_ci, [_vp]),
+    "pt_exchange_probe": (_ci, []),
+    "pt_exchange_create": (_ci, [_vp, _ci, _ci, _vp]),
+    "pt_exchange_create_loopback": (_ci, [_vp, _ci, _ci, _u64]),
+    "pt_exchange_frame": (_ci, [_vp, _vp, _vp, _u32, _u32, _ci, _ci]),
+    "pt_exchange_destroy": (_ci, [_vp]),
+    "pt_tiles_packed_bytes": (_sz, [_u32, _u32, _u32, _u32]),
+    "pt_tiles_pack": (_ci, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
+    "pt_tiles_unpack": (_ci, [_vp, _vp, _u32, _u32, _u32, _u32, _vp]),
+    # the extensions (additive: the ABI version stays 2)
+    "pt_set_adaptive": (_ci, [_vp, _vp]),
+    "pt_adaptive_read": (_ci, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "pt_set_aov": (_ci, [_vp, _vp]),
+    "pt_denoise": (_ci, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "pt_accum_save": (_ci, [_vp, _vp, _u32, _u32, _u32, _u32, _u64, _vp, _sz, _out(_sz)]),
+    "pt_accum_load": (_ci, [_vp, _vp, _sz, _vp]),
+    "pt_accum_inspect": (_ci, [_vp, _sz, _vp]),
+    "pt_set_lens": (_ci, [_vp, _vp]),
+    "pt_lens_focus_at": (_ci, [_vp, _vp, _vp, _f32, _f32, _out(_f32)]),
+    "pt_set_bake": (_ci, [_vp, _vp]),
+    "pt_bake_coverage": (_ci, [_vp, _u32, _u32, _vp, _vp]),
+    "pt_bake_dilate": (_ci, [_vp, _vp, _u32, _u32, _ci]),
+    "pt_set_probes": (_ci, [_vp, _vp, _vp]),
+    "pt_probe_project": (_ci, [_vp, _vp, _u32, _u32, _ci, _vp]),
+    "pt_set_matte": (_ci, [_vp, _vp, _vp]),
+    "pt_matte_id": (_u32, [C.c_char_p, _sz]),
+    "pt_matte_extract": (_ci, [_vp, _vp, _ci, _u32, _u32, _vp, _ci, _vp]),
+    "pt_motion_snapshot": (_ci, [_vp, _ci]),
+    "pt_motion_snapshot_state": (_ci, [_vp, _out(C.c_int32)]),
+    "pt_set_motion": (_ci, [_vp, _vp]),
+    "pt_reproject": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "pt_motion_blur": (_ci, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "pt_set_variance": (_ci, [_vp, _vp]),
+    "pt_noise_estimate": (_ci, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _f32, _vp, _vp, _vp]),
+    "pt_denoise_variance": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
+    "pt_bloom": (_ci, [_vp, _vp, _vp, _u32, _u32, _vp]),
+}
+
+
+class MiptError(RuntimeError):
+    pass
+
+
+def bind(L, table, header):
+    """Gives ctypes the prototypes of `table` (name -> (restype, argtypes)) for the library L; `header` names the file that declares them.
+    The only place a restype or an argtypes of libmipt.so is assigned."""
+    missing = [s for s in table if not hasattr(L, s)]
+    if missing:
+        raise MiptError("libmipt.so lacks symbols declared in %s: %s" % (header, missing))
+    for name, (restype, argtypes) in table.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, list(argtypes)

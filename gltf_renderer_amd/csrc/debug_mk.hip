@@ -3,6 +3,7 @@
 // traversal driver on caller-supplied rays, and the kernels' math routines.  No frame runs anything in this file.
 #include "pt_debug_kernels.h"
 #include "dev_buf.h"
+#include "mipt_debug.h"
 
 namespace pt {
 

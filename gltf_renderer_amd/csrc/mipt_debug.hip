@@ -1,10 +1,11 @@
-// mipt_debug.hip -- the test hooks of libmipt.so (pt_debug_*, not part of include/mipt.h): the product's own device code run on the
-// caller's queries, for tests/ and tools/ to compare with the oracle.  Host code only: this file has no kernel; what the hooks launch is in
-// debug_wf.hip and debug_mk.hip (compiled as pt_wavefront.hip and pt_kernel.hip are) and motion.hip.  The product itself is mipt_api.hip and
-// the feature files beside it.
+// mipt_debug.hip -- the test hooks of libmipt.so (pt_debug_*, declared in mipt_debug.h, not part of include/mipt.h): the product's own
+// device code run on the caller's queries, for tests/ and tools/ to compare with the oracle.  Host code only: this file has no kernel; what
+// the hooks launch is in debug_wf.hip and debug_mk.hip (compiled as pt_wavefront.hip and pt_kernel.hip are) and motion.hip.  The product
+// itself is mipt_api.hip and the feature files beside it.
 #include <cstdio>
 #include <cstdlib>
 
+#include "mipt_debug.h"
 #include "pt_ctx.h"
 
 using namespace pt;

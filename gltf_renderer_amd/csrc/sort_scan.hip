@@ -14,6 +14,7 @@
 
 #include <cstdint>
 
+#include "mipt_debug.h"
 #include "pt_host.h"
 
 namespace pt {

@@ -9,13 +9,6 @@ import numpy as np
 from . import abi
 from .renderer import MiptError, load_library
 
-SCENE_EXPORTS = ["gs_load_file", "gs_free", "gs_last_error", "gs_get_counts", "gs_get_primitive", "gs_get_morph_target", "gs_get_material",
-                 "gs_get_texture", "gs_get_sampler", "gs_get_camera", "gs_get_node", "gs_get_node_weights", "gs_get_scene_nodes", "gs_get_skin", "gs_get_animation",
-                 "gs_get_channel", "gs_sample_channel", "gs_apply_rest_transforms", "gs_animate", "gs_calculate_global_transforms", "gs_player_tick",
-                 "gs_gather_lights", "gs_gather_bones", "gs_upload", "gs_unload", "gs_frame", "img_load_rgba8", "img_decode_rgba8", "img_load_rgb32f",
-                 "img_decode_rgb32f", "img_free", "img_write_png", "img_write_pfm", "img_write_exr"]
-
-
 class GsCounts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("meshes", "primitives", "materials", "nodes", "scenes", "skins", "animations", "lights", "textures", "samplers",
                                        "cameras", "dynamic_meshes")]
@@ -48,6 +41,46 @@ class GsPlayer(C.Structure):
     _fields_ = [("animation", C.c_int), ("playhead", C.c_float), ("playing", C.c_int), ("loop", C.c_int)]
 
 
+# Every function of include/mipt_scene.h: name -> (restype, argtypes), as abi.PROTOTYPES states include/mipt.h.
+_vp, _ci, _sz, _f32, _str = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_char_p
+SCENE_PROTOTYPES = {
+    "gs_load_file": (_ci, [_str, C.POINTER(_vp)]),
+    "gs_free": (None, [_vp]),
+    "gs_last_error": (_str, []),
+    "gs_get_counts": (_ci, [_vp, _vp]),
+    "gs_get_primitive": (_ci, [_vp, _ci, _vp]),
+    "gs_get_morph_target": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp]),
+    "gs_get_material": (_ci, [_vp, _ci, _vp]),
+    "gs_get_texture": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "gs_get_sampler": (_ci, [_vp, _ci, _vp]),
+    "gs_get_camera": (_ci, [_vp, _ci, _vp]),
+    "gs_get_node": (_ci, [_vp, _ci, _vp]),
+    "gs_get_node_weights": (_ci, [_vp, _ci, _vp, _ci]),
+    "gs_get_scene_nodes": (_ci, [_vp, _ci, _vp, _ci]),
+    "gs_get_skin": (_ci, [_vp, _ci, _vp, _vp, _vp]),
+    "gs_get_animation": (_ci, [_vp, _ci, _vp, _vp]),
+    "gs_get_channel": (_ci, [_vp, _ci, _ci, _vp]),
+    "gs_sample_channel": (_ci, [_vp, _ci, _ci, _f32, _ci, _vp]),
+    "gs_apply_rest_transforms": (_ci, [_vp]),
+    "gs_animate": (_ci, [_vp, _ci, _f32]),
+    "gs_calculate_global_transforms": (_ci, [_vp, _ci]),
+    "gs_player_tick": (_ci, [_vp, _vp, _f32]),
+    "gs_gather_lights": (_ci, [_vp, _ci, _vp, _ci]),
+    "gs_gather_bones": (_ci, [_vp, _ci, _vp, _ci]),
+    "gs_upload": (_ci, [_vp, _vp]),
+    "gs_unload": (_ci, [_vp, _vp]),
+    "gs_frame": (_ci, [_vp, _vp, _ci, _vp]),
+    "img_load_rgba8": (_ci, [_str, _vp, _vp, _vp]),
+    "img_decode_rgba8": (_ci, [_vp, _sz, _vp, _vp, _vp]),
+    "img_load_rgb32f": (_ci, [_str, _vp, _vp, _vp, _vp]),
+    "img_decode_rgb32f": (_ci, [_vp, _sz, _ci, _vp, _vp, _vp, _vp]),
+    "img_free": (None, [_vp]),
+    "img_write_png": (_ci, [_str, _vp, _ci, _ci, _ci]),
+    "img_write_pfm": (_ci, [_str, _vp, _ci, _ci]),
+    "img_write_exr": (_ci, [_str, _vp, _ci, _ci, _ci]),
+}
+SCENE_EXPORTS = list(SCENE_PROTOTYPES)
+
 _READY = False
 
 
@@ -55,22 +88,7 @@ def _lib():
     global _READY
     L = load_library()
     if not _READY:
-        missing = [s for s in SCENE_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise MiptError("libmipt.so lacks symbols declared in include/mipt_scene.h: %s" % missing)
-        L.gs_last_error.restype = C.c_char_p
-        L.gs_free.restype = None
-        L.img_free.restype = None
-        L.img_free.argtypes = [C.c_void_p]
-        L.gs_free.argtypes = [C.c_void_p]
-        L.gs_load_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        for name in ("gs_get_counts", "gs_get_primitive", "gs_get_material", "gs_get_sampler", "gs_get_camera", "gs_get_node", "gs_get_channel"):
-            getattr(L, name).argtypes = None
-        L.gs_sample_channel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
-        L.gs_animate.argtypes = [C.c_void_p, C.c_int, C.c_float]
-        L.gs_player_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
-        L.img_decode_rgba8.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.img_decode_rgb32f.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        abi.bind(L, SCENE_PROTOTYPES, "include/mipt_scene.h")
         _READY = True
     return L
 

@@ -14,46 +14,8 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmipt.so")
 
-# every symbol include/mipt.h declares
-EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_buffer_create", "pt_buffer_update", "pt_buffer_read",
-           "pt_texture_create", "pt_sampler_create", "pt_scene_set_materials", "pt_scene_set_lights", "pt_scene_set_instances",
-           "pt_env_create", "pt_env_read", "pt_build_accel", "pt_skin_run", "pt_trace", "pt_set_bounce_limit", "pt_set_samples_per_trace", "pt_set_null_shadow_culling", "pt_enable_counters",
-           "pt_set_kernel_mode",
-           "pt_get_stats", "pt_reset_stats", "pt_readback", "pt_tonemap",
-           # ABI 2
-           "pt_buffer_destroy", "pt_texture_destroy", "pt_env_destroy", "pt_accel_request_rebuild", "pt_set_accel_builder", "pt_enable_stage_timing",
-           "pt_exchange_unique_id", "pt_exchange_probe", "pt_exchange_create", "pt_exchange_create_loopback", "pt_exchange_frame", "pt_exchange_destroy",
-           "pt_tiles_packed_bytes", "pt_tiles_pack", "pt_tiles_unpack",
-           # adaptive sampling (additive: the ABI version stays 2)
-           "pt_set_adaptive", "pt_adaptive_read",
-           # first-hit AOVs (additive likewise)
-           "pt_set_aov",
-           # the denoiser over them (additive likewise)
-           "pt_denoise",
-           # saving and resuming an accumulation (additive likewise)
-           "pt_accum_save", "pt_accum_load", "pt_accum_inspect",
-           # thin-lens depth of field (additive likewise)
-           "pt_set_lens", "pt_lens_focus_at",
-           # texture-space baking (additive likewise)
-           "pt_set_bake", "pt_bake_coverage", "pt_bake_dilate",
-           # light-probe baking (additive likewise)
-           "pt_set_probes", "pt_probe_project",
-           # ID mattes (additive likewise)
-           "pt_set_matte", "pt_matte_id", "pt_matte_extract",
-           # motion vectors and temporal reprojection (additive likewise)
-           "pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject",
-           # motion blur along the motion vectors (additive likewise)
-           "pt_motion_blur",
-           # the variance AOV and the noise report (additive likewise)
-           "pt_set_variance", "pt_noise_estimate",
-           # the denoiser steered by the variance (additive likewise)
-           "pt_denoise_variance",
-           # the reference's bloom (additive likewise)
-           "pt_bloom"]
-
-
-class MiptError(RuntimeError):
-    pass
+EXPORTS = list(abi.PROTOTYPES)      # every symbol include/mipt.h declares
+MiptError = abi.MiptError
 
 
 _LIB = None
@@ -72,82 +34,9 @@ def load_library():
     # torch BEFORE libmipt.so so that it is torch's copy (loading /opt/rocm's first makes later device queries fail).
     import torch  # noqa: F401
     L = C.CDLL(lib_path)
-    missing = [s for s in EXPORTS if not hasattr(L, s)]
-    if missing:
-        raise MiptError("libmipt.so lacks symbols declared in include/mipt.h: %s" % missing)
+    abi.bind(L, abi.PROTOTYPES, "include/mipt.h")
     if L.pt_abi_version() != 2:
         raise MiptError("libmipt.so ABI version mismatch")
-    vp, ci = C.c_void_p, C.c_int
-    L.pt_create.argtypes = [ci, vp, vp, C.POINTER(vp)]
-    L.pt_destroy.argtypes = [vp]
-    L.pt_destroy.restype = None
-    L.pt_last_error.argtypes = [vp]
-    L.pt_last_error.restype = C.c_char_p
-    L.pt_buffer_create.argtypes = [vp, vp, C.c_size_t, ci, C.POINTER(ci)]
-    L.pt_buffer_update.argtypes = [vp, ci, vp, C.c_size_t]
-    L.pt_buffer_read.argtypes = [vp, ci, vp, C.c_size_t]
-    L.pt_texture_create.argtypes = [vp, vp, ci, ci, ci, C.POINTER(ci)]
-    L.pt_sampler_create.argtypes = [vp, vp, C.POINTER(ci)]
-    L.pt_scene_set_materials.argtypes = [vp, vp, ci]
-    L.pt_scene_set_lights.argtypes = [vp, vp, ci]
-    L.pt_scene_set_instances.argtypes = [vp, vp, ci]
-    L.pt_env_create.argtypes = [vp, vp, ci, ci, C.POINTER(ci)]
-    L.pt_env_read.argtypes = [vp, ci, C.POINTER(ci), vp, vp]
-    L.pt_build_accel.argtypes = [vp]
-    L.pt_skin_run.argtypes = [vp, vp, vp, ci]
-    L.pt_trace.argtypes = [vp, vp, vp]
-    L.pt_set_bounce_limit.argtypes = [vp, ci]
-    L.pt_set_samples_per_trace.argtypes = [vp, ci]
-    L.pt_set_null_shadow_culling.argtypes = [vp, ci]
-    L.pt_enable_counters.argtypes = [vp, ci]
-    L.pt_set_kernel_mode.argtypes = [vp, ci, ci]
-    L.pt_get_stats.argtypes = [vp, vp]
-    L.pt_reset_stats.argtypes = [vp]
-    L.pt_readback.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
-    L.pt_tonemap.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.pt_buffer_destroy.argtypes = [vp, ci]
-    L.pt_texture_destroy.argtypes = [vp, ci]
-    L.pt_env_destroy.argtypes = [vp, ci]
-    L.pt_accel_request_rebuild.argtypes = [vp]
-    L.pt_set_accel_builder.argtypes = [vp, ci]
-    L.pt_enable_stage_timing.argtypes = [vp, ci]
-    L.pt_exchange_unique_id.argtypes = [vp]
-    L.pt_exchange_create.argtypes = [vp, ci, ci, vp]
-    L.pt_exchange_probe.argtypes = []
-    L.pt_exchange_create_loopback.argtypes = [vp, ci, ci, C.c_uint64]
-    L.pt_exchange_frame.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, ci, ci]
-    L.pt_exchange_destroy.argtypes = [vp]
-    L.pt_tiles_packed_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
-    L.pt_tiles_packed_bytes.restype = C.c_size_t
-    L.pt_tiles_pack.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    L.pt_tiles_unpack.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    L.pt_set_adaptive.argtypes = [vp, vp]
-    L.pt_adaptive_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    L.pt_set_aov.argtypes = [vp, vp]
-    L.pt_denoise.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
-    L.pt_accum_save.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.pt_accum_load.argtypes = [vp, vp, C.c_size_t, vp]
-    L.pt_accum_inspect.argtypes = [vp, C.c_size_t, vp]
-    L.pt_set_lens.argtypes = [vp, vp]
-    L.pt_lens_focus_at.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.POINTER(C.c_float)]
-    L.pt_set_bake.argtypes = [vp, vp]
-    L.pt_bake_coverage.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.pt_bake_dilate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci]
-    L.pt_set_probes.argtypes = [vp, vp, vp]
-    L.pt_probe_project.argtypes = [vp, vp, C.c_uint32, C.c_uint32, ci, vp]
-    L.pt_set_matte.argtypes = [vp, vp, vp]
-    L.pt_matte_id.argtypes = [C.c_char_p, C.c_size_t]
-    L.pt_matte_id.restype = C.c_uint32
-    L.pt_matte_extract.argtypes = [vp, vp, ci, C.c_uint32, C.c_uint32, vp, ci, vp]
-    L.pt_motion_snapshot.argtypes = [vp, ci]
-    L.pt_motion_snapshot_state.argtypes = [vp, C.POINTER(C.c_int32)]
-    L.pt_set_motion.argtypes = [vp, vp]
-    L.pt_reproject.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.pt_motion_blur.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
-    L.pt_set_variance.argtypes = [vp, vp]
-    L.pt_noise_estimate.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp, vp]
-    L.pt_denoise_variance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
-    L.pt_bloom.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     _LIB = L
     return L
 
@@ -157,7 +46,32 @@ def sheen_lut():
 
 
 def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    """A numpy array's host pointer; None for None."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _dp(t):
+    """A tensor's device pointer; None for None."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ref(struct):
+    """byref of a config structure; None (= the library's defaults) for None."""
+    return C.byref(struct) if struct is not None else None
+
+
+def _tiles(h, w):
+    return (h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE
+
+
+def _tile_samples(tile_samples, h, w):
+    """The per-tile sample counts of an (h, w) image as a contiguous uint32 array, one per tile; None for None."""
+    if tile_samples is None:
+        return None
+    ts = np.ascontiguousarray(tile_samples, np.uint32)
+    ty, tx = _tiles(h, w)
+    assert ts.size == ty * tx
+    return ts
 
 
 class Renderer:
@@ -180,6 +94,20 @@ class Renderer:
         if rc != 0:
             raise MiptError("pt_create failed: %d" % rc)
         self.h = h
+
+    # ---- the contract of every image argument, said once
+    def _image(self, x, like=None, optional=False):
+        """x is a float32 CUDA contiguous (H, W, 4) tensor -- of like's shape, if one is given; None passes if optional.  Returns x."""
+        if x is None and optional:
+            return x
+        assert x.is_cuda and x.is_contiguous() and x.dtype == self.torch.float32 and x.dim() == 3 and x.shape[2] == 4
+        assert like is None or x.shape == like.shape
+        return x
+
+    def _plane(self, x, h, w, optional=False):
+        """x is a float32 CUDA contiguous (h, w) tensor; None passes if optional.  Returns x."""
+        assert (x is None and optional) or (x.is_cuda and x.is_contiguous() and x.dtype == self.torch.float32 and tuple(x.shape) == (h, w))
+        return x
 
     def _check(self, rc):
         if rc != 0:
@@ -284,7 +212,7 @@ class Renderer:
     def adaptive_read(self, width, height):
         """State after the last adaptive trace: (active tile count, samples (tiles_y, tiles_x) uint32, error (tiles_y, tiles_x)
         float32, half image (height, width, 4) float32).  Tiles another rank renders read 0."""
-        ty, tx = (height + abi.TILE - 1) // abi.TILE, (width + abi.TILE - 1) // abi.TILE
+        ty, tx = _tiles(height, width)
         active = C.c_int32()
         samples = np.zeros((ty, tx), np.uint32)
         error = np.zeros((ty, tx), np.float32)
@@ -297,9 +225,8 @@ class Renderer:
         hit distance) are float32 CUDA tensors (H, W, 4) like the output, caller-owned; either may be None, both None turns AOVs off.
         They accumulate with the output, sample for sample.  The next trace() starts a new accumulation."""
         for t in (albedo, normal_depth):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4)
-        cfg = abi.PtAovConfig(int(albedo is not None or normal_depth is not None), albedo.data_ptr() if albedo is not None else None,
-                              normal_depth.data_ptr() if normal_depth is not None else None)
+            self._image(t, optional=True)
+        cfg = abi.PtAovConfig(int(albedo is not None or normal_depth is not None), _dp(albedo), _dp(normal_depth))
         self._check(self.L.pt_set_aov(self.h, C.byref(cfg)))
         self._aov = (albedo, normal_depth)           # the library keeps the pointers: keep the tensors alive with the renderer
 
@@ -308,21 +235,17 @@ class Renderer:
         (H, W, 4) -- the output of trace() and the targets of set_aov(), or any images of that layout.  out: where the result goes (None = a
         new tensor; `color` itself filters in place); config: abi.PtDenoiseConfig (None = the defaults).  Asynchronous on the context's
         stream.  Returns the output tensor."""
-        t = self.torch
         if out is None:
-            out = t.empty_like(color)
+            out = self.torch.empty_like(color)
         for x in (color, albedo, normal_depth, out):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+            self._image(x, like=color)
         h, w = color.shape[:2]
-        self._check(self.L.pt_denoise(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
-                                      C.c_void_p(albedo.data_ptr()), C.c_void_p(normal_depth.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
+        self._check(self.L.pt_denoise(self.h, _ref(config), _dp(color), _dp(albedo), _dp(normal_depth), w, h, _dp(out)))
         return out
 
     # ---- saving and resuming an accumulation (include/mipt.h pt_accum_save / pt_accum_load / pt_accum_inspect)
     def _accum_images(self, output, albedo, normal_depth):
-        for t in (output, albedo, normal_depth):
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4)
-        return abi.PtAccumImages(*[t.data_ptr() if t is not None else None for t in (output, albedo, normal_depth)])
+        return abi.PtAccumImages(*[_dp(self._image(t, optional=True)) for t in (output, albedo, normal_depth)])
 
     def accum_save(self, width, height, output, albedo=None, normal_depth=None, rank=0, world=1, next_frame=0):
         """The accumulation as one bytes blob: the images given (the output of trace() and, if AOVs are on, the targets of set_aov()), the
@@ -411,7 +334,7 @@ class Renderer:
         # an atlas has at most (W / 16) * (H / 16) cells: room for any layout of this size, however the probes were set.
         cells = max(1, (atlas.shape[1] // 16) * (atlas.shape[0] // 16))
         sh = np.full((cells, 9, 3), np.nan, np.float32)
-        self._check(self.L.pt_probe_project(self.h, C.c_void_p(atlas.data_ptr()), atlas.shape[1], atlas.shape[0], int(kind), _p(sh)))
+        self._check(self.L.pt_probe_project(self.h, _dp(atlas), atlas.shape[1], atlas.shape[0], int(kind), _p(sh)))
         written = ~np.isnan(sh).all(axis=(1, 2))                       # the rows the library wrote: its probe count (non-finite texels count as 0)
         return np.ascontiguousarray(sh[:int(np.nonzero(written)[0].max()) + 1 if written.any() else 0])
 
@@ -427,7 +350,7 @@ class Renderer:
             self._matte = None
             return
         for t in layers:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == self.torch.float32 and t.dim() == 3 and t.shape[2] == 4
+            self._image(t)
         idv = None if ids is None else np.ascontiguousarray(ids, np.uint32)
         cfg = abi.PtMatteConfig(1, int(kind), 2 * len(layers), 0 if idv is None else len(idv))
         for j, t in enumerate(layers[:4]):
@@ -456,7 +379,7 @@ class Renderer:
             self._check(self.L.pt_set_motion(self.h, C.byref(abi.PtMotionConfig())))
             self._motion = None
             return
-        assert motion.is_cuda and motion.is_contiguous() and motion.dtype == self.torch.float32 and motion.dim() == 3 and motion.shape[2] == 4
+        self._image(motion)
         cfg = abi.PtMotionConfig()
         cfg.enable = 1
         cfg.motion = motion.data_ptr()
@@ -477,13 +400,11 @@ class Renderer:
         if out_length is None:
             out_length = t.empty((h, w), dtype=t.float32, device=color.device)
         for x in (color, motion, prev_color, prev_motion, out_color):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+            self._image(x, like=color)
         for x in (prev_length, out_length):
-            assert x is None or (x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and tuple(x.shape) == (h, w))
-        self._check(self.L.pt_reproject(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
-                                        C.c_void_p(motion.data_ptr()), C.c_void_p(prev_color.data_ptr()), C.c_void_p(prev_motion.data_ptr()),
-                                        C.c_void_p(prev_length.data_ptr()) if prev_length is not None else None, w, h,
-                                        C.c_void_p(out_color.data_ptr()), C.c_void_p(out_length.data_ptr())))
+            self._plane(x, h, w, optional=True)
+        self._check(self.L.pt_reproject(self.h, _ref(config), _dp(color), _dp(motion), _dp(prev_color), _dp(prev_motion), _dp(prev_length), w, h,
+                                        _dp(out_color), _dp(out_length)))
         return out_color, out_length
 
     def motion_blur(self, color, motion, out=None, config=None):
@@ -491,28 +412,24 @@ class Renderer:
         `motion` target of set_motion() (or any images of that layout), both float32 CUDA tensors (H, W, 4).  out: where the result goes
         (None = a new tensor; never an input: there is no in-place mode).  config: abi.PtMotionBlurConfig (None = the defaults).
         Asynchronous on the context's stream.  Returns the output tensor."""
-        t = self.torch
         if out is None:
-            out = t.empty_like(color)
+            out = self.torch.empty_like(color)
         for x in (color, motion, out):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+            self._image(x, like=color)
         h, w = color.shape[:2]
-        self._check(self.L.pt_motion_blur(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
-                                          C.c_void_p(motion.data_ptr()), w, h, C.c_void_p(out.data_ptr())))
+        self._check(self.L.pt_motion_blur(self.h, _ref(config), _dp(color), _dp(motion), w, h, _dp(out)))
         return out
 
     def bloom(self, color, out=None, config=None):
         """The reference's dual-filter bloom over a mip pyramid (include/mipt.h pt_bloom): out = color + strength * the blurred, prefiltered
         `color`, a float32 CUDA tensor (H, W, 4).  out: where the result goes (None = a new tensor; `color` itself filters in place).
         config: abi.PtBloomConfig (None = the defaults).  Asynchronous on the context's stream.  Returns the output tensor."""
-        t = self.torch
         if out is None:
-            out = t.empty_like(color)
+            out = self.torch.empty_like(color)
         for x in (color, out):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+            self._image(x, like=color)
         h, w = color.shape[:2]
-        self._check(self.L.pt_bloom(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()), w, h,
-                                    C.c_void_p(out.data_ptr())))
+        self._check(self.L.pt_bloom(self.h, _ref(config), _dp(color), w, h, _dp(out)))
         return out
 
     def set_variance(self, variance):
@@ -525,8 +442,7 @@ class Renderer:
             self._check(self.L.pt_set_variance(self.h, C.byref(abi.PtVarianceConfig())))
             self._variance = None
             return
-        assert variance.is_cuda and variance.is_contiguous() and variance.dtype == self.torch.float32 and variance.dim() == 3 and variance.shape[2] == 4
-        self._check(self.L.pt_set_variance(self.h, C.byref(abi.PtVarianceConfig(1, 0, variance.data_ptr()))))
+        self._check(self.L.pt_set_variance(self.h, C.byref(abi.PtVarianceConfig(1, 0, _dp(self._image(variance))))))
         self._variance = variance                     # the library keeps the pointer: keep the tensor alive with the renderer
 
     def noise_estimate(self, image, variance, samples=0, tile_samples=None, threshold=0.0):
@@ -536,17 +452,14 @@ class Renderer:
         Returns (tile_mean, tile_max, summary): two (tiles_y, tiles_x) float32 arrays and an abi.PtNoiseSummary whose tiles_above counts
         the tiles whose max exceeds `threshold`.  Synchronises the stream."""
         for x in (image, variance):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == self.torch.float32 and x.dim() == 3 and x.shape == image.shape and x.shape[2] == 4
+            self._image(x, like=image)
         h, w = image.shape[:2]
-        ty, tx = (h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE
-        ts = None
-        if tile_samples is not None:
-            ts = np.ascontiguousarray(tile_samples, np.uint32)
-            assert ts.size == ty * tx
+        ty, tx = _tiles(h, w)
+        ts = _tile_samples(tile_samples, h, w)
         mean, mx = np.zeros((ty, tx), np.float32), np.zeros((ty, tx), np.float32)
         summary = abi.PtNoiseSummary()
-        self._check(self.L.pt_noise_estimate(self.h, C.c_void_p(image.data_ptr()), C.c_void_p(variance.data_ptr()), w, h, _p(ts) if ts is not None else None,
-                                             int(samples), float(threshold), _p(mean), _p(mx), C.byref(summary)))
+        self._check(self.L.pt_noise_estimate(self.h, _dp(image), _dp(variance), w, h, _p(ts), int(samples), float(threshold), _p(mean), _p(mx),
+                                             C.byref(summary)))
         return mean, mx, summary
 
     def denoise_variance(self, color, albedo, normal_depth, variance, samples=0, tile_samples=None, out=None, config=None):
@@ -556,19 +469,14 @@ class Renderer:
         pixels of a tile below 2 come out as they went in).  out: where the result goes (None = a new tensor; `color` itself filters in
         place); config: abi.PtDenoiseVarianceConfig (None = the defaults).  Asynchronous on the context's stream.  Returns the output
         tensor."""
-        t = self.torch
         if out is None:
-            out = t.empty_like(color)
+            out = self.torch.empty_like(color)
         for x in (color, albedo, normal_depth, variance, out):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == t.float32 and x.dim() == 3 and x.shape == color.shape and x.shape[2] == 4
+            self._image(x, like=color)
         h, w = color.shape[:2]
-        ts = None
-        if tile_samples is not None:
-            ts = np.ascontiguousarray(tile_samples, np.uint32)
-            assert ts.size == ((h + abi.TILE - 1) // abi.TILE) * ((w + abi.TILE - 1) // abi.TILE)
-        self._check(self.L.pt_denoise_variance(self.h, C.byref(config) if config is not None else None, C.c_void_p(color.data_ptr()),
-                                               C.c_void_p(albedo.data_ptr()), C.c_void_p(normal_depth.data_ptr()), C.c_void_p(variance.data_ptr()),
-                                               w, h, _p(ts) if ts is not None else None, int(samples), C.c_void_p(out.data_ptr())))
+        ts = _tile_samples(tile_samples, h, w)
+        self._check(self.L.pt_denoise_variance(self.h, _ref(config), _dp(color), _dp(albedo), _dp(normal_depth), _dp(variance), w, h, _p(ts),
+                                               int(samples), _dp(out)))
         return out
 
     def matte_extract(self, layers, ids, out=None):
@@ -578,10 +486,10 @@ class Renderer:
         h, w = layers[0].shape[:2]
         if out is None:
             out = t.empty((h, w), dtype=t.float32, device=layers[0].device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == t.float32 and tuple(out.shape) == (h, w)
+        self._plane(out, h, w)
         ptrs = (C.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
         idv = np.ascontiguousarray(ids, np.uint32).reshape(-1)
-        self._check(self.L.pt_matte_extract(self.h, ptrs, 2 * len(layers), w, h, _p(idv), len(idv), C.c_void_p(out.data_ptr())))
+        self._check(self.L.pt_matte_extract(self.h, ptrs, 2 * len(layers), w, h, _p(idv), len(idv), _dp(out)))
         return out
 
     @staticmethod
@@ -651,7 +559,7 @@ class Renderer:
         """local: this rank's accumulation image (H, W, 4) CUDA tensor, only read.  frame: where the root assembles the frame
         (None = in place over the other ranks' tiles of `local`).  Asynchronous on the context's stream."""
         h, w = local.shape[:2]
-        self._check(self.L.pt_exchange_frame(self.h, C.c_void_p(local.data_ptr()), C.c_void_p(frame.data_ptr()) if frame is not None else None, w, h, mode, dst))
+        self._check(self.L.pt_exchange_frame(self.h, _dp(local), _dp(frame), w, h, mode, dst))
 
     def exchange_destroy(self):
         self._check(self.L.pt_exchange_destroy(self.h))
@@ -663,13 +571,13 @@ class Renderer:
         h, w = image.shape[:2]
         n = self.tiles_packed_bytes(w, h, rank, world) // 16
         packed = self.torch.empty((max(n, 1), 4), dtype=self.torch.float32, device=image.device)
-        self._check(self.L.pt_tiles_pack(self.h, C.c_void_p(image.data_ptr()), w, h, rank, world, C.c_void_p(packed.data_ptr())))
+        self._check(self.L.pt_tiles_pack(self.h, _dp(image), w, h, rank, world, _dp(packed)))
         return packed[:n]
 
     def tiles_unpack(self, packed, image, rank, world):
         h, w = image.shape[:2]
         assert packed.numel() * 4 >= self.tiles_packed_bytes(w, h, rank, world)
-        self._check(self.L.pt_tiles_unpack(self.h, C.c_void_p(packed.data_ptr()), w, h, rank, world, C.c_void_p(image.data_ptr())))
+        self._check(self.L.pt_tiles_unpack(self.h, _dp(packed), w, h, rank, world, _dp(image)))
 
     def skin_run(self, params, bones):
         if bones is None or len(bones) == 0:
@@ -700,7 +608,7 @@ class Renderer:
     def readback(self, output):
         h, w = output.shape[:2]
         out = np.zeros((h, w, 4), np.float32)
-        self._check(self.L.pt_readback(self.h, C.c_void_p(output.data_ptr()), w, h, _p(out)))
+        self._check(self.L.pt_readback(self.h, _dp(output), w, h, _p(out)))
         return out
 
     def tonemap(self, output, config=None, want_rgba8=False):
@@ -708,5 +616,5 @@ class Renderer:
         h, w = output.shape[:2]
         rgb = np.zeros((h, w, 3), np.float32)
         q = np.zeros((h, w, 4), np.uint8) if want_rgba8 else None
-        self._check(self.L.pt_tonemap(self.h, C.byref(cfg), C.c_void_p(output.data_ptr()), w, h, _p(rgb), _p(q) if want_rgba8 else None))
+        self._check(self.L.pt_tonemap(self.h, C.byref(cfg), _dp(output), w, h, _p(rgb), _p(q)))
         return (rgb, q) if want_rgba8 else rgb

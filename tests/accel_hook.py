@@ -4,15 +4,15 @@ build (pt_debug_accel_keys) for tests/builder_ref.py."""
 import ctypes as C
 import numpy as np
 
+from tests import hooks
+
 
 def accel_read(renderer):
     """Builds or refits what is pending, then -> (info [8] uint32, nodes [wide_nodes, 64] uint8, ranges [wide_nodes, 32] uint8 or None if the
     scratch no longer holds them, tris [n_tris, 64] uint8, shade [n_tris, 128] uint8).  info: n_tris, wide_nodes, root, stack_need,
     seg_leaves, builder, fallbacks, ranges present (accel_ref.INFO_*)."""
-    f = renderer.L.pt_debug_accel_read
+    f = hooks.lib().pt_debug_accel_read
     vp = C.c_void_p
-    f.argtypes = [vp, vp, vp, vp, vp, vp]
-    f.restype = C.c_int
     info = np.zeros(8, np.uint32)
 
     def call(*arrays):
@@ -30,9 +30,7 @@ def accel_read(renderer):
 def accel_keys(renderer):
     """Builds what is pending, then -> [n_tris] uint64, the sorted Morton keys of the last full build.  Raises RuntimeError with the library's
     message after a refit, once the scratch is released, and for fewer than two triangles."""
-    f = renderer.L.pt_debug_accel_keys
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_accel_keys
     n = int(accel_read(renderer)[0][0])
     out = np.zeros(n, np.uint64)
     rc = f(renderer.h, out.ctypes.data_as(C.c_void_p), n)

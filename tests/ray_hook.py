@@ -4,6 +4,8 @@ not part of include/mipt.h."""
 import ctypes as C
 import numpy as np
 
+from tests import hooks
+
 RF_CULL_BACK, RF_CULL_FRONT, RF_FORCE_NON_OPAQUE, RF_ACCEPT_FIRST = 1, 2, 4, 8        # csrc/pt_traverse.h
 
 
@@ -16,9 +18,7 @@ def gpu_intersect(renderer, rays, ray_flags=0, mode=0):
     """rays [n, 8] float32 (origin, tmin, direction, tmax) -> [n, 8] float32 (committed, t, u, v, instance, primitive, front, transmission)."""
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
     out = np.zeros((len(rays), 8), np.float32)
-    f = renderer.L.pt_debug_intersect
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_intersect
     rc = f(renderer.h, rays.ctypes.data_as(C.c_void_p), len(rays), ray_flags, mode, out.ctypes.data_as(C.c_void_p))
     if rc != 0: raise RuntimeError("pt_debug_intersect: %d %s" % (rc, renderer.last_error() if hasattr(renderer, "last_error") else ""))
     return out
@@ -33,7 +33,7 @@ def shadow_counter(bounce):
     return CNT_SHADOW_ODD if bounce & 1 else CNT_SHADOW_EVEN
 
 
-def trace_queues_rc(L, h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce, blocks_per_shard, which):
+def trace_queues_rc(h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce, blocks_per_shard, which):
     """The raw call: (return code, closest [n_c, 8] float32, shadow [n_s] float32, counters [256, 7] uint32, stray [2] uint32)."""
     closest = np.ascontiguousarray(np.zeros((0, 8)) if closest is None else closest, np.float32).reshape(-1, 8)
     shadow = np.ascontiguousarray(np.zeros((0, 6)) if shadow is None else shadow, np.float32).reshape(-1, 6)
@@ -42,10 +42,8 @@ def trace_queues_rc(L, h, closest, closest_shard, shadow, shadow_shard, is_light
     ss = np.ascontiguousarray(np.zeros(n_s) if shadow_shard is None else np.broadcast_to(shadow_shard, (n_s,)), np.uint32)
     il = np.ascontiguousarray(np.zeros(n_s) if is_light is None else np.broadcast_to(is_light, (n_s,)), np.uint8)
     out_c = np.zeros((n_c, 8), np.float32); out_s = np.zeros(n_s, np.float32); cnt = np.zeros((256, 7), np.uint32); stray = np.zeros(2, np.uint32)
-    f = L.pt_debug_trace_queues
+    f = hooks.lib().pt_debug_trace_queues
     vp = C.c_void_p
-    f.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_float, C.c_uint32, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp]
-    f.restype = C.c_int
     ptr = lambda a: a.ctypes.data_as(vp) if a.size else None
     rc = f(h, ptr(closest), ptr(cs), n_c, ptr(shadow), ptr(ss), ptr(il), n_s, shadow_tmax, flags, bounce, blocks_per_shard, which,
            ptr(out_c), ptr(out_s), cnt.ctypes.data_as(vp), stray.ctypes.data_as(vp))
@@ -56,7 +54,7 @@ def trace_queues(renderer, closest=None, closest_shard=None, shadow=None, shadow
                  blocks_per_shard=1, which=TQ_TRACE):
     """closest [n_c, 8] float32 (origin, 0, direction, tmax) and shadow [n_s, 6] float32 (origin, direction) rays with the shard (0..255, an array
     or one number) each is queued in -> (closest results [n_c, 8] as gpu_intersect's, shadow transmissions [n_s], counter words [256, 7], stray [2])."""
-    rc, out_c, out_s, cnt, stray = trace_queues_rc(renderer.L, renderer.h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce,
+    rc, out_c, out_s, cnt, stray = trace_queues_rc(renderer.h, closest, closest_shard, shadow, shadow_shard, is_light, shadow_tmax, flags, bounce,
                                                    blocks_per_shard, which)
     if rc != 0: raise RuntimeError("pt_debug_trace_queues: %d %s" % (rc, renderer.L.pt_last_error(renderer.h).decode()))
     return out_c, out_s, cnt, stray
@@ -128,9 +126,8 @@ def oracle_math(lib, op, a, b):
     return out
 
 
-def gpu_math(lib, op, a, b):
+def gpu_math(op, a, b):
     a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32); out = np.zeros_like(a)
-    lib.pt_debug_math.restype = C.c_int
-    rc = lib.pt_debug_math(C.c_int(MATH_OPS[op]), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.c_uint32(len(a)))
+    rc = hooks.lib().pt_debug_math(C.c_int(MATH_OPS[op]), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.c_uint32(len(a)))
     assert rc == 0, rc
     return out

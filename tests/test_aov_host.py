@@ -1,9 +1,7 @@
-"""CPU-only checks of the first-hit AOVs: the pt_aov_config mirror's layout against the header, the C-ABI symbol in the header and in the
-built library, and the numpy restatement (tests/aov_ref.py) of the per-sample rules and the fold that tests/test_gpu_aov.py holds the
-GPU to."""
+"""CPU-only checks of the first-hit AOVs: the numpy restatement (tests/aov_ref.py) of the per-sample rules and the fold that
+tests/test_gpu_aov.py holds the GPU to.  (The pt_aov_config mirror and the prototype of pt_set_aov: tests/test_host_abi.py.)"""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
@@ -16,31 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV = (0.25, 0.5, 0.75)
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
-
-
-def test_aov_config_layout_matches_the_header():
-    m = re.search(r"typedef struct pt_aov_config \{(.*?)\} pt_aov_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_aov_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+\s*\*?)\s*([a-z_]+)\s*;", body)]
-    assert fields == [("int32_t", "enable"), ("void*", "albedo"), ("void*", "normal_depth")]
-    A = abi.PtAovConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert C.sizeof(A) == 24                                        # int32, 4 bytes of padding, two pointers
-    assert (A.enable.offset, A.albedo.offset, A.normal_depth.offset) == (0, 8, 16)
-    assert (A.enable.size, A.albedo.size, A.normal_depth.size) == (4, 8, 8)
-
-
 def test_the_library_exports_pt_set_aov_and_the_header_declares_it():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_set_aov\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_aov_config\s*\*\s*\w*\s*\)\s*;", text)
-    assert "pt_set_aov" in renderer.EXPORTS
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declaration against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
-    assert hasattr(L, "pt_set_aov")
-    assert L.pt_abi_version() == 2
+    assert "pt_set_aov" in renderer.EXPORTS and hasattr(L, "pt_set_aov")
     # no context: the argument check answers before anything touches a device
     cfg = abi.PtAovConfig(0, None, None)
     assert L.pt_set_aov(None, C.byref(cfg)) == -1

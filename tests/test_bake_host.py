@@ -1,51 +1,27 @@
-"""CPU-only checks of texture-space baking (include/mipt.h pt_set_bake): the pt_bake_config mirror's layout against the header, the C-ABI symbols
-in the header and in the built library, and the restatement (tests/bake_ref.py) that tests/test_gpu_bake.py holds the GPU to, on hand-worked
-cases."""
+"""CPU-only checks of texture-space baking (include/mipt.h pt_set_bake): the calls that answer without a device and the
+restatement (tests/bake_ref.py) that tests/test_gpu_bake.py holds the GPU to, on hand-worked
+cases.  (The pt_bake_config mirror and the prototypes: tests/test_host_abi.py.)"""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from gltf_renderer_amd import abi, renderer
 from tests import bake_ref as br
+from tests import hooks
 
 f32, f64 = np.float32, np.float64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def tri(inst, prim, uv, v0=(0, 0, 0), e1=(1, 0, 0), e2=(0, 1, 0), mirrored=False):
     return br.Tri(inst, prim, [np.asarray(uv, f32), None], v0, e1, e2, mirrored)
 
 
-def test_bake_config_layout_matches_the_header():
-    m = re.search(r"typedef struct pt_bake_config \{(.*?)\} pt_bake_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_bake_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+)\s+([a-z_]+)\s*;", body)]
-    assert fields == [("int32_t", "enable"), ("int32_t", "tex_coord"), ("int32_t", "instance"), ("float", "surface_offset")]
-    A = abi.PtBakeConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert C.sizeof(A) == 16
-    assert [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12]
-    assert [getattr(A, n).size for n, _ in A._fields_] == [4] * 4
-
-
 def test_the_library_exports_the_bake_symbols_and_the_header_declares_them():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_set_bake\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_bake_config\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_bake_coverage\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*int32_t\s*\*\s*\w*\s*,\s*uint32_t\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_bake_dilate\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*void\s*\*\s*\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*int\s+\w*\s*\)\s*;", text)
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declarations against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
     for name in ("pt_set_bake", "pt_bake_coverage", "pt_bake_dilate"):
         assert name in renderer.EXPORTS and hasattr(L, name), name
-    assert hasattr(L, "pt_debug_bake_rays") and "pt_debug_bake_rays" not in text       # the test hook: exported, not part of the header
-    assert L.pt_abi_version() == 2
+    assert hasattr(L, "pt_debug_bake_rays") and "pt_debug_bake_rays" not in renderer.EXPORTS      # the test hook: exported, not part of the header
 
 
 def test_calls_without_a_context_return_minus_one_and_write_nothing():
@@ -59,8 +35,7 @@ def test_calls_without_a_context_return_minus_one_and_write_nothing():
     img = np.full((2, 2, 4), 3.0, f32)
     assert L.pt_bake_dilate(None, img.ctypes.data_as(C.c_void_p), 2, 2, 1) == -1
     assert (img == 3.0).all()
-    f = L.pt_debug_bake_rays
-    f.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p]
+    f = hooks.lib().pt_debug_bake_rays
     out = np.full(8, 5.0, f32)
     q = np.zeros(3, np.uint32)
     assert f(None, None, None, q.ctypes.data_as(C.c_void_p), 1, out.ctypes.data_as(C.c_void_p)) == -1 and (out == 5.0).all()

@@ -18,22 +18,16 @@ Where a property is not exact its tolerance comes from the float64 run of the sa
     is a copy.
 """
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, renderer
+from tests import header_check as hc
 from tests import bloom_ref as bl
 
 f32, f64, u32 = np.float32, np.float64, np.uint32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(17, 33), (40, 3), (1, 1), (2, 1), (67, 35), (130, 70)]
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def bits(a):
@@ -41,29 +35,19 @@ def bits(a):
 
 
 def test_the_symbol_is_exported_and_declared():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_bloom\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_bloom_config\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*\w*\s*,"
-                     r"\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*void\s*\*\s*\w*\s*\)\s*;", text)
-    assert text.index("pt_motion_blur(") < text.index("pt_bloom(")                # after pt_motion_blur
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)                   # additive: the version stays
-    assert hasattr(renderer.load_library(), "pt_bloom") and "pt_bloom" in renderer.EXPORTS
-    assert callable(getattr(renderer.Renderer, "bloom"))
+    """Where the header declares it and that Renderer wraps it (the prototype itself: tests/test_host_abi.py)."""
+    text = hc.header_text(comments=False)
+    assert text.index("pt_motion_blur(") < text.index("pt_bloom(")           # after pt_motion_blur
+    assert "pt_bloom" in renderer.EXPORTS and callable(getattr(renderer.Renderer, "bloom"))
 
 
 def test_the_config_mirror_matches_the_header():
-    m = re.search(r"typedef struct pt_bloom_config \{(.*?)\} pt_bloom_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_bloom_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = re.findall(r"(float|int32_t)\s+([a-z_]+)\s*;", body)
-    assert fields == [("int32_t", "iterations"), ("float", "strength"), ("float", "threshold")]
+    """The defaults and what the header tells a caller (the layout itself: tests/test_host_abi.py)."""
     A = abi.PtBloomConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert [t for _, t in A._fields_] == [C.c_float if t == "float" else C.c_int32 for t, _ in fields]
-    assert C.sizeof(A) == 12 and [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8]
     d = A.defaults()
     assert (d.iterations, f32(d.strength), f32(d.threshold)) == (4, f32(0.01), f32(0.0))
     assert (d.iterations, d.strength, d.threshold) == tuple(f32(v) if isinstance(v, float) else v for v in bl.DEFAULTS.values())
-    h = header()
+    h = hc.header_text()
     for words in ("Bloom::Execute", "Bloom.cpp:57-164", "float32 where upstream's is half", "fixed-point", "parity with real D3D output is unpinned",
                   "neither spreads nor changes", "after the exchange", "REPLACES"):
         assert words in h, words                                  # what a caller has to know is stated where a caller reads it

@@ -3,21 +3,15 @@ device, and the restatement (tests/blur_ref.py) that tests/test_gpu_blur.py hold
 input's bits, the tile maximum's tie rule and the neighbour maximum's order, how far a streak reaches, and what a bright moving block does
 to the ground behind it."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, renderer
+from tests import header_check as hc
 from tests import blur_ref as br
 
 f32, u32 = np.float32, np.uint32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def bits(a):
@@ -25,29 +19,19 @@ def bits(a):
 
 
 def test_the_symbol_is_exported_and_declared():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_motion_blur\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_motion_blur_config\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*\w*\s*,"
-                     r"\s*const\s+void\s*\*\s*\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*void\s*\*\s*\w*\s*\)\s*;", text)
+    """Where the header declares it and that Renderer wraps it (the prototype itself: tests/test_host_abi.py)."""
+    text = hc.header_text(comments=False)
     assert text.index("pt_reproject(") < text.index("pt_motion_blur(")           # after pt_reproject
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)                   # additive: the version stays
-    assert hasattr(renderer.load_library(), "pt_motion_blur") and "pt_motion_blur" in renderer.EXPORTS
-    assert callable(getattr(renderer.Renderer, "motion_blur"))
+    assert "pt_motion_blur" in renderer.EXPORTS and callable(getattr(renderer.Renderer, "motion_blur"))
 
 
 def test_the_config_mirror_matches_the_header():
-    m = re.search(r"typedef struct pt_motion_blur_config \{(.*?)\} pt_motion_blur_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_motion_blur_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = re.findall(r"(float|int32_t)\s+([a-z_]+)\s*;", body)
-    assert fields == [("float", "shutter"), ("float", "max_radius"), ("int32_t", "taps"), ("int32_t", "jitter"), ("float", "depth_softness")]
+    """The defaults and what the header tells a caller (the layout itself: tests/test_host_abi.py)."""
     A = abi.PtMotionBlurConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert [t for _, t in A._fields_] == [C.c_float if t == "float" else C.c_int32 for t, _ in fields]
-    assert C.sizeof(A) == 20 and [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12, 16]
     d = A.defaults()
     assert (f32(d.shutter), f32(d.max_radius), d.taps, d.jitter, f32(d.depth_softness)) == (f32(0.5), f32(32.0), 16, 1, f32(0.05))
     assert (d.shutter, d.max_radius, d.taps, d.jitter, f32(d.depth_softness)) == tuple(f32(v) if isinstance(v, float) else v for v in br.DEFAULTS.values())
-    h = header()
+    h = hc.header_text()
     for words in ("not ray-traced motion blur", "does not blur", "centred on the frame", "linear over the frame", "3.97", "12 %"):
         assert words in h, words                                  # the limits are stated where a caller reads them
 

@@ -1,5 +1,5 @@
-"""CPU-only checks of the accumulation checkpoint (include/mipt.h pt_accum_save / pt_accum_load / pt_accum_inspect): the ctypes mirrors
-against the header, the exports, pt_accum_inspect on blobs written by the independent writer tests/checkpoint_ref.py -- every field read
+"""CPU-only checks of the accumulation checkpoint (include/mipt.h pt_accum_save / pt_accum_load / pt_accum_inspect): the section flags
+against the header, pt_accum_inspect on blobs written by the independent writer tests/checkpoint_ref.py -- every field read
 back, every refusal the header promises, one malformation a case -- and a sanitizer-instrumented mutation fuzzer of the validator
 (tests/fuzz/accum_fuzz.cpp), a stand-alone program built from accum_state.cpp alone."""
 import ctypes as C
@@ -15,14 +15,11 @@ import pytest
 
 from gltf_renderer_amd import abi, renderer
 from tests import checkpoint_ref as cr
+from tests import header_check as hc
 
 f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = -1
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def inspect(blob):
@@ -61,34 +58,12 @@ def patched(blob, offset, fmt, value, reseal=True):
 
 
 def test_mirrors_match_the_header_and_the_library_exports_the_three_calls():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"typedef struct pt_accum_images \{(.*?)\} pt_accum_images;", text, re.S)
-    assert m and re.findall(r"void\s*\*\s*([a-z_]+)\s*;", m.group(1)) == ["output", "albedo", "normal_depth"]
-    I = abi.PtAccumImages
-    assert [n for n, _ in I._fields_] == ["output", "albedo", "normal_depth"]
-    assert C.sizeof(I) == 24 and [getattr(I, n).offset for n, _ in I._fields_] == [0, 8, 16]
-    m = re.search(r"typedef struct pt_accum_info \{(.*?)\} pt_accum_info;", text, re.S)
-    assert m
-    names = []
-    for typ, decl in re.findall(r"(uint32_t|int32_t|uint64_t|pt_adaptive_config)\s+([a-z_, ]+);", m.group(1)):
-        names += [(typ, n.strip()) for n in decl.split(",")]
-    assert names == [("uint32_t", "sections"), ("uint32_t", "width"), ("uint32_t", "height"), ("uint32_t", "tile_rank"),
-                     ("uint32_t", "tile_rank_count"), ("int32_t", "accumulated_frames"), ("uint32_t", "tiles"),
-                     ("uint64_t", "next_frame"), ("uint64_t", "total_bytes"), ("pt_adaptive_config", "adaptive")]
-    A = abi.PtAccumInfo
-    assert [n for n, _ in A._fields_] == [n for _, n in names]
-    assert C.sizeof(A) == 64
-    assert [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12, 16, 20, 24, 32, 40, 48]
-    assert [getattr(A, n).size for n, _ in A._fields_] == [4, 4, 4, 4, 4, 4, 4, 8, 8, 16]
+    """The section flags and the exports (the pt_accum_images / pt_accum_info mirrors and the three prototypes: tests/test_host_abi.py)."""
     assert (abi.ACCUM_OUTPUT, abi.ACCUM_ALBEDO, abi.ACCUM_NORMAL_DEPTH, abi.ACCUM_ADAPTIVE) == (1, 2, 4, 8)
-    assert re.search(r"PT_ACCUM_OUTPUT = 1 << 0, PT_ACCUM_ALBEDO = 1 << 1, PT_ACCUM_NORMAL_DEPTH = 1 << 2, PT_ACCUM_ADAPTIVE = 1 << 3", text)
-    for name in ("pt_accum_save", "pt_accum_load", "pt_accum_inspect"):
-        assert re.search(r"\bint\s+%s\s*\(" % name, text), name
-        assert name in renderer.EXPORTS
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    assert "PT_ACCUM_OUTPUT = 1 << 0, PT_ACCUM_ALBEDO = 1 << 1, PT_ACCUM_NORMAL_DEPTH = 1 << 2, PT_ACCUM_ADAPTIVE = 1 << 3" in hc.header_text(comments=False)
     L = renderer.load_library()
-    assert all(hasattr(L, n) for n in ("pt_accum_save", "pt_accum_load", "pt_accum_inspect"))
-    assert L.pt_abi_version() == 2
+    for name in ("pt_accum_save", "pt_accum_load", "pt_accum_inspect"):
+        assert name in renderer.EXPORTS and hasattr(L, name), name
     # no context, no blob: answered before anything touches a device
     n = C.c_size_t()
     assert L.pt_accum_save(None, None, 4, 4, 0, 1, 0, None, 0, C.byref(n)) == INVALID
@@ -98,7 +73,7 @@ def test_mirrors_match_the_header_and_the_library_exports_the_three_calls():
 
 def test_the_header_comment_gives_the_offsets_the_writer_uses():
     """The field table of include/mipt.h, read as (offset, type) pairs, is the layout tests/checkpoint_ref.py packs."""
-    m = re.search(r"Header, 160 bytes:(.*?)Payload, from offset 160", header(), re.S)
+    m = re.search(r"Header, 160 bytes:(.*?)Payload, from offset 160", hc.header_text(), re.S)
     assert m
     rows = re.findall(r"^\s*\*\s+(?:offset\s+)?(\d+)\s+(char\[8\]|u32\[4\]|f32\[16\]|u32|u64|i32|pt_adaptive_config)", m.group(1), re.M)
     size = {"char[8]": 8, "u32": 4, "u64": 8, "i32": 4, "f32[16]": 64, "pt_adaptive_config": 16, "u32[4]": 16}

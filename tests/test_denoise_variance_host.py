@@ -1,9 +1,8 @@
-"""CPU-only checks of pt_denoise_variance: the pt_denoise_variance_config mirror's layout against the header, the C-ABI symbol in the header
-and in the built library, and the numpy restatement (tests/denoise_variance_ref.py) that tests/test_gpu_denoise_variance.py holds the GPU
+"""CPU-only checks of pt_denoise_variance (its config mirror and prototype: tests/test_host_abi.py): the size and the defaults the header
+states, the call without a context, and the numpy restatement (tests/denoise_variance_ref.py) that tests/test_gpu_denoise_variance.py holds the GPU
 to -- its exact properties, what it does to the noise of the synthetic scene where pt_denoise's restatement is the yardstick, and its own
 float32 conditioning."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -12,15 +11,11 @@ import pytest
 from gltf_renderer_amd import abi, renderer
 from tests import denoise_ref as dr
 from tests import denoise_variance_ref as dv
+from tests import header_check as hc
 
 f32, f64 = np.float32, np.float64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 3                           # the scene's random stream; the restatement alone meets the bounds below with it
 W, H = 72, 40
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def bits(a):
@@ -32,18 +27,11 @@ def same(a, b):
 
 
 def test_config_layout_and_defaults_match_the_header():
-    m = re.search(r"typedef struct pt_denoise_variance_config \{(.*?)\} pt_denoise_variance_config;\s*/\* (\d+) bytes \*/", header(), re.S)
-    assert m, "include/mipt.h lacks pt_denoise_variance_config"
-    defaults = re.findall(r"default (\S+?)[ .]*(?:\(.*?\))? \*/", m.group(1))
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+\s*\*?)\s+([a-z_0-9]+)\s*;", body)]
-    assert fields == [("int32_t", "iterations"), ("int32_t", "demodulate"), ("int32_t", "normal_power_log2"),
-                      ("float", "sigma_depth"), ("float", "sigma_variance")]
+    """The size and the defaults the header's comments state (the layout itself: tests/test_host_abi.py)."""
+    body, _ = hc.typedef_struct("pt_denoise_variance_config")
+    defaults = re.findall(r"default (\S+?)[ .]*(?:\(.*?\))? \*/", body)
     D = abi.PtDenoiseVarianceConfig
-    assert [n for n, _ in D._fields_] == [n for _, n in fields]
-    assert int(m.group(2)) == C.sizeof(D) == 20
-    assert [getattr(D, n).offset for n, _ in D._fields_] == [0, 4, 8, 12, 16]
-    assert [getattr(D, n).size for n, _ in D._fields_] == [4] * 5
+    assert hc.stated_bytes("pt_denoise_variance_config") == C.sizeof(D) == 20
     d = D.default()
     assert (d.iterations, d.demodulate, d.normal_power_log2) == (5, 1, 7)
     assert (d.sigma_depth, d.sigma_variance) == (float(f32(0.02)), 4.0)
@@ -53,16 +41,9 @@ def test_config_layout_and_defaults_match_the_header():
 
 
 def test_the_library_exports_pt_denoise_variance_and_the_header_declares_it():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_denoise_variance\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_denoise_variance_config\s*\*\s*\w*\s*,"
-                     r"\s*const\s+void\s*\*\s*color\s*,\s*const\s+void\s*\*\s*albedo\s*,\s*const\s+void\s*\*\s*normal_depth\s*,"
-                     r"\s*const\s+void\s*\*\s*variance\s*,\s*uint32_t\s+width\s*,\s*uint32_t\s+height\s*,"
-                     r"\s*const\s+uint32_t\s*\*\s*tile_samples\s*,\s*uint32_t\s+samples\s*,\s*void\s*\*\s*out\s*\)\s*;", text)
-    assert "pt_denoise_variance" in renderer.EXPORTS
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declaration against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
-    assert hasattr(L, "pt_denoise_variance")
-    assert L.pt_abi_version() == 2
+    assert "pt_denoise_variance" in renderer.EXPORTS and hasattr(L, "pt_denoise_variance")
     # no context: the argument check answers before anything touches a device
     cfg = abi.PtDenoiseVarianceConfig.default()
     assert L.pt_denoise_variance(None, C.byref(cfg), None, None, None, None, 4, 4, None, 8, None) == -1

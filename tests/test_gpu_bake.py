@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, meshgen, scenes
+from tests import hooks
 from gltf_renderer_amd.renderer import MiptError
 from tests import bake_ref as br
 from tests import lens_ref as lr
@@ -153,9 +154,7 @@ def hook_rays(c, st, queries):
     """pt_debug_bake_rays: queries [n, 3] uint32 {px, py, seed} -> [n, 8] float32 (origin, tmin, direction, tmax)."""
     q = np.ascontiguousarray(queries, np.uint32).reshape(-1, 3)
     out = np.zeros((len(q), 8), f32)
-    f = c.r.L.pt_debug_bake_rays
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_bake_rays
     params = c.params(0)
     rc = f(c.r.h, C.byref(st), C.byref(params), q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p))
     assert rc == 0, (rc, c.r.L.pt_last_error(c.r.h))

@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi
+from tests import hooks
 
 import bsdf_ref as B
 
@@ -64,22 +65,11 @@ def gpu(R, oracle_lib):
     r.close(); o.close()
 
 
-def _fn(L, name, argtypes):
-    f = getattr(L, name)
-    f.restype = C.c_int
-    f.argtypes = argtypes
-    return f
-
-
-BSDF_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
-LIGHT_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-
-
 def gpu_bsdf(r, unit, op, flags, q):
     q = np.ascontiguousarray(q, f32)
     assert q.ndim == 2 and q.shape[1] == 48
     out = np.full((len(q), 16), 7.0, f32)                                  # the hook writes all 16
-    rc = _fn(r.L, "pt_debug_bsdf_query", BSDF_ARGS)(r.h, unit, op, flags, q.ctypes.data, len(q), out.ctypes.data)
+    rc = hooks.lib().pt_debug_bsdf_query(r.h, unit, op, flags, q.ctypes.data, len(q), out.ctypes.data)
     assert rc == 0, rc
     return out
 
@@ -87,7 +77,7 @@ def gpu_bsdf(r, unit, op, flags, q):
 def gpu_lights(r, unit, small, n_lights, index, p):
     index = np.ascontiguousarray(index, u32); p = np.ascontiguousarray(p, f32)
     out = np.full((len(index), 8), 7.0, f32)
-    rc = _fn(r.L, "pt_debug_light_query", LIGHT_ARGS)(r.h, unit, small, n_lights, index.ctypes.data, p.ctypes.data, len(index), out.ctypes.data)
+    rc = hooks.lib().pt_debug_light_query(r.h, unit, small, n_lights, index.ctypes.data, p.ctypes.data, len(index), out.ctypes.data)
     assert rc == 0, rc
     return out
 
@@ -704,7 +694,7 @@ def test_bsdf_and_light_hooks_reject_bad_arguments(gpu):
     r, o = gpu
     INVALID = -1                                                            # PT_ERR_INVALID_ARGUMENT
     q = np.zeros((70, 48), f32); out = np.full((70, 16), 7.0, f32)
-    fb = _fn(r.L, "pt_debug_bsdf_query", BSDF_ARGS)
+    fb = hooks.lib().pt_debug_bsdf_query
     for unit, op in [(2, 0), (-1, 0), (0, 2), (1, -1)]:
         assert fb(r.h, unit, op, MIS, q.ctypes.data, 70, out.ctypes.data) == INVALID, (unit, op)
     assert fb(r.h, 0, 0, MIS, None, 70, out.ctypes.data) == INVALID
@@ -714,7 +704,7 @@ def test_bsdf_and_light_hooks_reject_bad_arguments(gpu):
     assert (out == 7.0).all()                                               # nothing was launched
     table = crafted_lights(np.random.default_rng(1))[:33]
     r.set_lights(list(as_pt_lights(table)))
-    fl = _fn(r.L, "pt_debug_light_query", LIGHT_ARGS)
+    fl = hooks.lib().pt_debug_light_query
     idx = np.zeros(70, u32); p = np.ones((70, 3), f32); lo = np.full((70, 8), 7.0, f32)
     call = lambda unit, small, n_lights, i=idx, pp=p, oo=lo, h=r.h: fl(h, unit, small, n_lights, None if i is None else i.ctypes.data, None if pp is None else pp.ctypes.data, 70,
                                                                       None if oo is None else oo.ctypes.data)

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import scenes
+from tests import hooks
 
 f32 = np.float32
 u32 = np.uint32
@@ -42,19 +43,12 @@ def R():
     return Renderer
 
 
-def _fn(L, name, argtypes):
-    f = getattr(L, name)
-    f.restype = C.c_int
-    f.argtypes = argtypes
-    return f
-
-
 def gpu_query(r, env, unit, op, inp):
     inp = np.asarray(inp, f32)
     q = np.zeros((len(inp), 8), f32)
     q[:, :inp.shape[1]] = inp
     out = np.zeros((len(q), 16), f32)
-    f = _fn(r.L, "pt_debug_env_query", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p])
+    f = hooks.lib().pt_debug_env_query
     rc = f(r.h, env, unit, op, q.ctypes.data, len(q), out.ctypes.data)
     assert rc == 0, rc
     return out
@@ -63,7 +57,7 @@ def gpu_query(r, env, unit, op, inp):
 def gpu_create_raw(r, n, cube, pyramid):
     cube = np.ascontiguousarray(cube, np.uint16); pyramid = np.ascontiguousarray(pyramid, f32)
     out = C.c_int()
-    f = _fn(r.L, "pt_debug_env_create_raw", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    f = hooks.lib().pt_debug_env_create_raw
     rc = f(r.h, n, cube.ctypes.data, pyramid.ctypes.data, C.addressof(out))
     assert rc == 0, rc
     return out.value
@@ -71,7 +65,7 @@ def gpu_create_raw(r, n, cube, pyramid):
 
 def gpu_read_blocked(r, env):
     out = np.zeros(16 + 256 + 4096 + 65536 + IMP * IMP, f32)
-    f = _fn(r.L, "pt_debug_env_read_blocked", [C.c_void_p, C.c_int, C.c_void_p])
+    f = hooks.lib().pt_debug_env_read_blocked
     rc = f(r.h, env, out.ctypes.data)
     assert rc == 0, rc
     return out
@@ -557,14 +551,14 @@ def test_env_query_hooks_reject_bad_arguments(R):
     eg = r.env_create(np.ones((4, 8, 3), f32))
     q = np.zeros((300, 8), f32)
     out = np.zeros((300, 16), f32)
-    f = _fn(r.L, "pt_debug_env_query", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p])
+    f = hooks.lib().pt_debug_env_query
     for env, unit, op in [(eg + 1, 0, 0), (-1, 1, 1), (eg, 2, 0), (eg, -1, 0), (eg, 0, 4), (eg, 1, -1)]:
         assert f(r.h, env, unit, op, q.ctypes.data, 300, out.ctypes.data) != 0, (env, unit, op)
     assert f(r.h, eg, 0, 0, None, 300, out.ctypes.data) != 0
     assert f(r.h, eg, 0, 0, q.ctypes.data, 0, out.ctypes.data) == 0
-    fb = _fn(r.L, "pt_debug_env_read_blocked", [C.c_void_p, C.c_int, C.c_void_p])
+    fb = hooks.lib().pt_debug_env_read_blocked
     assert fb(r.h, eg + 7, out.ctypes.data) != 0
-    fr = _fn(r.L, "pt_debug_env_create_raw", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    fr = hooks.lib().pt_debug_env_create_raw
     h = C.c_int()
     assert fr(r.h, 0, q.ctypes.data, q.ctypes.data, C.addressof(h)) != 0
     r.close()

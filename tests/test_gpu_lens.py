@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, meshgen, scenes
+from tests import hooks
 from tests import adaptive_ref as ar
 from tests import lens_ref as lr
 from tests import ray_hook
@@ -99,9 +100,7 @@ def hook_rays(r, st, params, queries):
     """pt_debug_camera_rays: queries [n, 3] uint32 {px, py, seed} -> [n, 8] float32 (origin, tmin, direction, tmax)."""
     q = np.ascontiguousarray(queries, np.uint32).reshape(-1, 3)
     out = np.zeros((len(q), 8), f32)
-    f = r.L.pt_debug_camera_rays
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_camera_rays
     rc = f(r.h, C.byref(st), C.byref(params), q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p))
     assert rc == 0, (rc, r.L.pt_last_error(r.h))
     return out

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, meshgen, scenes
+from tests import hooks
 from gltf_renderer_amd.renderer import MiptError
 from tests import lens_ref as lr
 from tests import probe_ref as pr
@@ -99,9 +100,7 @@ def hook_rays(c, st, queries):
     """pt_debug_probe_rays: queries [n, 3] uint32 {px, py, seed} -> [n, 8] float32 (origin, tmin, direction, tmax)."""
     q = np.ascontiguousarray(queries, np.uint32).reshape(-1, 3)
     out = np.zeros((len(q), 8), f32)
-    f = c.r.L.pt_debug_probe_rays
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_probe_rays
     params = c.params(0)
     rc = f(c.r.h, C.byref(st), C.byref(params), q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p))
     assert rc == 0, (rc, c.r.L.pt_last_error(c.r.h))
@@ -266,9 +265,7 @@ def test_no_geometry_in_reach_gives_the_environments_miss_answer_bit_for_bit():
         qin[:, 0:3] = rays[:, 4:7]
         qin[:, 4] = st.environment_intensity
         res = np.zeros((len(rays), 16), f32)
-        fq = c.r.L.pt_debug_env_query
-        fq.restype = C.c_int
-        fq.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        fq = hooks.lib().pt_debug_env_query
         assert fq(c.r.h, env, 0, 3, qin.ctypes.data, len(qin), res.ctypes.data) == 0
         want = np.concatenate([res[:, 0:3], np.ones((len(res), 1), f32)], axis=1).reshape(H5, W5, 4)
         assert same(out[present], want[present]), f

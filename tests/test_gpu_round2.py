@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, meshgen, scenes
+from tests import hooks
 
 pytestmark = pytest.mark.gpu
 
@@ -719,7 +720,7 @@ def test_interleaved_texel_footprint_is_bit_identical_to_the_general_path(R, ora
         r = R()
         if mode == "megakernel": r.set_kernel_mode(1)
         h = s.upload(r)
-        n = (r.L.pt_debug_interleaved_materials(r.h), r.L.pt_debug_interleaved_emissive(r.h))
+        n = (hooks.lib().pt_debug_interleaved_materials(r.h), hooks.lib().pt_debug_interleaved_emissive(r.h))
         out = r.create_output(s.width, s.height)
         for f in range(frames):
             r.trace(s.settings, s.execute_params(frame=f), out)
@@ -744,12 +745,12 @@ def test_interleaved_copies_follow_the_material_table(R):
     s, n, _ = interleave_scene(64)
     r = R()
     h = s.upload(r)
-    assert r.L.pt_debug_interleaved_materials(r.h) == n
+    assert hooks.lib().pt_debug_interleaved_materials(r.h) == n
     out = r.create_output(s.width, s.height)
     r.trace(s.settings, s.execute_params(frame=0), out)
     first = r.readback(out).copy()
     r.set_materials([abi.PtMaterial.default() for _ in s.materials])          # no texture named any more: every copy goes
-    assert r.L.pt_debug_interleaved_materials(r.h) == 0
+    assert hooks.lib().pt_debug_interleaved_materials(r.h) == 0
     r.trace(s.settings, s.execute_params(frame=0), out)
     r.close()
     r = R()

@@ -521,10 +521,9 @@ def test_hand_written_radix_sort_is_numpys_stable_sort(R, n):
     boundaries, a partial last tile, heavy duplicates (stability decides the order of the values), keys that differ only in their top bits
     and only in their bottom bits, and the all-equal case."""
     import ctypes as C
-    from gltf_renderer_amd.renderer import load_library
+    from tests import hooks
     r = R()                                                           # a context makes the device current; the hook itself needs none
-    L = load_library()
-    L.pt_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L = hooks.lib()
     rng = np.random.default_rng(n)
     cases = {"random 63-bit": rng.integers(0, 1 << 63, n, dtype=np.uint64),
              "few distinct (stability)": rng.integers(0, 7, n, dtype=np.uint64) << np.uint64(40),
@@ -545,10 +544,9 @@ def test_hand_written_radix_sort_is_numpys_stable_sort(R, n):
 def test_hand_written_exclusive_scan_is_numpys_cumsum(R, n):
     """u32 exclusive scan (tiles of 2048, tile sums scanned recursively: one, two and three levels)."""
     import ctypes as C
-    from gltf_renderer_amd.renderer import load_library
+    from tests import hooks
     r = R()
-    L = load_library()
-    L.pt_debug_exclusive_scan.argtypes = [C.c_void_p, C.c_size_t]
+    L = hooks.lib()
     rng = np.random.default_rng(n)
     for data in (rng.integers(0, 2, n, dtype=np.uint32), rng.integers(0, 400, n, dtype=np.uint32), np.ones(n, np.uint32)):
         d = data.copy()
@@ -606,7 +604,7 @@ def test_defined_math_is_bit_identical_to_the_oracles(R, op):
     from ray_hook import math_inputs, oracle_math, gpu_math
     r = R()
     a, b = math_inputs()[op]
-    g = gpu_math(r.L, op, a, b); c = oracle_math(pyoracle.lib(), op, a, b)
+    g = gpu_math(op, a, b); c = oracle_math(pyoracle.lib(), op, a, b)
     same = (g.view(np.uint32) == c.view(np.uint32)) | (np.isnan(g) & np.isnan(c))
     bad = np.nonzero(~same)[0]
     for k in bad[:8]: print("   %s(%r, %r): gpu %r oracle %r" % (op, a[k], b[k], g[k], c[k]))
@@ -625,7 +623,7 @@ def test_shortened_division_is_the_ieee_quotient(R):
     with np.errstate(all="ignore"):
         q = a.astype(np.float64) / b.astype(np.float64)
     normal = np.isfinite(q) & (np.abs(q) > 1.2e-38) & (np.abs(q) < 3.4e38) & (np.abs(b) > 1.2e-38) & (np.abs(b) < 8.5e37) & (np.abs(a) > 1.2e-38) & np.isfinite(a) & np.isfinite(b)
-    g = gpu_math(r.L, "div", a, b); c = oracle_math(pyoracle.lib(), "div", a, b)
+    g = gpu_math("div", a, b); c = oracle_math(pyoracle.lib(), "div", a, b)
     assert normal.sum() > 700_000
     bad = np.nonzero(normal & (g.view(np.uint32) != c.view(np.uint32)))[0]
     for k in bad[:16]: print("   %r / %r: gpu %r oracle %r" % (a[k], b[k], g[k], c[k]))

@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, meshgen, scenes
+from tests import hooks
 
 import surface_ref
 from accel_hook import accel_read
@@ -453,9 +454,7 @@ def non_finite_share(e):
 
 # ---------------------------------------------------------------- the GPU side
 def hook(r, unit, small, flags, records):
-    f = r.L.pt_debug_surface_query
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    f = hooks.lib().pt_debug_surface_query
     rec = np.ascontiguousarray(records, f32)
     out = np.zeros((len(rec), OUT), f32)
     rc = f(r.h, unit, small, flags, rec.ctypes.data_as(C.c_void_p), len(rec), out.ctypes.data_as(C.c_void_p))
@@ -541,7 +540,7 @@ def test_materials_under_the_four_flag_sets(material_gpu, oracle_lib):
     general footprints; normal adaptation and geometric normals on and off, under random and grazing views."""
     g = material_gpu
     L = g.r.L
-    assert (L.pt_debug_interleaved_materials(g.r.h), L.pt_debug_interleaved_emissive(g.r.h)) == TRIO_EXPECTED
+    assert (hooks.lib().pt_debug_interleaved_materials(g.r.h), hooks.lib().pt_debug_interleaved_emissive(g.r.h)) == TRIO_EXPECTED
     g.check_a_b(oracle_lib)
 
 
@@ -642,7 +641,7 @@ def test_table_limits(R, oracle_lib, size):
         g.check_a_b(oracle_lib)
         if not g.small_ok:                                                                # the host refuses what the LDS copies cannot hold
             rec = g.case.q.take(np.arange(1)).records(g.packet); out = np.zeros((1, OUT), f32)
-            assert g.r.L.pt_debug_surface_query(g.r.h, 0, 1, 0, rec.ctypes.data_as(C.c_void_p), 1, out.ctypes.data_as(C.c_void_p)) == -1
+            assert hooks.lib().pt_debug_surface_query(g.r.h, 0, 1, 0, rec.ctypes.data_as(C.c_void_p), 1, out.ctypes.data_as(C.c_void_p)) == -1
     finally:
         g.close()
 
@@ -650,9 +649,7 @@ def test_table_limits(R, oracle_lib, size):
 def hook_camera_rays(r, st, params, queries):
     q = np.ascontiguousarray(queries, u32).reshape(-1, 3)
     out = np.zeros((len(q), 8), f32)
-    f = r.L.pt_debug_camera_rays
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    f.restype = C.c_int
+    f = hooks.lib().pt_debug_camera_rays
     assert f(r.h, C.byref(st), C.byref(params), q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p)) == 0
     return out
 
@@ -705,9 +702,7 @@ def test_surface_hook_rejects_bad_arguments(R):
     """Argument errors come back as error codes; no query reaches the device."""
     g = Gpu(R, table_case(129, 97))
     try:
-        f = g.r.L.pt_debug_surface_query
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        f = hooks.lib().pt_debug_surface_query
         rec = g.case.q.take(np.arange(2)).records(g.packet)
         out = np.zeros((2, OUT), f32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)

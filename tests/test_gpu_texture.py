@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi
+from tests import hooks
 
 from texture_ref import sample_level0, transform_rows
 
@@ -63,9 +64,7 @@ def R():
 
 
 def _hook(L):
-    f = L.pt_debug_sample_texture
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    f = hooks.lib().pt_debug_sample_texture
     return f
 
 
@@ -215,7 +214,7 @@ def run_table(bench, table, mat_slot, tc, monkeypatch, expect_counts=None):
         if env is None: monkeypatch.delenv("MIPT_TEXTURE_INTERLEAVE", raising=False)
         else: monkeypatch.setenv("MIPT_TEXTURE_INTERLEAVE", env)
         r.set_materials(bench.materials(table, (bench.gpu_tex, bench.gpu_smp)))
-        counts = (r.L.pt_debug_interleaved_materials(r.h), r.L.pt_debug_interleaved_emissive(r.h))
+        counts = (hooks.lib().pt_debug_interleaved_materials(r.h), hooks.lib().pt_debug_interleaved_emissive(r.h))
         if expect_counts is not None:
             assert counts == (expect_counts if env is None else (0, 0)), (env, counts, expect_counts)
         for unit in (0, 1):

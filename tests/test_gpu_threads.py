@@ -525,10 +525,8 @@ def hooks_script(env, rounds=3):
     """pt_debug_math, pt_debug_sort_pairs and pt_debug_exclusive_scan: test hooks without a context, on the null stream, ending in a
     device synchronise."""
     import ray_hook
-    from gltf_renderer_amd.renderer import load_library
-    L = load_library()
-    L.pt_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.pt_debug_exclusive_scan.argtypes = [C.c_void_p, C.c_size_t]
+    from tests import hooks
+    L = hooks.lib()
     inputs = ray_hook.math_inputs(seed=3, n=2000)
     n = 2049                       # one full tile of 2048 and a second block
     rng = np.random.default_rng(n)
@@ -536,7 +534,7 @@ def hooks_script(env, rounds=3):
     for i in range(rounds):
         for op, (a, b) in inputs.items():
             check(env)
-            res["%s@%d" % (op, i)] = ray_hook.gpu_math(L, op, a, b)
+            res["%s@%d" % (op, i)] = ray_hook.gpu_math(op, a, b)
         keys, vals = rng.integers(0, 1 << 63, n, dtype=np.uint64), np.arange(n, dtype=np.uint32)
         check(env)
         assert L.pt_debug_sort_pairs(keys.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), n) == 0

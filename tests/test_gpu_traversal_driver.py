@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, scenes
+from tests import hooks
 import lens_ref as lr
 import traversal_ref as tr
 import traversal_scenes as tscenes
@@ -361,9 +362,7 @@ def _params_hook(r, name, st, params, rows, width):
     """pt_debug_camera_rays (rows [n, 3] uint32 {px, py, seed}) or pt_debug_motion (rows [n, 8] float32 rays): -> [n, 8] float32."""
     rows = np.ascontiguousarray(rows).reshape(-1, width)
     out = np.zeros((len(rows), 8), np.float32)
-    f = getattr(r.L, name)
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    f.restype = C.c_int
+    f = getattr(hooks.lib(), name)
     rc = f(r.h, C.byref(st), C.byref(params), rows.ctypes.data_as(C.c_void_p), len(rows), out.ctypes.data_as(C.c_void_p))
     assert rc == 0, (name, rc, r.L.pt_last_error(r.h))
     return out

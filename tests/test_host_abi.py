@@ -10,34 +10,66 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, camera, scenes
+from tests import header_check as hc
+from tests import hooks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "mipt.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pt_[a-z_0-9]+)\s*\(", text)))
 
 
 def test_library_builds_loads_and_exports_every_declared_symbol():
     import __graft_entry__
     __graft_entry__.build()
-    from gltf_renderer_amd import renderer
+    from gltf_renderer_amd import gltf, renderer
     L = renderer.load_library()
-    syms = declared_symbols()
+    syms = hc.declared_functions("mipt.h", r"pt_[a-z_0-9]+")
     assert len(syms) >= 20
     for s in syms:
         assert hasattr(L, s), "libmipt.so does not export %s" % s
-    assert sorted(renderer.EXPORTS) == syms
-    assert L.pt_abi_version() == 2
+    assert sorted(renderer.EXPORTS) == sorted(abi.PROTOTYPES) == syms
+    assert L.pt_abi_version() == 2 and re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", hc.header_text(comments=False))    # the extensions are additive
     # the scene side (include/mipt_scene.h): loader, animation, image readers
-    from gltf_renderer_amd import gltf
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mipt_scene.h")).read(), flags=re.S)
-    scene_syms = sorted(set(re.findall(r"\b((?:gs|img)_[a-z_0-9]+)\s*\(", text)))
-    assert len(scene_syms) >= 25 and sorted(gltf.SCENE_EXPORTS) == scene_syms
+    scene_syms = hc.declared_functions("mipt_scene.h", r"(?:gs|img)_[a-z_0-9]+")
+    assert len(scene_syms) >= 25 and sorted(gltf.SCENE_EXPORTS) == sorted(gltf.SCENE_PROTOTYPES) == scene_syms
     for s in scene_syms:
         assert hasattr(L, s), "libmipt.so does not export %s" % s
+    # the test hooks (csrc/mipt_debug.h, not part of the ABI): what the header declares = what tests/hooks.py binds = every extern "C"
+    # pt_debug_* the sources define, but for the two of the diagnostic builds (pt_wavefront.hip under PT_TIMING / PT_UTIL_PROBE)
+    hook_syms = hc.declared_functions("mipt_debug.h", r"pt_debug_[a-z_0-9]+")
+    defined = set()
+    for f in sorted(os.listdir(hc.CSRC)):
+        if f.endswith(".hip"):
+            defined |= set(re.findall(r'extern\s+"C"\s+[\w\s\*]*?\b(pt_debug_[a-z_0-9]+)\s*\(', open(os.path.join(hc.CSRC, f)).read()))
+    assert {"pt_debug_read_timing", "pt_debug_read_util"} <= defined
+    assert sorted(defined - {"pt_debug_read_timing", "pt_debug_read_util"}) == hook_syms == sorted(hooks.HOOKS) and len(hook_syms) >= 20
+    assert not set(hook_syms) & set(syms)
+    HL = hooks.lib()
+    for s in hook_syms:
+        assert hasattr(HL, s), "libmipt.so does not export %s" % s
+
+
+def test_every_structure_mirror_is_its_typedef_to_the_compiler(tmp_path):
+    """Every ctypes.Structure of abi.py and gltf.py against include/mipt.h and mipt_scene.h: the compiler (g++ -fsyntax-only) checks one
+    static_assert on each mirror's size and, per field, on its offset, its size and its class (floating, signed or unsigned integer of that
+    width, pointer, or the nested typedef; an array by its element).  Every typedef struct of the headers has a mirror and every mirror a
+    typedef."""
+    from gltf_renderer_amd import gltf
+    structs = {**hc.mirrors(abi), **hc.mirrors(gltf)}
+    assert "pt_material" in structs and "gs_node_info" in structs and len(structs) >= 34
+    assert sorted(structs) == sorted(hc.typedef_structs("mipt.h") + hc.typedef_structs("mipt_scene.h"))
+    assert hc.check_layouts(structs, tmp_path) == ""
+
+
+def test_every_prototype_row_is_its_declaration_to_the_compiler(tmp_path):
+    """Every row of abi.PROTOTYPES, gltf.SCENE_PROTOTYPES and tests/hooks.py HOOKS against the declaration of that name in include/mipt.h,
+    include/mipt_scene.h and csrc/mipt_debug.h: the compiler prints, from decltype(&name), the class of the return type and of each
+    parameter (void, pointer, float, signed or unsigned integer of that width); the row has the same count and the same classes."""
+    from gltf_renderer_amd import gltf
+    for table in (abi.PROTOTYPES, gltf.SCENE_PROTOTYPES, hooks.HOOKS):
+        assert all(t is not None for _, argtypes in table.values() for t in argtypes)
+        declared, stated = hc.declared_signatures(list(table), tmp_path), hc.table_signatures(table)
+        assert list(declared) == list(table)
+        for name in table:
+            assert stated[name] == declared[name], "%s: the table says %s, the header %s" % (name, stated[name], declared[name])
 
 
 def test_product_fails_loudly_without_gpu():

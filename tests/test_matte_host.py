@@ -1,7 +1,7 @@
 """CPU-only checks of the ID mattes (include/mipt.h pt_set_matte, pt_matte_id, pt_matte_extract): pt_matte_id against a MurmurHash3_x86_32
-written here, the exponent fix on integers, the pt_matte_config mirror's layout against the header, the C-ABI symbols, the calls that answer
-without a device, and the restatement (tests/matte_ref.py) that tests/test_gpu_matte.py holds the GPU to -- its own properties: a batch of S
-records equals S calls, the stated order of the ranks, dropped ids, and the mask of pt_matte_extract."""
+written here, the exponent fix on integers, the constants against the header, the calls that answer without a device, and the restatement
+(tests/matte_ref.py) that tests/test_gpu_matte.py holds the GPU to -- its own properties: a batch of S records equals S calls, the stated
+order of the ranks, dropped ids, and the mask of pt_matte_extract.  (The pt_matte_config mirror and the prototypes: tests/test_host_abi.py.)"""
 import ctypes as C
 import os
 import re
@@ -11,14 +11,11 @@ import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, renderer
+from tests import header_check as hc
 from tests import matte_ref as mr
 
 f32, u32 = np.float32, np.uint32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 # ---- MurmurHash3_x86_32, written from the algorithm's description (Appleby's reference: 4-byte little-endian blocks, a tail of up to three
@@ -93,35 +90,20 @@ def test_the_fix_on_integers_and_on_names_whose_raw_hash_needs_it():
         assert (raw >> 23) & 0xff == e and lib_id(name) == raw ^ (1 << 23) and (lib_id(name) >> 23) & 0xff == (1 if e == 0 else 254)
 
 
-def test_matte_config_layout_matches_the_header():
-    m = re.search(r"typedef struct pt_matte_config \{(.*?)\} pt_matte_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_matte_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+\s*\*?)\s+([a-z_]+)(?:\[4\])?\s*;", body)]
-    assert fields == [("int32_t", "enable"), ("int32_t", "kind"), ("int32_t", "ranks"), ("int32_t", "id_count"), ("void*", "layers")], fields
-    assert re.search(r"void\*\s+layers\[4\]", body)
-    A = abi.PtMatteConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert C.sizeof(A) == 48
-    assert [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12, 16]
+def test_the_matte_constants_are_the_headers():
+    h = hc.header_text()
     assert (abi.MATTE_INSTANCE, abi.MATTE_MATERIAL, abi.MATTE_MAX_RANKS) == (0, 1, 8)
-    assert re.search(r"enum\s*\{\s*PT_MATTE_INSTANCE\s*=\s*0\s*,\s*PT_MATTE_MATERIAL\s*=\s*1\s*\}", header())
-    assert re.search(r"#define\s+PT_MATTE_MAX_RANKS\s+8\b", header())
+    assert re.search(r"enum\s*\{\s*PT_MATTE_INSTANCE\s*=\s*0\s*,\s*PT_MATTE_MATERIAL\s*=\s*1\s*\}", h)
+    assert re.search(r"#define\s+PT_MATTE_MAX_RANKS\s+8\b", h)
 
 
 def test_the_library_exports_the_matte_symbols_and_the_header_declares_them():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_set_matte\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_matte_config\s*\*\s*\w*\s*,\s*const\s+uint32_t\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\buint32_t\s+pt_matte_id\s*\(\s*const\s+char\s*\*\s*\w*\s*,\s*size_t\s+\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_matte_extract\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*const\s*\*\s*\w*\s*,\s*int\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,"
-                     r"\s*const\s+uint32_t\s*\*\s*\w*\s*,\s*int\s+\w*\s*,\s*void\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declarations against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
     for name in ("pt_set_matte", "pt_matte_id", "pt_matte_extract"):
         assert name in renderer.EXPORTS and hasattr(L, name), name
-    assert L.pt_abi_version() == 2
+    h = hc.header_text()
     # the header says what a full pixel loses, and what must not be done to a layer
-    h = header()
     assert "DROPPED" in h and "raises `ranks`" in h and "PT_EXCHANGE_REDUCE must not be used on a layer" in h
 
 

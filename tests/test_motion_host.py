@@ -1,5 +1,5 @@
-"""CPU-only checks of motion vectors and temporal reprojection (include/mipt.h pt_set_motion, pt_motion_snapshot, pt_reproject): the config
-mirrors' layout against the header, the C-ABI symbols, the calls that answer without a device, and the restatement (tests/motion_ref.py) that
+"""CPU-only checks of motion vectors and temporal reprojection (include/mipt.h pt_set_motion, pt_motion_snapshot, pt_reproject): the documented
+defaults and snapshot states (the mirrors and the prototypes: tests/test_host_abi.py), the calls that answer without a device, and the restatement (tests/motion_ref.py) that
 tests/test_gpu_motion.py holds the GPU to -- its own properties: an unmoved triangle under an unchanged camera gives exactly (0, 0, z, z), the
 float32 record stays within the derived bound of the float64 one, and the filter's pass-through, integer-vector and rejection cases."""
 import ctypes as C
@@ -9,35 +9,19 @@ import re
 import numpy as np
 
 from gltf_renderer_amd import abi, camera, renderer
+from tests import header_check as hc
 from tests import motion_ref as mo
 
 f32, f64, u32 = np.float32, np.float64, np.uint32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
-
-
 def bits(a):
     return np.ascontiguousarray(a, f32).view(u32)
 
 
-def test_config_layouts_match_the_header():
-    h = header()
-    m = re.search(r"typedef struct pt_motion_config \{(.*?)\} pt_motion_config;", h, re.S)
-    assert m, "include/mipt.h lacks pt_motion_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+\s*\*?)\s+([a-z_]+)(?:\[16\])?\s*;", body)]
-    assert fields == [("int32_t", "enable"), ("int32_t", "_pad"), ("void*", "motion"), ("float", "prev_world_to_view"), ("float", "prev_view_to_clip")], fields
-    A = abi.PtMotionConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert C.sizeof(A) == 144 and [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 16, 80]
-    m = re.search(r"typedef struct pt_reproject_config \{(.*?)\} pt_reproject_config;", h, re.S)
-    assert m, "include/mipt.h lacks pt_reproject_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    assert re.findall(r"float\s+([a-z_]+)\s*;", body) == ["alpha_min", "max_history", "depth_tolerance"] == [n for n, _ in abi.PtReprojectConfig._fields_]
-    assert C.sizeof(abi.PtReprojectConfig) == 12
+def test_config_defaults_and_snapshot_states_match_the_header():
+    h = hc.header_text()
     d = abi.PtReprojectConfig.defaults()
     assert (f32(d.alpha_min), f32(d.max_history), f32(d.depth_tolerance)) == (f32(0.1), f32(32.0), f32(0.02))
     assert re.search(r"PT_MOTION_SNAPSHOT_NONE\s*=\s*0\s*,\s*PT_MOTION_SNAPSHOT_VALID\s*=\s*1\s*,\s*PT_MOTION_SNAPSHOT_STALE\s*=\s*2", h)
@@ -46,18 +30,11 @@ def test_config_layouts_match_the_header():
 
 
 def test_the_library_exports_the_motion_symbols():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_motion_snapshot\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*int\s+\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_motion_snapshot_state\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*int32_t\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_set_motion\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_motion_config\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_reproject\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_reproject_config\s*\*", text)
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declarations against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
-    for name in ("pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject", "pt_debug_motion"):
-        assert hasattr(L, name), name
     for name in ("pt_motion_snapshot", "pt_motion_snapshot_state", "pt_set_motion", "pt_reproject"):
-        assert name in renderer.EXPORTS
-    assert "pt_debug_motion" not in renderer.EXPORTS and "pt_debug_motion" not in text          # a hook, not part of the header
+        assert name in renderer.EXPORTS and hasattr(L, name), name
+    assert hasattr(L, "pt_debug_motion") and "pt_debug_motion" not in renderer.EXPORTS            # a hook, not part of the header
 
 
 def test_calls_without_a_context_return_minus_one_and_write_nothing():

@@ -1,52 +1,34 @@
-"""CPU-only checks of light-probe baking (include/mipt.h pt_set_probes, pt_probe_project): the pt_probe_config mirror's layout against the
-header, the C-ABI symbols, the calls that answer without a device, and the restatement (tests/probe_ref.py) that tests/test_gpu_probe.py
+"""CPU-only checks of light-probe baking (include/mipt.h pt_set_probes, pt_probe_project): the SH kinds against the header's enum (the
+pt_probe_config mirror and the prototypes: tests/test_host_abi.py), the calls that answer without a device, and the restatement (tests/probe_ref.py) that tests/test_gpu_probe.py
 holds the GPU to -- its own properties: the Gram matrix of the texel-centre quadrature, a constant field, a clamped-cosine lobe, the atlas
 layout, and the cube-face quadrature the end-to-end test compares with."""
 import ctypes as C
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
 from gltf_renderer_amd import abi, renderer
+from tests import header_check as hc
 from tests import probe_ref as pr
 
 f32, f64 = np.float32, np.float64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # max |G - I| of the texel-centre quadrature, float64; include/mipt.h states them to two digits
 GRAM = {16: 9.6294e-3, 32: 2.4335e-3, 64: 6.0984e-4}
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
-
-
-def test_probe_config_layout_matches_the_header():
-    m = re.search(r"typedef struct pt_probe_config \{(.*?)\} pt_probe_config;", header(), re.S)
-    assert m, "include/mipt.h lacks pt_probe_config"
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z_0-9]+)\s+([a-z_]+)\s*;", body)]
-    assert fields == [("int32_t", "enable"), ("int32_t", "resolution"), ("int32_t", "count"), ("int32_t", "columns"), ("float", "max_distance")]
-    A = abi.PtProbeConfig
-    assert [n for n, _ in A._fields_] == [n for _, n in fields]
-    assert C.sizeof(A) == 20
-    assert [getattr(A, n).offset for n, _ in A._fields_] == [0, 4, 8, 12, 16]
+def test_the_sh_kinds_are_the_headers_enum():
     assert (abi.PROBE_SH_RADIANCE, abi.PROBE_SH_IRRADIANCE) == (0, 1)
-    assert re.search(r"enum\s*\{\s*PT_PROBE_SH_RADIANCE\s*=\s*0\s*,\s*PT_PROBE_SH_IRRADIANCE\s*=\s*1\s*\}", header())
+    assert re.search(r"enum\s*\{\s*PT_PROBE_SH_RADIANCE\s*=\s*0\s*,\s*PT_PROBE_SH_IRRADIANCE\s*=\s*1\s*\}", hc.header_text())
 
 
 def test_the_library_exports_the_probe_symbols_and_the_header_declares_them():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    assert re.search(r"\bint\s+pt_set_probes\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_probe_config\s*\*\s*\w*\s*,\s*const\s+float\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"\bint\s+pt_probe_project\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+void\s*\*\s*\w*\s*,\s*uint32_t\s+\w*\s*,\s*uint32_t\s+\w*\s*,\s*int\s+\w*\s*,\s*float\s*\*\s*\w*\s*\)\s*;", text)
-    assert re.search(r"#define\s+MIPT_ABI_VERSION\s+2\b", text)      # additive: the version stays
+    """(The declarations against the binding: tests/test_host_abi.py.)"""
     L = renderer.load_library()
     for name in ("pt_set_probes", "pt_probe_project"):
         assert name in renderer.EXPORTS and hasattr(L, name), name
-    assert hasattr(L, "pt_debug_probe_rays") and "pt_debug_probe_rays" not in text     # the test hook: exported, not part of the header
-    assert L.pt_abi_version() == 2
+    assert hasattr(L, "pt_debug_probe_rays") and "pt_debug_probe_rays" not in renderer.EXPORTS    # the test hook: exported, not part of the header
 
 
 def test_calls_without_a_context_return_minus_one_and_write_nothing():
@@ -62,7 +44,7 @@ def test_calls_without_a_context_return_minus_one_and_write_nothing():
 
 
 def test_the_header_states_the_quadratures_gram_deviation():
-    text = re.sub(r"\s*\n \*\s*", " ", header())
+    text = re.sub(r"\s*\n \*\s*", " ", hc.header_text())
     for n, g in (("16", "9.6e-3"), ("32", "2.4e-3"), ("64", "6.1e-4")):
         assert (g + " at n = " + n) in text, n
         assert abs(float(g) - GRAM[int(n)]) <= 0.5 * 10.0 ** (math.floor(math.log10(GRAM[int(n)])) - 1) * 1.0001, n     # the figure to two digits

@@ -139,10 +139,8 @@ def test_oracle_tree_equals_its_exhaustive_search_under_force_non_opaque(oracle_
 def test_trace_queues_hook_refuses_bad_arguments_without_a_context():
     """pt_debug_trace_queues answers PT_ERR_INVALID_ARGUMENT -- before it touches a device or dereferences the context -- for a shard above 255,
     a closest ray with tmin != 0, blocks_per_shard < 1, `which` outside 0..2, a fused launch at bounce 0, and for a NULL context."""
-    from gltf_renderer_amd import renderer
-    L = renderer.load_library()
     ray = np.array([[0, 0, 1, 0, 0, 0, -1, 10]], np.float32); sh = np.array([[0, 0, 1, 0, 0, -1]], np.float32)
-    call = lambda **kw: trace_queues_rc(L, None, **{**dict(closest=ray, closest_shard=0, shadow=sh, shadow_shard=0, is_light=1, shadow_tmax=10.0, flags=0, bounce=1,
+    call = lambda **kw: trace_queues_rc(None, **{**dict(closest=ray, closest_shard=0, shadow=sh, shadow_shard=0, is_light=1, shadow_tmax=10.0, flags=0, bounce=1,
                                                             blocks_per_shard=1, which=0), **kw})[0]
     bad = -1                                                               # PT_ERR_INVALID_ARGUMENT (include/mipt.h)
     tmin = ray.copy(); tmin[0, 3] = 1e-3

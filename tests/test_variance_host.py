@@ -1,26 +1,20 @@
 """The variance AOV and the noise report on the host (include/mipt.h pt_set_variance / pt_noise_estimate): the float32 restatement of
 tests/variance_ref.py against float64, the struct layouts, and the calls that answer without a device."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from gltf_renderer_amd import abi, renderer
+from tests import header_check as hc
 from tests import variance_ref as vr
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIXELS = 4096
 COUNTS = (2, 3, 8, 64, 1024)
 # The largest relative error of the float32 fold against the float64 population variance of the same float32 samples, per count, over
 # PIXELS pixels x 4 channels of the samples below (seed 11), as measured on the CPU the test was written on.  The test allows 4 x these
 # for other seeds, libraries and roundings of the samples' generation.  DESIGN.md section 4 has the same table.
 MEASURED = {2: 6.5e-5, 3: 2.7e-6, 8: 3.8e-7, 64: 7.6e-7, 1024: 2.5e-6}
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "mipt.h")).read()
 
 
 def heavy_tailed(rng, n, pixels):
@@ -117,18 +111,9 @@ def test_the_noise_restatement_on_planted_values():
 
 
 def test_struct_layouts_match_the_header():
-    h = header()
-    m = re.search(r"typedef struct pt_variance_config \{(.*?)\} pt_variance_config;\s*/\* (\d+) bytes \*/", h, re.S)
-    assert m, "include/mipt.h lacks pt_variance_config"
-    assert re.findall(r"^\s*(\w+\*?)\s+(\w+);", m.group(1), re.M) == [("int32_t", "enable"), ("int32_t", "_pad"), ("void*", "variance")]
-    assert int(m.group(2)) == C.sizeof(abi.PtVarianceConfig) == 16
-    assert [f for f, _ in abi.PtVarianceConfig._fields_] == ["enable", "_pad", "variance"]
-    m = re.search(r"typedef struct pt_noise_summary \{(.*?)\} pt_noise_summary;\s*/\* (\d+) bytes \*/", h, re.S)
-    assert m, "include/mipt.h lacks pt_noise_summary"
-    fields = re.findall(r"^\s*(\w+)\s+(\w+);", m.group(1), re.M)
-    assert fields == [("uint32_t", "tiles"), ("uint32_t", "tiles_estimated"), ("uint32_t", "tiles_above"), ("float", "mean"), ("float", "max")]
-    assert int(m.group(2)) == C.sizeof(abi.PtNoiseSummary) == 20
-    assert [f for f, _ in abi.PtNoiseSummary._fields_] == [n for _, n in fields]
+    """The sizes the header's comments state (the layouts themselves: tests/test_host_abi.py)."""
+    assert hc.stated_bytes("pt_variance_config") == C.sizeof(abi.PtVarianceConfig) == 16
+    assert hc.stated_bytes("pt_noise_summary") == C.sizeof(abi.PtNoiseSummary) == 20
 
 
 def test_calls_without_a_context_return_minus_one_and_write_nothing():
