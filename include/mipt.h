@@ -384,6 +384,10 @@ int pt_env_destroy(pt_ctx* ctx, int env);
  *     instances' packets are rewritten and every box re-derived.  Hits equal a full rebuild's; the tree's quality follows the
  *     pose it was built for, as upstream's refitted BLAS does (upstream never rebuilds one);
  *   - an instance table identical to the current one -> nothing.
+ * A row that differs from the current one in its material_id alone leaves the tree and its packets as they are (the packets name the row,
+ * not the material): neither a build nor a refit.  A pt_buffer_update or pt_skin_run that writes a buffer no row of the current instance
+ * table reads changes nothing for the tree.  A call that is refused (any return code but PT_OK from pt_scene_set_instances,
+ * pt_scene_set_materials or pt_buffer_update) changes nothing: tables, buffers, what is pending and the motion snapshot's state stay.
  * pt_accel_request_rebuild forces the next call to build from scratch (e.g. after a pose has drifted far from the built one). */
 int pt_build_accel(pt_ctx* ctx);
 int pt_accel_request_rebuild(pt_ctx* ctx);

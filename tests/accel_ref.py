@@ -18,6 +18,11 @@ Every violation is "<name>: <detail>"; the names and what each demands:
   tri.flags           TriPacket::flags is the instance row's mask_flags (mipt_api.hip pt_scene_set_instances, restated in scene_rows)
   tri.shade_inst      ShadePacket::inst == TriPacket::inst
   tri.shade_pos       the ShadePacket's three positions are the primitive's object-space vertices, bit for bit
+  tri.shade_tangent   ShadePacket::v[k].tangent_space is the instance's packed tangent-space word at the de-indexed vertex; 0 without the stream
+  tri.shade_uv0       ShadePacket::uv0[k] is the instance's first texcoord pair at the de-indexed vertex, bit for bit; zeros without the stream
+  tri.shade_uv1       ShadePacket::uv1[k] likewise for the second set
+  tri.shade_color     ShadePacket::color[k] is the two words of the instance's R16G16B16A16 colour at the de-indexed vertex; zeros without the
+                      stream (k_shade_packets at a build and k_refit_packets at a refit write all four; offsets from pt_types.h ShadePacket)
   tri.transform       v0, e1, e2 are mul_point's float32 expression M0 x + M4 y + M8 z + M12 (left to right) and w1 - w0, w2 - w0, bit for bit
   ranges              WideRanges first / count of child k is the leaf range found by walking below it; count 0 for an empty slot
   contain.exact_lo    origin + qlo * step <= min lo of the triangles below the child, in float64, where the sum is exact (pt_slab.h
@@ -50,13 +55,17 @@ NODE_BYTES, RANGE_BYTES, TRI_BYTES, SHADE_BYTES = 64, 32, 64, 128
 TF_CULL_DISABLE, TF_FORCE_NON_OPAQUE, TF_MIRRORED = 1 << 8, 1 << 9, 1 << 10
 INFO_N_TRIS, INFO_WIDE_NODES, INFO_ROOT, INFO_STACK_NEED, INFO_SEG_LEAVES, INFO_BUILDER, INFO_FALLBACKS, INFO_HAVE_RANGES = range(8)
 Q_OFFSET = 32                                                                                  # byte of qlox[0]: qlo[a][k] at 32 + 8 a + k, qhi 4 further
+# ShadePacket in 32-bit words (pt_types.h): v[k] = {pos[3], tangent_space} at 4 k, uv0[3][2] at 12, inst at 18, uv1[3][2] at 20, color[3][2] at 26
+SHADE_TANGENT, SHADE_UV0, SHADE_INST, SHADE_UV1, SHADE_COLOR = (3, 7, 11), 12, 18, 20, 26
+STREAMS = ("tangent", "uv0", "uv1", "color")                                                   # scene_rows keys; words per vertex 1, 2, 2, 2
 
 
 # ---- the scene's side -------------------------------------------------------------------------------------------------------------------
 def scene_rows(scene, transforms=None, positions=None):
-    """What check_tree needs of a scenes.SceneData: per instance its float32 positions, its indices (or None), the 16 floats of its transform
-    and the packets' flags word.  transforms / positions override the scene's own for a moved or rewritten instance: {instance: 16 floats,
-    column-major} and {instance: [vertices, 3]}."""
+    """What check_tree needs of a scenes.SceneData: per instance its float32 positions, its indices (or None), the 16 floats of its transform,
+    the packets' flags word and the four optional vertex streams as 32-bit words ("tangent" [vertices], "uv0" / "uv1" / "color" [vertices, 2];
+    None where the instance has no such stream).  transforms / positions override the scene's own for a moved or rewritten instance:
+    {instance: 16 floats, column-major} and {instance: [vertices, 3]}."""
     rows = []
     for i, d in enumerate(scene.instances):
         g = d.gpu
@@ -68,9 +77,18 @@ def scene_rows(scene, transforms=None, positions=None):
                 (TF_MIRRORED if det < 0 else 0)
         idx = None if g.index_descriptor == -1 else np.asarray(take(g.index_descriptor)).astype(np.int64)[:d.num_of_indices]
         pos = take(g.position_descriptor) if positions is None or i not in positions else positions[i]
+        words = lambda h, per: None if h == -1 else np.ascontiguousarray(take(h)).reshape(-1).view(u32).reshape(-1, per)
         rows.append({"positions": np.asarray(pos, f32).reshape(-1, 3), "indices": idx, "transform": M,
-                     "mask_flags": flags, "triangles": d.num_of_indices // 3})
+                     "mask_flags": flags, "triangles": d.num_of_indices // 3,
+                     "tangent": None if g.tangent_space_descriptor == -1 else words(g.tangent_space_descriptor, 1).reshape(-1),
+                     "uv0": words(g.texcoord_descriptors[0], 2), "uv1": words(g.texcoord_descriptors[1], 2), "color": words(g.color_descriptor, 2)})
     return rows
+
+
+def row_corners(row):
+    """[triangles, 3] the vertex each corner of each primitive reads (the index stream's entry, or 3 prim + k without one)."""
+    n = row["triangles"]
+    return (np.arange(3 * n) if row["indices"] is None else row["indices"][:3 * n]).reshape(n, 3)
 
 
 def row_vertices(row):
@@ -224,18 +242,28 @@ def check_triangles(rep, n, tris, shade, scene):
     want = np.concatenate([np.full(c, i, np.int64) << 32 | np.arange(c, dtype=np.int64) for i, c in enumerate(counts)]) if n else np.zeros(0, np.int64)
     got = np.sort(inst << 32 | prim)
     rep.add("tri.multiset", got != want, lambda at: "sorted (inst, prim) %d / %d, expected %d / %d" % (got[at] >> 32, got[at] & 0xffffffff, want[at] >> 32, want[at] & 0xffffffff))
-    rep.add("tri.shade_inst", sw[:, 18] != tw[:, 3], lambda at: "shade.inst %d, tris.inst %d" % (sw[at][18], tw[at][3]))
+    rep.add("tri.shade_inst", sw[:, SHADE_INST] != tw[:, 3], lambda at: "shade.inst %d, tris.inst %d" % (sw[at][SHADE_INST], tw[at][3]))
     ok = (inst < len(scene)) & (prim < counts[np.minimum(inst, len(scene) - 1)])
     if not ok.all(): return                                            # (already a tri.multiset violation)
     pos = np.zeros((n, 3, 3), f32); world = np.zeros((n, 3, 3), f32); flags = np.zeros(n, u32)
+    stream = {"tangent": np.zeros((n, 3, 1), u32), "uv0": np.zeros((n, 3, 2), u32), "uv1": np.zeros((n, 3, 2), u32), "color": np.zeros((n, 3, 2), u32)}
     for i, r in enumerate(scene):
         m = inst == i
         if not m.any(): continue
         v = row_vertices(r)[prim[m]]
         pos[m] = v; world[m] = mul_point(r["transform"], v); flags[m] = r["mask_flags"]
+        corners = row_corners(r)[prim[m]]
+        for name in STREAMS:
+            if r.get(name) is not None: stream[name][m] = np.asarray(r[name]).view(u32).reshape(len(r[name]), -1)[corners]       # (absent: zeros)
     rep.add("tri.flags", tw[:, 11] != flags, lambda at: "flags %#x, the instance row's %#x" % (tw[at][11], flags[at]))
     spos = np.stack([sw[:, 0:3], sw[:, 4:7], sw[:, 8:11]], axis=1)
     rep.add("tri.shade_pos", (spos != pos.view(u32)).any(axis=(1, 2)), "shading packet positions differ from the primitive's vertices")
+    got_s = {"tangent": sw[:, list(SHADE_TANGENT)].reshape(n, 3, 1), "uv0": sw[:, SHADE_UV0:SHADE_UV0 + 6].reshape(n, 3, 2),
+             "uv1": sw[:, SHADE_UV1:SHADE_UV1 + 6].reshape(n, 3, 2), "color": sw[:, SHADE_COLOR:SHADE_COLOR + 6].reshape(n, 3, 2)}
+    for name in STREAMS:
+        g, w = got_s[name], stream[name]
+        rep.add("tri.shade_" + name, (g != w).any(axis=(1, 2)), lambda at, g=g, w=w: "packet %d (instance %d primitive %d) holds %s, the stream says %s" %
+                (at[0], inst[at[0]], prim[at[0]], [hex(int(x)) for x in g[at[0]].reshape(-1)], [hex(int(x)) for x in w[at[0]].reshape(-1)]))
     with np.errstate(over="ignore", invalid="ignore"):
         want_t = np.stack([world[:, 0], (world[:, 1] - world[:, 0]).astype(f32), (world[:, 2] - world[:, 0]).astype(f32)], axis=1)
     got_t = np.stack([tw[:, 0:3], tw[:, 4:7], tw[:, 8:11]], axis=1)

@@ -43,6 +43,16 @@ def host_build(P):
     tris[:, 3] = order >= half; tris[:, 7] = np.where(order >= half, order - half, order); tris[:, 11] = 1
     for k in range(3): shade[:, 4 * k:4 * k + 3] = V[:, k].view(u32)
     shade[:, 18] = tris[:, 3]
+    # the second instance has all four optional streams (non-zero words, one value per vertex and field), the first has none: zeros
+    nv = 3 * (n - half)
+    rng = np.random.default_rng(n)
+    streams = {"tangent": rng.integers(1, 2 ** 32, nv, dtype=np.uint64).astype(u32), "uv0": rng.uniform(0.1, 1, (nv, 2)).astype(f32),
+               "uv1": rng.uniform(1.1, 2, (nv, 2)).astype(f32), "color": rng.integers(1, 2 ** 32, (nv, 2), dtype=np.uint64).astype(u32)}
+    second = np.nonzero(order >= half)[0]
+    corner = 3 * (order[second] - half)[:, None] + np.arange(3)[None, :]                       # [packets of the second instance, 3] vertex
+    shade[second[:, None], np.array(ar.SHADE_TANGENT)[None, :]] = streams["tangent"][corner]
+    for name, at in (("uv0", ar.SHADE_UV0), ("uv1", ar.SHADE_UV1), ("color", ar.SHADE_COLOR)):
+        shade[second, at:at + 6] = streams[name].view(u32)[corner].reshape(-1, 6)
     lo_t, hi_t = ar.tri_boxes(tris)
     box = lambda b: (lo_t[b[0]:b[0] + b[1]].min(axis=0), hi_t[b[0]:b[0] + b[1]].max(axis=0))
     key = lambda b: float(ar.area_key(*box(b)))
@@ -71,7 +81,7 @@ def host_build(P):
     nodes = ar.node_bytes(o, e, child, ql, qh)
     ident = np.eye(4, dtype=f32).reshape(-1)
     scene = [{"positions": P[:half].reshape(-1, 3), "indices": None, "transform": ident, "mask_flags": 1, "triangles": half},
-             {"positions": P[half:].reshape(-1, 3), "indices": None, "transform": ident, "mask_flags": 1, "triangles": n - half}]
+             dict({"positions": P[half:].reshape(-1, 3), "indices": None, "transform": ident, "mask_flags": 1, "triangles": n - half}, **streams)]
     info = np.array([n, W, 0, need_max, 256, 0, 0, 1], u32)
     return info, nodes, ranges, tris, shade, scene
 
@@ -173,7 +183,36 @@ def m_shade_inst(t, p):
     t[4][len(t[4]) // 2, 18] ^= 1
 
 
-MUTATIONS = [(m_qhi_lowered, "contain.exact_hi"), (m_qlo_raised, "contain.exact_lo"), (m_qlo_loose, "tight.lo"), (m_exponent, "tight.exp"),
+def of_second_instance(t):
+    """A packet of the second instance (the one with the optional streams), and one of the first."""
+    inst = t[3][:, 3]
+    return int(np.nonzero(inst == 1)[0][-1]), int(np.nonzero(inst == 0)[0][0])
+
+
+def m_shade_tangent(t, p):
+    t[4][of_second_instance(t)[0], ar.SHADE_TANGENT[1]] ^= 1 << 20                    # the second vertex's packed word
+
+
+def m_shade_uv0(t, p):
+    t[4][of_second_instance(t)[0], ar.SHADE_UV0 + 5] ^= 1                              # the last ulp of the third vertex's v
+
+
+def m_shade_uv1(t, p):
+    t[4][of_second_instance(t)[0], ar.SHADE_UV1] ^= 1
+
+
+def m_shade_color(t, p):
+    t[4][of_second_instance(t)[0], ar.SHADE_COLOR + 3] ^= 1 << 31
+
+
+def m_shade_stale_uv(t, p):
+    """The words of another vertex of the same stream: what a refit that skipped the packet after an index rewrite would leave."""
+    at = of_second_instance(t)[0]
+    t[4][at, ar.SHADE_UV0:ar.SHADE_UV0 + 2], t[4][at, ar.SHADE_UV0 + 2:ar.SHADE_UV0 + 4] = t[4][at, ar.SHADE_UV0 + 2:ar.SHADE_UV0 + 4].copy(), t[4][at, ar.SHADE_UV0:ar.SHADE_UV0 + 2].copy()
+
+
+MUTATIONS = [(m_shade_tangent, "tri.shade_tangent"), (m_shade_uv0, "tri.shade_uv0"), (m_shade_uv1, "tri.shade_uv1"), (m_shade_color, "tri.shade_color"),
+             (m_shade_stale_uv, "tri.shade_uv0"), (m_qhi_lowered, "contain.exact_hi"), (m_qlo_raised, "contain.exact_lo"), (m_qlo_loose, "tight.lo"), (m_exponent, "tight.exp"),
              (m_range_shifted, "ranges"), (m_leaf_duplicated, "shape.leaf_tiling"), (m_triangle_dropped, "tri.multiset"),
              (m_children_swapped, "order"), (m_stack_need, "stack_need"), (m_shade_inst, "tri.shade_inst")]
 # what else a mutation may set off: a changed byte is also not what the restated quantiser writes, a lowered hi or raised lo plane may also
@@ -186,7 +225,7 @@ ALSO["shape.leaf_tiling"] = BOXES | {"ranges"}
 
 
 @pytest.mark.parametrize("n", (5, 40, 300))
-@pytest.mark.parametrize("mutate,name", MUTATIONS, ids=[name for _, name in MUTATIONS])
+@pytest.mark.parametrize("mutate,name", MUTATIONS, ids=[name + ("-stale" if m is m_shade_stale_uv else "") for m, name in MUTATIONS])
 def test_each_mutation_is_reported_under_its_own_name(trees, n, mutate, name):
     t = copy_of(trees[n])
     mutate(t, parts(trees[n]))
@@ -208,10 +247,35 @@ def test_the_order_is_demanded_only_of_the_nodes_named(trees):
 
 def test_the_two_triangle_tree_reports_what_it_can(trees):
     """Two leaves under one node: the mutations that need no inner structure."""
-    for mutate, name in ((m_stack_need, "stack_need"), (m_shade_inst, "tri.shade_inst"), (m_triangle_dropped, "tri.multiset"), (m_range_shifted, "ranges")):
+    for mutate, name in ((m_stack_need, "stack_need"), (m_shade_inst, "tri.shade_inst"), (m_triangle_dropped, "tri.multiset"), (m_range_shifted, "ranges"),
+                         (m_shade_tangent, "tri.shade_tangent"), (m_shade_uv0, "tri.shade_uv0"), (m_shade_uv1, "tri.shade_uv1"), (m_shade_color, "tri.shade_color")):
         t = copy_of(trees[2])
         mutate(t, parts(trees[2]))
         assert name in ar.names(ar.check_tree(*t)), name
+
+
+@pytest.mark.parametrize("word,name", [(ar.SHADE_TANGENT[0], "tri.shade_tangent"), (ar.SHADE_UV0 + 1, "tri.shade_uv0"), (ar.SHADE_UV1 + 4, "tri.shade_uv1"),
+                                       (ar.SHADE_COLOR + 5, "tri.shade_color")])
+def test_a_word_of_a_stream_the_instance_lacks_must_be_zero(trees, word, name):
+    """The first instance has none of the four streams: its packets hold zeros there, and one set bit is reported under the field's name."""
+    t = copy_of(trees[40])
+    t[4][of_second_instance(t)[1], word] = 1
+    assert ar.names(ar.check_tree(*t)) == [name]
+
+
+def test_an_indexed_row_is_checked_at_the_vertex_its_index_names(trees):
+    """The same arrays against a scene row that reaches the same vertices through an index stream: clean; with two indices of one triangle
+    exchanged (a rewritten index stream that the packets did not follow): the positions and every stream of that packet are reported."""
+    info, nodes, ranges, tris, shade, scene = copy_of(trees[40])
+    row = dict(scene[1]); nv = len(row["positions"])
+    perm = np.random.default_rng(7).permutation(nv)
+    back = np.empty(nv, np.int64); back[perm] = np.arange(nv)
+    for key in ("positions",) + ar.STREAMS: row[key] = row[key][perm]
+    row["indices"] = back
+    assert ar.check_tree(info, nodes, ranges, tris, shade, [scene[0], row]) == []
+    row["indices"] = back.copy(); row["indices"][[0, 1]] = row["indices"][[1, 0]]
+    got = set(ar.names(ar.check_tree(info, nodes, ranges, tris, shade, [scene[0], row])))
+    assert {"tri.shade_pos", "tri.shade_tangent", "tri.shade_uv0", "tri.shade_uv1", "tri.shade_color", "tri.transform"} <= got, got
 
 
 def test_the_worked_example_is_seen_by_the_float64_check_alone():
