@@ -318,6 +318,21 @@ class PtBloomConfig(C.Structure):
         return cls(4, 0.01, 0.0)
 
 
+class PtEnvFilterConfig(C.Structure):
+    """pt_env_filter_config (pt_env_filter)."""
+    _fields_ = [("ggx_samples", C.c_int32), ("ggx_mip_bias", C.c_float), ("ggx_mips", C.c_int32),
+                ("diffuse_samples", C.c_int32), ("diffuse_mip_bias", C.c_float), ("diffuse_resolution", C.c_int32)]
+
+    @classmethod
+    def defaults(cls):
+        return cls(256, 2.0, 0, 512, 3.0, 256)
+
+
+class PtEnvFilterInfo(C.Structure):
+    """pt_env_filter_info: the sizes and roughnesses of an environment's filtered cubes (pt_env_filter_info_get)."""
+    _fields_ = [("ggx_resolution", C.c_int32), ("ggx_mips", C.c_int32), ("diffuse_resolution", C.c_int32), ("ggx_roughness", C.c_float * 16)]
+
+
 class PtVarianceConfig(C.Structure):
     """pt_variance_config: the variance AOV (pt_set_variance; an extension, absent upstream)."""
     _fields_ = [("enable", C.c_int32), ("_pad", C.c_int32), ("variance", C.c_void_p)]
@@ -362,6 +377,7 @@ STAGE_NAMES = ("generate", "trace", "shade", "shadow", "resolve")
 EXCHANGE_GATHER, EXCHANGE_REDUCE = 0, 1
 BUILDER_LBVH, BUILDER_PLOC, BUILDER_PLOC_REINSERT = 0, 1, 2
 EXCHANGE_ID_BYTES = 128
+ENV_FILTER_GGX, ENV_FILTER_DIFFUSE = 0, 1       # pt_env_filter_read's `which`
 
 
 assert C.sizeof(PtSettings) == 64
@@ -449,6 +465,9 @@ PROTOTYPES = {
     "pt_noise_estimate": (_ci, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _f32, _vp, _vp, _vp]),
     "pt_denoise_variance": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "pt_bloom": (_ci, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "pt_env_filter": (_ci, [_vp, _ci, _vp]),
+    "pt_env_filter_info_get": (_ci, [_vp, _ci, _vp]),
+    "pt_env_filter_read": (_ci, [_vp, _ci, _ci, _ci, _out(_ci), _vp, _out(_vp)]),
 }
 
 

@@ -1,7 +1,7 @@
 // envmap.hip -- environment-map prerequisites of the path tracer on gfx950.
 //
-// EnvironmentMap::CreateEnvironmentMap (Source/EnvironmentMap.cpp:84-130) minus the raster-only GGX /
-// diffuse cubes:  equirect RGB32F -> RGBA16F cube (ConvertEquirectangularToCubemap.cs.hlsl) -> cube mip
+// EnvironmentMap::CreateEnvironmentMap (Source/EnvironmentMap.cpp:84-130), the part the path tracer reads (the GGX /
+// diffuse cubes of the raster pass: envfilter.hip):  equirect RGB32F -> RGBA16F cube (ConvertEquirectangularToCubemap.cs.hlsl) -> cube mip
 // chain (GenerateMipLevelArray.cs.hlsl) -> 1024^2 luminance importance map
 // (GenerateEnvironmentImportanceMap.cs.hlsl) -> sum pyramid (GenerateEnvironmentImportanceMapLevel.cs.hlsl).
 // One-off streaming kernels, one lane per output texel, coalesced along x.
@@ -163,6 +163,8 @@ hipError_t env_build_raw(EnvDevice& e, int n, const uint16_t* cube_rgba16f, cons
 void env_free(EnvDevice& e) {
     hipFree(e.cube); hipFree(e.importance); hipFree(e.blocked);
     e.cube = nullptr; e.importance = nullptr; e.blocked = nullptr;
+    hipFree(e.ggx); hipFree(e.diffuse); hipFree(e.filter_table);           // pt_env_filter's (envfilter.hip)
+    e.ggx = nullptr; e.diffuse = nullptr; e.filter_table = nullptr; e.ggx_halfs = e.diffuse_halfs = 0; e.filtered = false;
 }
 
 }  // namespace pt

@@ -1,5 +1,5 @@
 // pt_ctx.h -- the context behind the C-ABI of include/mipt.h, and what the translation units with entry points need of it: mipt_api.hip (the
-// core of the product), a feature's own file (bake, probe, matte, motion, blur, bloom, variance, denoise .hip) and mipt_debug.hip (the test hooks).
+// core of the product), a feature's own file (bake, probe, matte, motion, blur, bloom, envfilter, variance, denoise .hip) and mipt_debug.hip (the test hooks).
 #pragma once
 #include <cstring>
 #include <string>

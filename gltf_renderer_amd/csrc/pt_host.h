@@ -72,7 +72,28 @@ struct EnvDevice {
     float* blocked = nullptr;          // 4x4-blocked copies of levels 4^2, 16^2, 64^2, 256^2, 1024^2 (EnvRec::blocked)
     uint32_t blocked_offset[5] = {0};
     float total = 0.f;                 // the pyramid's apex (sum of the whole map), read back once: a kernel argument instead of a load per sample
+    // pt_env_filter (envfilter.hip): the GGX chain and the diffuse cube, RGBA16F, face-major level by level; absent until the first filter
+    bool filtered = false;
+    uint16_t* ggx = nullptr; size_t ggx_halfs = 0;         // allocated halfs: a filter with other sizes reallocates
+    size_t ggx_offset[16] = {0};       // in halfs
+    int ggx_n[16] = {0};
+    int ggx_mips = 0;
+    float ggx_roughness[16] = {0};
+    uint16_t* diffuse = nullptr; size_t diffuse_halfs = 0;
+    int diffuse_n = 0;
+    float4* filter_table = nullptr;    // the per-sample table of one level's launch (kEnvFilterMaxSamples entries)
 };
+constexpr int kEnvFilterMaxSamples = 4096;
+constexpr int kEnvFilterMaxResolution = 1024;
+// One level of a filtered cube: what the two kernels of a level take beside the source cube (envfilter.hip).
+struct EnvFilterLevel {
+    int kind;                          // 0 GGX, 1 diffuse
+    int samples;
+    float roughness, mip_bias;
+    uint16_t* out; int n;              // 6 * n * n RGBA16F texels
+};
+// Enqueues the table and filter kernels of one level.  e.filter_table must exist.  Asynchronous.
+hipError_t env_filter_level(const EnvDevice& e, const EnvFilterLevel& level, hipStream_t stream);
 hipError_t env_build(EnvDevice& e, const float* d_equirect, int w, int h, hipStream_t stream);
 // A map from a cube mip 0 (n x n RGBA16F faces) and a whole sum pyramid given on the host (test hook pt_debug_env_create_raw)
 hipError_t env_build_raw(EnvDevice& e, int n, const uint16_t* cube_rgba16f, const float* pyramid, hipStream_t stream);

@@ -195,6 +195,25 @@ class Renderer:
         self._check(self.L.pt_env_read(self.h, env, C.byref(n), _p(cube), _p(pyr)))
         return n.value, cube, pyr
 
+    def env_filter(self, env, config=None):
+        """The environment's GGX chain and diffuse cube (include/mipt.h pt_env_filter); config: abi.PtEnvFilterConfig, None = the reference's
+        values.  Asynchronous."""
+        self._check(self.L.pt_env_filter(self.h, env, _ref(config)))
+
+    def env_filter_info(self, env):
+        info = abi.PtEnvFilterInfo()
+        self._check(self.L.pt_env_filter_info_get(self.h, env, C.byref(info)))
+        return info
+
+    def env_filter_read(self, env, which, mip=0, host=True):
+        """One level of the GGX chain (which = abi.ENV_FILTER_GGX) or the diffuse cube (abi.ENV_FILTER_DIFFUSE): (the (6, n, n, 4) uint16
+        RGBA16F texels, or None with host=False; the context-owned device pointer to them as an int)."""
+        n, dev = C.c_int(), C.c_void_p()
+        self._check(self.L.pt_env_filter_read(self.h, env, which, mip, C.byref(n), None, None))
+        texels = np.zeros((6, n.value, n.value, 4), np.uint16) if host else None
+        self._check(self.L.pt_env_filter_read(self.h, env, which, mip, C.byref(n), _p(texels), C.byref(dev)))
+        return texels, dev.value
+
     def set_bounce_limit(self, limit):
         self._check(self.L.pt_set_bounce_limit(self.h, limit))
 

@@ -367,14 +367,75 @@ int pt_scene_set_lights(pt_ctx* ctx, const pt_light* lights, int count);
 /* Pathtracer::BuildTlas instance list (Source/Pathtracer.cpp:185-257); marks the accel dirty. */
 int pt_scene_set_instances(pt_ctx* ctx, const pt_instance_desc* instances, int count);
 
-/* EnvironmentMap::CreateEnvironmentMap (Source/EnvironmentMap.cpp:84-130) minus the raster-only
- * GGX / diffuse cubes: equirect RGB32F -> RGBA16F cube (+mips) -> 1024^2 importance pyramid. */
+/* EnvironmentMap::CreateEnvironmentMap (Source/EnvironmentMap.cpp:84-130), the part the path tracer reads:
+ * equirect RGB32F -> RGBA16F cube (+mips) -> 1024^2 importance pyramid.  The GGX / diffuse cubes of the raster
+ * pass are made on request by pt_env_filter (below). */
 int pt_env_create(pt_ctx* ctx, const float* equirect_rgb32f, int width, int height, int* env_out);
 /* Test hook: copy out the preprocessed maps.  cube_rgba16f: 6*N*N*4 halfs of mip 0 (may be NULL);
  * importance: the whole pyramid, level 0 first (may be NULL).  Sizes via the out params. */
 int pt_env_read(pt_ctx* ctx, int env, int* cube_size_out, uint16_t* cube_rgba16f, float* importance_pyramid);
 /* EnvironmentMap::Destroy (the reference replaces its one environment in place, Source/EnvironmentMap.cpp:84-130). */
 int pt_env_destroy(pt_ctx* ctx, int env);
+/* The environment's GGX and diffuse cubes: EnvironmentMap::GenerateGgxCube / GenerateDiffuseCube -> FilterCube
+ * (Source/EnvironmentMap.cpp:348-401, Shaders/FilterEnvironmentCubeMap.cs.hlsl) -- the prefiltered specular chain and the irradiance cube a
+ * host's raster pass lights with (EnvironmentMap::Map::ggx / ::diffuse).  pt_trace never reads them: the call changes nothing the path tracer
+ * sees (the cube, the pyramid, images, ray counts).  Enqueued on the context's stream, asynchronous like pt_trace; a second call on the same
+ * environment replaces the cubes (a call whose sizes differ from the last one's waits for the stream before it reallocates); pt_env_destroy
+ * and pt_destroy free them.  An environment from the test hook pt_debug_env_create_raw filters like any other.
+ *   Everything below is float32 in the order written, products and sums not fused; / is the correctly rounded division, sqrt the correctly
+ * rounded root; sin, cos are those of pt_trace (evaluated in double, rounded once), log2 is pt_trace's defined log2 (csrc/pt_math.h co_log2);
+ * fmin / fmax return the operand that is not a NaN, saturate(x) = fmin(fmax(x, 0), 1), so saturate(NaN) = 0.  PI = 3.14159265359f, TAU = 2 PI.
+ * N, M: the environment cube's mip-0 size and mip count (sizes N >> k down to 1).
+ *   Levels.  GGX level i = 0 .. ggx_mips - 1 has resolution n_0 = N, n_{i+1} = n_i / 2 (integer: 33, 16, 8) and roughness
+ * a_i = r r with r = (float)i / ((float)ggx_mips - 1.0f) (MipToRoughness, EnvironmentMap.cpp:17-22).  Upstream divides 0 by 0 there when
+ * the chain has ONE level; here a chain of one level has roughness 0 (quirk q30).  The diffuse cube has one level of diffuse_resolution.
+ *   Per output texel (face, x, y) of a level of resolution n, with S = the level's sample count:
+ *     uu = ((float)x + 0.5f) / (float)n;  vv likewise;  d = F + (2 uu - 1) U + (2 vv - 1) V with (F, U, V) of the face
+ *         (CubemapToDirection, Transforms.hlsli:10-50);  normal = d / sqrt((d.x d.x + d.y d.y) + d.z d.z)
+ *     CreateBasis (Common.hlsli:33-42): b = |normal.x| > |normal.z| ? (-normal.y, normal.x, 0) : (0, -normal.z, normal.y), normalised as
+ *         above;  t = cross(b, normal)
+ *     total = (0, 0, 0);  total_weight = 0;  for i = 0 .. S - 1, in this order (one lane sums one texel):
+ *       R2 (Random.hlsli:80-85): g = 1.324717957244746f, c = (1.0f / g, 1.0f / (g g));  s = 0.5f + (float)i c;  u = s - floor(s)
+ *       GGX:      cs, sn = cos, sin(TAU u.x);  ct = sqrt((1 - u.y) / (1 + (a a - 1) u.y));  st = sqrt(1 - ct ct);  h = (st cs, st sn, ct)
+ *                 D = (a a) (h.z > 0 ? 1 : 0) / (e (PI e)) with e = (h.z h.z) (a a - 1) + 1;   pdf = D / 4
+ *                 hw = t h.x + b h.y + normal h.z (per component, summed left to right);  v = -normal;
+ *                 l = v - (2 dot(hw, v)) hw;  weight = saturate(dot(normal, l))
+ *       diffuse:  cs, sn = cos, sin(TAU u.x);  y = 2 u.y - 1;  r = sqrt(1 - y y);  l = normal + (r cs, r sn, y), normalised as above;
+ *                 pdf = saturate(dot(l, normal) / PI);  weight = 1
+ *       omega_s = 1.0f / ((float)S pdf);  omega_p = (4.0f PI) / ((6.0f (float)N) (float)N);  level = 0.5f log2(omega_s / omega_p) + mip_bias
+ *       level = fmin(fmax(level, 0), (float)(M - 1)): D3D's clamp, so a NaN level becomes 0 and +infinity becomes M - 1.  Both occur: at
+ *           a = 0 (GGX level 0) e is 0 and D is 0 / 0, so every sample reads mip 0; a diffuse sample with pdf 0 reads the last mip
+ *       l0 = (int)floor(level);  f = level - (float)l0;  A = the bilinear cube lookup along l in mip l0 (the seamless four-tap lookup of
+ *           pt_trace's environment, csrc/pt_shading.h sample_cube);  c = A if f == 0 or l0 == M - 1, else A (1 - f) + B f with B the
+ *           lookup in mip l0 + 1 (what pt_env_create's importance map does)
+ *       total = total + weight c;  total_weight = total_weight + weight
+ *     out.rgb = total / total_weight rounded to nearest-even half; out.a = 0, as the cube's own mips write it.
+ *   The per-sample values that do not depend on the texel (GGX: h and the clamped level; diffuse: the point (r cs, r sn, y)) are computed
+ * once per level; the result is the per-texel text above bit for bit.  Non-finite texels get no special treatment.  Upstream's sampler
+ * weights are the hardware's fixed-point ones, so parity with real D3D output is unpinned, as everywhere else in this project.
+ *   PT_ERR_BAD_HANDLE for an env that is not live; PT_ERR_INVALID_ARGUMENT, with nothing changed, for a config value out of range;
+ * pt_env_filter_info_get and pt_env_filter_read answer PT_ERR_NOT_READY before the first pt_env_filter of the environment. */
+typedef struct pt_env_filter_config {
+    int32_t ggx_samples;         /* 1..4096, default 256  (EnvironmentMap.cpp:395) */
+    float   ggx_mip_bias;        /* finite,  default 2 */
+    int32_t ggx_mips;            /* 0 = the reference's rule max((int)floor(log2((float)N)) + 1 - 4, 1) (EnvironmentMap.cpp:106-107);
+                                    otherwise 1 .. the number of levels whose resolution N >> i is >= 1 (at most 16) */
+    int32_t diffuse_samples;     /* 1..4096, default 512  (EnvironmentMap.cpp:400) */
+    float   diffuse_mip_bias;    /* finite,  default 3 */
+    int32_t diffuse_resolution;  /* 1..1024, default 256  (EnvironmentMap.cpp:114) */
+} pt_env_filter_config;          /* 24 bytes */
+typedef struct pt_env_filter_info {
+    int32_t ggx_resolution, ggx_mips, diffuse_resolution;
+    float   ggx_roughness[16];   /* a_i of level i; 0 beyond ggx_mips */
+} pt_env_filter_info;            /* 76 bytes */
+int pt_env_filter(pt_ctx* ctx, int env, const pt_env_filter_config* config /* NULL = the reference's values */);
+int pt_env_filter_info_get(pt_ctx* ctx, int env, pt_env_filter_info* out);
+/* One level of one of the two cubes.  which: 0 = GGX, 1 = diffuse (mip 0 only).  *size_out = the level's resolution n.  host and device_out
+ * may each be NULL.  host receives 6 * n * n * 4 halfs (face-major, like pt_env_read) after the stream has been synchronised; device_out
+ * receives the context-owned device pointer to the same texels, valid until the next pt_env_filter on this environment or its
+ * pt_env_destroy, for a host's raster pass (without host the call does not wait: order the reader behind the context's stream).
+ * PT_ERR_INVALID_ARGUMENT for a `which` or `mip` that does not exist. */
+int pt_env_filter_read(pt_ctx* ctx, int env, int which, int mip, int* size_out, uint16_t* host, void** device_out);
 
 /* BuildAllBlas / UpdateAllBlas / BuildTlas (Source/Pathtracer.cpp:138-257).  Called implicitly
  * by pt_trace when the scene is dirty; exposed so it can be timed on its own.

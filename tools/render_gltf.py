@@ -76,6 +76,11 @@ given, the reference's default), applied last before tone mapping: after --denoi
 lets only what is brighter than T glow (default 0 = everything, as upstream).  Not with --bake or --probes: an atlas is not a picture.
   python tools/render_gltf.py lantern.glb --spp 256 --denoise --bloom 0.04 --bloom-radius 6 --out frame.png
 
+--env-cubes PREFIX: with --env, the environment's two raster-pass cubes (pt_env_filter at the reference's values): the prefiltered GGX chain as
+PREFIX_ggx_0.npy, PREFIX_ggx_1.npy, ... (level i holds roughness (i / (levels - 1))^2) and the diffuse irradiance cube as PREFIX_diffuse.npy,
+each a float16 array [6, n, n, 4].  The render itself is unchanged: the path tracer does not read them.
+  python tools/render_gltf.py scene.glb --env sky.hdr --env-cubes sky --out frame.png
+
 --variance-out PREFIX: the variance pass (pt_set_variance), accumulated with the frame: PREFIX.exr (32-bit float RGBA; a name ending in .npy
 gives an array) holds the variance of each pixel's mean, V / (n - 1): rgb per channel, a of the channel sum.  --noise-target X keeps tracing
 batches of --batch samples until no tile's relative standard error (pt_noise_estimate, adaptive sampling's own normalisation) exceeds X, or
@@ -240,7 +245,10 @@ def main():
     ap.add_argument("--bloom", type=float, nargs="?", const=0.01, default=None, metavar="STRENGTH", help="add the reference's bloom to the finished frame; STRENGTH >= 0 (0.01 unless given)")
     ap.add_argument("--bloom-radius", type=int, default=None, metavar="N", help="with --bloom: pyramid levels (0..8, default 4)")
     ap.add_argument("--bloom-threshold", type=float, default=None, metavar="T", help="with --bloom: only what is brighter than T glows (default 0 = everything, as upstream)")
+    ap.add_argument("--env-cubes", default="", metavar="PREFIX", help="with --env: write the environment's GGX chain and diffuse cube (pt_env_filter) as PREFIX_ggx_<level>.npy and PREFIX_diffuse.npy")
     a = ap.parse_args()
+    if a.env_cubes and not a.env:
+        ap.error("--env-cubes needs --env FILE")
     if a.bloom is None and (a.bloom_radius is not None or a.bloom_threshold is not None):
         ap.error("--bloom-radius and --bloom-threshold need --bloom [STRENGTH]")
     if a.bloom is not None:
@@ -358,6 +366,15 @@ def main():
     if a.env:
         img, _ = gltf.load_rgb32f(a.env)
         env = r.env_create(np.ascontiguousarray(img))
+        if a.env_cubes:
+            r.env_filter(env)                                            # the reference's sample counts, biases and sizes
+            info = r.env_filter_info(env)
+            for mip in range(info.ggx_mips):
+                np.save("%s_ggx_%d.npy" % (a.env_cubes, mip), r.env_filter_read(env, abi.ENV_FILTER_GGX, mip)[0].view(np.float16))
+            np.save(a.env_cubes + "_diffuse.npy", r.env_filter_read(env, abi.ENV_FILTER_DIFFUSE)[0].view(np.float16))
+            print("environment cubes: GGX %d^2, %d levels, roughness %s; diffuse %d^2 -> %s_ggx_<level>.npy, %s_diffuse.npy" % (
+                info.ggx_resolution, info.ggx_mips, ", ".join("%.4g" % v for v in list(info.ggx_roughness)[:info.ggx_mips]),
+                info.diffuse_resolution, a.env_cubes, a.env_cubes))
     st = abi.PtSettings.app_defaults()
     st.max_bounces = a.bounces
     if env is None:
