@@ -421,6 +421,7 @@ PROTOTYPES = {
     "pt_set_bounce_limit": (_ci, [_vp, _ci]),
     "pt_set_samples_per_trace": (_ci, [_vp, _ci]),
     "pt_set_null_shadow_culling": (_ci, [_vp, _ci]),
+    "pt_set_watertight": (_ci, [_vp, _ci]),
     "pt_enable_counters": (_ci, [_vp, _ci]),
     "pt_enable_stage_timing": (_ci, [_vp, _ci]),
     "pt_set_kernel_mode": (_ci, [_vp, _ci, _ci]),

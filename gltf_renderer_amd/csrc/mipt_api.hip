@@ -1081,6 +1081,13 @@ int pt_set_null_shadow_culling(pt_ctx* ctx, int enable) {
     return PT_OK;
 }
 
+int pt_set_watertight(pt_ctx* ctx, int enable) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (ctx->watertight != (enable != 0)) ctx->restart_pending = true;        // samples of two intersection rules do not share an image
+    ctx->watertight = enable != 0;
+    return PT_OK;
+}
+
 int pt_set_kernel_mode(pt_ctx* ctx, int mode, int stage_blocks) {
     if (!ctx || (mode != PT_MODE_WAVEFRONT && mode != PT_MODE_MEGAKERNEL)) return PT_ERR_INVALID_ARGUMENT;
     ctx->kernel_mode = mode;

@@ -85,6 +85,7 @@ struct pt_ctx {
     // reset starts a new accumulation (PathtraceScene consumes it; pt_accum_save refuses while it stands; pt_accum_load clears it)
     bool restart_pending = false;
     bool cull_null_shadow = false;
+    bool watertight = false;                                       // pt_set_watertight
     bool counters_enabled = false;
     // ---- adaptive sampling (pt_set_adaptive): per rank-local tile state and the half buffer, for one size and tile shard
     pt_adaptive_config adaptive = {0, 2, 2, 0.0f};
@@ -246,6 +247,7 @@ inline SceneRec scene_fill(const pt_ctx* ctx) {
     sc.n_materials = (uint32_t)ctx->n_materials; sc.n_instances = (uint32_t)ctx->instances.size();
     sc.nodes = ctx->d_nodes.as<Bvh4Node>(); sc.tris = ctx->d_tris.as<TriPacket>(); sc.shade = ctx->d_shade.as<ShadePacket>(); sc.root = ctx->root; sc.num_tris = ctx->n_tris;
     sc.sheen_e = ctx->d_sheen.as<float>(); sc.srgb_lut = ctx->d_srgb.as<float>(); sc.tangent_lut = ctx->d_tangent_lut.as<float2>();
+    sc.watertight = ctx->watertight ? 1u : 0u;
     return sc;
 }
 inline void scene_set_env(SceneRec& sc, const EnvDevice& ed) {

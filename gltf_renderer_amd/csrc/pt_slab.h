@@ -22,7 +22,12 @@
 //   - hence near <= the gate's distance as soon as E (1 - 2 u) >= u (6 |A| + 765 |S|); E = 8 u (|A| + 255 |S|) (1 + d3) leaves room for its
 //     own rounding (|A| 2^-21 and the constant 255 2^-21 are exact, the fma rounds once).
 //   The far side: far >= the gate's fl(fl(hi - o) inv), the mirror image.  The node test's entry distance is then <= the gate's and its exit
-//   distance >= the gate's, and max / min / the * 1.0000004 on the exit distance are monotone: the gate passing implies the node test passing.
+//   distance >= the gate's, and max / min / the * exit_pad on the exit distance are monotone: the gate passing implies the node test passing.
+//   The gate and the node test therefore share ONE pad, exit_pad(watertight).  With the watertight triangle test (pt_set_watertight) it is
+//   wider: a ray the edge rule of pt_traverse.h accepts passes its triangle's box corner within the rounding of its float32 direction, and
+//   with 1.0000004 the gate refuses 10 of the 210 000 edge, vertex and near rays of tests/test_watertight_host.py (printed there; with its edge
+//   and vertex cases at 10 000 rays each: 59 of 700 000, up to 1.4e-3 of the vertex-aimed rays of a rotated box; 1 with 1.000001, none from
+//   1.000002 on), with 1.000004 none.
 // Overflow.  No clamp on S is needed, because E overflows with it: S = +-inf gives E = inf, An = -inf, Af = +inf, and fma(q, S, An / Af) is
 //   NaN (q = 0: 0 inf; else inf - inf) or an infinity of the permissive sign; A = +-inf (|p - o| |inv| > 3.4e38 at inv = +-1e30) gives E = inf and
 //   An or Af = NaN.  fmaxf / fminf drop a NaN, i.e. the plane is not tested: conservative.  A finite fma that rounds to +-inf does so only
@@ -43,6 +48,10 @@
 #endif
 
 namespace pt {
+
+// the slack on a box's exit distance, in the node test and in the candidate gate alike (above)
+constexpr float kExitPad = 1.0000004f, kExitPadWatertight = 1.000004f;
+PT_HD float exit_pad(uint32_t watertight) { return watertight ? kExitPadWatertight : kExitPad; }
 
 // the grid step 2^(exp - 127) of a node axis, and the plane a quantised coordinate stands for in float: the builder checks its boxes
 // against this expression (and against the exact sum, below)

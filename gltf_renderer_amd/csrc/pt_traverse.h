@@ -21,8 +21,9 @@
 //                       slowest ray) while the VALU pipe was ~50 % busy: lane refill is the lever.
 //
 // DXR semantics kept: hit interval tmin < t < tmax, object-space facing (mirrored instances flip), instance
-// cull-disable / force-non-opaque flags, any-hit for MASK instances, accept-first-hit occlusion rays, and
-// the alpha-shadow transmittance product.
+// cull-disable / force-non-opaque flags, any-hit for MASK instances, accept-first-hit occlusion rays,
+// the alpha-shadow transmittance product, and, with pt_set_watertight, a WATERTIGHT triangle test: a ray cannot pass
+// between two triangles that share an edge or a vertex (edge_rule_inside below).
 #pragma once
 #include "pt_shading.h"
 
@@ -118,6 +119,7 @@ PT_DEV void trav_pop(Trav& t, const SceneRec& sc, const int* lds_stack, const in
     t.cur = v;
 }
 
+PT_DEV uint32_t watertight_on(const SceneRec& sc);
 #define PT_CSWAP(a, b) { const bool _s = b < a; const uint64_t _lo = _s ? b : a, _hi = _s ? a : b; a = _lo; b = _hi; }
 
 // One inner-node step: t.cur >= 0 on entry; on exit t.cur is the nearest hit child, or the popped entry, or kTravDone.
@@ -151,6 +153,7 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     // order) and inv is finite and not NaN for every finite direction (trav_init clamps it to +-1e30).  Measured: EXPERIMENTS.md.
     const bool nx = t.inv.x < 0.0f, ny = t.inv.y < 0.0f, nz = t.inv.z < 0.0f;
     const uint32_t wnx = nx ? whx : wlx, wfx = nx ? wlx : whx, wny = ny ? why : wly, wfy = ny ? wly : why, wnz = nz ? whz : wlz, wfz = nz ? wlz : whz;
+    const float pad = exit_pad(watertight_on(sc));                  // (uniform: a scalar select)
     bool enters[4];
     float entry[4];
 #define PT_Q(W, K) ((float)(((W) >> (8 * (K))) & 0xffu))
@@ -159,7 +162,7 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
         float a0 = slab_near(PT_Q(wnx, K), ax), b0 = slab_far(PT_Q(wfx, K), ax), a1 = slab_near(PT_Q(wny, K), ay);          \
         float b1 = slab_far(PT_Q(wfy, K), ay), a2 = slab_near(PT_Q(wnz, K), az), b2 = slab_far(PT_Q(wfz, K), az);           \
         float tn = fmaxf(fmaxf(a0, a1), fmaxf(a2, t.tmin));                                                                \
-        float tx = fminf(fminf(b0, b1), fminf(b2, limit)) * 1.0000004f;                                                    \
+        float tx = fminf(fminf(b0, b1), fminf(b2, limit)) * pad;                                                            \
         enters[K] = tn <= tx && CH != kEmptyChild; entry[K] = tn;                                                          \
     }
     PT_SLAB(0, c0) PT_SLAB(1, c1) PT_SLAB(2, c2) PT_SLAB(3, c3)
@@ -210,7 +213,56 @@ PT_DEV void trav_node_step(Trav& t, const SceneRec& sc, int* lds_stack, int* spi
     } else trav_pop(t, sc, lds_stack, spill);
 }
 
-// What makes the answer independent of the TREE (rare path: only for a triangle the float Moeller-Trumbore test has just accepted).
+// What makes a closed mesh WATERTIGHT (rare path: only for a candidate within the band of one of its triangle's edges).
+//   The float Moeller-Trumbore test takes every triangle by its own (v0, e1, e2), and nothing in that arithmetic makes the two triangles of an
+//   edge agree on which side of it a ray passes: of rays aimed at a shared edge of a closed mesh 2-14 % were refused by BOTH triangles, of rays
+//   aimed at a shared vertex 2-10 % by every triangle of the fan (tests/test_watertight_host.py), and went through the surface.  So inside a
+//   band around the edges, |min(u, v, 1 - (u + v))| < kEdgeBand * scale with scale = max(dot(|tv|, |p|), dot(|d|, |q|)) |1 / det|, the float
+//   test does not decide.  The three edges are evaluated from the EXACT world-space end points, E = d . ((P - o) x (Q - o)) in float64 without
+//   contraction, P and Q in the order of their bit patterns and the sign flipped back: the two triangles of an edge compute the SAME number,
+//   and E == 0 counts as inside for both (the tie rule below then picks one).  The candidate is inside if the three signs are the one the
+//   float determinant names (det = -(E01 + E12 + E20) in exact arithmetic).  Its t is the float test's, its (u, v) the float test's clamped
+//   to u, v >= 0, u + v <= 1.  Outside the band the float test decides as it always did, to the bit: every disagreement between the float
+//   test and the edge values that was found lay within 6.5 * 2^-24 * scale of an edge, and the band is 16.
+//   The exact end points: the packet holds e1 = fl(w1 - w0), not w1, so they are recomputed as k_setup and k_refit_packets computed them,
+//   mul_point of the instance row's transform on the object-space positions of the shading packet of the same index (both of which a refit
+//   keeps current) -- two triangles get the same bits from the same vertex.
+//   SceneRec::watertight (pt_set_watertight) switches it on, together with the wider exit pad it needs (pt_slab.h).  It is OFF by default:
+//   where the float test and the edge values disagree the hit moves to the neighbouring triangle or appears at all, for about one unaimed
+//   ray in 10^5 - 10^6, and every recorded parity figure of this repository was taken with the float test alone; off, every bit is as before.
+constexpr float kEdgeBand = 16.0f * 0x1p-24f;
+PT_DEV uint32_t watertight_on(const SceneRec& sc) {
+#ifdef PT_PROBE_WATERTIGHT    // diagnostic build only: the setting on for every context, so that bench.py as it stands times the watertight path (tools/build_variant.sh)
+    return 1u;
+#else
+    return sc.watertight;
+#endif
+}
+
+PT_DEV double edge_value(vec3 o, vec3 d, vec3 P, vec3 Q) {
+#pragma clang fp contract(off)
+    const uint32_t px = __float_as_uint(P.x), py = __float_as_uint(P.y), pz = __float_as_uint(P.z);
+    const uint32_t qx = __float_as_uint(Q.x), qy = __float_as_uint(Q.y), qz = __float_as_uint(Q.z);
+    const bool swap = qx < px || (qx == px && (qy < py || (qy == py && qz < pz)));
+    const vec3 A = swap ? Q : P, B = swap ? P : Q;
+    const double ax = (double)A.x - (double)o.x, ay = (double)A.y - (double)o.y, az = (double)A.z - (double)o.z;
+    const double bx = (double)B.x - (double)o.x, by = (double)B.y - (double)o.y, bz = (double)B.z - (double)o.z;
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double e = (double)d.x * cx + (double)d.y * cy + (double)d.z * cz;
+    return swap ? -e : e;
+}
+// v0: the packet's, which IS the first exact vertex (k_setup stores mul_point's result); the other two are recomputed.
+PT_DEV bool edge_rule_inside(vec3 o, vec3 d, vec3 v0, const float* __restrict__ M, const float4* __restrict__ pk, float det) {
+#pragma clang fp contract(off)
+    const float4 p1 = pk[1], p2 = pk[2];                              // ShadePacket::v[1..2].pos
+    // mul_point (pt_math.h), written out so that no including file may contract it
+    const vec3 w1 = v3(M[0] * p1.x + M[4] * p1.y + M[8] * p1.z + M[12], M[1] * p1.x + M[5] * p1.y + M[9] * p1.z + M[13], M[2] * p1.x + M[6] * p1.y + M[10] * p1.z + M[14]);
+    const vec3 w2 = v3(M[0] * p2.x + M[4] * p2.y + M[8] * p2.z + M[12], M[1] * p2.x + M[5] * p2.y + M[9] * p2.z + M[13], M[2] * p2.x + M[6] * p2.y + M[10] * p2.z + M[14]);
+    const double s = det > 0.0f ? -1.0 : 1.0;
+    return edge_value(o, d, v0, w1) * s >= 0.0 && edge_value(o, d, w1, w2) * s >= 0.0 && edge_value(o, d, w2, v0) * s >= 0.0;
+}
+
+// What makes the answer independent of the TREE (rare path: only for a triangle the triangle test has just accepted).
 //  (1) The box gate.  The float test does not decide "inside" exactly: it accepts rays that pass a few ulp (of the ray's length, more at
 //      grazing incidence) outside the triangle, hence sometimes outside the triangle's box, and whether a tree's boxes cull such a ray
 //      before the triangle is asked depends on the tree -- two trees (this one, the CPU oracle's binary one) then disagree on about one ray
@@ -230,7 +282,8 @@ PT_DEV bool candidate_stands(const Trav& t, const SceneRec& sc, vec3 v0, vec3 e1
     const float a2 = own_box_t(lo.z, t.o.z, t.inv.z), b2 = own_box_t(hi.z, t.o.z, t.inv.z);
     const float tn = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), t.tmin));
     const float tx = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fmaxf(a2, b2));
-    if (!(tn <= tx * 1.0000004f && tn <= tt * 1.0000004f)) return false;
+    const float pad = exit_pad(watertight_on(sc));
+    if (!(tn <= tx * pad && tn <= tt * pad)) return false;
     if (tt < limit) return true;
     if (!(t.mode == 0 && t.best.tri >= 0)) return false;                // tt == limit: the interval's end, or a tie with the hit held
     const uint4 h0 = *(const uint4*)((const float4*)sc.tris + (size_t)t.best.tri * kTriFloat4), h1 = *(const uint4*)((const float4*)sc.tris + (size_t)t.best.tri * kTriFloat4 + 1);
@@ -261,7 +314,19 @@ PT_DEV void trav_leaf_step(Trav& t, const SceneRec& sc, const int* lds_stack, co
         float v = dot(t.d, q) * invd;
         float tt = dot(e2, q) * invd;
         float limit = t.all_candidates ? t.tmax : t.best.t;
-        bool ok = (u >= 0.0f) && (u <= 1.0f) && (v >= 0.0f) && (u + v <= 1.0f) && (tt > t.tmin) && (tt <= limit);
+        bool inside = (u >= 0.0f) && (u <= 1.0f) && (v >= 0.0f) && (u + v <= 1.0f);
+        const bool in_range = (tt > t.tmin) && (tt <= limit);
+        if (watertight_on(sc)) {
+            // the band around the triangle's edges inside which the float test does not decide (above): kEdgeBand * scale, scale = the larger
+            // of dot(|tv|, |p|) and dot(|d|, |q|) times |1 / det| -- the products the sums of u and v are made of
+            const float su = fabsf(tv.x * p.x) + fabsf(tv.y * p.y) + fabsf(tv.z * p.z), sv = fabsf(t.d.x * q.x) + fabsf(t.d.y * q.y) + fabsf(t.d.z * q.z);
+            const float band = kEdgeBand * fmaxf(su, sv) * fabsf(invd);
+            if (__builtin_expect(in_range && fabsf(fminf(fminf(u, v), 1.0f - (u + v))) < band, 0)) {
+                inside = edge_rule_inside(t.o, t.d, v0, sc.instances[__float_as_uint(q0.w)].gpu.transform, (const float4*)(sc.shade + tri), det);
+                u = fminf(fmaxf(u, 0.0f), 1.0f); v = fminf(fmaxf(v, 0.0f), 1.0f - u);
+            }
+        }
+        bool ok = inside && in_range;
         if (ok) ok = candidate_stands(t, sc, v0, e1, e2, tt, limit, __float_as_uint(q0.w), __float_as_uint(q1.w));
         if (ok && (t.mask & tflags & 0xffu)) {
             bool front = (det > 0.0f) != ((tflags & TF_MIRRORED) != 0);

@@ -191,6 +191,7 @@ struct SceneRec {
     uint32_t deep_entries, deep_lanes;
     uint32_t small_tables;            // 1: every instance row, material and light of the scene is in the shade stage's LDS copies (set as a CONSTANT by the kernel
                                       // copy compiled for such scenes, k_wf_shade<.., true>: the table lookups then lose their global-memory branch); 0 elsewhere
+    uint32_t watertight;              // pt_set_watertight: the edge rule of the triangle test and the wider exit pad (pt_traverse.h, pt_slab.h)
 };
 
 // SceneConstants (PathTracer.lib.hlsl:10-30) plus the tile shard of this rank.

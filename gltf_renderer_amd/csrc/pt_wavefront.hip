@@ -394,8 +394,12 @@ PT_DEV void env_prepass(const SceneRec& sc, const FrameConstants& fc, const WfBu
     __syncthreads();                       // the stack memory goes back to the traversal
 }
 
+// Waves per SIMD the traversal kernels are compiled for.  Their 26-KiB LDS stacks admit six, and six need at most 80 VGPRs: the float64 edge
+// rule of the leaf step (pt_traverse.h edge_rule_inside, a branch only candidates within rounding of an edge take) would otherwise raise the kernels to
+// 101-117 VGPRs, four waves; bound to six the compiler spills inside that branch instead -- and one 8-byte value in the ray refill, which every build pays for,
+// the setting on or off (scratch 192 -> 240-352 B; no loss measured: profiles/EXPERIMENTS.md).
 #ifndef PT_TRACE_WAVES
-#define PT_TRACE_WAVES 1
+#define PT_TRACE_WAVES 6
 #endif
 // `bounce` = the bounce whose shade stage follows: it fills closest queue cur ^ 1 and the shadow counter of that bounce.
 // DEFAULTS (k_wf_trace, k_wf_traverse): a copy compiled for the settings that leave the rays' flags alone -- no back-face culling, no alpha

@@ -531,6 +531,10 @@ class Renderer:
         """Skip shadow rays whose contribution is exactly zero (same image, fewer rays than the reference traces)."""
         self._check(self.L.pt_set_null_shadow_culling(self.h, int(bool(on))))
 
+    def set_watertight(self, on):
+        """The watertight triangle test (include/mipt.h pt_set_watertight): no ray passes between two triangles that share an edge or a vertex."""
+        self._check(self.L.pt_set_watertight(self.h, int(bool(on))))
+
     def enable_counters(self, on):
         self._check(self.L.pt_enable_counters(self.h, int(on)))
 

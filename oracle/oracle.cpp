@@ -183,7 +183,7 @@ static float3 SampleCubeLevel(const EnvMap& e, float3 d, float level, int* taps1
 // ------------------------------------------------------------------------------------------------
 // Acceleration structure: CPU LBVH over world-space triangles (Morton -> sort -> radix-tree split
 // -> bottom-up fit).  Replaces the driver BVH (RayTracingAccelerationStructure.cpp:157,213,289).
-struct Tri { float3 v0, e1, e2; uint32_t inst, prim; uint32_t flags; };   // flags bit0: instance mirrored
+struct Tri { float3 v0, e1, e2; uint32_t inst, prim; uint32_t flags; float3 w1, w2; };   // flags bit0: instance mirrored; w1, w2: the exact world-space vertices (e1 = fl(w1 - v0))
 struct BNode { float3 lo[2], hi[2]; int child[2]; };                       // child<0: leaf ~tri
 struct Bvh {
     std::vector<Tri> tris;
@@ -380,6 +380,7 @@ struct Oracle {
     Bvh bvh;
     bool accel_dirty = true;
     bool brute_force = false;
+    bool watertight = false;               // orc_set_watertight: the edge rule of Tracer::intersect and the wider exit pad (off: the float test alone, as the product's default)
     // diagnostics (tools/diag_flip.py): trace only the pixels of a window; record every ray of one pixel with what it found
     uint32_t win[4] = {0, 0, 0xffffffffu, 0xffffffffu};             // x0, y0, x1, y1 (exclusive)
     int64_t log_px = -1, log_py = -1;
@@ -668,24 +669,57 @@ struct Tracer {
     //    so no ancestor culls a candidate that stands;
     //  * tie_with: the triangle that holds the current closest hit at distance tmax (or null): a candidate at EXACTLY that distance replaces
     //    it when its (instance, primitive) is lower -- DXR leaves equal distances to the traversal order.
+    // And, with orc_set_watertight (the product's pt_set_watertight), the rule that makes a closed mesh watertight (pt_traverse.h
+    // edge_rule_inside states it the same way): inside a band around the
+    // triangle's edges, |min(u, v, 1 - (u + v))| < kEdgeBand * max(dot(|tv|, |p|), dot(|d|, |q|)) |1 / det|, the float test does not decide.  The
+    // three edges are evaluated from the exact world-space end points (v0, w1, w2), E = d . ((P - o) x (Q - o)) in double, P and Q in the order
+    // of their bit patterns and the sign flipped back, so the two triangles of an edge compute the same number; zero counts as inside for both.
+    // t stays the float test's, (u, v) are the float test's clamped to u, v >= 0, u + v <= 1.  Outside the band every bit is the float test's.
+    static constexpr float kEdgeBand = 16.0f * 0x1p-24f;
+    // the slack on a box's exit distance, in the node test and the gate alike; wider with the edge rule (csrc/pt_slab.h exit_pad)
+    float exit_pad() const { return o.watertight ? 1.000004f : 1.0000004f; }
+    static double edge_value(const float3& o, const float3& d, const float3& P, const float3& Q) {
+        uint32_t pb[3], qb[3];
+        memcpy(pb, &P, 12); memcpy(qb, &Q, 12);
+        const bool swap = qb[0] < pb[0] || (qb[0] == pb[0] && (qb[1] < pb[1] || (qb[1] == pb[1] && qb[2] < pb[2])));
+        const float3& A = swap ? Q : P; const float3& B = swap ? P : Q;
+        const double ax = (double)A.x - (double)o.x, ay = (double)A.y - (double)o.y, az = (double)A.z - (double)o.z;
+        const double bx = (double)B.x - (double)o.x, by = (double)B.y - (double)o.y, bz = (double)B.z - (double)o.z;
+        const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+        const double e = (double)d.x * cx + (double)d.y * cy + (double)d.z * cz;
+        return swap ? -e : e;
+    }
+    static bool edge_rule_inside(const Tri& t, const RayDesc& r, float det) {
+        const double s = det > 0.0f ? -1.0 : 1.0;
+        return edge_value(r.origin, r.direction, t.v0, t.w1) * s >= 0.0 && edge_value(r.origin, r.direction, t.w1, t.w2) * s >= 0.0 &&
+               edge_value(r.origin, r.direction, t.w2, t.v0) * s >= 0.0;
+    }
     inline bool intersect(const Tri& t, const RayDesc& r, const float3& inv, float tmax, float& ot, float& ou, float& ov, bool& front, const Tri* tie_with = nullptr) const {
         float3 p = cross(r.direction, t.e2);
         float det = dot(t.e1, p);
         if (det == 0.0f || !(det == det)) return false;
         float invd = 1.0f / det;
         float3 tv = r.origin - t.v0;
-        float u = dot(tv, p) * invd;
-        if (!(u >= 0.0f) || u > 1.0f) return false;
+        const float ux = tv.x * p.x, uy = tv.y * p.y, uz = tv.z * p.z;
+        float u = (ux + uy + uz) * invd;
         float3 q = cross(tv, t.e1);
-        float v = dot(r.direction, q) * invd;
-        if (!(v >= 0.0f) || u + v > 1.0f) return false;
+        const float vx = r.direction.x * q.x, vy = r.direction.y * q.y, vz = r.direction.z * q.z;
+        float v = (vx + vy + vz) * invd;
         float tt = dot(t.e2, q) * invd;
         if (!(tt > r.tmin) || !(tt <= tmax)) return false;
+        bool inside = (u >= 0.0f) && (u <= 1.0f) && (v >= 0.0f) && (u + v <= 1.0f);
+        const float band = kEdgeBand * fmaxf(fabsf(ux) + fabsf(uy) + fabsf(uz), fabsf(vx) + fabsf(vy) + fabsf(vz)) * fabsf(invd);
+        if (o.watertight && fabsf(fminf(fminf(u, v), 1.0f - (u + v))) < band) {
+            inside = edge_rule_inside(t, r, det);
+            u = fminf(fmaxf(u, 0.0f), 1.0f); v = fminf(fmaxf(v, 0.0f), 1.0f - u);
+        }
+        if (!inside) return false;
         float3 lo, hi; tri_bounds(t, lo, hi);
         float3 t0 = (lo - r.origin) * inv, t1 = (hi - r.origin) * inv;
         float tn = hmax(hmax(hmin(t0.x, t1.x), hmin(t0.y, t1.y)), hmax(hmin(t0.z, t1.z), r.tmin));
         float tx = hmin(hmin(hmax(t0.x, t1.x), hmax(t0.y, t1.y)), hmax(t0.z, t1.z));
-        if (!(tn <= tx * 1.0000004f && tn <= tt * 1.0000004f)) return false;
+        const float pad = exit_pad();
+        if (!(tn <= tx * pad && tn <= tt * pad)) return false;
         if (!(tt < tmax)) {
             if (!(tie_with && (t.inst < tie_with->inst || (t.inst == tie_with->inst && t.prim < tie_with->prim)))) return false;
         }
@@ -755,7 +789,7 @@ struct Tracer {
                     float3 t0 = (n.lo[c] - r.origin) * inv, t1 = (n.hi[c] - r.origin) * inv;
                     float tmn = hmax(hmax(hmin(t0.x, t1.x), hmin(t0.y, t1.y)), hmax(hmin(t0.z, t1.z), r.tmin));
                     float tmx = hmin(hmin(hmax(t0.x, t1.x), hmax(t0.y, t1.y)), hmin(hmax(t0.z, t1.z), limit));
-                    tmx *= 1.0000004f;
+                    tmx *= exit_pad();
                     hitc[c] = tmn <= tmx; tn[c] = tmn;
                 }
                 if (hitc[0] && hitc[1]) {
@@ -1017,7 +1051,7 @@ static void build_accel(Oracle& o, int nthreads = 1) {
                     GetIndices(o, in.index_descriptor, p, v);
                     float3 w[3];
                     for (int k = 0; k < 3; k++) w[k] = xyz(mul(in.transform, F4(fetch_pos(o, in.position_descriptor, v[k]), 1)));
-                    Tri t; t.v0 = w[0]; t.e1 = w[1] - w[0]; t.e2 = w[2] - w[0]; t.inst = (uint32_t)ii; t.prim = p; t.flags = det < 0 ? 1u : 0u;
+                    Tri t; t.v0 = w[0]; t.e1 = w[1] - w[0]; t.e2 = w[2] - w[0]; t.inst = (uint32_t)ii; t.prim = p; t.flags = det < 0 ? 1u : 0u; t.w1 = w[1]; t.w2 = w[2];
                     o.bvh.tris[g] = t;
                 }
             }
@@ -1344,6 +1378,7 @@ void orc_math(int op, const float* a, const float* b, float* out, int n) {
 }
 void orc_set_bounce_limit(void* h, int limit) { ((Oracle*)h)->bounce_limit = limit; }
 void orc_set_brute_force(void* h, int on) { ((Oracle*)h)->brute_force = on != 0; }
+void orc_set_watertight(void* h, int on) { ((Oracle*)h)->watertight = on != 0; }
 // diagnostics: restrict orc_trace to a pixel window (x1 = 0: whole frame); log the rays of one pixel (x < 0: off) and read the log back
 void orc_set_window(void* h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     Oracle* o = (Oracle*)h;

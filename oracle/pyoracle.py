@@ -49,6 +49,7 @@ def lib():
         L.orc_env_read.restype = None
         L.orc_set_bounce_limit.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_brute_force.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_watertight.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_window.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.orc_set_window.restype = None
         L.orc_set_ray_log.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -199,6 +200,10 @@ class Oracle:
 
     def set_brute_force(self, on):
         self.L.orc_set_brute_force(self.h, int(on))
+
+    def set_watertight(self, on):
+        """The watertight triangle test, as the product's pt_set_watertight (off by default on both sides)."""
+        self.L.orc_set_watertight(self.h, int(bool(on)))
 
     def set_window(self, x0=0, y0=0, x1=0, y1=0):
         """Diagnostics: trace() touches only the pixels x0 <= x < x1, y0 <= y < y1 (no arguments: the whole frame again)."""
