@@ -7,7 +7,7 @@
 //   pt_matte_extract  k_matte_extract: one lane per pixel reads the pixel's K / 2 float4 and adds up, in rank order, the coverages whose id
 //                     is in the caller's set.  The set (at most 64 ids, fixed on the host) travels in the kernel's arguments: the lanes of
 //                     a wave compare against scalar registers, nothing is allocated or copied, and the call is one launch on the stream.
-// The record and resolve kernels (k_wf_matte, k_wf_matte_resolve) are stages of the wavefront pipeline and live in pt_wavefront.hip.
+// The record and resolve kernels (k_wf_matte, k_wf_matte_resolve) are stages of the wavefront pipeline and live in wf_passes.hip.
 #include "pt_ctx.h"
 #include "pt_matte.h"
 

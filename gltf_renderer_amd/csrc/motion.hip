@@ -7,7 +7,7 @@
 //   pt_reproject        k_reproject: one lane per pixel, four taps of the previous frame at the pixel's motion vector, no LDS.  A pure function
 //                       of its images; tests/motion_ref.py restates it in numpy float32, rounding for rounding.
 //   pt_debug_motion     (mipt_debug.hip) launches k_debug_motion: k_debug_intersect's closest hit, then pt_motion.h motion_record.
-// The record and resolve kernels (k_wf_motion, k_wf_motion_resolve) live in pt_wavefront.hip.  Compiled without floating-point contraction
+// The record and resolve kernels (k_wf_motion, k_wf_motion_resolve) live in wf_passes.hip.  Compiled without floating-point contraction
 // (Makefile), with IEEE division.
 #include <cmath>
 

@@ -1,5 +1,5 @@
 // pt_bake.h -- texture-space baking (pt_set_bake; include/mipt.h defines it operation by operation, tests/bake_ref.py restates it): the
-// device functions the UV rasteriser (bake.hip) and the bake's generate kernel (pt_wavefront.hip k_wf_generate_bake) share, so that the
+// device functions the UV rasteriser (bake.hip) and the bake's generate kernel (wf_passes.hip k_wf_generate_bake) share, so that the
 // triangle the coverage map chose and the triangle a sample starts on are told by ONE statement of the edge functions.
 // Both translation units are compiled without floating-point contraction (Makefile) and `/` and sqrtf are the compiler's correctly rounded
 // sequences: every operation below is the IEEE float32 operation, in the order written.

@@ -117,7 +117,7 @@ struct SkinArgs {
 void launch_skin(const SkinArgs& a, bool use_mfma, hipStream_t stream);
 void launch_tonemap(const float4* in, uint32_t w, uint32_t h, const pt_tonemap_config& cfg, float* out_rgb, uint32_t* out_rgba8, hipStream_t stream);
 
-// ---- pt_wavefront.hip / pt_kernel.hip ---------------------------------------------------------
+// ---- pt_wavefront.hip / wf_passes.hip / pt_kernel.hip -----------------------------------------
 size_t traversal_grid_lanes(int stage_blocks);   // lanes of the widest traversal launch of a wavefront trace with that many stage workgroups
 constexpr uint32_t kDeepStackMax = 1024;      // most stack entries a tree may ask for (64 on chip + a deep stack in memory); a clustered tree beyond it is rebuilt as a radix tree
 int traversal_stack_capacity();          // entries a ray's traversal stack holds on chip (LDS part + scratch spill); deeper trees get SceneRec::deep_stack
@@ -127,7 +127,10 @@ struct StageTimers {
     std::vector<hipEvent_t> ev;          // ev[0] = start; ev[k + 1] = after the k-th launch
     std::vector<uint8_t> kind;           // STAGE_* of the k-th launch
     size_t used = 0;                     // launches recorded by the last pt_trace
+    hipEvent_t event_at(size_t i);       // ev[i], created on first use; nullptr if it cannot be
+    void mark(int kind, hipStream_t stream);     // the launch just enqueued on `stream` was of stage `kind`
 };
+inline void mark_stage(StageTimers* timers, int kind, hipStream_t stream) { if (timers) timers->mark(kind, stream); }     // (null: timing is off)
 void launch_megakernel(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, hipStream_t stream);
 // pt_lens_focus_at: d_out = 2 floats {hit, view-space depth}
 void launch_lens_focus(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float sx, float sy, uint32_t rf, float* d_out, hipStream_t stream);
@@ -150,7 +153,7 @@ struct AdaptiveArgs {
 // First-hit AOVs (pt_set_aov): what k_wf_aov and the AOV instantiations of k_wf_resolve take as their own argument.  One record per
 // slot and target, written by k_wf_aov between the primary traversal and the first shade stage, blended by the resolve.
 struct AovArgs {
-    float4* rec_albedo;       // per slot: (sp.albedo, 1); zeros for a miss or a non-finite sample (workspace, set by launch_wavefront)
+    float4* rec_albedo;       // per slot: (sp.albedo, 1); zeros for a miss or a non-finite sample (workspace, set by passes_begin)
     float4* rec_normal;       // per slot: (sp.n, hit.t); zeros likewise
     float4* albedo;           // the caller's targets, res_x * res_y each; either may be nullptr
     float4* normal_depth;
@@ -174,7 +177,7 @@ struct ProbeArgs {
 // ID mattes (pt_set_matte): what k_wf_matte and k_wf_matte_resolve take as their own argument.  One id per slot, written by k_wf_matte
 // between the primary traversal and the first shade stage (beside k_wf_aov), folded into the caller's layers by k_wf_matte_resolve.
 struct MatteArgs {
-    uint32_t* rec;            // per slot: the id of the first ray's closest hit, 0 for a miss or a slot without a ray (workspace, set by launch_wavefront)
+    uint32_t* rec;            // per slot: the id of the first ray's closest hit, 0 for a miss or a slot without a ray (workspace, set by passes_begin)
     const uint32_t* ids;      // the id of every row of the instance table (PT_MATTE_INSTANCE) or the material table (owned by the context)
     uint32_t n_ids;
     int32_t kind, ranks;      // PT_MATTE_*; K = 2, 4, 6 or 8
@@ -184,7 +187,7 @@ struct MatteArgs {
 // k_wf_motion between the primary traversal and the first shade stage (beside k_wf_aov), blended into the caller's target by
 // k_wf_motion_resolve.  The matrices are wave-uniform kernel arguments (scalar registers).
 struct MotionArgs {
-    float4* rec;              // per slot: the sample's record, zeros for a miss or a non-finite record (workspace, set by launch_wavefront)
+    float4* rec;              // per slot: the sample's record, zeros for a miss or a non-finite record (workspace, set by passes_begin)
     const float4* snap;       // the previous pose: 3 float4 (v0, e1, e2) per triangle at InstanceRec::tri_offset + prim; nullptr = the current packets
     uint32_t n_snap;          // entries of snap
     uint32_t width, height;
@@ -198,7 +201,8 @@ struct VarianceArgs {
     float4* target;           // the caller's target, res_x * res_y: (population variance of r, g, b; of the channel sum)
 };
 // The optional passes of one wavefront trace: which are on, and the argument block of each that is (the block of a pass that is off is
-// not looked at).  PathtraceScene fills it (select_passes and the *_setup functions); launch_wavefront and wavefront_workspace_bytes read it.
+// not looked at).  PathtraceScene fills it (select_passes and the *_setup functions); launch_wavefront, wf_passes.hip
+// (the passes' kernels and their launches) and wavefront_workspace_bytes read it.
 struct WavefrontPasses {
     bool adaptive = false; AdaptiveArgs ad = {};   // off: every tile of the rank is rendered (the plain kernels); on: the adaptive generate / resolve run
     bool aov = false; AovArgs av = {};             // off: the plain resolve, no k_wf_aov launch; on: the caller's targets (the workspace holds the records; so below)

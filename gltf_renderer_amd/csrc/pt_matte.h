@@ -1,5 +1,5 @@
 // pt_matte.h -- ID mattes (pt_set_matte, include/mipt.h): the exponent fix of an id and the fold of a pixel's ranked (id, coverage) pairs,
-// shared by k_wf_matte_resolve (pt_wavefront.hip) and the host entry points and k_matte_extract (matte.hip).  tests/matte_ref.py restates it.
+// shared by k_wf_matte_resolve (wf_passes.hip) and the host entry points and k_matte_extract (matte.hip).  tests/matte_ref.py restates it.
 //
 // Ids are 32-bit patterns that travel through float4 images: they are moved and compared as integers only (__float_as_uint /
 // __uint_as_float are register renames), never through float arithmetic or a float compare -- an id may read as any normal float.
@@ -15,7 +15,7 @@ __host__ __device__ inline uint32_t matte_fix(uint32_t h) {
     return (e == 0u || e == 255u) ? h ^ (1u << 23) : h;
 }
 
-PT_DEV float4 blend_aov(float4 h, int accumulated, float4 v);           // pt_wavefront.hip: the running mean of four components
+PT_DEV float4 blend_aov(float4 h, int accumulated, float4 v);           // pt_wf_stage.h: the running mean of four components
 
 template <int R>
 struct MatteRanks { uint32_t id[R]; float cov[R]; };                    // id 0 = an empty rank, whose coverage is +0

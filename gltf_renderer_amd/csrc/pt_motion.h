@@ -1,4 +1,4 @@
-// pt_motion.h -- motion vectors (pt_set_motion, include/mipt.h): the record of one sample, shared by k_wf_motion (pt_wavefront.hip), the
+// pt_motion.h -- motion vectors (pt_set_motion, include/mipt.h): the record of one sample, shared by k_wf_motion (wf_passes.hip), the
 // hook's k_debug_motion and k_motion_snapshot (motion.hip).  Device code only; the arithmetic is that of the header, operation by operation,
 // and both translation units compile it without floating-point contraction (Makefile), so that the hook's records are pt_trace's.
 #pragma once

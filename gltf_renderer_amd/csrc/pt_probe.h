@@ -1,5 +1,5 @@
 // pt_probe.h -- light-probe baking (pt_set_probes, pt_probe_project; include/mipt.h defines both operation by operation, tests/probe_ref.py
-// restates them): the device functions the probes' generate kernel and its hook (pt_wavefront.hip k_wf_generate_probe, debug_wf.hip debug_probe_ray)
+// restates them): the device functions the probes' generate kernel and its hook (wf_passes.hip k_wf_generate_probe, debug_wf.hip debug_probe_ray)
 // and the projection (probe.hip) share, so that the direction a texel is traced along and the direction it is projected with are told by ONE
 // mapping: square_to_sphere of pt_shading.h, the equal-area octahedral map of the environment importance map.
 // Both translation units are compiled without floating-point contraction (Makefile): every operation below is the float32 operation, in the

@@ -1,5 +1,6 @@
-// pt_wavefront.h -- what the wavefront stages (pt_wavefront.hip) share with their test hooks (debug_wf.hip): the kernels' buffer record, the
-// queue formats' constants and the traversal stages' ray flags and launches, so that the hook launches what a frame launches.
+// pt_wavefront.h -- what the wavefront stages (pt_wavefront.hip, wf_passes.hip) share with their test hooks (debug_wf.hip): the kernels' buffer
+// record, the queue formats' constants and the traversal stages' ray flags and launches, so that the hook launches what a frame launches; and
+// the host functions of the optional passes that launch_wavefront calls.  No device code: the stage kernels' own vocabulary is pt_wf_stage.h.
 #pragma once
 #include "pt_traverse.h"
 #include "pt_host.h"
@@ -61,5 +62,13 @@ void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& 
 void launch_wf_traverse(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int nxt, int b, uint32_t rf,
                         uint32_t rmask, Counters* counters);
 void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const WfBuffers& w, int b, uint32_t flags, float tmax, Counters* counters);
+
+// ---- the optional passes (wf_passes.hip), in the order launch_wavefront calls them.  PassArgs: the call's passes, stream and timers, and the
+// argument blocks as the kernels take them (passes_begin: zeros for a pass that is off, the record pointers from the layout, the records cleared).
+struct PassArgs { const WavefrontPasses& on; hipStream_t stream; StageTimers* timers; AdaptiveArgs ad; AovArgs av; MatteArgs mt; MotionArgs mo; };
+hipError_t passes_begin(PassArgs& a, void* workspace, const WorkspaceLayout& lay, uint32_t slots);
+void launch_pass_generate(const PassArgs& a, dim3 stage, const FrameConstants& fc, const WfBuffers& wf, Counters* counters);     // a bake's or a probe atlas's
+void launch_first_hit_passes(const PassArgs& a, dim3 stage, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& wf);  // AOV, matte, motion
+void launch_pass_resolves(const PassArgs& a, dim3 full, const FrameConstants& fc, const WfBuffers& wf, const float4* output);    // matte, motion, variance
 
 }  // namespace pt

@@ -18,17 +18,11 @@
 // env-shadow term, then the light-shadow term of that vertex), independent of queue order, so frames are
 // bit-reproducible and N tile shards compose bit-exactly.
 //
+// This file: the stages every trace runs -- generate, trace, shade, fused traversal, shadow, resolve -- and the driver, launch_wavefront.  The
+// optional passes (bake / probe generate, AOVs, mattes, motion vectors, variance) are wf_passes.hip's; pt_wf_stage.h is what the two share.
 // Product code only: the test hooks that run this file's stages are compiled with its flags in debug_wf.hip (pt_wavefront.h: what they share).
 #define PT_LUT_LDS 1          // every stage kernel of this file stages the sRGB table into LDS (pt_shading.h stage_luts)
-#include <type_traits>
-
-#include "pt_vertex.h"
-#include "pt_wavefront.h"
-#include "pt_workspace.h"
-#include "pt_bake.h"
-#include "pt_probe.h"
-#include "pt_matte.h"
-#include "pt_motion.h"
+#include "pt_wf_stage.h"
 
 #ifdef PT_TIMING                 // diagnostic build only (tools/shade_sections.py); not part of the C-ABI
 namespace pt { __device__ unsigned long long pt_timing[12]; }
@@ -63,17 +57,6 @@ extern "C" int pt_debug_read_util(unsigned long long* out16, int reset) {
 #endif
 namespace pt {
 
-// (WfBuffers, kMissTri, kNoHint and shadow_counter: pt_wavefront.h, shared with the test hooks of debug_wf.hip)
-// Queue entries are written once and read once, a stage apart, by then long evicted from the 4-MiB L2s: they are moved with the
-// non-temporal hint (QLD / QST) so that they do not push the tree's nodes and triangle packets out on their way through.  The per-path
-// state records are accessed plainly.
-typedef float nt_v4f __attribute__((ext_vector_type(4)));
-PT_DEV float4 nt_load(const float4& p) { const nt_v4f v = __builtin_nontemporal_load((const nt_v4f*)&p); return make_float4(v.x, v.y, v.z, v.w); }
-PT_DEV uint32_t nt_load(const uint32_t& p) { return __builtin_nontemporal_load(&p); }
-PT_DEV void nt_store(float4& p, const float4 v) { nt_v4f q; q.x = v.x; q.y = v.y; q.z = v.z; q.w = v.w; __builtin_nontemporal_store(q, (nt_v4f*)&p); }
-PT_DEV void nt_store(uint32_t& p, const uint32_t v) { __builtin_nontemporal_store(v, &p); }
-#define QLD(p) nt_load(p)
-#define QST(p, v) nt_store((p), (v))
 // A load that writes LDS and no register (gfx950 global_load_lds_dword / _dwordx4): every active lane's BYTES bytes at `src` land at
 // wave_base + lane * BYTES; a lane that is masked off writes nothing.  It counts in vmcnt like any load.  lds_fetch_queue: the queues' non-temporal
 // policy (the `nt` bit QLD's loads carry: 2).
@@ -86,8 +69,6 @@ PT_DEV void lds_fetch_queue(const uint32_t* src, uint32_t* wave_base) { PT_LDS_F
 PT_DEV void wait_vector_memory() { __builtin_amdgcn_s_waitcnt(0x0f70); asm volatile("" ::: "memory"); }
 PT_DEV void wait_lds() { asm volatile("" ::: "memory"); __builtin_amdgcn_s_waitcnt(0xc07f); asm volatile("" ::: "memory"); }
 
-#define PEND_ENV(s) wf.pend[2u * (s)]
-#define PEND_LIGHT(s) wf.pend[2u * (s) + 1u]
 // The random-sequence counter every path holds after its camera ray (camera_ray draws once): the state of a path at its FIRST vertex is a
 // constant -- L = 0, beta = 1, pdf = 0, throughput = 1, rc = kRcAfterCamera, nothing pending -- so the generate stage writes no state and
 // the first shade stage reads none.
@@ -97,35 +78,6 @@ constexpr int kRcAfterCamera = 1;
 // consumer, the shade stage of the next vertex, which already reads the path's queue entry: they ride in two more arrays parallel to the
 // closest-ray queue (q_beta / q_thr, coalesced both ways) instead of two slot-indexed arrays (a divergent load and store each).
 
-// wave64 ballot compaction into a shard counter: lanes with `pred` get consecutive indices; one atomic per wave.
-PT_DEV uint32_t queue_push(uint32_t* counter, bool pred) {
-    const unsigned long long m = __ballot(pred);
-    if (m == 0) return 0;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t rank = __popcll(m & ((1ull << lane) - 1ull));
-    uint32_t base = 0;
-    const int leader = __ffsll((long long)m) - 1;
-    if ((int)lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = __shfl(base, leader, 64);
-    return base + rank;
-}
-
-// Every stage launch has the same grid: kShards * blocks_per_shard workgroups.  Workgroup b: shard b % kShards, member b / kShards.
-struct ShardView { uint32_t shard, member, stride; };
-PT_DEV ShardView shard_view(const WfBuffers& wf) {
-    ShardView v;
-    v.shard = blockIdx.x % kShards;
-    v.member = blockIdx.x / kShards;
-    v.stride = wf.blocks_per_shard * kBlock;
-    return v;
-}
-// Where the generate and shade stages count (flush_shard_tallies, pt_vertex.h): the spare words of the shard's line of cnt[3], the closest
-// trace stage's fetch head.  That line is quiet while either stage runs -- nothing fetches from it, the shade stage's member 0 only stores
-// word 0 -- so a launch puts ~32 atomics on each of 256 lines where it used to put ~8 000 on the one line of Counters.  launch_wavefront's
-// memset clears the words with the counters; k_wf_resolve, the last launch of every trace, folds them into Counters.  (The generate and
-// shade kernels keep their `counters` argument, now unread: the kernel-argument layout stays what it was.)
-static_assert((kTallyPrimary + kTallies) * 8 <= (int)kCounterStride * 4, "the tallies must fit the shard counter's line behind its word 0");
-PT_DEV unsigned long long* shard_tallies(const WfBuffers& wf, uint32_t shard) { return (unsigned long long*)(wf.cnt[3] + shard * kCounterStride); }
 // One wave of the resolve's workgroup 0: four shards a lane, a wave64 sum, one atomic per field.  (Atomic because the counting copies of
 // the traversal kernels and the megakernel book into the same struct.)
 PT_DEV void fold_shard_tallies(const WfBuffers& wf, Counters* __restrict__ counters) {
@@ -150,14 +102,6 @@ PT_DEV void fold_shard_tallies(const WfBuffers& wf, Counters* __restrict__ count
 // a path lives its whole life on ONE XCD.  Tiles are dealt round-robin over all workgroups, so every XCD sees the whole screen: giving
 // each XCD a contiguous band of tiles was slower, because the XCD whose band holds the expensive part of the picture finishes last
 // while the others idle (profiles/EXPERIMENTS.md).  (kXcds: pt_workspace.h)
-// Adaptive sampling (pt_set_adaptive): is the tile of a workgroup-round's (tile, sample) pair still active?  `slot0` = the round's first
-// slot (workgroup-uniform), so the state is read once per round; a retired tile pushes no ray and every later stage is unchanged.
-PT_DEV bool adaptive_tile_active(const FrameConstants& fc, const AdaptiveArgs& ad, uint32_t slot0) {
-    const uint32_t pair = slot0 >> 8;                                 // sample * my_tiles + rank-local tile
-    if (pair >= fc.my_tiles * fc.spp) return false;
-    const uint32_t local_tile = pair - slot_sample(fc, slot0) * fc.my_tiles;
-    return ad.tiles[local_tile].active != 0;
-}
 // LENS: the instantiations of calls with a thin lens (pt_set_lens); the others are compiled without the lens branch and its registers
 // (82 against 34 VGPRs), so that a pinhole call runs the kernel it always ran.
 template <bool ADAPTIVE, bool LENS>
@@ -189,77 +133,6 @@ __global__ __launch_bounds__(kBlock) void k_wf_generate(FrameConstants fc, WfBuf
             QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
             QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
             n_primary++;
-        }
-    }
-    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
-}
-
-// Texture-space baking (pt_set_bake): the generate stage of an image whose "camera" is a surface.  Slots, tiles, shards and the queue are
-// k_wf_generate's; the ray of a (texel, sample) is bake_ray's (pt_bake.h) -- one coverage word, one ShadePacket and one TriPacket per covered
-// sample -- and everything behind this launch is the code a camera frame runs.  An uncovered texel pushes no ray and counts none: no later
-// stage would write its slot, so its records are written here -- radiance 0 with nothing pending and, with AOVs on, zero records (`av` as
-// k_wf_aov takes it, all null without AOVs) -- and the unchanged resolve blends a defined value.
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_generate_bake(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, BakeArgs bk, AovArgs av) {
-    const ShardView sv = shard_view(wf);
-    unsigned n_primary = 0;
-    for (uint32_t rnd = 0; rnd < wf.gen_rounds; rnd++) {
-        const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-        const uint32_t sample = slot_sample(fc, slot);
-        uint32_t px = 0, py = 0;
-        bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
-        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
-        int rc = 0;
-        Ray ray;
-        ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
-        bool covered = false;
-        if (valid) covered = bake_ray(fc, bk, sample_seed(fc, sample), px, py, rc, ray);
-        const uint32_t idx = queue_push(wf.cnt[0] + sv.shard * kCounterStride, covered);
-        if (covered) {
-            const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
-            QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
-            QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
-            n_primary++;
-        } else if (valid) {
-            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wf.L[slot] = zero;
-            if (av.albedo) QST(av.rec_albedo[slot], zero);
-            if (av.normal_depth) QST(av.rec_normal[slot], zero);
-        }
-    }
-    flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
-}
-
-// Light-probe baking (pt_set_probes): the generate stage of an atlas whose "camera" is a set of points -- k_wf_generate_bake with another ray.
-// Slots, tiles, shards and the queue are k_wf_generate's; the ray of a (texel, sample) is probe_ray's (pt_probe.h).  The resolution is a
-// multiple of PT_TILE, so a workgroup-round (one tile of one sample) lies in one probe's map: the probe index is wave-uniform and the position
-// is read once per wave.  A cell without a probe pushes no ray and counts none; its records are written here, as an uncovered bake texel's.
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock, 7) void k_wf_generate_probe(FrameConstants fc, WfBuffers wf, Counters* __restrict__ counters, AdaptiveArgs ad, ProbeArgs pa, AovArgs av) {
-    const ShardView sv = shard_view(wf);
-    unsigned n_primary = 0;
-    for (uint32_t rnd = 0; rnd < wf.gen_rounds; rnd++) {
-        const uint32_t slot = (rnd * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-        const uint32_t sample = slot_sample(fc, slot);
-        uint32_t px = 0, py = 0;
-        bool valid = slot < wf.capacity && slot_pixel(fc, slot, px, py);
-        if (ADAPTIVE) { const bool tile_on = adaptive_tile_active(fc, ad, (rnd * gridDim.x + blockIdx.x) * kBlock); valid = valid && tile_on; }
-        int rc = 0;
-        Ray ray;
-        ray.o = v3(0); ray.d = v3(0, 0, 1); ray.tmin = 0; ray.tmax = 0;
-        bool present = false;
-        if (valid) present = probe_ray<true>(fc, pa, sample_seed(fc, sample), px, py, rc, ray);
-        const uint32_t idx = queue_push(wf.cnt[0] + sv.shard * kCounterStride, present);
-        if (present) {
-            const size_t e = (size_t)sv.shard * wf.seg_cap + idx;
-            QST(wf.ray_o[0][e], make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tmax));
-            QST(wf.ray_d[0][e], make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(slot)));
-            n_primary++;
-        } else if (valid) {
-            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wf.L[slot] = zero;
-            if (av.albedo) QST(av.rec_albedo[slot], zero);
-            if (av.normal_depth) QST(av.rec_normal[slot], zero);
         }
     }
     flush_shard_tallies(shard_tallies(wf, sv.shard), threadIdx.x & 63, n_primary, 0, 0, 0, 0);
@@ -442,17 +315,6 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_traverse(SceneRec
         flush_counters(counters, threadIdx.x & 63, 0, 0, 0, 0, st_shadow, true); flush_counters(counters, threadIdx.x & 63, 0, 0, 0, 0, st);
         if (st.deep | st_shadow.deep) atomicAdd(&counters->deep_pushes, (unsigned long long)st.deep + st_shadow.deep);
     } else if (st.overflow | st_shadow.overflow | st.deep | st_shadow.deep) { flush_rare(counters, st); flush_rare(counters, st_shadow); }
-}
-
-// The reference multiplies the light colour by the shadow transmission BEFORE `if (any(color > 0))` and never evaluates
-// the BSDF of an occluded sample: an occluded sample contributes nothing even when its pending term is NaN.
-// Both pending records are fetched whatever the flags say (the slots always exist): three loads in one round trip instead of
-// the flags first and the records behind them.
-// `pf` = the pending bits that travel in L.w.
-PT_DEV void apply_pending(const WfBuffers& wf, uint32_t slot, uint32_t pf, vec3& L) {
-    const float4 pe = PEND_ENV(slot), pl = PEND_LIGHT(slot);
-    if ((pf & 1u) && pe.w > 0.0f) L += v3(pe.x, pe.y, pe.z) * pe.w;
-    if ((pf & 2u) && pl.w > 0.0f) L += v3(pl.x, pl.y, pl.z) * pl.w;
 }
 
 // Constants of the dead set-aside scaffolding in k_wf_shade (see the comment there): "no note held", notes in a wave that triggered the
@@ -754,72 +616,6 @@ __global__ __launch_bounds__(kBlock, PT_TRACE_WAVES) void k_wf_shadow(SceneRec s
     else if (st.overflow | st.deep) flush_rare(counters, st);
 }
 
-// First-hit AOVs (pt_set_aov): albedo, shading normal and depth of the vertex the camera ray reaches, one 32-B record per slot.  A stage
-// of its own between the primary traversal and the first shade stage -- queue 0's rays and wf.hit are intact in that window -- so that
-// the shade stage, priced by the register allocation of its one function, stays what it is.  It walks the shard's segment like every
-// stage, stages the tables the vertex fetch and get_surface read, and runs exactly the code the shade stage runs up to the debug
-// outputs COLOR / SHADING_NORMAL (shade_closest_hit): the records are those values bit for bit.  A miss writes zeros; so does a
-// target whose sample has a non-finite component (no luminance clamp, SHOW_NAN / SHOW_INF do not apply).  Texture taps are not counted.
-// The records are written once and read once by the resolve: non-temporal, like the queues.
-PT_DEV bool aov_finite(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w); }
-__global__ __launch_bounds__(kBlock) void k_wf_aov(SceneRec sc_in, FrameConstants fc, WfBuffers wf, AovArgs av) {
-    SceneRec sc = sc_in; sc.small_tables = 0u;
-    const ShardView sv = shard_view(wf);
-    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
-    if (sv.member * kBlock >= n) return;                              // (workgroup-uniform) nothing of the segment is this workgroup's
-    stage_luts(sc);
-    stage_tangent_lut(sc);
-    stage_instances(sc);
-    stage_materials(sc);
-    const size_t base = (size_t)sv.shard * wf.seg_cap;
-    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
-        const float4 o = QLD(wf.ray_o[0][base + i]), d = QLD(wf.ray_d[0][base + i]), h = QLD(wf.hit[base + i]);
-        const uint32_t slot = __float_as_uint(d.w), hb = __float_as_uint(h.w);
-        float4 ra = make_float4(0, 0, 0, 0), rn = ra;
-        if (hb != kMissTri) {
-            const ShadePacket* packet_at = sc.shade + (hb & 0x7fffffffu);
-            RawPacket packet = load_shade_packet_raw(packet_at);
-            const ShadeInst inst = load_shade_inst(sc, raw_packet_inst(packet));
-            if (inst.streams & (SI_TEXCOORD1 | SI_COLOR)) load_shade_packet_extra(packet, packet_at);
-            const PacketVerts pv = unpack_shade_packet(packet);
-            const RMat* mat = sc.rmats + inst.material_id;
-            const MatHeader mh = material_header(sc, inst.material_id);
-            HitGeom va = get_vertex_attributes(sc, inst, pv, v3(1 - h.y - h.z, h.y, h.z));
-            if (!(hb >> 31)) { va.ng = -va.ng; va.n = -va.n; va.t = -va.t; va.tw = -va.tw; }
-            const vec3 view = -normalize(v3(d.x, d.y, d.z));
-            unsigned taps = 0;
-            const Surface sp = get_surface(sc, fc.flags, mat, mh, va, view, taps);
-            ra = make_float4(sp.albedo.x, sp.albedo.y, sp.albedo.z, 1.0f);
-            rn = make_float4(sp.n.x, sp.n.y, sp.n.z, h.x);
-            if (!aov_finite(ra)) ra = make_float4(0, 0, 0, 0);
-            if (!aov_finite(rn)) rn = make_float4(0, 0, 0, 0);
-        }
-        if (av.albedo) QST(av.rec_albedo[slot], ra);
-        if (av.normal_depth) QST(av.rec_normal[slot], rn);
-    }
-}
-// the running mean of a four-component AOV record: blend_sample's weight on every component
-PT_DEV float4 blend_aov(float4 h, int accumulated, float4 v) {
-    const float blend = fdiv(1.0f, (float)accumulated + 1.0f);
-    return make_float4(h.x + blend * (v.x - h.x), h.y + blend * (v.y - h.y), h.z + blend * (v.z - h.z), h.w + blend * (v.w - h.w));
-}
-// The AOV part of a resolve thread: the batch's records of pixel slot `pslot` blended in sample order into one target, with the
-// beauty's counts (`first` = samples already in the target; < 0: the call does not accumulate and the target takes the one sample).
-PT_DEV void resolve_aov_target(const FrameConstants& fc, const WfBuffers& wf, const float4* __restrict__ rec, float4* __restrict__ target, uint32_t pslot, size_t at, int first) {
-    float4 pixel = make_float4(0, 0, 0, 0);
-    if (first > 0) pixel = target[at];
-    for (uint32_t k = 0; k < fc.spp; k++) {
-        const float4 v = QLD(rec[k * fc.pixel_slots + pslot]);
-        const int n = first + (int)k;
-        pixel = n > 0 ? blend_aov(pixel, n, v) : v;
-    }
-    target[at] = pixel;
-}
-PT_DEV void resolve_aov(const FrameConstants& fc, const WfBuffers& wf, const AovArgs& av, uint32_t pslot, size_t at, int first) {
-    if (av.albedo) resolve_aov_target(fc, wf, av.rec_albedo, av.albedo, pslot, at, first);
-    if (av.normal_depth) resolve_aov_target(fc, wf, av.rec_normal, av.normal_depth, pslot, at, first);
-}
-
 // Adaptive sampling: the per-pixel error of the accumulated image I against the half buffer A (the mean of the samples with an even
 // per-tile index), in float32 in this order with IEEE division and a correctly rounded square root; a NaN counts as +inf.
 PT_DEV float adaptive_pixel_error(const float4 I, const float4 A) {
@@ -845,11 +641,7 @@ PT_DEV void resolve_adaptive(const FrameConstants& fc, const WfBuffers& wf, floa
         float4 pixel = make_float4(0, 0, 0, 0), half = pixel;
         if (fc.accumulated_frames != 0) { pixel = output[at]; half = ad.half[at]; }
         for (uint32_t k = 0; k < fc.spp; k++) {
-            const uint32_t slot = k * fc.pixel_slots + pslot;
-            float4 Lq = wf.L[slot];
-            vec3 L = v3(Lq.x, Lq.y, Lq.z);
-            apply_pending(wf, slot, __float_as_uint(Lq.w), L);
-            L = sanitize_sample(fc, L);
+            const vec3 L = resolved_sample(fc, wf, k * fc.pixel_slots + pslot);
             const int n = fc.accumulated_frames + (int)k;             // the sample's per-tile index
             pixel = n != 0 ? blend_sample(pixel, n, L) : make_float4(L.x, L.y, L.z, 1.0f);
             if ((n & 1) == 0) half = n != 0 ? blend_sample(half, n >> 1, L) : make_float4(L.x, L.y, L.z, 1.0f);
@@ -893,130 +685,12 @@ __global__ __launch_bounds__(kBlock) void k_wf_resolve(FrameConstants fc, WfBuff
     float4 pixel = make_float4(0, 0, 0, 0);
     if (accumulate && fc.accumulated_frames != 0) pixel = *outp;
     for (uint32_t k = 0; k < fc.spp; k++) {
-        const uint32_t slot = k * fc.pixel_slots + pslot;
-        float4 Lq = wf.L[slot];
-        vec3 L = v3(Lq.x, Lq.y, Lq.z);
-        apply_pending(wf, slot, __float_as_uint(Lq.w), L);
-        L = sanitize_sample(fc, L);
+        const vec3 L = resolved_sample(fc, wf, k * fc.pixel_slots + pslot);
         const int accumulated = fc.accumulated_frames + (int)k;
         pixel = (accumulate && accumulated != 0) ? blend_sample(pixel, accumulated, L) : make_float4(L.x, L.y, L.z, 1.0f);
     }
     *outp = pixel;
     if (AOV) resolve_aov(fc, wf, av, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
-}
-
-// ID mattes (pt_set_matte): which object or material each sample's first ray sees, one 32-bit id per slot.  A stage of its own in k_wf_aov's
-// window -- queue 0's entries and wf.hit are intact between the primary traversal and the first shade stage -- and far lighter: per entry
-// the slot word of the ray, the hit word, the instance word of the hit's shading packet, for the material kind the row's material_id, the
-// id of that row, and one store.  None of the shade stage's LDS tables is needed and none is staged.  The records were cleared before the
-// generate stage, so a slot that never had a ray (an uncovered bake texel, a cell without a probe) reads 0 like a miss.
-__global__ __launch_bounds__(kBlock) void k_wf_matte(SceneRec sc, WfBuffers wf, MatteArgs ma) {
-    const ShardView sv = shard_view(wf);
-    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
-    const size_t base = (size_t)sv.shard * wf.seg_cap;
-    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
-        const uint32_t slot = QLD(((const uint32_t*)(wf.ray_d[0] + base + i))[3]), hb = QLD(((const uint32_t*)(wf.hit + base + i))[3]);
-        uint32_t id = 0u;
-        if (hb != kMissTri) {
-            uint32_t row = sc.shade[hb & 0x7fffffffu].inst;
-            if (ma.kind == PT_MATTE_MATERIAL) row = sc.instances[row].gpu.material_id;
-            if (row < ma.n_ids) id = ma.ids[row];
-        }
-        if (slot < wf.capacity) QST(ma.rec[slot], id);
-    }
-}
-// The matte part of a resolve, a kernel of its own launched right before k_wf_resolve (whose adaptive instantiations update the tiles'
-// `active` flags this one reads) on the resolve's grid: one block per rank-local tile, one thread per pixel slot.  A thread reads its
-// pixel's K / 2 float4 once, folds the batch's records in sample order with the output's counts (pt_matte.h), sorts and writes once; the K
-// ranks stay in registers (RANKS is a template constant: every index is static).  A tile retired by adaptive sampling is not written.
-template <int RANKS, bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_matte_resolve(FrameConstants fc, AdaptiveArgs ad, MatteArgs ma) {
-    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
-    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t px, py;
-    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
-    const size_t at = (size_t)py * fc.res_x + px;
-    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
-    const int first = accumulate ? fc.accumulated_frames : -1;          // samples already in the layers; < 0: every sample is the first
-    MatteRanks<RANKS> m;
-#pragma unroll
-    for (int j = 0; j < RANKS / 2; j++) matte_unpack(m, j, first > 0 ? ma.layers[j][at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t k = 0; k < fc.spp; k++) {
-        const uint32_t h = QLD(ma.rec[k * fc.pixel_slots + pslot]);
-        matte_fold_sample(m, h, first < 0 ? 0 : first + (int)k);
-    }
-    matte_sort(m);
-#pragma unroll
-    for (int j = 0; j < RANKS / 2; j++) ma.layers[j][at] = matte_pack(m, j);
-}
-
-// Motion vectors (pt_set_motion): where the surface each sample's first ray sees was in the previous frame, one float4 per slot.  A stage of
-// its own in k_wf_aov's window, as light as k_wf_matte: per entry the slot word of the ray, the hit, the hit's TriPacket (one 64-byte line),
-// the instance row's tri_offset and the 48-byte snapshot entry, then one non-temporal store.  The four matrices are kernel arguments, hence
-// wave-uniform scalars; none of the shade stage's LDS tables is staged.  The records were cleared before the generate stage.
-__global__ __launch_bounds__(kBlock) void k_wf_motion(SceneRec sc, WfBuffers wf, MotionArgs ma) {
-    const ShardView sv = shard_view(wf);
-    const uint32_t n = wf.cnt[0][sv.shard * kCounterStride];
-    const size_t base = (size_t)sv.shard * wf.seg_cap;
-    for (uint32_t i = sv.member * kBlock + threadIdx.x; i < n; i += sv.stride) {
-        const uint32_t slot = QLD(((const uint32_t*)(wf.ray_d[0] + base + i))[3]);
-        const float4 h = QLD(wf.hit[base + i]);
-        const uint32_t hb = __float_as_uint(h.w), tri = hb & 0x7fffffffu;
-        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (hb != kMissTri && tri < sc.num_tris) r = motion_record(sc, ma, tri, h.y, h.z);
-        if (slot < wf.capacity) QST(ma.rec[slot], r);
-    }
-}
-// The motion part of a resolve, a kernel of its own launched right before k_wf_resolve (whose adaptive instantiations update the tiles'
-// `active` flags this one reads) on the resolve's grid: the target is the running mean of the records with the output's counts, by
-// resolve_aov_target.  A tile retired by adaptive sampling is not written.
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_motion_resolve(FrameConstants fc, WfBuffers wf, AdaptiveArgs ad, MotionArgs ma) {
-    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
-    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t px, py;
-    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
-    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
-    resolve_aov_target(fc, wf, ma.rec, ma.target, pslot, (size_t)py * fc.res_x + px, accumulate ? fc.accumulated_frames : -1);
-}
-
-// The variance AOV (pt_set_variance): the per-pixel population variance of the samples the output blends, a kernel of its own launched
-// right before k_wf_resolve on the resolve's grid.  At that point the output still holds the means before the batch, every sample's radiance
-// is still in the workspace, and the tiles' `active` flags are those the call started with.  A thread keeps the mean m and the variance V in
-// registers over the batch: the output is read once, the target read and written once.  Each sample comes through apply_pending and
-// sanitize_sample, the resolve's own functions, and m advances by blend_sample, the output's own blend -- so x and m' are the resolve's
-// values bit for bit, and nothing of m is written.  Welford's update in running-mean form (include/mipt.h states it operation by operation;
-// tests/variance_ref.py restates it).  A non-finite product is replaced by 0 (a select).  A tile retired by adaptive sampling is not written.
-PT_DEV float variance_finite_or_zero(float q) { return isfinite(q) ? q : 0.0f; }
-template <bool ADAPTIVE>
-__global__ __launch_bounds__(kBlock) void k_wf_variance_resolve(FrameConstants fc, WfBuffers wf, const float4* __restrict__ output, AdaptiveArgs ad, VarianceArgs va) {
-    if (ADAPTIVE) { if (ad.tiles[blockIdx.x].active == 0) return; }     // (block-uniform)
-    const uint32_t pslot = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t px, py;
-    if (pslot >= fc.pixel_slots || !slot_pixel(fc, pslot, px, py)) return;
-    const size_t at = (size_t)py * fc.res_x + px;
-    const bool accumulate = ADAPTIVE || (fc.flags & PT_FLAG_ACCUMULATE) != 0;     // (an adaptive call accumulates)
-    const int first = accumulate ? fc.accumulated_frames : 0;           // samples already in the pixel (a call that does not accumulate has one sample: zeros)
-    float4 m = make_float4(0, 0, 0, 0), V = m;
-    if (first > 0) { m = output[at]; V = va.target[at]; }
-    for (uint32_t k = 0; k < fc.spp; k++) {
-        const uint32_t slot = k * fc.pixel_slots + pslot;
-        const float4 Lq = wf.L[slot];
-        vec3 x = v3(Lq.x, Lq.y, Lq.z);
-        apply_pending(wf, slot, __float_as_uint(Lq.w), x);
-        x = sanitize_sample(fc, x);
-        const int n = first + (int)k;
-        if (n == 0) { V = make_float4(0, 0, 0, 0); m = make_float4(x.x, x.y, x.z, 1.0f); continue; }
-        const float b = fdiv(1.0f, (float)n + 1.0f);
-        const float4 mn = blend_sample(m, n, x);                        // m' = m + b * d0, the output's own blend
-        const vec3 d0 = v3(x.x - m.x, x.y - m.y, x.z - m.z), d1 = v3(x.x - mn.x, x.y - mn.y, x.z - mn.z);
-        const float qr = variance_finite_or_zero(d0.x * d1.x), qg = variance_finite_or_zero(d0.y * d1.y), qb = variance_finite_or_zero(d0.z * d1.z);
-        const float s0 = (d0.x + d0.y) + d0.z, s1 = (d1.x + d1.y) + d1.z;
-        const float qs = variance_finite_or_zero(s0 * s1);
-        V = make_float4(V.x + b * (qr - V.x), V.y + b * (qg - V.y), V.z + b * (qb - V.z), V.w + b * (qs - V.w));
-        m = mn;
-    }
-    va.target[at] = V;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -1044,10 +718,6 @@ size_t traversal_grid_lanes(int stage_blocks) { return (size_t)kShards * blocks_
 // ---- the traversal stages' kernel copies and launches (pt_wavefront.h: declared there, with the ray flags, for the test hook too)
 // the traversal kernels compiled for rays with no flags, if that is what the frame's settings give them
 static bool traversal_defaults(uint32_t flags) { return (flags & kTravFlagMask) == 0; }
-// A run-time bool as a compile-time one: f(std::true_type()) or f(std::false_type()), so that a launch line is written once for both
-// kernel copies.  pick2: two of them.
-template <class F> static void pick(bool a, F&& f) { if (a) f(std::true_type()); else f(std::false_type()); }
-template <class F> static void pick2(bool a, bool b, F&& f) { pick(a, [&](auto A) { pick(b, [&](auto B) { f(A, B); }); }); }
 void launch_wf_trace(dim3 grid, hipStream_t stream, bool count, const SceneRec& sc, const FrameConstants& fc, const WfBuffers& w, int cur, int b, uint32_t rf,
                      uint32_t rmask, Counters* counters) {
     pick2(count, traversal_defaults(fc.flags), [&](auto COUNT, auto DEFAULTS) { hipLaunchKernelGGL((k_wf_trace<COUNT.value, DEFAULTS.value>), grid, dim3(kBlock), 0, stream, sc, fc, w, cur, b, rf, rmask, counters); });
@@ -1060,54 +730,38 @@ void launch_wf_shadow(dim3 grid, hipStream_t stream, bool count, const SceneRec&
     pick(count, [&](auto COUNT) { hipLaunchKernelGGL(k_wf_shadow<COUNT.value>, grid, dim3(kBlock), 0, stream, sc, w, b, flags, tmax, counters); });
 }
 
+// pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
+// events cost a few microseconds each)
+hipEvent_t StageTimers::event_at(size_t i) {
+    while (ev.size() <= i) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; ev.push_back(e); }
+    return ev[i];
+}
+void StageTimers::mark(int stage_kind, hipStream_t stream) {
+    const size_t k = used;
+    hipEvent_t e = event_at(k + 1);
+    if (!e) return;
+    if (kind.size() < k + 1) kind.resize(k + 1);
+    kind[k] = (uint8_t)stage_kind;
+    hipEventRecord(e, stream);
+    used = k + 1;
+}
+
 hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const LensArgs& lens, float4* output, Counters* counters, bool count, void* workspace,
                             int stage_blocks, StageTimers* timers, hipStream_t stream, const WavefrontPasses& passes) {
     if (timers) timers->used = 0;
     if (fc.my_tiles == 0) return hipSuccess;
-    // pt_enable_stage_timing: an event after every launch, so that the time of a launch can be split by stage (diagnostic: the
-    // events cost a few microseconds each)
-    auto event_at = [&](size_t i) -> hipEvent_t {
-        while (timers->ev.size() <= i) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; timers->ev.push_back(e); }
-        return timers->ev[i];
-    };
-    auto mark = [&](int kind) {                              // the launch just enqueued was of stage `kind`
-        if (!timers) return;
-        const size_t k = timers->used;
-        hipEvent_t ev = event_at(k + 1);
-        if (!ev) return;
-        if (timers->kind.size() < k + 1) timers->kind.resize(k + 1);
-        timers->kind[k] = (uint8_t)kind;
-        hipEventRecord(ev, stream);
-        timers->used = k + 1;
-    };
     const uint32_t slots = fc.my_tiles * kBlock * fc.spp;
     const WorkspaceLayout lay = workspace_layout(fc.my_tiles, fc.spp, stage_blocks, passes.records(), kBlock);
     WfBuffers wf = carve(workspace, lay, slots);
     hipError_t e = hipMemsetAsync(wf.cnt[0], 0, (size_t)kCounterArrays * kShards * kCounterStride * 4, stream);     // the counter arrays are contiguous
     if (e) return e;
     const dim3 block(kBlock), full(fc.my_tiles), stage(kShards * wf.blocks_per_shard);
-    if (timers) { hipEvent_t ev = event_at(0); if (ev) hipEventRecord(ev, stream); else timers = nullptr; }
-    // the argument blocks as the kernels take them: zeros for a pass that is off, the record pointers from the layout
-    const bool adaptive = passes.adaptive, aov = passes.aov, matte = passes.matte, motion = passes.motion;
-    const AdaptiveArgs ad = adaptive ? passes.ad : AdaptiveArgs{};
-    AovArgs av = aov ? passes.av : AovArgs{};
-    MatteArgs mt = matte ? passes.mt : MatteArgs{};
-    MotionArgs mo = motion ? passes.mo : MotionArgs{};
-    if (aov) { av.rec_albedo = (float4*)((char*)workspace + lay.rec_albedo); av.rec_normal = (float4*)((char*)workspace + lay.rec_normal); }
-    if (matte) {                                                        // the records start as misses: no generate kernel knows of them
-        mt.rec = (uint32_t*)((char*)workspace + lay.rec_matte);
-        if ((e = hipMemsetAsync(mt.rec, 0, (size_t)slots * 4, stream)) != hipSuccess) return e;
-    }
-    if (motion) {                                                       // likewise
-        mo.rec = (float4*)((char*)workspace + lay.rec_motion);
-        if ((e = hipMemsetAsync(mo.rec, 0, (size_t)slots * 16, stream)) != hipSuccess) return e;
-    }
-    pick(adaptive, [&](auto ADAPTIVE) {
-        if (passes.probes) hipLaunchKernelGGL((k_wf_generate_probe<ADAPTIVE.value>), stage, block, 0, stream, fc, wf, counters, ad, passes.pa, av);
-        else if (passes.bake) hipLaunchKernelGGL((k_wf_generate_bake<ADAPTIVE.value>), stage, block, 0, stream, fc, wf, counters, ad, passes.bk, av);
-        else pick(lens.enable != 0, [&](auto LENS) { hipLaunchKernelGGL((k_wf_generate<decltype(ADAPTIVE)::value, LENS.value>), stage, block, 0, stream, fc, wf, counters, ad, lens); });
-    });
-    mark(STAGE_GENERATE);
+    if (timers) { hipEvent_t ev = timers->event_at(0); if (ev) hipEventRecord(ev, stream); else timers = nullptr; }
+    PassArgs pass = {passes, stream, timers};                           // the optional passes (wf_passes.hip): their argument blocks, their records cleared
+    if ((e = passes_begin(pass, workspace, lay, slots)) != hipSuccess) return e;
+    if (passes.probes || passes.bake) launch_pass_generate(pass, stage, fc, wf, counters);
+    else pick2(passes.adaptive, lens.enable != 0, [&](auto ADAPTIVE, auto LENS) { hipLaunchKernelGGL((k_wf_generate<ADAPTIVE.value, LENS.value>), stage, block, 0, stream, fc, wf, counters, pass.ad, lens); });
+    mark_stage(timers, STAGE_GENERATE, stream);
     const uint32_t flags = fc.flags;
     const int iterations = fc.debug_output != PT_DEBUG_OUTPUT_NONE ? 1 : fc.max_bounces + 1;
     // the shade kernel compiled for this frame's flags, if there is one (k_wf_shade)
@@ -1145,45 +799,24 @@ hipError_t launch_wavefront(const SceneRec& sc, const FrameConstants& fc, const 
         traversal_ray_flags(flags, 0, rf, rmask);
         const dim3 g0 = cap(stage, env_trace_bps);
         launch_wf_trace(g0, stream, count, sc, fc, wf_of(g0), 0, 0, rf, rmask, counters);
-        mark(STAGE_TRACE);
+        mark_stage(timers, STAGE_TRACE, stream);
     }
-    if (aov) { hipLaunchKernelGGL(k_wf_aov, stage, block, 0, stream, sc, fc, wf, av); mark(STAGE_SHADE); }     // the primary hits, before shade(0) + traverse(0) reuse the arrays
-    if (matte) { hipLaunchKernelGGL(k_wf_matte, stage, block, 0, stream, sc, wf, mt); mark(STAGE_SHADE); }         // likewise
-    if (motion) { hipLaunchKernelGGL(k_wf_motion, stage, block, 0, stream, sc, wf, mo); mark(STAGE_SHADE); }        // likewise
+    launch_first_hit_passes(pass, stage, sc, fc, wf);     // the primary hits, before shade(0) + traverse(0) reuse the arrays
     for (int b = 0; b < iterations; b++) {
         const int cur = b & 1;
         const dim3 gs = cap(grid_of(b), env_shade_bps), gt = cap(grid_of(b), env_trace_bps);
         const WfBuffers ws = wf_of(gs), wt = wf_of(gt);
         launch_shade(gs, ws, cur, b);
-        mark(STAGE_SHADE);
+        mark_stage(timers, STAGE_SHADE, stream);
         uint32_t rf, rmask;
         traversal_ray_flags(flags, b + 1, rf, rmask);
         if (b + 1 < iterations) launch_wf_traverse(gt, stream, count, sc, fc, wt, cur ^ 1, b, rf, rmask, counters);
         else launch_wf_shadow(gt, stream, count, sc, wt, b, flags, fc.max_ray_length, counters);         // the last vertex pushes no bounce ray
-        mark(STAGE_SHADOW);
+        mark_stage(timers, STAGE_SHADOW, stream);
     }
-    if (matte) {                                                        // before the resolve retires tiles: both see the call's `active` flags
-        pick(adaptive, [&](auto ADAPTIVE) {
-            auto launch_matte = [&](auto ranks) { hipLaunchKernelGGL((k_wf_matte_resolve<decltype(ranks)::value, decltype(ADAPTIVE)::value>), full, block, 0, stream, fc, ad, mt); };
-            switch (mt.ranks) {
-                case 2: launch_matte(std::integral_constant<int, 2>()); break;
-                case 4: launch_matte(std::integral_constant<int, 4>()); break;
-                case 6: launch_matte(std::integral_constant<int, 6>()); break;
-                default: launch_matte(std::integral_constant<int, 8>()); break;
-            }
-        });
-        mark(STAGE_RESOLVE);
-    }
-    if (motion) {                                                       // likewise
-        pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_motion_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, ad, mo); });
-        mark(STAGE_RESOLVE);
-    }
-    if (passes.variance) {                                              // likewise, and before the resolve replaces the means the output holds
-        pick(adaptive, [&](auto ADAPTIVE) { hipLaunchKernelGGL((k_wf_variance_resolve<ADAPTIVE.value>), full, block, 0, stream, fc, wf, (const float4*)output, ad, passes.va); });
-        mark(STAGE_RESOLVE);
-    }
-    pick2(adaptive, aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, ad, av, counters); });
-    mark(STAGE_RESOLVE);
+    launch_pass_resolves(pass, full, fc, wf, output);     // before the resolve retires tiles and replaces the output's means
+    pick2(passes.adaptive, passes.aov, [&](auto ADAPTIVE, auto AOV) { hipLaunchKernelGGL((k_wf_resolve<ADAPTIVE.value, AOV.value>), full, block, 0, stream, fc, wf, output, pass.ad, pass.av, counters); });
+    mark_stage(timers, STAGE_RESOLVE, stream);
     return hipGetLastError();
 }
 

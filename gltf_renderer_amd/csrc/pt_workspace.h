@@ -1,5 +1,5 @@
 // pt_workspace.h -- the layout of a wavefront trace's workspace, stated once and on the host alone: plain integers in, byte offsets out.
-// pt_wavefront.hip hands the arrays out by it (carve, launch_wavefront) and sizes the allocation by it (wavefront_workspace_bytes);
+// pt_wavefront.hip hands the arrays out by it (carve, launch_wavefront; the passes' records: wf_passes.hip passes_begin) and sizes the allocation by it (wavefront_workspace_bytes);
 // tests/host/workspace_layout_check.cpp holds it against the formulas it replaced.  Nothing here knows of HIP.
 #pragma once
 #include <cstddef>

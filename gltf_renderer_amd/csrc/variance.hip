@@ -6,7 +6,7 @@
 //                     (block-uniform).  Otherwise every in-image lane forms its pixel's relative standard error e; the tile's max and sum are
 //                     reduced per wave64 by cross-lane swaps and the four waves combined through LDS (resolve_adaptive's reduction of E).
 //                     Lanes off the image carry -infinity into the max and 0 into the sum; the mean divides by the in-image pixel count.
-// The variance pass itself (k_wf_variance_resolve) reads the wavefront workspace and lives with the resolve in pt_wavefront.hip.
+// The variance pass itself (k_wf_variance_resolve) reads the wavefront workspace and lives with the other pass resolves in wf_passes.hip.
 // Compiled without floating-point contraction (Makefile), with IEEE division and square root.
 #include <algorithm>
 #include <cmath>

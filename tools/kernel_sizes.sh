@@ -1,6 +1,6 @@
 #!/bin/bash
 # instruction counts + resource usage of the wavefront kernels (CPU-side, no GPU needed), compiled with the flags the Makefile gives
-# the path-tracing kernels and their test hooks (pt_wavefront.hip, pt_kernel.hip, debug_wf.hip, debug_mk.hip, motion.hip).  One line per kernel, sorted by name, so that two listings diff cleanly:
+# the path-tracing kernels and their test hooks (pt_wavefront.hip, wf_passes.hip, pt_kernel.hip, debug_wf.hip, debug_mk.hip, motion.hip).  One line per kernel, sorted by name, so that two listings diff cleanly:
 #   tools/kernel_sizes.sh [file.hip] > listing.txt
 cd "$(dirname "$0")/../gltf_renderer_amd/csrc"
 OUT=$(mktemp /tmp/ks_dev.XXXXXX.s)
